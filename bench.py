@@ -9,8 +9,16 @@ fold) over one batch of synthetic reads already resident in HBM.  Prints ONE JSO
   N > 1   BASELINE configs[2] shape: the feature table is hash-range-sharded over the N
           GPUs (one process per GPU), features go to their owners and hits come back by
           RCCL all-to-all -- that is `value`; the same reads on a replicated table
-          ("replicas only", no collective) are reported beside it as the second curve.
+          ("replicas only", no collective) are reported beside it as the second curve (--full).
           The database grows with N (--species x N species) unless --db-fixed.
+
+  A plain run sets up, warms up, times the K steps and prints the line.  --full adds everything else the benchmark
+  measures or checks (per-kernel times and roofline, PCIe-inclusive leg, CPU baseline and parity check against the
+  oracle, RefSeq-scale side block, replicas-only leg at N > 1).  --dump-outputs DIR writes the last timed step's
+  results as .npy files, for comparing two builds on the same seeded inputs.
+  Compare ms_per_step only between lines of the same kind: with --full the timed steps carry the per-kernel / per-stage
+  event timing (on the sharded leg an event synchronise per reused buffer set), a plain run times the path without it.
+  At N > 1 a plain run has no replicas leg to fall back on: if the sharded leg fails it prints no line and exits 3.
 
   python bench.py --gpus N --steps K --warmup W      (starts the N ranks itself)
   python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N ...   (or is started as one of them)
@@ -35,8 +43,9 @@ HBM_PEAK_GBS = 8000.0          # MI355X_MICROARCH.md: HBM3E 8 TB/s spec peak
 # does); the workgroup kernels (plain, and the one with the two-class tail behind it)
 KERNELS = {"fused": ("k_query_wave", "k_query_wave16+k_query_wave32", "k_query_block"),
            "sharded": ("k_query_wave<sharded>", "k_query_wave16+k_query_wave32<sharded>", "k_query_block<sharded>")}
-EXIT_SHARDED_FAILED = 3        # the line is printed (replicas leg), the exit status says the sharded leg failed
+EXIT_SHARDED_FAILED = 3        # the sharded leg failed; the replicas leg's line is printed if that leg ran (--full), else none
 EXIT_PARITY_FAILED = 4         # GPU result differs from the CPU oracle / the fused kernel
+DUMP_BYTES = 60 << 20          # --dump-outputs: all files of all ranks together stay below 64 MB
 
 
 def parse():
@@ -55,9 +64,9 @@ def parse():
     ap.add_argument("--emulate-ranks", type=int, default=2, help="reference rank count whose results are reproduced")
     ap.add_argument("--max-cand", type=int, default=2)
     ap.add_argument("--mode", default="auto", choices=["auto", "replicas", "sharded"],
-                    help="auto = fused kernel at N = 1, sharded (+ replicas beside it) at N > 1")
+                    help="auto = fused kernel at N = 1, sharded (+ replicas beside it with --full) at N > 1")
     ap.add_argument("--backend", default="nccl", choices=["nccl", "gloo"], help="gloo only to rehearse N>1 on a box with one GPU")
-    ap.add_argument("--no-replicas-leg", action="store_true", help="N>1: skip the replicated-table measurement")
+    ap.add_argument("--no-replicas-leg", action="store_true", help="--full at N>1: skip the replicated-table measurement")
     ap.add_argument("--sharded-timeout", type=int, default=240, help="seconds the sharded leg may take before the run ends without it")
     ap.add_argument("--small", action="store_true", help="tiny DB / few reads (plumbing check)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
@@ -90,7 +99,13 @@ def parse():
     ap.add_argument("--shard-serial", action="store_true",
                     help="diagnosis: the sharded leg without overlap -- no `next` batch, a sync after every step -- so that stage_ms_per_step are the stages' times ALONE (results invalid as a throughput)")
     ap.add_argument("--no-refseq-block", action="store_true",
-                    help="default N = 1 line: skip the `refseq_scale` side block (the RefSeq-scale table built and timed in the same run, ~80 s)")
+                    help="--full N = 1 line: skip the `refseq_scale` side block (the RefSeq-scale table built and timed in the same run, ~80 s)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure and check what the headline figure does not need: per-kernel times and roofline, the PCIe-inclusive "
+                         "leg, the CPU baseline with its parity check, the RefSeq-scale side block, and at N > 1 the replicas-only leg")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the timed path's results of its last step as DIR/<name>.npy (float64; a seeded sample of the queries "
+                         "above %d MB)" % (DUMP_BYTES >> 20))
     a = ap.parse_args()
     # defaults that depend on --refseq-scale (explicit values win, however they were abbreviated)
     if a.species is None: a.species = 2600 if a.refseq_scale else 50
@@ -141,6 +156,24 @@ def algorithmic_bytes(n_bases, st):
     return n_bases + 16 * st["n_features"] + 8 * st["n_locations"] + 16 * st["n_cands"]
 
 
+def dump_outputs(out_dir, cands, ncand, rank=0, world=1):
+    """--dump-outputs: what a caller of the timed path receives for the last timed step, as float64 (exact for u32):
+    n_cand [q] and cands [q, max_cand, 4] = (tax, hits, win_beg, win_end), slots past n_cand zeroed (never read by a
+    caller).  Above DUMP_BYTES a fixed seeded sample of the queries, sorted; query_index [q] says which.  At N > 1 every
+    rank writes its own files (suffix _rank<r>)."""
+    n = ncand.cpu().numpy().view(np.uint32)
+    c = cands.cpu().numpy().view(np.uint32).copy()
+    c[np.arange(c.shape[1])[None, :] >= n[:, None]] = 0
+    keep = DUMP_BYTES // world // (8 * (2 + c[0].size))
+    idx = np.arange(n.size)
+    if n.size > keep:
+        idx = np.sort(np.random.default_rng(12345).choice(n.size, keep, replace=False))
+    os.makedirs(out_dir, exist_ok=True)
+    sfx = "_rank%d" % rank if world > 1 else ""
+    for name, arr in (("query_index", idx), ("n_cand", n[idx]), ("cands", c[idx])):
+        np.save(os.path.join(out_dir, name + sfx + ".npy"), arr.astype(np.float64))
+
+
 def main():
     a = parse()
     if "WORLD_SIZE" not in os.environ and a.gpus > 1:
@@ -149,7 +182,6 @@ def main():
     if a.small:
         a.species, a.strains, a.genome_min, a.genome_max = 6, 4, 150_000, 300_000
         a.batch = min(a.batch, 1 << 16)
-        a.steps = min(a.steps, 4)
     world = int(os.environ.get("WORLD_SIZE", "1"))
     rank = int(os.environ.get("RANK", "0"))
     local = int(os.environ.get("LOCAL_RANK", "0"))
@@ -189,14 +221,14 @@ def main():
 
     # N = 1: the fused kernel on the whole table.  N > 1: the hash-range-sharded table with the all-to-all exchange is
     # the primary number (north_star / configs[2]); "replicas only" (table replicated, reads split, no collective: what
-    # one would deploy while the table fits one 288 GB GPU) is measured in the same run as the second curve.
+    # one would deploy while the table fits one 288 GB GPU) is measured in the same run as the second curve (--full).
     mode = a.mode
     if mode == "auto":
         mode = "single" if world == 1 else "sharded"
     if world == 1 and mode == "replicas":
         mode = "single"
     with_sharded = mode == "sharded"
-    with_fused = mode != "sharded" or not a.no_replicas_leg
+    with_fused = mode != "sharded" or (a.full and not a.no_replicas_leg)
     n_species = a.species * (world if (world > 1 and not a.db_fixed) else 1)
 
     def setup_data():
@@ -265,7 +297,7 @@ def main():
             db_shard = parts.database(sp32.data_ptr(), n_shards=world, shard_id=rank, flags=lflags) if with_sharded else None
             parts.close()
             # the CPU leg (the checker) works on the part of the table a batch can touch, read back through the staged entry points
-            want_cpu = rank == 0 and not a.no_cpu_baseline and not a.stop_stage and with_fused
+            want_cpu = a.full and rank == 0 and not a.no_cpu_baseline and not a.stop_stage and with_fused
             host_table = None
         else:
             table = eng.Table(gen_bases.data_ptr(), gen_off.data_ptr(), n_targets, emulate_ranks=a.emulate_ranks, flags=bflags,
@@ -283,7 +315,7 @@ def main():
             db = make_db() if with_fused else None
             db_shard = make_db(world, rank) if with_sharded else None
             n_keys, n_locs = table.n_keys, table.n_locs
-            want_cpu = rank == 0 and not a.no_cpu_baseline and not a.stop_stage and (world == 1 or n_locs <= 600_000_000)
+            want_cpu = a.full and rank == 0 and not a.no_cpu_baseline and not a.stop_stage and (world == 1 or n_locs <= 600_000_000)
             host_table = table.to_host()[:3] if want_cpu else None      # only the CPU baseline (the checker) reads these
             table.close()
             del gen_bases
@@ -378,10 +410,11 @@ def main():
     fused_elapsed, st, kms, kn = None, None, None, 0
     phase_clocks = None
     if with_fused:
-        fused_elapsed = timed(step_fused, lambda: ws.timing(True))
+        fused_elapsed = timed(step_fused, (lambda: ws.timing(True)) if a.full else None)
         st = ws.sync()
-        kms, kn = ws.kernel_times()
-        ws.timing(False)
+        if a.full:
+            kms, kn = ws.kernel_times()
+            ws.timing(False)
         phase_clocks = ws.phase_clocks()
 
     # (state of the sharded leg; roofline() / make_line() are defined BEFORE that leg so that its watchdog can print a line)
@@ -544,28 +577,29 @@ def main():
             def start_sharded_clock():
                 sharded.timing(True)
                 xb0.update(sharded.exchange_bytes())
-            sharded_elapsed = timed(step_sharded, start_sharded_clock)
+            sharded_elapsed = timed(step_sharded, start_sharded_clock if a.full else None)
             sh_stats = sharded.sync(stream)
-            sh_kms, sh_kn = sharded.kernel_times()
-            stage_ms, stage_n = sharded.stage_times()
-            sharded.timing(False)
-            xb1 = sharded.exchange_bytes()
-            nbt = max(1, xb1["batches"] - xb0["batches"])
-            per = {k: (xb1[k] - xb0[k]) / nbt for k in ("x1", "x2_ends", "x2_locations", "own_blocks")}
-            loc_bytes = (db_shard.layout()["loc_bytes"])
-            payload = 4 * sh_stats["n_features"] + 4 * sh_stats["n_features"] + loc_bytes * sh_stats["n_locations"]
-            sent = per["x1"] + per["x2_ends"] + per["x2_locations"] + per["own_blocks"]
-            sh_stats["exchange_bytes_per_step"] = dict(
-                per, rccl_ranks=xb1["rccl_ranks"], block_features=xb1["block_features"], block_locations=xb1["block_locations"],
-                to_other_ranks=per["x1"] + per["x2_ends"] + per["x2_locations"],
-                padding_share=(1.0 - payload / sent) if sent else None,
-                note="bytes this rank hands to the transport per batch: X1 feature blocks, X2 list ends + tile starts, X2 locations (%d-B words); "
-                     "own_blocks never leave the device; padding_share = 1 - (features x 4 B out + list ends x 4 B + locations back) / all of it" % loc_bytes)
-            sh_stats["stage_ms_per_step"] = dict({k: v / max(1, stage_n) for k, v in stage_ms.items()},
-                                                 S3=sum(sh_kms) / max(1, sh_kn),
-                                                 note="events around the stages on their streams (they overlap across batches: the sum exceeds ms_per_step); "
-                                                      "S1 sketch + route, X1 features out, S2 owner-side lookup, X2 lists back, S3 home-side reduce kernels")
-            sh_stats["exchange_block_features_locations"] = list(sharded.caps())
+            if a.full:
+                sh_kms, sh_kn = sharded.kernel_times()
+                stage_ms, stage_n = sharded.stage_times()
+                sharded.timing(False)
+                xb1 = sharded.exchange_bytes()
+                nbt = max(1, xb1["batches"] - xb0["batches"])
+                per = {k: (xb1[k] - xb0[k]) / nbt for k in ("x1", "x2_ends", "x2_locations", "own_blocks")}
+                loc_bytes = (db_shard.layout()["loc_bytes"])
+                payload = 4 * sh_stats["n_features"] + 4 * sh_stats["n_features"] + loc_bytes * sh_stats["n_locations"]
+                sent = per["x1"] + per["x2_ends"] + per["x2_locations"] + per["own_blocks"]
+                sh_stats["exchange_bytes_per_step"] = dict(
+                    per, rccl_ranks=xb1["rccl_ranks"], block_features=xb1["block_features"], block_locations=xb1["block_locations"],
+                    to_other_ranks=per["x1"] + per["x2_ends"] + per["x2_locations"],
+                    padding_share=(1.0 - payload / sent) if sent else None,
+                    note="bytes this rank hands to the transport per batch: X1 feature blocks, X2 list ends + tile starts, X2 locations (%d-B words); "
+                         "own_blocks never leave the device; padding_share = 1 - (features x 4 B out + list ends x 4 B + locations back) / all of it" % loc_bytes)
+                sh_stats["stage_ms_per_step"] = dict({k: v / max(1, stage_n) for k, v in stage_ms.items()},
+                                                     S3=sum(sh_kms) / max(1, sh_kn),
+                                                     note="events around the stages on their streams (they overlap across batches: the sum exceeds ms_per_step); "
+                                                          "S1 sketch + route, X1 features out, S2 owner-side lookup, X2 lists back, S3 home-side reduce kernels")
+                sh_stats["exchange_block_features_locations"] = list(sharded.caps())
             if with_fused:
                 # same batch through the fused kernel on the replicated table: bit-identical results expected on every rank
                 last = a.warmup + a.steps - 1
@@ -582,6 +616,14 @@ def main():
             sharded_error = sharded_error or "%s: %s" % (type(e).__name__, str(e)[:300])
         dog.cancel()
 
+    if sharded_elapsed is None and fused_elapsed is None:       # the sharded leg failed and no other leg ran: no line
+        sys.stderr.write("[bench rank %d] sharded leg failed: %s\n" % (rank, sharded_error))
+        sys.stderr.flush()
+        os._exit(EXIT_SHARDED_FAILED)
+    if a.dump_outputs:
+        on_sharded = mode == "sharded" and sharded_elapsed is not None
+        dump_outputs(a.dump_outputs, *((cands_s, ncand_s) if on_sharded else (cands, ncand)), rank=rank, world=world)
+
     out = make_line(mode, sharded_elapsed, sharded_error)
     if phase_clocks and any(phase_clocks):
         out["DIAGNOSTIC_phase_clocks_of_the_workgroup_kernel"] = phase_clocks
@@ -589,7 +631,7 @@ def main():
         out["INVALID_profiling_stop_stage"] = a.stop_stage
     if a.shard_serial:
         out["INVALID_diagnostic_run_without_overlap"] = True
-    if world == 1 and mode == "single" and a.workload == "c2" and not a.stop_stage and not a.small and not a.no_pcie_leg:
+    if a.full and world == 1 and mode == "single" and a.workload == "c2" and not a.stop_stage and not a.small and not a.no_pcie_leg:
         # the boundary may hand over HOST buffers (what the reference's readers fill): mcq_query_pipelined keeps two batches
         # in flight -- copy in, compute, copy out on three streams -- from pinned memory; once with ASCII bases (PCIe Gen5 x16
         # carries 157 MB per step) and once with MCQ_BATCH_PACKED (59 MB).  Reported for DESIGN.md, never as `value`.
@@ -655,9 +697,9 @@ def main():
                                            gc, gn, B, paired, bounded=world > 1 or host_table is None, note=note)
         parity_ok = out["cpu_baseline"]["gpu_matches_cpu_on_first_batch"] is not False
     out["timed_region_ms"] = 1e3 * (sharded_elapsed if (mode == "sharded" and sharded_elapsed is not None) else fused_elapsed)
-    if (world == 1 and mode == "single" and a.workload == "c2" and not a.small and not a.refseq_scale and a.species == 50 and not a.stop_stage
+    if (a.full and world == 1 and mode == "single" and a.workload == "c2" and not a.small and not a.refseq_scale and a.species == 50 and not a.stop_stage
             and not a.no_cpu_baseline and not a.no_pcie_leg and not a.no_refseq_block and not a.packed_input and a.contigs == 1):
-        # the regime north_star targets, in the same driver-timed run (a side block like pcie_inclusive: never `value`): everything of
+        # the regime north_star targets, in the same --full run (a side block like pcie_inclusive: never `value`): everything of
         # the configs[1] measurement is released first
         try:
             if ws is not None:
@@ -688,7 +730,7 @@ def main():
 
 
 def refseq_side_block(a, eng, synth, torch, dev, stream):
-    """The regime north_star targets, timed in the driver's own default run (never `value`): BASELINE configs[2]'s table --
+    """The regime north_star targets, timed in the --full run at the default size (never `value`): BASELINE configs[2]'s table --
     2 600 species x 10 strains (>= 100 Gbp), every genome two sequences (52 001 targets), one 16 Mbp chromosome, built with
     -remove-overpopulated-features in feature-hash parts -- on this ONE GPU; 8 timed steps of 1 M x 150 bp reads and of 524 288
     pairs of 2 x 150 bp through the fused path, the same through mcq_shard_* at one rank (the N > 1 product path; a rank's own

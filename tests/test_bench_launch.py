@@ -47,3 +47,35 @@ def test_line_builders_are_defined_before_the_sharded_leg():
     """the fallback line is built by make_line(): it must exist when the watchdog is armed"""
     src = open(os.path.join(ROOT, "bench.py")).read()
     assert src.index("def make_line(") < src.index("arm_watchdog(a.sharded_timeout") and src.index("def roofline(") < src.index("arm_watchdog(a.sharded_timeout")
+
+
+def test_dump_outputs_writes_the_callers_view_within_64_mb(tmp_path):
+    """--dump-outputs: float64 .npy files of the last step's result; candidate slots past n_cand zeroed; above the byte cap
+    a fixed seeded sample of the queries (the same one every run); every rank's files together below 64 MB"""
+    import numpy as np
+    import torch
+    sys.path.insert(0, ROOT)
+    import bench
+    g = torch.Generator().manual_seed(0)
+    nq, M = 1 << 20, 2
+    cands = torch.randint(-2 ** 31, 2 ** 31 - 1, (nq, M, 4), dtype=torch.int32, generator=g)
+    ncand = torch.randint(0, M + 1, (nq,), dtype=torch.int32, generator=g)
+    for world in (1, 2):
+        d = tmp_path / ("w%d" % world)
+        for r in range(world):
+            bench.dump_outputs(str(d), cands, ncand, rank=r, world=world)
+        assert sum(f.stat().st_size for f in d.iterdir()) < 64 << 20
+    files = {f.name: np.load(f) for f in (tmp_path / "w1").iterdir()}
+    assert sorted(files) == ["cands.npy", "n_cand.npy", "query_index.npy"]
+    assert all(a.dtype == np.float64 for a in files.values())
+    idx = files["query_index.npy"].astype(np.int64)
+    assert 0 < idx.size < nq and np.all(np.diff(idx) > 0)
+    n, c = files["n_cand.npy"], files["cands.npy"]
+    assert np.array_equal(n, ncand.numpy()[idx])
+    live = np.arange(M)[None, :] < n[:, None]
+    assert np.array_equal(c[live], cands.numpy().view(np.uint32)[idx][live].astype(np.float64)) and not c[~live].any()
+    bench.dump_outputs(str(tmp_path / "again"), cands, ncand)
+    assert np.array_equal(np.load(tmp_path / "again" / "query_index.npy"), files["query_index.npy"])
+    # small results are written whole
+    bench.dump_outputs(str(tmp_path / "small"), cands[:1000], ncand[:1000])
+    assert np.array_equal(np.load(tmp_path / "small" / "query_index.npy"), np.arange(1000))
