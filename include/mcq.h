@@ -468,6 +468,36 @@ int mcq_parts_builder_finish(mcq_parts_builder* b, mcq_parts** out);
 int mcq_parts_builder_free(mcq_parts_builder* b);
 const char* mcq_build_last_error(void);
 
+/* ---- classification and per-taxon read counts on the device (csrc/mcq_classify.hip) ------------------------------------
+ * classify() (src/classification.cpp:235-265, ranked_lca src/taxonomy.h:531-537) of every query's candidate list, as
+ * mcq_refdb_classify of include/mcq_host.h computes it, bit for bit, and the count of classified queries per taxon the
+ * reference keeps for its abundance tables (++taxCounts[cls.best], src/classification.cpp:712-714).
+ * A taxonomy is the ranked-lineage table of the database (mcq_refdb_lineages): lineage[t * 21 + r] = taxon index at rank r
+ * in the lineage of taxon t or 0xFFFFFFFF, rank[t] = rank of taxon t (host pointers; copied to `device`).             */
+typedef struct mcq_taxonomy mcq_taxonomy;
+typedef struct {
+    uint32_t hits_min;            /* -hitmin (already defaulted: mcq_default_hits_min)                             */
+    float hits_diff_fraction;     /* -hitdiff as the reference stores it (80 -> 0.8f)                              */
+    uint32_t highest_rank;        /* -highest (MCQ_RANK_* of include/mcq_host.h)                                   */
+    uint32_t flags;               /* 0                                                                             */
+} mcq_classify_opts;
+int mcq_taxonomy_create(const uint32_t* lineage, const uint8_t* rank, uint32_t n_taxa, int32_t device, mcq_taxonomy** out);
+int mcq_taxonomy_destroy(mcq_taxonomy* tx);
+/* cands: the device result of mcq_query / mcq_shard_query (flags MCQ_DEVICE_PTRS), n_queries lists of max_cand slots.
+ * best (device, may be NULL): per query the taxon index of the classification or 0xFFFFFFFF.  counts (device, may be
+ * NULL): [n_taxa + 1] u64, ADDED to: counts[t] += queries classified as taxon t, counts[n_taxa] += unclassified ones.
+ * Only enqueues work on `stream`.  Integer counts: the sums do not depend on the order of the adds.                 */
+int mcq_classify(const mcq_taxonomy* tx, const mcq_result* cands, uint64_t n_queries, uint32_t max_cand,
+                 const mcq_classify_opts* opts, uint32_t* best, uint64_t* counts, void* stream);
+/* While a taxonomy is attached (tx != NULL; NULL detaches), every mcq_query / mcq_query_pipelined on the workspace also
+ * classifies its batch on the device -- on the batch's stream, before the copy-out -- and adds into the workspace's
+ * counts ([n_taxa + 1], zeroed when first attached or attached with another n_taxa).  The taxonomy must outlive the
+ * attachment and live on the workspace's device.                                                                     */
+int mcq_ws_set_classify(mcq_ws* ws, const mcq_taxonomy* tx, const mcq_classify_opts* opts);
+/* waits for the last batch that classified, copies the workspace's counts ([n_taxa + 1] of the taxonomy attached last)
+ * to host_out; reset != 0 zeroes them afterwards                                                                      */
+int mcq_ws_taxon_counts(mcq_ws* ws, uint64_t* host_out, int reset);
+
 /* ---- debug / parity taps ------------------------------------------------------------
  * Row 5 in isolation is mcq_count_windows + mcq_sketch above (the sketches of every window).
  * Rows 7-8 in isolation: the sorted match list of every query (what merge_sort returns,

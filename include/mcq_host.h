@@ -21,6 +21,7 @@
  */
 #ifndef MCQ_HOST_H
 #define MCQ_HOST_H
+#include <stddef.h>
 #include <stdint.h>
 #ifdef __cplusplus
 extern "C" {
@@ -109,6 +110,22 @@ uint32_t mcq_refdb_ancestor(const mcq_refdb* db, uint32_t key, uint32_t rank);
  * Returns the taxon index of the classification or MCQ_NO_TAXON.                      */
 uint32_t mcq_refdb_classify(const mcq_refdb* db, const uint32_t* cands, uint32_t n,
                             uint32_t hits_min, float hits_diff_fraction, uint32_t highest_rank);
+
+/* the ranked lineages classify works on, for the device (mcq_taxonomy_create of include/mcq.h): lineage[t * 21 + r] =
+ * taxon index at rank r in the lineage of taxon t (the taxon itself included) or MCQ_NO_TAXON, rank[t] = its rank.
+ * lineage holds n_taxa x 21 u32, rank n_taxa bytes.                                                                */
+int mcq_refdb_lineages(const mcq_refdb* db, uint32_t* lineage, uint8_t* rank);
+
+/* The reference's abundance tables (show_abundances / show_abundance_estimates, src/printing.cpp:474-517) from the
+ * number of classified queries per taxon: counts[n_taxa], indexed by taxon index (bit 31 of the keys stripped);
+ * total = queries processed, classified or not (the denominator of the percentages).  est_rank = MCQ_RANK_NONE: the
+ * plain table ("# query summary: ..."); a rank below root: estimate_abundance (src/classification.cpp:362-428) to that
+ * rank first ("# estimated abundance ...").  The text, its comment line included, goes to buf (NUL-terminated, cut
+ * to cap - 1 bytes); returns its length (call with cap = 0 to learn it), negative on error.
+ * Counts are exact u64 and become float once, here; the reference adds floats, which differs past 2^24 on one taxon
+ * (DESIGN.md section 12).                                                                                          */
+int64_t mcq_refdb_abundance_text(const mcq_refdb* db, const uint64_t* counts, uint64_t total, uint32_t est_rank,
+                                 char* buf, size_t cap);
 
 /* default of -hitmin when unset: src/mode_query.cpp:247-259 */
 uint32_t mcq_default_hits_min(uint32_t sketch_size);

@@ -6,8 +6,10 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 _HDR = os.path.join(os.path.dirname(_HERE), "include", "mcq.h")
 # translation unit -> what it depends on besides itself
 _UNITS = {
-    os.path.join(_HERE, "csrc", "mcq_engine.hip"): [os.path.join(_HERE, "csrc", "mcq_device.hpp"), os.path.join(_HERE, "csrc", "mcq_shard.hpp"), _HDR],
+    os.path.join(_HERE, "csrc", "mcq_engine.hip"): [os.path.join(_HERE, "csrc", "mcq_device.hpp"), os.path.join(_HERE, "csrc", "mcq_shard.hpp"),
+                                                     os.path.join(_HERE, "csrc", "mcq_classify.hpp"), _HDR],
     os.path.join(_HERE, "csrc", "mcq_build.hip"): [_HDR],       # table construction (rocPRIM sorts)
+    os.path.join(_HERE, "csrc", "mcq_classify.hip"): [os.path.join(_HERE, "csrc", "mcq_classify.hpp"), _HDR],   # classification + taxon counts
 }
 _OBJ = os.path.join(_HERE, "csrc", "_obj")
 
@@ -58,7 +60,7 @@ def build_host(force=False, verbose=False):
     hdr = os.path.join(os.path.dirname(_HERE), "include", "mcq_host.h")
     out = host_lib_path()
     if force or not os.path.exists(out) or os.path.getmtime(out) < max(os.path.getmtime(src), os.path.getmtime(hdr)):
-        cmd = ["g++", "-std=c++14", "-O2", "-Wall", "-shared", "-fPIC", src, "-o", out]
+        cmd = ["g++", "-std=c++14", "-O2", "-ffp-contract=off", "-Wall", "-shared", "-fPIC", src, "-o", out]   # (no contraction: the abundance estimate is float arithmetic restated op for op)
         if verbose:
             print(" ".join(cmd))
         subprocess.check_call(cmd)

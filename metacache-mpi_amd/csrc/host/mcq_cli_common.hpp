@@ -11,6 +11,10 @@
 //   * one mapping line per read (pair)         show_query_mapping       src/classification.cpp:583-632
 //         taxon formats (rank:name default, -taxids, -taxids-only, -omit-ranks, -lineage)  show_taxon / show_lineage /
 //         show_no_taxon src/printing.cpp:117-201, :305-330;  -tophits list  show_matches src/printing.cpp:333-360
+//   * -abundances / -abundance-per R tables   show_abundances / show_abundance_estimates src/printing.cpp:474-517,
+//                                              estimate_abundance src/classification.cpp:362-428 (mcq_refdb_abundance_text)
+//         after the mapping lines, into the -out file or the -abundances FILE (src/mode_query.cpp:59-117); the counts come
+//         from the device (mcq_classify), checked against the host classification's total
 //   * the summary                              show_summary             src/printing.cpp:622-641,
 //                                              show_taxon_statistics    src/printing.cpp:522-555
 // After sorting, the file equals the reference's byte for byte except for the measured values of the "# time:" and
@@ -19,8 +23,9 @@
 //
 // usage: mcq_query_cli <dbprefix> <n_ranks> <r1.fq> <r2.fq|-> [-lowest R] [-highest R] [-maxcand N] [-hitmin N]
 //            [-hitdiff X] [-insertsize N] [-threads N] [-tophits] [-taxids] [-taxids-only] [-omit-ranks] [-lineage]
-//            [-mapped-only] [-nomap] [-noquirks] [-out FILE] [-batch N] [-batch-bases N]
-// (-batch / -batch-bases: queries / bases per batch; the reads go through in batches, see mcq_query_cli.cpp)
+//            [-mapped-only] [-nomap] [-noquirks] [-abundances [FILE]] [-abundance-per R] [-out FILE] [-batch N] [-batch-bases N]
+// (-batch / -batch-bases: queries / bases per batch; the reads go through in batches, see mcq_query_cli.cpp;
+//  -abundances [FILE] / -abundance-per R (aliases -abundances-per, -abundance_per, -abundances_per): src/query_options.cpp:310-323)
 #include <chrono>
 #include <cstdio>
 #include <cstdlib>
@@ -116,6 +121,10 @@ struct Options {
     uint32_t lowest = MCQ_RANK_SEQUENCE, highest = MCQ_RANK_DOMAIN, maxcand = 2, hitmin = 0, threads = 1;
     float hitdiff = 1.0f; uint64_t insertsize = 0; bool quirks = true;
     bool show_ranks = true, taxids = false, taxids_only = false, lineage = false, tophits = false, mapped_only = false, nomap = false;
+    bool abundances = false;             // -abundances [FILE]: the plain per-taxon table
+    std::string abundance_file;          // ... its FILE (cleared when it names the -out file: src/query_options.cpp:355)
+    uint32_t abundance_rank = MCQ_RANK_NONE;   // -abundance-per R: the estimate to rank R (< root)
+    bool tax_counts() const { return abundances || abundance_rank != MCQ_RANK_NONE; }
     std::string transport = "rccl";      // mcq_query_mpi: rccl | mpi (blocks through the host and MPI_Alltoallv)
     uint64_t batch = 1u << 19, batch_bases = 256u << 20;   // mcq_query_mpi: queries / bases per rank and batch
     bool paired() const { return f2 != "-"; }
@@ -146,7 +155,15 @@ static bool parse_options(int argc, char** argv, Options& o) {
         else if (a == "-batch") o.batch = std::max<uint64_t>(1, std::strtoull(next(), nullptr, 10));
         else if (a == "-batch-bases") o.batch_bases = std::max<uint64_t>(1024, std::strtoull(next(), nullptr, 10));
         else if (a == "-out") o.outfile = next();
+        else if (a == "-abundances") {                                       // the FILE is the next token unless it is an option
+            o.abundances = true;
+            if (i + 1 < argc && argv[i + 1][0] != '-') o.abundance_file = argv[++i];
+        }
+        else if (a == "-abundance-per" || a == "-abundances-per" || a == "-abundance_per" || a == "-abundances_per") {
+            const uint32_t r = mcq_rank_from_name(next()); if (r < MCQ_RANK_ROOT) o.abundance_rank = r;
+        }
     }
+    if (o.abundance_file == o.outfile) o.abundance_file.clear();
     if (o.lowest > o.highest) o.lowest = o.highest;
     if (o.nomap && o.tophits) { o.nomap = false; o.mapped_only = true; }   // "showing hits changes the mapping mode", src/query_options.cpp:289-292
     return true;
@@ -171,6 +188,9 @@ static void write_head(std::ostream& os, const Out& o, const Options& p, uint32_
     os << cm << "At maximum " << p.maxcand << " classification candidates will be considered per query.\n";
     if (p.paired()) os << cm << "File based paired-end mode:\n" << cm << "  Reads from two consecutive files will be interleaved.\n"
                        << cm << "  Max insert size considered " << p.insertsize << ".\n";
+    if (p.abundance_rank != MCQ_RANK_NONE)                                  // (the reference keys the -abundances line on -hits-per-seq, :100-103)
+        os << cm << "A list of absolute and relative abundances for each '" << mcq_rank_name(p.abundance_rank)
+           << "' will be generated after the read mapping.\n";
     os << cm << "Using " << p.threads << " threads\n";
     if (!p.nomap) {
         os << cm << "TABLE_LAYOUT: query_header" << o.col;
@@ -233,6 +253,54 @@ static void write_summary(std::ostream& os, const Out& o, const Options& p, cons
             }
         }
     } else std::cerr << cm << "No valid query sequences found.\n";
+}
+
+// the taxonomy of the database on `device` for mcq_classify (the ranked lineages mcq_refdb_classify works on)
+static mcq_taxonomy* make_taxonomy(mcq_refdb* rdb, int device) {
+    mcq_refdb_info info; mcq_refdb_get_info(rdb, &info);
+    std::vector<uint32_t> lin((size_t)info.n_taxa * 21); std::vector<uint8_t> rank(info.n_taxa);
+    mcq_taxonomy* tx = nullptr;
+    if (mcq_refdb_lineages(rdb, lin.data(), rank.data())) { std::fprintf(stderr, "ABORT: %s\n", mcq_host_last_error()); return nullptr; }
+    if (mcq_taxonomy_create(lin.data(), rank.data(), info.n_taxa, device, &tx)) { std::fprintf(stderr, "ABORT: %s\n", mcq_last_error()); return nullptr; }
+    return tx;
+}
+static mcq_classify_opts classify_opts(const Options& p, uint32_t hitmin) {
+    mcq_classify_opts co; co.hits_min = hitmin; co.hits_diff_fraction = p.hitdiff; co.highest_rank = p.highest; co.flags = 0;
+    return co;
+}
+
+// the abundance tables (src/classification.cpp:744-757) from the device's counts ([n_taxa + 1], the last slot the unclassified
+// queries), after checking them against the host classification's statistics.  They go to the -abundances FILE if one was
+// named, else to `os` (the -out file or stdout): src/mode_query.cpp:59-117.  false = mismatch or write error (reported).
+static bool write_abundances(std::ostream& os, mcq_refdb* rdb, const Options& p, const std::vector<uint64_t>& counts, const uint64_t* assigned) {
+    mcq_refdb_info info; mcq_refdb_get_info(rdb, &info);
+    uint64_t classified = 0;
+    for (uint32_t t = 0; t < info.n_taxa; ++t) classified += counts[t];
+    if (classified != assigned[MCQ_RANK_ROOT] || counts[info.n_taxa] != assigned[MCQ_RANK_NONE]) {
+        std::fprintf(stderr, "ABORT: the device classified %llu queries (%llu not), the host %llu (%llu not)\n", (unsigned long long)classified,
+                     (unsigned long long)counts[info.n_taxa], (unsigned long long)assigned[MCQ_RANK_ROOT], (unsigned long long)assigned[MCQ_RANK_NONE]);
+        return false;
+    }
+    const uint64_t total = assigned[MCQ_RANK_ROOT] + assigned[MCQ_RANK_NONE];      // statistics.total()
+    std::ofstream fab;
+    if (!p.abundance_file.empty()) {
+        fab.open(p.abundance_file);
+        if (!fab.good()) { std::fprintf(stderr, "ABORT: Could not write to file %s\n", p.abundance_file.c_str()); return false; }
+        std::cout << "Per-Taxon mappings will be written to file: " << p.abundance_file << std::endl;
+    }
+    std::ostream& ao = p.abundance_file.empty() ? os : fab;
+    auto table = [&](uint32_t rank) -> bool {           // rank MCQ_RANK_NONE: the plain table, else the estimate to it
+        const int64_t n = mcq_refdb_abundance_text(rdb, counts.data(), total, rank, nullptr, 0);
+        if (n < 0) { std::fprintf(stderr, "ABORT: %s\n", mcq_host_last_error()); return false; }
+        std::string text((size_t)n + 1, '\0');
+        mcq_refdb_abundance_text(rdb, counts.data(), total, rank, &text[0], text.size());
+        text.resize((size_t)n);
+        ao << text;
+        return true;
+    };
+    if (p.abundances && !table(MCQ_RANK_NONE)) return false;
+    if (p.abundance_rank != MCQ_RANK_NONE && !table(p.abundance_rank)) return false;
+    return ao.good();
 }
 
 // The reference's shard files -> the queryable handle of shard `shard_id` of `n_shards` (include/mcq_open.hpp: the host-side union

@@ -398,6 +398,93 @@ extern "C" uint32_t mcq_refdb_classify(const mcq_refdb* db, const uint32_t* c, u
     return db->taxa[lca].rank <= highest_rank ? lca : MCQ_NO_TAXON;
 }
 
+extern "C" int mcq_refdb_lineages(const mcq_refdb* db, uint32_t* lineage, uint8_t* rank) {
+    if (!db || !lineage || !rank) return fail("bad argument");
+    std::memcpy(lineage, db->lineage.data(), db->lineage.size() * 4);
+    for (size_t i = 0; i < db->taxa.size(); ++i) rank[i] = db->taxa[i].rank;
+    return 0;
+}
+
+// ---- abundance tables: taxon_count_map (src/classification.h:107-115), estimate_abundance (src/classification.cpp:362-428),
+// show_abundances / show_abundance_estimates / show_abundance_table (src/printing.cpp:474-517).  The arithmetic is the
+// reference's, type for type and in its order: float counts, u64 (query_id) weights that float sums are truncated into, the
+// share of a child computed as parent * (child + weight) / sum in float.  Built without FP contraction (build.py).
+namespace {
+struct ByRank {                                  // sortTaxaByRank: rank descending (root first), then id ascending
+    const mcq_refdb* db;
+    bool operator()(uint32_t a, uint32_t b) const {
+        const Taxon& x = db->taxa[a]; const Taxon& y = db->taxa[b];
+        if (x.rank != y.rank) return x.rank > y.rank;
+        return x.id < y.id;
+    }
+};
+using CountMap = std::map<uint32_t, float, ByRank>;
+
+void estimate_abundance(const mcq_refdb* db, CountMap& counts, uint32_t rank) {
+    const uint32_t* lin = db->lineage.data();
+    if (rank != MCQ_RANK_SEQUENCE) {
+        // prune below the rank: from lower_bound(taxon{id 0, rank - 1}) on, into the first ranked ancestor at or above it
+        auto begin = counts.begin();
+        while (begin != counts.end()) {
+            const Taxon& t = db->taxa[begin->first];
+            if (!(t.rank > rank - 1 || (t.rank == rank - 1 && t.id < 0))) break;
+            ++begin;
+        }
+        for (auto it = begin; it != counts.end();) {
+            uint32_t anc = MCQ_NO_TAXON;
+            for (uint32_t r = rank; anc == MCQ_NO_TAXON && r < (uint32_t)kNumRanks; ++r) anc = lin[(size_t)it->first * kNumRanks + r];
+            if (anc != MCQ_NO_TAXON) {
+                counts[anc] += it->second;
+                it = counts.erase(it);
+            } else ++it;
+        }
+    }
+    std::unordered_map<uint32_t, std::vector<uint32_t>> children;
+    std::unordered_map<uint32_t, uint64_t> weight;   // query_id
+    for (const auto& c : counts) weight[c.first] = 0;
+    for (auto it = counts.rbegin(); it != counts.rend(); ++it) {          // leaves to root
+        for (uint32_t r = (uint8_t)(db->taxa[it->first].rank + 1); r < (uint32_t)kNumRanks; ++r) {
+            const uint32_t parent = lin[(size_t)it->first * kNumRanks + r];
+            if (parent != MCQ_NO_TAXON && weight.count(parent)) {
+                weight[parent] += weight[it->first] + it->second;
+                children[parent].push_back(it->first);
+                break;
+            }
+        }
+    }
+    for (auto it = counts.begin(); it != counts.end();) {                 // root to leaves: distribute, erase the parents
+        auto ch = children.find(it->first);
+        if (ch == children.end()) { ++it; continue; }
+        const uint64_t sum = weight[it->first];
+        for (uint32_t c : ch->second) counts[c] += it->second * (counts[c] + weight[c]) / sum;
+        it = counts.erase(it);
+    }
+}
+}  // namespace
+
+extern "C" int64_t mcq_refdb_abundance_text(const mcq_refdb* db, const uint64_t* counts, uint64_t total, uint32_t est_rank,
+                                            char* buf, size_t cap) {
+    if (!db || !counts || (cap && !buf) || est_rank == MCQ_RANK_ROOT || est_rank > MCQ_RANK_NONE) return fail("bad argument");
+    CountMap m(ByRank{db});
+    for (uint32_t i = 0; i < db->taxa.size(); ++i)
+        if (counts[i]) m.emplace(i, (float)counts[i]);       // exact u64 counts, one conversion (counts past 2^24)
+    std::string s;
+    if (est_rank == MCQ_RANK_NONE) s = "# query summary: number of queries mapped per taxon\n";
+    else {
+        estimate_abundance(db, m, est_rank);
+        s = std::string("# estimated abundance (number of queries) per ") + mcq_rank_name(est_rank) + "\n";
+    }
+    char num[64];
+    for (const auto& c : m) {                    // default ostream formatting of a float and of a double: %g
+        const Taxon& t = db->taxa[c.first];
+        s += mcq_rank_name(t.rank); s += ':'; s += t.name; s += "\t|\t";
+        std::snprintf(num, sizeof num, "%g", (double)c.second); s += num; s += "\t|\t";
+        std::snprintf(num, sizeof num, "%g", (double)c.second / double(total) * 100); s += num; s += "%\n";
+    }
+    if (cap) { const size_t n = std::min(cap - 1, s.size()); std::memcpy(buf, s.data(), n); buf[n] = 0; }
+    return (int64_t)s.size();
+}
+
 extern "C" uint32_t mcq_default_hits_min(uint32_t s) { return s >= 6 ? (uint32_t)(s / 3.0) : (s >= 4 ? 2u : 1u); }
 
 static const char* kRankNames[] = {"sequence", "form", "variety", "subspecies", "species", "subgenus", "genus", "subtribe",

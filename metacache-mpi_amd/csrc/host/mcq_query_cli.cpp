@@ -38,6 +38,12 @@ int main(int argc, char** argv) {
     }
     mcq_ws* ws = nullptr;
     if (mcq_ws_create(edb, max_q, max_b + 1, 0, &ws)) { std::fprintf(stderr, "ABORT: %s\n", mcq_last_error()); return 1; }
+    mcq_taxonomy* tx = nullptr;                                 // -abundances / -abundance-per: every batch is also classified on the GPU
+    if (p.tax_counts()) {
+        const mcq_classify_opts co = classify_opts(p, hitmin);
+        if (!(tx = make_taxonomy(rdb, 0))) return 1;
+        if (mcq_ws_set_classify(ws, tx, &co)) { std::fprintf(stderr, "ABORT: %s\n", mcq_last_error()); return 1; }
+    }
     mcq_query_opts qo; qo.max_cand = p.maxcand; qo.emulate_ranks = p.P; qo.insert_size_max = p.insertsize;
     qo.flags = p.quirks ? MCQ_QUIRK_SEQ_DROP : 0;
     constexpr int NS = 3;
@@ -73,7 +79,13 @@ int main(int argc, char** argv) {
     }
     if (nb >= 2 && !finish(nb - 2)) return 1;
     if (nb >= 1 && !finish(nb - 1)) return 1;
+    if (tx) {
+        mcq_refdb_info info; mcq_refdb_get_info(rdb, &info);
+        std::vector<uint64_t> counts((size_t)info.n_taxa + 1);
+        if (mcq_ws_taxon_counts(ws, counts.data(), 0)) { std::fprintf(stderr, "ABORT: %s\n", mcq_last_error()); return 1; }
+        if (!write_abundances(os, rdb, p, counts, assigned)) return 1;
+    }
     write_summary(os, o, p, assigned, std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_start).count());
-    mcq_ws_destroy(ws); mcq_db_destroy(edb); mcq_refdb_close(rdb);
+    mcq_ws_destroy(ws); mcq_taxonomy_destroy(tx); mcq_db_destroy(edb); mcq_refdb_close(rdb);
     return 0;
 }

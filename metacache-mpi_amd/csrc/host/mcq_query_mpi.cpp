@@ -101,6 +101,15 @@ int main(int argc, char** argv) {
         HIP_OR_DIE(hipEventCreateWithFlags(&ev_out[s], hipEventDisableTiming));
     }
 
+    // -abundances / -abundance-per: every batch's device results are classified on the GPU into per-taxon counts (reduced to rank 0)
+    mcq_taxonomy* tx = nullptr; uint64_t* d_counts = nullptr; uint32_t n_taxa = 0;
+    const mcq_classify_opts co = classify_opts(p, hitmin);
+    if (p.tax_counts()) {
+        mcq_refdb_info info; mcq_refdb_get_info(rdb, &info); n_taxa = info.n_taxa;
+        if (!(tx = make_taxonomy(rdb, device))) MPI_Abort(MPI_COMM_WORLD, 1);
+        HIP_OR_DIE(hipMalloc(&d_counts, ((size_t)n_taxa + 1) * 8));
+    }
+
     MPI_Barrier(MPI_COMM_WORLD);                                            // src/mode_query.cpp:129
     const auto t_start = std::chrono::steady_clock::now();
     // every rank reads the files and keeps its contiguous slice of the queries
@@ -157,6 +166,7 @@ int main(int argc, char** argv) {
     for (int attempt = 0; attempt < 2; ++attempt) {
         const uint32_t flags = attempt ? MCQ_SHARD_EXACT : 0;
         lines.str(""); std::memset(assigned, 0, sizeof(assigned));
+        if (d_counts) HIP_OR_DIE(hipMemsetAsync(d_counts, 0, ((size_t)n_taxa + 1) * 8, st));
         if (nb) stage(0);
         for (size_t j = 0; j < nb; ++j) {
             const int s = (int)(j % NS);
@@ -165,6 +175,7 @@ int main(int argc, char** argv) {
             mcq_result res; res.cands = d_cands[s]; res.n_cand = d_ncand[s]; res.flags = MCQ_DEVICE_PTRS;
             MCQ_OR_DIE(mcq_shard_query(ctx, &in[j], &qo, &res, st, flags, j + 1 < nb ? &in[j + 1] : nullptr));
             const size_t nqj = hi(j) - lo(j);
+            if (tx && nqj) MCQ_OR_DIE(mcq_classify(tx, &res, nqj, p.maxcand, &co, nullptr, d_counts, st));
             if (nqj) {
                 HIP_OR_DIE(hipMemcpyAsync(h_cands[s], d_cands[s], nqj * p.maxcand * sizeof(mcq_cand), hipMemcpyDeviceToHost, st));
                 HIP_OR_DIE(hipMemcpyAsync(h_ncand[s], d_ncand[s], nqj * 4, hipMemcpyDeviceToHost, st));
@@ -193,12 +204,21 @@ int main(int argc, char** argv) {
     unsigned long long a_loc[MCQ_RANK_NONE + 1], a_all[MCQ_RANK_NONE + 1];
     for (int i = 0; i <= (int)MCQ_RANK_NONE; ++i) a_loc[i] = assigned[i];
     MPI_Reduce(a_loc, a_all, MCQ_RANK_NONE + 1, MPI_UNSIGNED_LONG_LONG, MPI_SUM, 0, MPI_COMM_WORLD);
+    std::vector<uint64_t> counts, counts_all;
+    if (tx) {
+        counts.resize((size_t)n_taxa + 1); counts_all.resize((size_t)n_taxa + 1);
+        HIP_OR_DIE(hipStreamSynchronize(st));
+        HIP_OR_DIE(hipMemcpy(counts.data(), d_counts, counts.size() * 8, hipMemcpyDeviceToHost));
+        static_assert(sizeof(unsigned long long) == sizeof(uint64_t), "u64 counts travel as MPI_UNSIGNED_LONG_LONG");
+        MPI_Reduce(counts.data(), counts_all.data(), (int)counts.size(), MPI_UNSIGNED_LONG_LONG, MPI_SUM, 0, MPI_COMM_WORLD);
+    }
     if (rank == 0) {
         std::ofstream fout; if (!p.outfile.empty()) fout.open(p.outfile);
         std::ostream& os = p.outfile.empty() ? std::cout : fout;
         write_head(os, o, p, hitmin);
         os << all;
         for (int i = 0; i <= (int)MCQ_RANK_NONE; ++i) assigned[i] = a_all[i];
+        if (tx && !write_abundances(os, rdb, p, counts_all, assigned)) MPI_Abort(MPI_COMM_WORLD, 1);
         write_summary(os, o, p, assigned, std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_start).count());
     }
     for (int s = 0; s < NS; ++s) {
@@ -206,6 +226,8 @@ int main(int argc, char** argv) {
         (void)hipHostFree(h_cands[s]); (void)hipHostFree(h_ncand[s]); (void)hipEventDestroy(ev_out[s]);
     }
     (void)hipStreamDestroy(st);
+    if (d_counts) (void)hipFree(d_counts);
+    mcq_taxonomy_destroy(tx);
     mcq_shard_destroy(ctx); mcq_db_destroy(shard); mcq_refdb_close(rdb);
     MPI_Finalize();
     return 0;

@@ -27,6 +27,7 @@
 
 #include "../../include/mcq.h"
 #include "mcq_device.hpp"
+#include "mcq_classify.hpp"
 
 using namespace mcq;
 
@@ -41,6 +42,7 @@ static int fail(int code, const std::string& msg) { g_err = msg; return code; }
     return fail(MCQ_E_HIP, std::string(#expr) + ": " + hipGetErrorString(e_)); } } while (0)
 
 extern "C" const char* mcq_last_error(void) { return g_err.c_str(); }
+int mcq::set_error(int code, const char* msg) { g_err = msg; return code; }
 extern "C" const char* mcq_version(void) { return "mcq 0.1 (gfx950)"; }
 
 // ------------------------------------------------------------------ persistent grids
@@ -119,6 +121,13 @@ struct mcq_ws {
     std::vector<TimedLaunch>* ev_used;
     std::vector<TimedLaunch>* ev_free;
     double timed_ms[MCQ_N_TIMED]; u64 timed_launches;
+    // classification of every batch while a taxonomy is attached (mcq_ws_set_classify): counts [cls_n] on the device,
+    // cls_ev recorded behind the last batch that added into them
+    const mcq_taxonomy* cls_tx;
+    mcq_classify_opts cls_opt;
+    unsigned long long* cls_counts;
+    u32 cls_n;
+    hipEvent_t cls_ev;
 };
 
 // ------------------------------------------------------------------ kernels: table build
@@ -2755,6 +2764,8 @@ extern "C" int mcq_ws_destroy(mcq_ws* ws) {
         }
         (void)hipStreamDestroy(ws->pipe.s_in); (void)hipStreamDestroy(ws->pipe.s_k); (void)hipStreamDestroy(ws->pipe.s_out);
     }
+    if (ws->cls_counts) (void)hipFree(ws->cls_counts);
+    if (ws->cls_ev) (void)hipEventDestroy(ws->cls_ev);
     for (auto* v : {ws->ev_used, ws->ev_free}) {
         if (!v) continue;
         for (auto& t : *v) for (auto e : t.ev) (void)hipEventDestroy(e);
@@ -2967,6 +2978,49 @@ static int launch_query(const mcq_db* db, mcq_ws* ws, const BatchDev& b, const O
     return MCQ_OK;
 }
 
+// ------------------------------------------------------------------ classification of the batch (mcq_ws_set_classify)
+// behind the kernels of a batch on its own stream, before its copy-out: the device candidate lists -> the workspace's counts
+static int classify_batch(mcq_ws* ws, const OutDev& o, u64 nq, u32 max_cand, hipStream_t st) {
+    if (!ws->cls_tx || !nq) return MCQ_OK;
+    mcq_result r; r.cands = (mcq_cand*)o.cands; r.n_cand = o.ncand; r.flags = MCQ_DEVICE_PTRS;
+    const int rc = mcq_classify(ws->cls_tx, &r, nq, max_cand, &ws->cls_opt, nullptr, (uint64_t*)ws->cls_counts, st);
+    if (rc) return rc;
+    HIPCHK(hipEventRecord(ws->cls_ev, st));
+    return MCQ_OK;
+}
+
+extern "C" int mcq_ws_set_classify(mcq_ws* ws, const mcq_taxonomy* tx, const mcq_classify_opts* opts) {
+    if (!ws) return fail(MCQ_E_ARG, "null argument");
+    if (!tx) { ws->cls_tx = nullptr; return MCQ_OK; }
+    int rc = mcq::check_classify_opts(opts);
+    if (rc) return rc;
+    if (tx->device != ws->device) return fail(MCQ_E_ARG, "the taxonomy lives on another device than the workspace");
+    HIPCHK(hipSetDevice(ws->device));
+    if (!ws->cls_ev) HIPCHK(hipEventCreateWithFlags(&ws->cls_ev, hipEventDisableTiming));
+    if (!ws->cls_counts || ws->cls_n != tx->n_taxa + 1) {
+        if (ws->cls_counts) { HIPCHK(hipEventSynchronize(ws->cls_ev)); (void)hipFree(ws->cls_counts); ws->cls_counts = nullptr; }
+        HIPCHK(hipMalloc(&ws->cls_counts, ((u64)tx->n_taxa + 1) * 8));
+        HIPCHK(hipMemsetAsync(ws->cls_counts, 0, ((u64)tx->n_taxa + 1) * 8, nullptr));
+        HIPCHK(hipStreamSynchronize(nullptr));
+        ws->cls_n = tx->n_taxa + 1;
+    }
+    ws->cls_tx = tx; ws->cls_opt = *opts;
+    return MCQ_OK;
+}
+
+extern "C" int mcq_ws_taxon_counts(mcq_ws* ws, uint64_t* host_out, int reset) {
+    if (!ws || !host_out) return fail(MCQ_E_ARG, "null argument");
+    if (!ws->cls_counts) return fail(MCQ_E_ARG, "no taxonomy was ever attached to this workspace (mcq_ws_set_classify)");
+    HIPCHK(hipSetDevice(ws->device));
+    HIPCHK(hipEventSynchronize(ws->cls_ev));
+    HIPCHK(hipMemcpy(host_out, ws->cls_counts, (u64)ws->cls_n * 8, hipMemcpyDeviceToHost));
+    if (reset) {
+        HIPCHK(hipMemsetAsync(ws->cls_counts, 0, (u64)ws->cls_n * 8, nullptr));
+        HIPCHK(hipStreamSynchronize(nullptr));
+    }
+    return MCQ_OK;
+}
+
 extern "C" int mcq_query(const mcq_db* db, mcq_ws* ws, const mcq_batch* in, const mcq_query_opts* opt,
                          mcq_result* out, void* stream) {
     if (!db || !ws || !in || !opt || !out) return fail(MCQ_E_ARG, "null argument");
@@ -3002,6 +3056,8 @@ extern "C" int mcq_query(const mcq_db* db, mcq_ws* ws, const mcq_batch* in, cons
     else { o.cands = (u32*)out->cands; o.ncand = out->n_cand; }
     DebugDev dbg; memset(&dbg, 0, sizeof(dbg));
     rc = launch_query(db, ws, b, od, o, st, force_bits(opt->flags), dbg);
+    if (rc) return rc;
+    rc = classify_batch(ws, o, nq, od.max_cand, st);
     if (rc) return rc;
     if (!dev_out && nq) {
         HIPCHK(hipMemcpyAsync(out->cands, ws->d_cands, nq * od.max_cand * 16, hipMemcpyDeviceToHost, st));
@@ -3068,6 +3124,7 @@ extern "C" int mcq_query_pipelined(const mcq_db* db, mcq_ws* ws, const mcq_batch
     OutDev o; o.cands = p.d_cands[k]; o.ncand = p.d_ncand[k];
     DebugDev dbg; memset(&dbg, 0, sizeof(dbg));
     rc = launch_query(db, ws, b, od, o, p.s_k, force_bits(opt->flags), dbg); if (rc) return rc;
+    rc = classify_batch(ws, o, nq, od.max_cand, p.s_k); if (rc) return rc;
     HIPCHK(hipEventRecord(p.ev_k[k], p.s_k));
     // out
     HIPCHK(hipStreamWaitEvent(p.s_out, p.ev_k[k], 0));

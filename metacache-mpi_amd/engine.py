@@ -73,6 +73,10 @@ class Result(C.Structure):
     _fields_ = [("cands", C.c_void_p), ("n_cand", C.c_void_p), ("flags", C.c_uint32)]
 
 
+class ClassifyOpts(C.Structure):
+    _fields_ = [("hits_min", C.c_uint32), ("hits_diff_fraction", C.c_float), ("highest_rank", C.c_uint32), ("flags", C.c_uint32)]
+
+
 class Stats(C.Structure):
     _fields_ = [("n_queries", C.c_uint64), ("n_features", C.c_uint64), ("n_hit_features", C.c_uint64),
                 ("n_locations", C.c_uint64), ("n_cands", C.c_uint64), ("n_overflow", C.c_uint64), ("n_two_class", C.c_uint64), ("n_two_class_retry", C.c_uint64), ("n_narrow_queued", C.c_uint64)]
@@ -156,6 +160,12 @@ def lib():
                                  C.POINTER(QueryOpts), C.POINTER(Result), C.c_void_p]
         L.mcq_packed_bytes.restype = C.c_uint64; L.mcq_packed_bytes.argtypes = [C.c_uint64]
         L.mcq_pack_bases.argtypes = [C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint32, C.c_void_p]
+        L.mcq_taxonomy_create.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_int32, C.POINTER(C.c_void_p)]
+        L.mcq_taxonomy_destroy.argtypes = [C.c_void_p]
+        L.mcq_classify.argtypes = [C.c_void_p, C.POINTER(Result), C.c_uint64, C.c_uint32, C.POINTER(ClassifyOpts), C.c_void_p,
+                                   C.c_void_p, C.c_void_p]
+        L.mcq_ws_set_classify.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(ClassifyOpts)]
+        L.mcq_ws_taxon_counts.argtypes = [C.c_void_p, C.c_void_p, C.c_int]
         L.mcq_shard_create.argtypes = [C.c_void_p, C.POINTER(ShardCfg), C.POINTER(C.c_void_p)]
         L.mcq_shard_destroy.argtypes = [C.c_void_p]
         L.mcq_shard_unique_id.argtypes = [C.c_void_p]
@@ -347,6 +357,22 @@ class Workspace:
     def wait(self, ticket):
         _chk(lib().mcq_ws_wait(self.h, ticket))
 
+    # ---- classification of every batch on the device (mcq_ws_set_classify / mcq_ws_taxon_counts)
+    def set_classify(self, taxonomy, hits_min=1, hits_diff_fraction=1.0, highest_rank=19):
+        """attaches a Taxonomy (None detaches): every query call then adds its classified queries into the counts"""
+        if taxonomy is None:
+            _chk(lib().mcq_ws_set_classify(self.h, None, None)); self._tx = None
+            return
+        o = ClassifyOpts(hits_min, hits_diff_fraction, highest_rank, 0)
+        _chk(lib().mcq_ws_set_classify(self.h, taxonomy.h, C.byref(o)))
+        self._tx = taxonomy; self._cls_n = taxonomy.n_taxa + 1
+
+    def taxon_counts(self, reset=False):
+        """u64 [n_taxa + 1]: classified queries per taxon index, the last slot the unclassified ones"""
+        out = np.zeros(getattr(self, "_cls_n", 0), np.uint64)
+        _chk(lib().mcq_ws_taxon_counts(self.h, _np_ptr(out), 1 if reset else 0))
+        return out
+
     def timing(self, enable):
         _chk(lib().mcq_ws_timing(self.h, 1 if enable else 0))
 
@@ -387,6 +413,37 @@ class Workspace:
         m = np.zeros(max(1, int(moff[nq])), np.uint64)
         _chk(lib().mcq_debug_matches(self.db.h, self.h, C.byref(b), path_flags, _np_ptr(moff), _np_ptr(m), len(m)))
         return moff, m[:int(moff[nq])]
+
+
+class Taxonomy:
+    """The ranked-lineage table classify needs, on the device (mcq_taxonomy_create): lineage u32 [n_taxa, 21], rank u8
+    [n_taxa], as host.RefDb.lineages() returns them."""
+
+    def __init__(self, lineage, rank, device=0):
+        self._lin = np.ascontiguousarray(lineage, np.uint32)
+        self._rank = np.ascontiguousarray(rank, np.uint8)
+        self.n_taxa = len(self._rank)
+        assert self._lin.size == self.n_taxa * 21
+        h = C.c_void_p()
+        _chk(lib().mcq_taxonomy_create(_np_ptr(self._lin), _np_ptr(self._rank), self.n_taxa, device, C.byref(h)))
+        self.h = h
+
+    def classify(self, cands_ptr, ncand_ptr, n_queries, max_cand, hits_min=1, hits_diff_fraction=1.0, highest_rank=19,
+                 best_ptr=None, counts_ptr=None, stream=None):
+        """mcq_classify on device buffers (enqueue only): best u32 [n_queries], counts u64 [n_taxa + 1] (added to)"""
+        r = Result(cands_ptr, ncand_ptr, MCQ_DEVICE_PTRS)
+        o = ClassifyOpts(hits_min, hits_diff_fraction, highest_rank, 0)
+        _chk(lib().mcq_classify(self.h, C.byref(r), n_queries, max_cand, C.byref(o), best_ptr, counts_ptr, stream))
+
+    def close(self):
+        if getattr(self, "h", None):
+            lib().mcq_taxonomy_destroy(self.h); self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:       # interpreter shutdown
+            pass
 
 
 class Shard:

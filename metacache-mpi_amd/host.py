@@ -7,6 +7,7 @@ import numpy as np
 from .build import host_lib_path
 
 NO_TAXON = 0xFFFFFFFF
+RANK_SEQUENCE, RANK_SPECIES, RANK_ROOT, RANK_NONE = 0, 4, 20, 21
 
 
 class Info(C.Structure):
@@ -67,6 +68,9 @@ def lib():
         L.mcq_refdb_ancestor.restype = C.c_uint32; L.mcq_refdb_ancestor.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32]
         L.mcq_refdb_classify.restype = C.c_uint32
         L.mcq_refdb_classify.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_float, C.c_uint32]
+        L.mcq_refdb_lineages.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
+        L.mcq_refdb_abundance_text.restype = C.c_int64
+        L.mcq_refdb_abundance_text.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint32, C.c_char_p, C.c_size_t]
         L.mcq_default_hits_min.restype = C.c_uint32; L.mcq_default_hits_min.argtypes = [C.c_uint32]
         L.mcq_rank_from_name.restype = C.c_uint32; L.mcq_rank_from_name.argtypes = [C.c_char_p]
         L.mcq_rank_name.restype = C.c_char_p; L.mcq_rank_name.argtypes = [C.c_uint32]
@@ -157,6 +161,36 @@ class RefDb:
         c = np.ascontiguousarray(cands, np.uint32).reshape(-1, 4)
         return int(lib().mcq_refdb_classify(self.h, c.ctypes.data_as(C.c_void_p), len(c), hits_min,
                                             C.c_float(hits_diff_fraction), highest_rank))
+
+    def taxon_rank(self, key):
+        return int(lib().mcq_refdb_taxon_rank(self.h, int(key)))
+
+    def taxon_name(self, key):
+        return lib().mcq_refdb_taxon_name(self.h, int(key)).decode("latin-1")
+
+    def ancestor(self, key, rank):
+        return int(lib().mcq_refdb_ancestor(self.h, int(key), int(rank)))
+
+    def lineages(self):
+        """(lineage u32 [n_taxa, 21], rank u8 [n_taxa]): the table mcq_taxonomy_create takes"""
+        n = self.info.n_taxa
+        lin = np.zeros((n, 21), np.uint32); rank = np.zeros(n, np.uint8)
+        if lib().mcq_refdb_lineages(self.h, lin.ctypes.data_as(C.c_void_p), rank.ctypes.data_as(C.c_void_p)) != 0:
+            raise RuntimeError(lib().mcq_host_last_error().decode())
+        return lin, rank
+
+    def abundance_text(self, counts, total, est_rank=RANK_NONE):
+        """counts: u64 [n_taxa] classified queries per taxon index; est_rank RANK_NONE = the plain table, else the
+        estimate to that rank (mcq_refdb_abundance_text)"""
+        c = np.ascontiguousarray(counts, np.uint64)
+        if len(c) < self.info.n_taxa:
+            raise ValueError("counts needs n_taxa entries")
+        n = lib().mcq_refdb_abundance_text(self.h, c.ctypes.data_as(C.c_void_p), int(total), int(est_rank), None, 0)
+        if n < 0:
+            raise RuntimeError(lib().mcq_host_last_error().decode())
+        buf = C.create_string_buffer(n + 1)
+        lib().mcq_refdb_abundance_text(self.h, c.ctypes.data_as(C.c_void_p), int(total), int(est_rank), buf, n + 1)
+        return buf.raw[:n].decode("latin-1")
 
 
 def rank_from_name(name):
