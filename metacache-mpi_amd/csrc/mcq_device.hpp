@@ -180,7 +180,7 @@ struct CountersDev {         // one block of u64/u32 words, zeroed per call
     unsigned long long n_short;       // direct mode: queued queries whose list the first wave stage would have kept (<= 512 locations)
     unsigned long long n_geom;        // queries with more than 128 features: the workgroup kernels' by their geometry alone
     u32 blk_cursor[4];                // the workgroup kernels' shared cursors over the front queue ([0,1] plain kernel: long queries first, then the rest; [2,3] two-class kernel)
-    u32 w_cursor[2];                  // (-DMCQ_WAVE_DYNQ) the same for the second / third wave stage
+    u32 w_cursor[2];                  // unused (reserved: keeps the offsets of the fields behind it)
     unsigned long long n_long;        // queries of MCQ_BLOCK_LONG_FIRST bases and more (the workgroup kernels take those first: a pass of its own)
     unsigned long long pad_[17];      // (diagnostic builds, -DMCQ_PHASE_CLOCK: phase clocks of the workgroup kernel)
     unsigned long long* probe_buf;
@@ -335,10 +335,6 @@ __device__ __forceinline__ u32 range_width(u64 qlen, u64 insert_size_max, u32 tg
 }
 
 // ------------------------------------------------------------------ wave primitives
-__device__ __forceinline__ u32 lane_id() {
-    return __builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, 0u));
-}
-
 // number of set bits of a wave-wide mask below this lane (v_mbcnt_lo/hi: the lane id itself is mbcnt(~0))
 __device__ __forceinline__ u32 lane_rank(u64 mask) {
     return __builtin_amdgcn_mbcnt_hi((u32)(mask >> 32), __builtin_amdgcn_mbcnt_lo((u32)mask, 0u));
@@ -424,6 +420,8 @@ __device__ __forceinline__ u64 cmpex(u64 v, u64 o, u64 keepmin) {
 //   MCQ_CX2: the lanes that keep the minimum are a union of 4-lane banks / 16-lane rows, so the two
 //            instructions write disjoint lane sets of the result directly (DPP bank_mask / row_mask).
 //   MCQ_CX3: any other lane pattern (period 2 or 4): min and max everywhere, v_cndmask picks per lane.
+//            (The lane mask goes into vcc by two s_mov; as an SGPR-pair operand instead: -382 static SALU, +329 s_nop,
+//            +129 spill reloads, no gain.)
 // Network: "flip" form of the bitonic sorter (first stage of a K-block merge pairs i with i ^ (K-1),
 // then half-cleaners i ^ J), every comparator ascending, up to K = 32; for the last level the keys of
 // rows 2,3 are kept complemented during levels 2..32 so that lanes 32..63 come out descending and the
@@ -434,19 +432,11 @@ __device__ __forceinline__ u64 cmpex(u64 v, u64 o, u64 keepmin) {
 #define MCQ_CX2(v, DPP_MIN, DPP_MAX) do { u32 r_; \
     asm("s_nop 1\n\tv_min_u32_dpp %0, %1, %1 " DPP_MIN "\n\tv_max_u32_dpp %0, %1, %1 " DPP_MAX \
         : "=&v"(r_) : "v"(v)); v = r_; } while (0)
-#ifdef MCQ_CX3_SGPR_MASK        // tuning knob (A/B; r03: -382 static SALU, +329 s_nop, +129 spill reloads: no gain): the lane mask as an SGPR-pair operand instead of two s_mov into vcc
-#define MCQ_CX3(v, DPP, MASK32) do { u32 lo_, hi_; const u64 m_ = ((u64)(MASK32##u) << 32) | (MASK32##u); \
-    asm("s_nop 1\n\t" \
-        "v_min_u32_dpp %0, %2, %2 " DPP MCQ_DPP_ALL "\n\tv_max_u32_dpp %1, %2, %2 " DPP MCQ_DPP_ALL "\n\t" \
-        "v_cndmask_b32_e64 %0, %1, %0, %3" \
-        : "=&v"(lo_), "=&v"(hi_) : "v"(v), "s"(m_)); v = lo_; } while (0)
-#else
 #define MCQ_CX3(v, DPP, MASK32) do { u32 lo_, hi_; \
     asm("s_mov_b32 vcc_lo, " #MASK32 "\n\ts_mov_b32 vcc_hi, " #MASK32 "\n\t"   /* the two wait states before the DPP reads */ \
         "v_min_u32_dpp %0, %2, %2 " DPP MCQ_DPP_ALL "\n\tv_max_u32_dpp %1, %2, %2 " DPP MCQ_DPP_ALL "\n\t" \
         "v_cndmask_b32_e32 %0, %1, %0, vcc" \
         : "=&v"(lo_), "=&v"(hi_) : "v"(v) : "vcc"); v = lo_; } while (0)
-#endif
 
 // half-cleaners at lane distance 8, 4, 2, 1 (ascending everywhere)
 __device__ __forceinline__ u32 cx_j8(u32 v) { MCQ_CX2(v, "row_ror:8 row_mask:0xf bank_mask:0x3", "row_ror:8 row_mask:0xf bank_mask:0xc"); return v; }
@@ -505,11 +495,6 @@ __device__ __forceinline__ u32 wave_sort64(u32 v, u32 lane) {
     v = cx_j32(v); v = cx_j16(v); v = cx_j8(v); v = cx_j4(v); v = cx_j2(v); v = cx_j1(v);
     return v;
 }
-// ascending sort of lanes 0-31 (lanes 32-63 hold padding and sort among themselves)
-__device__ __forceinline__ u32 wave_sort32_low(u32 v, u32 lane) {
-    (void)lane;
-    return wave_sort_blocks32(v);
-}
 
 // ---- the same networks as ONE asm block each (r04) ------------------------------------------------------------------------
 // Stage by stage (above) every compare-exchange is its own asm statement: it opens with the two wait states a DPP read needs
@@ -519,7 +504,7 @@ __device__ __forceinline__ u32 wave_sort32_low(u32 v, u32 lane) {
 // registers sorted side by side (wave_sort64_x2, cx_chain6_x2: stage by stage, a's instructions, then b's) need none at all --
 // each register's DPP read sits two or more instructions behind its own last write -- and share the lane-mask moves.
 // Registers ping-pong (x -> y -> x ...): min and max write disjoint lanes of the destination while both read the source.
-// -DMCQ_SORT_STAGEWISE (A/B knob): the stage-by-stage forms.
+// (The stage-by-stage forms above are what tests/native/sort_networks.hip checks these against.)
 #define MQ_ALL " row_mask:0xf bank_mask:0xf"
 #define MQ_NOP2 "s_nop 1\n\t"
 #define MQ_NOP1 "s_nop 0\n\t"
@@ -574,7 +559,6 @@ __device__ __forceinline__ u32 wave_sort32_low(u32 v, u32 lane) {
     MQ_MOV(ZA, YA) MQ_MOV(ZB, YB) MQ_NOP1 MQ_SWAP16(YA, ZA) MQ_SWAP16(YB, ZB) MQ_J16_TAIL(XA, YA, ZA) MQ_J16_TAIL(XB, YB, ZB) \
     MQ_CX2_2(YA, XA, YB, XB, MQ_J8) MQ_CX2_2(XA, YA, XB, YB, MQ_J4) MQ_CX3_2(MQ_M3, YA, XA, ZA, YB, XB, ZB, MQ_J2) MQ_CX3_2(MQ_M5, XA, YA, ZA, XB, YB, ZB, MQ_J1)
 
-#ifndef MCQ_SORT_STAGEWISE
 // every aligned block of 32 lanes sorted ascending
 __device__ __forceinline__ u32 wave_sort_blocks32_1(u32 v) {
     u32 y, z, w;
@@ -611,13 +595,6 @@ __device__ __forceinline__ void cx_chain6_x2(u32& a, u32& b) {
     asm(MQ_CHAIN6_2("%[xa]", "%[ya]", "%[za]", "%[xb]", "%[yb]", "%[zb]")
         : [xa] "+v"(a), [ya] "=&v"(ya), [za] "=&v"(za), [xb] "+v"(b), [yb] "=&v"(yb), [zb] "=&v"(zb) : : "vcc");
 }
-#else
-__device__ __forceinline__ u32 wave_sort_blocks32_1(u32 v) { return wave_sort_blocks32(v); }
-__device__ __forceinline__ u32 wave_sort64_1(u32 v) { return wave_sort64(v, 0); }
-__device__ __forceinline__ u32 cx_chain6_1(u32 v) { v = cx_j32(v); v = cx_j16(v); v = cx_j8(v); v = cx_j4(v); v = cx_j2(v); return cx_j1(v); }
-__device__ __forceinline__ void wave_sort64_x2(u32& a, u32& b) { a = wave_sort64(a, 0); b = wave_sort64(b, 0); }
-__device__ __forceinline__ void cx_chain6_x2(u32& a, u32& b) { a = cx_chain6_1(a); b = cx_chain6_1(b); }
-#endif
 
 // Sketch of seq[0..n), n <= 128, by one full wave.  Lane l encodes bases 2l and 2l+1;
 // 8 lanes form one 16-base word (2 bits per base, first base in the top bits), 16 lanes
@@ -893,16 +870,7 @@ __device__ __forceinline__ void regsort_stage(KeyT (&r)[E], u32 lane) {
             }
         }
     } else {
-#ifdef MCQ_CMPEX_GENERIC        // tuning knob: masks as SGPR constants chosen by the compiler
-#pragma unroll
-        for (int e = 0; e < E; ++e) {
-            const u64 km = (K >= 64) ? ((((e * 64) & K) == 0) ? keepmin_mask(64, J, true) : keepmin_mask(64, J, false))
-                                     : keepmin_mask(K, J, true);
-            r[e] = cmpex(r[e], xlane<J>(r[e], lane), km);
-        }
-#else
         regsort_xstage<KeyT, E, K, J, 0>(r, lane);
-#endif
     }
 }
 template <class KeyT, int E, int K, int J>
@@ -942,7 +910,6 @@ __device__ __forceinline__ void regsort_levels_u32(u32 (&r)[E], u32 lane) {
 #endif
 template <class KeyT, int E>
 __device__ __forceinline__ void wave_regsort(KeyT (&r)[E], u32 lane) {
-#ifndef MCQ_REGSORT_GENERIC     // tuning knob (A/B)
     if constexpr (sizeof(KeyT) == 4 && E >= MCQ_REGSORT_U32_MIN_E) {
         static_assert(E % 2 == 0, "registers are sorted in pairs");
 #pragma unroll
@@ -953,8 +920,7 @@ __device__ __forceinline__ void wave_regsort(KeyT (&r)[E], u32 lane) {
         }
         regsort_levels_u32<E, 64 * E>(r, lane);
     } else
-#endif
-    regsort_levels<KeyT, E, 64 * E>(r, lane);
+        regsort_levels<KeyT, E, 64 * E>(r, lane);
 }
 
 // ---- workgroup bitonic sort with the wave-local stages in registers --------------------------------
@@ -970,14 +936,12 @@ __device__ __forceinline__ KeyT cx_dir(KeyT v, u32 lane, bool up) {
 template <class KeyT>
 __device__ __forceinline__ void merge128(KeyT& r0, KeyT& r1, u32 lane, bool up) {
     { const KeyT a = r0, b = r1; const bool sw = (a > b) == up; r0 = sw ? b : a; r1 = sw ? a : b; }
-#ifndef MCQ_REGSORT_GENERIC
     if constexpr (sizeof(KeyT) == 4) {          // min/max half-cleaners (ascending; complemented keys for descending)
         u32 a = up ? (u32)r0 : ~(u32)r0, b = up ? (u32)r1 : ~(u32)r1;
         cx_chain6_x2(a, b);
         r0 = (KeyT)(up ? a : ~a); r1 = (KeyT)(up ? b : ~b);
         return;
     }
-#endif
     r0 = cx_dir<KeyT, 32>(r0, lane, up); r1 = cx_dir<KeyT, 32>(r1, lane, up);
     r0 = cx_dir<KeyT, 16>(r0, lane, up); r1 = cx_dir<KeyT, 16>(r1, lane, up);
     r0 = cx_dir<KeyT, 8>(r0, lane, up);  r1 = cx_dir<KeyT, 8>(r1, lane, up);
@@ -1349,11 +1313,6 @@ __device__ __forceinline__ u32 topk_fold_write(const DbDev& db, const OptDev& op
 // word between hits and position (6 bits), M selection rounds per 64 run heads with DPP maxima, no lists, no fold levels
 // -- the same cost for -n 64 as for -n 2.  Not under MCQ_QUIRK_SEQ_DROP on a table with sequence-level taxa (a dropped entry
 // has held a slot of an intermediate list: the lists and the levels are carried out then).
-#ifdef MCQ_LIN_ONLY                     // tuning knob (A/B): the wave kernels without the code of the lists (wrong results where they are needed)
-#define MCQ_OPT_LIN(opt) true
-#else
-#define MCQ_OPT_LIN(opt) ((opt).lin != 0)
-#endif
 template <class HT, int JB>
 __device__ __forceinline__ HT lin_word(HT cv, u32 cr) {
     return ((cv >> JB) << (JB + 6)) | ((HT)(63u - cr) << JB) | (cv & (((HT)1 << JB) - 1));
@@ -1786,12 +1745,12 @@ __device__ __forceinline__ u32 topk_two_class(const DbDev& db, const OptDev& opt
         if (hits && tgt < db.n_targets) tax[c] = db.tgt2tax[tgt];
         rk[c] = (P > 1) ? (p2 ? (tgt & (P - 1)) : (tgt % P)) : 0;
         if (hits && tax[c] != MCQ_EMPTY) w[c] = ((unsigned long long)hits << 32) | (u32)~key;
-        if (MCQ_OPT_LIN(opt)) {                                            // one list: (hits, rank, word) in one 64-bit order
+        if (opt.lin != 0) {                                                // one list: (hits, rank, word) in one 64-bit order
             if (rk[c] >= opt.keep) w[c] = 0;
             if (w[c] != 0) w[c] = ((unsigned long long)((hits << 6) | (63u - rk[c])) << 32) | (u32)~key;
         }
     }
-    if (MCQ_OPT_LIN(opt)) {
+    if (opt.lin != 0) {
         u32 Ltax = MCQ_EMPTY; unsigned long long Lw = 0;
         for (u32 i = 0; i < M; ++i) {
             unsigned long long v = w[0];
@@ -1886,7 +1845,7 @@ __device__ __forceinline__ u32 topk_two_class_lds(const DbDev& db, const OptDev&
         }
     }
     wave_sync();
-    if (MCQ_OPT_LIN(opt)) {
+    if (opt.lin != 0) {
         for (u32 e = lane; e < NE; e += 64) {
             const unsigned long long w = EW[e];
             const u32 r = ER[e];
@@ -2059,7 +2018,7 @@ __device__ __forceinline__ u32 topk_block(const DbDev& db, const OptDev& opt, co
                                           u32 T, u32 numWindows, const LF& lf, u64 q, u32 tid, u32 NTB,
                                           TopkBlockScratch<HT>* scr, u32* bl, Sync sync) {
     if constexpr (FORM == 2) return topk_block_lin<KeyT, HT, JB>(db, opt, out, B, H, T, lf, q, tid, NTB, scr);
-    if constexpr (RTLIN) { if (MCQ_OPT_LIN(opt)) return topk_block_lin_call<KeyT, HT, JB>(db, opt, out, B, H, T, lf, q, tid, NTB, scr); }
+    if constexpr (RTLIN) { if (opt.lin != 0) return topk_block_lin_call<KeyT, HT, JB>(db, opt, out, B, H, T, lf, q, tid, NTB, scr); }
     const u32 M = opt.max_cand, P = opt.P, seg = opt.seg;
     const bool p2 = (P & (P - 1)) == 0;
     constexpr bool big = FORM == 1;

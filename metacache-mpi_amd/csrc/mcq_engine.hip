@@ -321,35 +321,11 @@ template <class KeyT, class LF> __device__ __forceinline__ u64 key_expand(KeyT k
     return ((u64)t << 32) | (u64)(k - tb);
 }
 
-// Gather E*64 list elements into registers: r[e] = element e*64 + lane of the concatenated lists.
-// Which list an element belongs to: every non-empty list marks its first element's slot with (its lane + 1)
-// in `mark` (64 * E words of the wave's LDS), an inclusive prefix maximum over the slots spreads the marks
-// to the right (6 DPP steps per register instead of a 6-step shuffle search per element).
-template <class KeyT, int E>
-__device__ __forceinline__ void gather_regs_marks(const DbDev& db, KeyT (&r)[E], u32 T, u32 pos, u32 len, u64 off, u32 lane, u32* mark) {
-    const KeyT* __restrict__ locs = static_cast<const KeyT*>(db.locs);
-#pragma unroll
-    for (int e = 0; e < E; ++e) mark[e * 64 + lane] = 0;
-    wave_sync();
-    if (len > 0) mark[pos] = lane + 1;
-    wave_sync();
-    u32 carry = 0;
-#pragma unroll
-    for (int e = 0; e < E; ++e) {
-        const u32 t = e * 64 + lane;
-        u32 v = wave_incl_max_dpp(mark[t]);
-        v = v > carry ? v : carry;
-        carry = bcast(v, 63);
-        const u32 j = v - 1;                             // v >= 1: the first list starts at slot 0
-        const u32 pj = __shfl(pos, (int)j, 64);
-        const u32 olo = __shfl((u32)off, (int)j, 64), ohi = __shfl((u32)(off >> 32), (int)j, 64);
-        r[e] = key_pad<KeyT>();
-        if (t < T) r[e] = locs[(((u64)ohi << 32) | olo) + (t - pj)];
-    }
-    wave_sync();                                         // mark[] is the caller's again
-}
-// The same for up to 128 lists, two per lane (list l of the lane's first feature, list 64 + l of its second):
-// the marks run to 128, and the list's start comes out of the first or the second register set.
+// Gather E*64 list elements into registers: r[e] = element e*64 + lane of the concatenated lists, for up to 128 lists, two
+// per lane (list l of the lane's first feature, list 64 + l of its second).  The prefix-maximum form: every non-empty list
+// marks its first element's slot with (its lane + 1, or 65 + lane for the second) in `mark` (64 * E words of the wave's LDS),
+// an inclusive prefix maximum over the slots spreads the marks to the right (6 DPP steps per register instead of a 6-step
+// shuffle search per element), and the list's start comes out of the first or the second register set.
 // E > 32 (the 64-register form of the third wave stage): the marks are bytes, so that 4096 of them fit the 2048 words
 template <int E>
 __device__ __forceinline__ void gather_regs2_marks(const DbDev& db, u32 (&r)[E], u32 T, u32 pos0, u32 len0, u64 off0,
@@ -397,10 +373,6 @@ __device__ __forceinline__ void gather_regs2_marks(const DbDev& db, u32 (&r)[E],
 // v_mbcnt on the row's bits plus the starts of the rows before (a scalar popcount) -- and one ds_read_b64 fetches that list's
 // offset.  ~16 instructions per register row instead of ~40 (12 of them a DPP chain with wait states, three shuffles),
 // and the rows no longer depend on one another.  mark: 64 + 128 words (2E <= 64 bitmap words, then the table, 8-B aligned).
-#ifdef MCQ_GATHER_MARKS          // tuning knob (A/B): the prefix-maximum form
-#define gather_regs gather_regs_marks
-#define gather_regs2 gather_regs2_marks
-#else
 template <class KeyT, int E>
 __device__ __forceinline__ void gather_regs(const DbDev& db, KeyT (&r)[E], u32 T, u32 pos, u32 len, u64 off, u32 lane, u32* mark) {
     static_assert(E <= 32, "the bitmap of one register");
@@ -433,11 +405,9 @@ __device__ __forceinline__ void gather_regs(const DbDev& db, KeyT (&r)[E], u32 T
 template <int E>
 __device__ __forceinline__ void gather_regs2(const DbDev& db, u32 (&r)[E], u32 T, u32 pos0, u32 len0, u64 off0,
                                              u32 pos1, u32 len1, u64 off1, bool two, u32 lane, u32* mark) {
-#ifndef MCQ_GATHER_SB            // tuning knob (A/B): the bitmap form for 32 and 64 registers too, with scheduling barriers every 8 rows
     // (32 / 64 registers per lane: with independent rows the compiler hoists their table reads and loads and spills 100
     // VGPRs in k_query_wave32 -- RefSeq-scale pairs 13.3 -> 13.9 ms; the prefix-maximum form's carry keeps them in order)
     if constexpr (E >= 32) { gather_regs2_marks<E>(db, r, T, pos0, len0, off0, pos1, len1, off1, two, lane, mark); return; }
-#endif
     const u32* __restrict__ locs = static_cast<const u32*>(db.locs);
     u32* bm = mark;
     unsigned long long* fb = reinterpret_cast<unsigned long long*>(mark + 128);
@@ -461,13 +431,9 @@ __device__ __forceinline__ void gather_regs2(const DbDev& db, u32 (&r)[E], u32 T
         before += (u32)__builtin_popcount(lo) + (u32)__builtin_popcount(hi);
         const unsigned long long base = fb[(cnt - 1u) & 127u];
         if (t < T) r[e] = locs[base + t];
-#ifdef MCQ_GATHER_SB
-        if constexpr (E >= 32) { if ((e & 7) == 7) __builtin_amdgcn_sched_barrier(0); }
-#endif
     }
     wave_sync();                                         // mark[] is the caller's again
 }
-#endif
 // ... sort them there and leave the sorted keys in the wave's LDS segment for the sweep.
 template <class KeyT, int E>
 __device__ __forceinline__ void gather_sort_store(const DbDev& db, KeyT* buf, u32* hits, u32 T, u32 pos, u32 len, u64 off, u32 lane, int stop) {
@@ -498,11 +464,6 @@ __device__ __forceinline__ void gather_sort_store(const DbDev& db, KeyT* buf, u3
 #ifndef MCQ_DEDUP_MAX_D
 #define MCQ_DEDUP_MAX_D 256u
 #endif
-#ifdef MCQ_TOPK_DPP        // tuning knob: DPP reductions per rank instead of LDS maxima for all ranks at once
-#define MCQ_TOPK_DEDUP(db, opt, out, sk, h, D, nw, lf, q, lane, t1) topk_fold_write<u32, u32, 9>(db, opt, out, sk, h, D, nw, lf, q, lane)
-#else
-#define MCQ_TOPK_DEDUP(db, opt, out, sk, h, D, nw, lf, q, lane, t1) topk_dedup(db, opt, out, sk, h, D, nw, lf, q, lane, t1)
-#endif
 // top lists of the dedup path: more than 64 distinct keys (two to four rounds of 64 run heads) take all heads at once
 // t1 (D <= 64): the target of sorted key j in lane j, as dedup_finish looked it up
 template <class LF>
@@ -510,11 +471,10 @@ __device__ __forceinline__ u32 topk_dedup(const DbDev& db, const OptDev& opt, co
                                           u32 numWindows, const LF& lf, u64 q, u32 lane, u32 t1) {
     // one selection for all ranks (zero words among the heads do no harm).  (Tried: the taxon keys of the <= 64 sorted words
     // loaded before the sweep and shuffled in here -- one more live register in the 64-VGPR kernel, +1.5 % on configs[1].)
-    if (MCQ_OPT_LIN(opt)) {
+    if (opt.lin != 0) {
         if (D <= 64) return topk_lin_write<u32, 9, LF::lookup>(db, opt, out, sk, H, D, lf, q, lane, t1);
         return topk_lin_write<u32, 9>(db, opt, out, sk, H, D, lf, q, lane);
     }
-#ifndef MCQ_TOPK_DEDUP_CHUNKED                                      // tuning knob (A/B)
     if (D > 64) {
         u32 nheads = 0;
         for (u32 base = 0; base < D; base += 64) {                  // in place: writes trail reads
@@ -527,7 +487,6 @@ __device__ __forceinline__ u32 topk_dedup(const DbDev& db, const OptDev& opt, co
         wave_sync();
         return topk_all_lds<9, 4>(db, opt, out, sk, H, nheads, numWindows, lf, q, lane, H + 256);
     }
-#endif
     return topk_fold_write_lds<9, LF::lookup>(db, opt, out, sk, H, D, numWindows, lf, q, lane, H + 256, t1);
 }
 // -DMCQ_PHASE_CLOCK (diagnostic builds only): lane 0 of every wave of the second wave stage adds the shader clocks between the marks
@@ -657,17 +616,6 @@ __device__ __forceinline__ u32 load_dedup_insert(const u32* __restrict__ src, u3
     u32 r[E];
 #pragma unroll
     for (int e = 0; e < E; ++e) { const u32 t = e * 64 + lane; r[e] = t < T ? src[t] : MCQ_EMPTY; }
-    return dedup_insert<E>(r, buf, hits, T, lane);
-}
-
-// the same for a list that sits in the wave's own LDS (src may lie inside `hits`: everything is in registers before the
-// table is cleared)
-template <int E>
-__device__ __forceinline__ u32 lds_dedup_insert(const u32* src, u32* buf, u32* hits, u32 T, u32 lane) {
-    u32 r[E];
-#pragma unroll
-    for (int e = 0; e < E; ++e) { const u32 t = e * 64 + lane; r[e] = t < T ? src[t] : MCQ_EMPTY; }
-    wave_sync();
     return dedup_insert<E>(r, buf, hits, T, lane);
 }
 
@@ -859,12 +807,10 @@ __device__ __forceinline__ u32 topk_heads(const DbDev& db, const OptDev& opt, co
         nheads += (u32)__builtin_popcountll(hm);
     }
     wave_sync();
-    if (MCQ_OPT_LIN(opt)) return topk_lin_write<u32, JB>(db, opt, out, buf, hits, nheads, lf, q, lane);
-#ifndef MCQ_TOPK_CHUNKED                                            // tuning knob (A/B): M rounds per 64 heads only
+    if (opt.lin != 0) return topk_lin_write<u32, JB>(db, opt, out, buf, hits, nheads, lf, q, lane);
     constexpr int NC = CAP / 128;                                   // register budget: 2 words per 64 heads
     if (nheads <= 64u * NC)
         return topk_all_lds<JB, NC>(db, opt, out, buf, hits, nheads, numWindows, lf, q, lane, hits + (CAP - 128));
-#endif
     if (nheads <= (u32)CAP - 128u)
         return topk_fold_write_lds<JB>(db, opt, out, buf, hits, nheads, numWindows, lf, q, lane, hits + (CAP - 128));
     return topk_fold_write<u32, u32, JB>(db, opt, out, buf, hits, nheads, numWindows, lf, q, lane);
@@ -874,7 +820,7 @@ __device__ __forceinline__ u32 topk_heads(const DbDev& db, const OptDev& opt, co
 template <class KeyT, class LF>
 __device__ __forceinline__ u32 topk_heads64(const DbDev& db, const OptDev& opt, const OutDev& out, const KeyT* buf, u32* hits,
                                             u32 T, u32 numWindows, const LF& lf, u64 q, u32 lane) {
-    if (MCQ_OPT_LIN(opt)) return topk_lin_write<KeyT, 9>(db, opt, out, buf, hits, T, lf, q, lane);
+    if (opt.lin != 0) return topk_lin_write<KeyT, 9>(db, opt, out, buf, hits, T, lf, q, lane);
     return topk_fold_write<KeyT, u32, 9>(db, opt, out, buf, hits, T, numWindows, lf, q, lane);
 }
 
@@ -950,13 +896,10 @@ __global__ __launch_bounds__(256, sizeof(KeyT) == 4 ? (NL > 1 ? 5 : MCQ_WAVE_OCC
     // list that recently failed and sends lists at least that long straight to the raw sort (results are the same
     // either way; only the path differs).
     // (One word of LDS per wave, touched only by lists longer than 256: a loop-carried register costs the short reads.)
-#ifndef MCQ_NO_TFAIL                                   // tuning knob (A/B)
     __shared__ u32 s_tfail[4];
     if (lane == 0) s_tfail[wave] = MCQ_DEDUP_MAX_T + 1;
     wave_sync();
-#endif
 
-#ifndef MCQ_NO_DIRECT_MODE                             // tuning knob (A/B)
     // Direct mode (CountersDev::direct_mode, set by the batch before): most queries of such a batch leave this stage anyway -- it
     // would sketch, probe, scan, write 512 B of probe results and push one queue entry per wave and query (2.3 ms per 1 M reads at
     // RefSeq scale).  Instead one LANE per query looks at its geometry and every query is queued: wide and narrow ones to the back
@@ -988,7 +931,6 @@ __global__ __launch_bounds__(256, sizeof(KeyT) == 4 ? (NL > 1 ? 5 : MCQ_WAVE_OCC
             return;
         }
     }
-#endif
     for (u64 q = (u64)blockIdx.x * 4 + wave; q < b.nq; q += nwaves) {
         const ReadGeom g = read_geom(db, b, q, force_block);
         bool ovf = g.ovf;
@@ -1020,15 +962,10 @@ __global__ __launch_bounds__(256, sizeof(KeyT) == 4 ? (NL > 1 ? 5 : MCQ_WAVE_OCC
             // two queues in one array: 32-bit keys and either 513..1024 locations or 65..128 features from the back
             // (k_query_wave16: still one wave per query), everything else from the front (k_query_block)
             if (lane == 0) {
-#ifdef MCQ_NO_WAVE16_ROUTE                             // tuning knob (A/B): one queue, as before the second wave stage
-                if (false) {
-#else
                 if (sizeof(KeyT) == 4 && ((!g.ovf && T <= (u32)MCQ_LCAP_WAVE16) || g.wide) && !(force_block & 4)) {
-#endif
                     ovf_push(s_ovf[wave], 1, ctr, ovf_list, b.nq, (u32)q);
                 } else ovf_push(s_ovf[wave], 0, ctr, ovf_list, b.nq, (u32)q);
             }
-#if !defined(MCQ_NO_PROBE_HANDOVER) && !defined(MCQ_NO_WAVE16_ROUTE)     // tuning knob (A/B)
             if (sizeof(KeyT) == 4 && !g.ovf && T <= (u32)MCQ_LCAP_WAVE16 && !(force_block & 4)) {
                 wave_sync();                           // the slot lane 0 just took: next - 1 of the back queue
                 const u32 slot = s_ovf[wave][1] - 1;
@@ -1036,7 +973,6 @@ __global__ __launch_bounds__(256, sizeof(KeyT) == 4 ? (NL > 1 ? 5 : MCQ_WAVE_OCC
                 if constexpr (!SH) st_feat += nfeat;
                 st_hit += (u32)__builtin_popcountll(__ballot(len > 0));     // counted here, not in the second stage
             }
-#ifndef MCQ_NO_FRONT_HANDOVER                          // tuning knob (A/B)
             else if constexpr (sizeof(KeyT) == 4 && !SH) {
                 if (!g.ovf && opt.tc_limit != 0) {     // a front-queue entry the third wave stage will look at: the same, by front slot
                     wave_sync();
@@ -1044,8 +980,6 @@ __global__ __launch_bounds__(256, sizeof(KeyT) == 4 ? (NL > 1 ? 5 : MCQ_WAVE_OCC
                     ctr->probe_front[(u64)slot * 64 + lane] = lane < nfeat ? ((off << 16) | len) : 0xFFFFull;
                 }
             }
-#endif
-#endif
             continue;
         }
         if constexpr (!SH) st_feat += nfeat;             // (sharded: the sketch kernel counted the features)
@@ -1064,14 +998,10 @@ __global__ __launch_bounds__(256, sizeof(KeyT) == 4 ? (NL > 1 ? 5 : MCQ_WAVE_OCC
                 else if (T <= 192) D = gather_dedup_insert<3>(db, buf, hits, T, pos, len, off, lane, stop);
                 else if (T <= 256) D = gather_dedup_insert<4>(db, buf, hits, T, pos, len, off, lane, stop);
                 else {
-#ifndef MCQ_NO_TFAIL
                     const u32 t_fail = s_tfail[wave];
                     skipped = T >= t_fail;
-#endif
                     if (skipped) {                 // creep up, so that such lists are tried again now and then
-#ifndef MCQ_NO_TFAIL
                         if (lane == 0) s_tfail[wave] = t_fail + 2;
-#endif
                         D = MCQ_DEDUP_MAX_D + 1;
                     }
                     else if (T <= 384) D = gather_dedup_insert<6>(db, buf, hits, T, pos, len, off, lane, stop);
@@ -1092,14 +1022,12 @@ __global__ __launch_bounds__(256, sizeof(KeyT) == 4 ? (NL > 1 ? 5 : MCQ_WAVE_OCC
                             st_hit -= (u32)__builtin_popcountll(__ballot(len > 0)); st_loc -= T;
                         } else st_cand += nc;
                     } else
-                    st_cand += MCQ_TOPK_DEDUP(db, opt, out, dedup_sk(hits), reinterpret_cast<u32*>(buf), D, numWindows, lf, q, lane, t1);
+                    st_cand += topk_dedup(db, opt, out, dedup_sk(hits), reinterpret_cast<u32*>(buf), D, numWindows, lf, q, lane, t1);
                     wave_sync();
                     continue;
                 }
                 wave_sync();                       // more than 256 distinct keys: the raw list is sorted below
-#ifndef MCQ_NO_TFAIL
                 if (lane == 0 && !skipped) s_tfail[wave] = T;  // (T > 256) lists this long and longer skip the attempt for a while
-#endif
             }
         }
         if (T <= 64)       gather_sort_store<KeyT, 1>(db, buf, hits, T, pos, len, off, lane, stop);
@@ -1168,18 +1096,7 @@ __global__ __launch_bounds__(256, MCQ_WAVE16_OCC) void k_query_wave16(DbDev db, 
     float word_space;
     if constexpr (GW) word_space = (float)gwd.off[db.n_targets];
     else word_space = (db.wb < 32 && ((u64)db.n_targets << db.wb) < 0xFFFFFFFFull) ? (float)((u64)db.n_targets << db.wb) : 4294967040.0f;
-    // (-DMCQ_WAVE_DYNQ, tuning knob: the waves take their entries from a shared cursor, MCQ_WAVE_DYNQ_CH at a time, instead of striding)
-#ifdef MCQ_WAVE_DYNQ
-    for (u32 cb = 0;;) {
-        if (lane == 0) cb = atomicAdd(&ctr->w_cursor[0], (u32)MCQ_WAVE_DYNQ_CH);
-        cb = bcast(cb, 0);
-        if (cb >= n_mid) break;
-        const u32 ce = cb + (u32)MCQ_WAVE_DYNQ_CH < n_mid ? cb + (u32)MCQ_WAVE_DYNQ_CH : n_mid;
-    for (u32 it = cb; it < ce; ++it) {
-#else
-    {
     for (u32 it = blockIdx.x * 4 + wave; it < n_mid; it += nwaves) {
-#endif
         WCLK(7);
         const u32 qe = ovf_list[ovf_slot(b.nq, 1, ovf_visit(it, n_mid))];
         if (qe == MCQ_EMPTY) continue;                 // unused tail of a wave's reservation
@@ -1191,13 +1108,10 @@ __global__ __launch_bounds__(256, MCQ_WAVE16_OCC) void k_query_wave16(DbDev db, 
         u32 nfeat = 0;                                 // <= 128: the first stage queued nothing wider
         bool two = false;
         u64 off0 = 0, off1 = 0; u32 len0 = 0, len1 = 0;
-#ifndef MCQ_NO_PROBE_HANDOVER
         if (!fresh) {                                  // queued by its length: the first stage left its probe results
             const u64 pw = ctr->probe_buf[(u64)ovf_visit(it, n_mid) * 64 + lane];
             off0 = pw >> 16; len0 = (u32)(pw & 0xFFFFu);
-        } else
-#endif
-        {
+        } else {
             if constexpr (SH) {                        // feature slots of the exchange, two per lane
                 nfeat = (g.nw1 + g.nw2) * db.s;
                 two = nfeat > 64;
@@ -1230,21 +1144,15 @@ __global__ __launch_bounds__(256, MCQ_WAVE16_OCC) void k_query_wave16(DbDev db, 
                 fq_next = bcast(base, 0); fq_left = MCQ_OVF_CHUNK;
             }
             if (lane == 0) ovf_list[fq_next] = q32;
-#ifndef MCQ_NO_FRONT_HANDOVER
             // (direct mode) <= 64 features: the third wave stage reads such an entry's probe results from the slot's row, as it does
             // for the entries the first stage queues there itself; it counts the features (no bit 63)
             if constexpr (!SH) { if (!g.wide) ctr->probe_front[(u64)fq_next * 64 + lane] = lane < nfeat ? ((off0 << 16) | len0) : 0xFFFFull; }
-#endif
             ++fq_next; --fq_left;
             continue;
         }
         st_loc += T;
         if constexpr (TAP) { if (dbg.mode == 1 && lane == 0) dbg.match_cnt[q] = T; }
-#ifdef MCQ_NO_PROBE_HANDOVER
-        {
-#else
         if (fresh) {                                   // (the first stage counted the features of the others)
-#endif
             if constexpr (!SH) st_feat += nfeat;
             st_hit += (u32)__builtin_popcountll(__ballot(len0 > 0)) + (u32)__builtin_popcountll(__ballot(len1 > 0));
         }
@@ -1262,7 +1170,7 @@ __global__ __launch_bounds__(256, MCQ_WAVE16_OCC) void k_query_wave16(DbDev db, 
                 if constexpr (TAP) { if (dbg.mode == 2) tap_distinct(dbg, dedup_sk(hits), dedup_wp(hits), D, lf, q, lane); }
                 if (D <= 64 && numWindows <= 8) sweep_targets_regs(k1, incl1, tb1, buf, D, numWindows, lf, lane);
                 else sweep_targets_weighted(dedup_sk(hits), dedup_wp(hits), buf, D, numWindows, lf, lane);
-                st_cand += MCQ_TOPK_DEDUP(db, opt, out, dedup_sk(hits), buf, D, numWindows, lf, q, lane, t1);
+                st_cand += topk_dedup(db, opt, out, dedup_sk(hits), buf, D, numWindows, lf, q, lane, t1);
                 wave_sync();
                 continue;
             }
@@ -1286,12 +1194,10 @@ __global__ __launch_bounds__(256, MCQ_WAVE16_OCC) void k_query_wave16(DbDev db, 
                         fq_next = bcast(base, 0); fq_left = MCQ_OVF_CHUNK;
                     }
                     if (lane == 0) ovf_list[fq_next] = q32;
-#ifndef MCQ_NO_FRONT_HANDOVER
                     // <= 64 features: the third wave stage reads every such front entry's probe results from the slot's row
                     // (bit 63: features and hit features are counted already -- the first stage did that at its hand-over)
                     if constexpr (!SH) { if (!g.wide) ctr->probe_front[(u64)fq_next * 64 + lane] = fresh ? (lane < nfeat ? ((off0 << 16) | len0) : 0xFFFFull)
                                                                                                            : ((1ull << 63) | (off0 << 16) | len0); }
-#endif
                     ++fq_next; --fq_left;
                     wave_sync();
                     continue;
@@ -1307,7 +1213,6 @@ __global__ __launch_bounds__(256, MCQ_WAVE16_OCC) void k_query_wave16(DbDev db, 
         sweep_targets_wave<u32, JB>(buf, hits, T, numWindows, lf, lane);
         st_cand += topk_heads<JB, LCAP>(db, opt, out, buf, hits, T, numWindows, lf, q, lane);
         wave_sync();
-    }
     }
 #ifdef MCQ_PHASE_CLOCK
     WCLK(7);
@@ -1333,17 +1238,14 @@ __global__ __launch_bounds__(256, MCQ_WAVE16_OCC) void k_query_wave16(DbDev db, 
 // are bytes, the cell maps keep their 2^16 cells, at most 2048 heavy words.  It walks the FRONT queue before the workgroup kernels do: an entry it can answer -- few features, a list that fits
 // 32 registers per lane, lists provable by the two-class tail -- is answered and overwritten with the empty marker; every
 // other entry stays for the workgroup kernels, and the narrow ones among those are counted for them (see k_query_block).
-// Sketch and probe again (no hand-over: ~8 us of the ~50), two features per lane as in the second stage.  16 KB of LDS per
+// An entry of <= 64 features takes the probe results an earlier stage left in its slot's row (CountersDev::probe_front); the
+// others are sketched and probed again, two features per lane as in the second stage.  16 KB of LDS per
 // wave, two waves per SIMD.  Launched only when the two-class tail is (32-bit words, P x M <= 16).
 template <bool SH = false, bool GW = false, int BSH = -1>
 __global__ __launch_bounds__(256, 2) void k_query_wave32(DbDev db, BatchDev b, OptDev opt, OutDev out, CountersDev* ctr, u32* ovf_list,
                                                          int force_block, ShardDev sh, GwDev gwd) {
     constexpr int LSEG = 2048;                         // words per LDS segment
-#ifdef MCQ_WAVE32_ONLY                                 // tuning knob (A/B): without the 64-register form
-    constexpr int LCAP = 2048;
-#else
     constexpr int LCAP = 4096;
-#endif
     const typename LocOf<u32, GW>::type lf = loc_format<u32, GW>(db, gwd);
     __shared__ u32 s_buf[4][LSEG];
     __shared__ u32 s_hits[4][LSEG];
@@ -1359,17 +1261,7 @@ __global__ __launch_bounds__(256, 2) void k_query_wave32(DbDev db, BatchDev b, O
     float word_space;
     if constexpr (GW) word_space = (float)gwd.off[db.n_targets];
     else word_space = (db.wb < 32 && ((u64)db.n_targets << db.wb) < 0xFFFFFFFFull) ? (float)((u64)db.n_targets << db.wb) : 4294967040.0f;
-#ifdef MCQ_WAVE_DYNQ
-    for (u32 cb = 0;;) {
-        if (lane == 0) cb = atomicAdd(&ctr->w_cursor[1], (u32)MCQ_WAVE_DYNQ_CH);
-        cb = bcast(cb, 0);
-        if (cb >= n_front) break;
-        const u32 ce = cb + (u32)MCQ_WAVE_DYNQ_CH < n_front ? cb + (u32)MCQ_WAVE_DYNQ_CH : n_front;
-    for (u32 it = cb; it < ce; ++it) {
-#else
-    {
     for (u32 it = blockIdx.x * 4 + wave; it < n_front; it += nwaves) {
-#endif
         const u32 slot = ovf_visit(it, n_front);
         const u32 q32 = ovf_list[slot];
         if (q32 == MCQ_EMPTY) continue;                // unused tail of a wave's reservation
@@ -1387,7 +1279,6 @@ __global__ __launch_bounds__(256, 2) void k_query_wave32(DbDev db, BatchDev b, O
             if (lane < nfeat) shard_fetch(sh, sb + lane, off0, len0);
             if (two && 64 + lane < nfeat) shard_fetch(sh, sb + 64 + lane, off1, len1);
         }
-#ifndef MCQ_NO_FRONT_HANDOVER
         else if (!g.ovf) {                             // <= 64 features: the first stage left its probe results in the slot's row
             const u64 pw = ctr->probe_front[(u64)slot * 64 + lane];
             const u32 l = (u32)(pw & 0xFFFFu);
@@ -1395,7 +1286,6 @@ __global__ __launch_bounds__(256, 2) void k_query_wave32(DbDev db, BatchDev b, O
             len0 = l == 0xFFFFu ? 0u : l; off0 = (pw << 1) >> 17;
             counted = __ballot((pw >> 63) != 0) != 0;             // handed on by the second stage: counted by the first one
         }
-#endif
         else {
             for (u32 w = 0; w < g.nw1 + g.nw2; ++w) {
                 u64 at; u32 wl;
@@ -1422,13 +1312,9 @@ __global__ __launch_bounds__(256, 2) void k_query_wave32(DbDev db, BatchDev b, O
             gather_regs2<32>(db, r, T, pos0, len0, off0, pos1, len1, off1, two, lane, hits);
             n2 = two_class_tail<32>(db, opt, out, r, T, numWindows, word_space, lf, q, lane, buf, hits);
         } else {
-#ifndef MCQ_WAVE32_ONLY
             u32 r[64];
             gather_regs2<64>(db, r, T, pos0, len0, off0, pos1, len1, off1, two, lane, hits);
             n2 = two_class_tail<64>(db, opt, out, r, T, numWindows, word_space, lf, q, lane, buf, hits);
-#else
-            n2 = ~0u;
-#endif
         }
         wave_sync();
         if (n2 >= ~1u) { st_narrow += narrow; continue; }             // not taken / not provable: the entry stays
@@ -1438,7 +1324,6 @@ __global__ __launch_bounds__(256, 2) void k_query_wave32(DbDev db, BatchDev b, O
             st_hit += (u32)__builtin_popcountll(__ballot(len0 > 0)) + (u32)__builtin_popcountll(__ballot(len1 > 0));
         }
         st_loc += T; st_cand += n2; st_two += 1;
-    }
     }
     if (lane == 0 && st_two) atomicAdd(&ctr->n_two_class, st_two);
     if (lane == 0 && st_narrow) atomicAdd(&ctr->n_narrow, st_narrow);
@@ -1520,11 +1405,7 @@ __device__ __forceinline__ void block_tail(const DbDev& db, const OptDev& opt, c
                                            KeyT* B, HT* H, u32 T, u32 numWindows, const LF& lf, u64 q, u32 tid,
                                            const DebugDev& dbg, u32* biglist, Fill fill, bool filled = false) {
     const u32 n2p = pow2ceil(T), NTB = blockDim.x;
-#ifdef MCQ_SORT_PAD_FULL                                       // tuning knob (A/B): the whole power-of-two network
-    const u32 npad = n2p;
-#else
     const u32 npad = n2p < 256 ? n2p : ((T + 127u) & ~127u);  // padded to whole 128-key chunks (see bitonic_sort_block)
-#endif
     if (!filled) fill(B);                                      // B[0..T) = the unsorted match list
     for (u32 t = T + tid; t < npad; t += NTB) B[t] = key_pad<KeyT>();
     __syncthreads();
@@ -1769,11 +1650,7 @@ __global__ __launch_bounds__(NT, sizeof(KeyT) == 4 ? 8 : 4) void k_query_block(D
         nhit = wave_incl_scan_dpp(nhit);
         if (lane == 63 && nhit) atomicAdd(&s_w[19], nhit);
         u32 T;
-#ifndef MCQ_NO_SCAN4                                    // tuning knob (A/B)
         if (F <= 4 * NT && NT >= 256) T = block_excl_scan4(fpos, F, tid);       // (uniform; the thread scans the lengths it wrote itself)
-#else
-        if (false) { }
-#endif
         else { __syncthreads(); T = block_excl_scan(fpos, F, tid, s_w); }
         PHCLK(ph, 2);
         if (tid == 0) {
@@ -1830,11 +1707,6 @@ __global__ __launch_bounds__(NT, sizeof(KeyT) == 4 ? 8 : 4) void k_query_block(D
                 }
             }
         };
-#ifdef MCQ_NO_BLOCK_MID                                // tuning knob (A/B)
-        constexpr bool mid_ok = false;
-#else
-        constexpr bool mid_ok = sizeof(KeyT) == 4 && BIG == 2;
-#endif
         // (the sort is padded to whole 128-key chunks only, so a list fits the LDS whenever that many keys do)
         if (((T + 127u) & ~127u) <= (u32)LCAPB && pow2ceil(T) <= 8192u) {
             int tc = TC_NOT_TRIED;
@@ -1864,8 +1736,8 @@ __global__ __launch_bounds__(NT, sizeof(KeyT) == 4 ? 8 : 4) void k_query_block(D
         // took 23-27 us per kb of such a read against 6.5 below, everything in global scratch): the list sorts in the LDS of BOTH
         // segments (32-bit words; the query's feature arrays are in global scratch at this size), only the sweep's packed words and
         // the lists' scans go through global memory, the atomics reduced per run inside a wave first (sweep_targets<..., true>)
-        else if (mid_ok && !f_lds && dbg.mode == 0 && ((T + 127u) & ~127u) <= 2u * (u32)LCAPB) {
-            if constexpr (sizeof(KeyT) == 4 && BIG == 2)
+        else if (sizeof(KeyT) == 4 && BIG == 2 && !f_lds && dbg.mode == 0 && ((T + 127u) & ~127u) <= 2u * (u32)LCAPB) {
+            if constexpr (sizeof(KeyT) == 4 && BIG == 2)          // (instantiated for those only)
                 block_tail<KeyT, u32, 14, BIG, false, decltype(lf), decltype(fill), true>(db, opt, out, ctr, s_buf, reinterpret_cast<u32*>(ghits), T, numWindows, lf, q, tid, dbg, s_biglist, fill);
         }
         else                           block_tail<KeyT, u64, 32, BIG>(db, opt, out, ctr, gbuf, ghits, T, numWindows, lf, q, tid, dbg, s_biglist, fill);
@@ -2041,7 +1913,7 @@ __global__ __launch_bounds__(256) void k_reduce_wave(DbDev db, OptDev opt, OutDe
                 if (D != ~0u) {
                     if (D <= 64 && numWindows <= 8) sweep_targets_regs(k1, incl1, tb1, reinterpret_cast<u32*>(buf), D, numWindows, lf, lane);
                     else sweep_targets_weighted(dedup_sk(hits), dedup_wp(hits), reinterpret_cast<u32*>(buf), D, numWindows, lf, lane);
-                    st_cand += MCQ_TOPK_DEDUP(db, opt, out, dedup_sk(hits), reinterpret_cast<u32*>(buf), D, numWindows, lf, q, lane, t1);
+                    st_cand += topk_dedup(db, opt, out, dedup_sk(hits), reinterpret_cast<u32*>(buf), D, numWindows, lf, q, lane, t1);
                     wave_sync();
                     continue;
                 }
@@ -2969,10 +2841,8 @@ static int launch_query(const mcq_db* db, mcq_ws* ws, const BatchDev& b, const O
 #undef MCQ_LAUNCH_TC
     }
     rc = tm.end(); if (rc) return rc;
-#ifndef MCQ_NO_DIRECT_MODE
     if (db->d.compact && !tap && !many && !(force_block & 7) && !getenv("MCQ_NO_DIRECT_MODE")) hipLaunchKernelGGL(k_next_mode, dim3(1), dim3(1), 0, st, ws->ctr, b.nq);
     else HIPCHK(hipMemsetAsync(&ws->ctr->direct_mode, 0, 4, st));
-#endif
     HIPCHK(hipGetLastError());
     ws->last_nq = b.nq;
     return MCQ_OK;

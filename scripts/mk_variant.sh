@@ -10,10 +10,11 @@ if [ "$REV" = "-" ]; then SRC=$ROOT; else
   SRC=/tmp/mcq_variant_$NAME; rm -rf $SRC; mkdir -p $SRC
   git -C $ROOT archive $REV metacache-mpi_amd/csrc include | tar -x -C $SRC
 fi
-O=/tmp/mcq_variant_obj_$NAME; mkdir -p $O
-for u in mcq_engine mcq_build; do
-  /opt/rocm/bin/hipcc --offload-arch=gfx950 -O3 -std=c++17 -fPIC "$@" -c $SRC/metacache-mpi_amd/csrc/$u.hip -o $O/$u.o &
+O=/tmp/mcq_variant_obj_$NAME; rm -rf $O; mkdir -p $O
+pids=()
+for src in $SRC/metacache-mpi_amd/csrc/*.hip; do     # every unit of the revision, as build.py links them
+  /opt/rocm/bin/hipcc --offload-arch=gfx950 -O3 -std=c++17 -fPIC "$@" -c $src -o $O/$(basename $src .hip).o & pids+=($!)
 done
-wait
-/opt/rocm/bin/hipcc --offload-arch=gfx950 -shared -fPIC $O/mcq_engine.o $O/mcq_build.o -o $ROOT/scripts/_ab/libmcq_hip_$NAME.so -ldl
+for p in "${pids[@]}"; do wait $p; done
+/opt/rocm/bin/hipcc --offload-arch=gfx950 -shared -fPIC $O/*.o -o $ROOT/scripts/_ab/libmcq_hip_$NAME.so -ldl
 echo built scripts/_ab/libmcq_hip_$NAME.so
