@@ -2297,6 +2297,21 @@ extern "C" uint32_t mcq_owner(uint32_t feature, uint32_t n_shards) {
     return (u32)(((u64)x * (n_shards ? n_shards : 1)) >> 32);
 }
 
+// ------------------------------------------------------------------ a handle's form as template arguments
+// The only code that turns d.compact, g.on and d.bsh into the template arguments of the kernels a handle launches.  The location
+// word: LocForm<u64, false> = 64-bit bit fields, <u32, false> = 32-bit bit fields, <u32, true> = the 32-bit global-window index.
+// The bucket layout BSH: 2 = 64-B buckets, 0 = 16-B slots.  f gets the form as a value of the tag type.
+template <class KeyT, bool GW> struct LocForm { using Key = KeyT; static constexpr bool gw = GW; };
+template <int V> using IntC = std::integral_constant<int, V>;
+template <class F> static auto with_loc_form(bool compact, bool gw, F&& f) {
+    if (!compact) return f(LocForm<u64, false>{});
+    return gw ? f(LocForm<u32, true>{}) : f(LocForm<u32, false>{});
+}
+template <class F> static auto with_loc_form(const mcq_db* db, F&& f) { return with_loc_form(db->d.compact != 0, db->g.on != 0, f); }
+template <class F> static auto with_layout(const mcq_db* db, F&& f) {
+    return db->d.bsh != 0 ? f(IntC<2>{}) : f(IntC<0>{});
+}
+
 // ------------------------------------------------------------------ db
 // temporaries are released on every way out; the handle itself by mcq_db_destroy on failure
 struct DevTemps {
@@ -2429,12 +2444,16 @@ static int create_table(const mcq_db_desc* desc, const std::vector<PartView>& pa
         u64 part_ext = 0;
         DBCHK(hipMemcpy(&part_ext, d_new + pv.n_keys, 8, hipMemcpyDeviceToHost));
         if (ext_base + part_ext > std::max<u64>(1, nl_ext)) { (void)mcq_db_destroy(db); return fail(MCQ_E_ARG, "the parts changed between the two passes"); }
-        if (compact) hipLaunchKernelGGL(k_insert_keys<u32>, ig, dim3(TB), 0, 0, db->slots, (u32)(nslots - 1), bq, inl, pv, (const u64*)d_len, (const u64*)d_new, ext_base, wb, (const u32*)d_gwoff);
-        else         hipLaunchKernelGGL(k_insert_keys<u64>, ig, dim3(TB), 0, 0, db->slots, (u32)(nslots - 1), bq, inl, pv, (const u64*)d_len, (const u64*)d_new, ext_base, 32u, (const u32*)nullptr);
+        // (64-bit words: wb = 32 and no window table)
+        with_loc_form(compact, gw, [&](auto L) {
+            hipLaunchKernelGGL(k_insert_keys<typename decltype(L)::Key>, ig, dim3(TB), 0, 0, db->slots, (u32)(nslots - 1), bq, inl, pv, (const u64*)d_len, (const u64*)d_new, ext_base, wb, (const u32*)d_gwoff);
+        });
         DBCHK(hipGetLastError());
         const dim3 cg((u32)std::min<u64>((pv.n_keys * 64 + TB - 1) / TB, 1u << 20));
-        if (compact) hipLaunchKernelGGL(k_copy_lists<u32>, cg, dim3(TB), 0, 0, pv, (const u64*)d_new, reinterpret_cast<u32*>(ext) + ext_base, wb, (const u32*)d_gwoff);
-        else         hipLaunchKernelGGL(k_copy_lists<u64>, cg, dim3(TB), 0, 0, pv, (const u64*)d_new, reinterpret_cast<u64*>(ext) + ext_base, 32u, (const u32*)nullptr);
+        with_loc_form(compact, gw, [&](auto L) {
+            using Key = typename decltype(L)::Key;
+            hipLaunchKernelGGL(k_copy_lists<Key>, cg, dim3(TB), 0, 0, pv, (const u64*)d_new, reinterpret_cast<Key*>(ext) + ext_base, wb, (const u32*)d_gwoff);
+        });
         DBCHK(hipGetLastError());
         ext_base += part_ext;
     }
@@ -2585,15 +2604,14 @@ extern "C" int mcq_ws_create(const mcq_db* db, uint64_t max_queries, uint64_t ma
     if (const char* e = getenv("MCQ_BLOCK_WGS")) ws->n_block_wgs = std::max(1, atoi(e));      // tuning knob
     ws->ev_used = new std::vector<TimedLaunch>();
     ws->ev_free = new std::vector<TimedLaunch>();
-    ws->cap_wave = db->g.on ? resident_blocks(k_query_wave<u32, 512, false, false, true, 2>, 256, db->device)
-                 : db->d.compact ? resident_blocks(k_query_wave<u32, 512, false, false, false, 2>, 256, db->device)
-                                 : resident_blocks(k_query_wave<u64, 512, false, false, false, 2>, 256, db->device);
-    ws->cap_wave16 = db->g.on ? resident_blocks(k_query_wave16<false, false, true, 2>, 256, db->device)
-                              : resident_blocks(k_query_wave16<false, false, false, 2>, 256, db->device);
-    ws->cap_reduce16 = db->g.on ? resident_blocks(k_reduce_wave16<true>, 256, db->device) : resident_blocks(k_reduce_wave16<false>, 256, db->device);
-    ws->cap_wave_many = db->g.on ? resident_blocks(k_query_wave<u32, 512, false, false, true, 2, 4>, 256, db->device)
-                               : resident_blocks(k_query_wave<u32, 512, false, false, false, 2, 4>, 256, db->device);
-    ws->cap_wave32 = db->g.on ? resident_blocks(k_query_wave32<false, true, 2>, 256, db->device) : resident_blocks(k_query_wave32<false, false, 2>, 256, db->device);
+    with_loc_form(db, [&](auto L) {     // (every cap_* measured on the BSH = 2 instantiation, whatever the table's layout)
+        constexpr bool GW = decltype(L)::gw;
+        ws->cap_wave = resident_blocks(k_query_wave<typename decltype(L)::Key, 512, false, false, GW, 2>, 256, db->device);
+        ws->cap_wave16 = resident_blocks(k_query_wave16<false, false, GW, 2>, 256, db->device);
+        ws->cap_reduce16 = resident_blocks(k_reduce_wave16<GW>, 256, db->device);
+        ws->cap_wave_many = resident_blocks(k_query_wave<u32, 512, false, false, GW, 2, 4>, 256, db->device);
+        ws->cap_wave32 = resident_blocks(k_query_wave32<false, GW, 2>, 256, db->device);
+    });
     const u64 nb = (u64)ws->n_block_wgs;
 #define WSCHK(expr) HIPCHK_OR(expr, (void)mcq_ws_destroy(ws))
     WSCHK(hipMalloc(&ws->ctr, sizeof(CountersDev)));
@@ -2786,60 +2804,53 @@ static int launch_query(const mcq_db* db, mcq_ws* ws, const BatchDev& b, const O
     const int force_block = force_block_in | ((od_in.big && !many) ? 1 : 0) | (many ? 4 : 0);
     OptDev od_many = od;
     if (many) { od_many.big = 0; od_many.seg = (u32)pow2ceil64(od_in.max_cand); }
-    const bool gw = db->g.on != 0;      // 32-bit locations in the global-window form: the GW instantiations
-    const bool b64 = db->d.bsh != 0;    // table layout: the wave kernels are instantiated per layout (taps and the sharded home side: run-time / unused)
-#define MCQ_LAUNCH_WAVE(KT, TAPV, SHV, GWV, BSHV) hipLaunchKernelGGL((k_query_wave<KT, kLcapWave, TAPV, SHV, GWV, BSHV>), dim3(grid), dim3(256), 0, st, D, b, od, o, ws->ctr, ws->ovf_list, force_block, dbg, sh, db->g)
-#define MCQ_LAUNCH_WAVE_L(KT, GWV) do { if (b64) MCQ_LAUNCH_WAVE(KT, false, false, GWV, 2); else MCQ_LAUNCH_WAVE(KT, false, false, GWV, 0); } while (0)
-    if (shp)                { if (!db->d.compact) MCQ_LAUNCH_WAVE(u64, false, true, false, -1); else if (gw) MCQ_LAUNCH_WAVE(u32, false, true, true, -1); else MCQ_LAUNCH_WAVE(u32, false, true, false, -1); }
-    else if (tap)           { if (!db->d.compact) MCQ_LAUNCH_WAVE(u64, true, false, false, -1); else if (gw) MCQ_LAUNCH_WAVE(u32, true, false, true, -1); else MCQ_LAUNCH_WAVE(u32, true, false, false, -1); }
-    else if (many) {
-#define MCQ_LAUNCH_MANY(GWV, BSHV) hipLaunchKernelGGL((k_query_wave<u32, kLcapWave, false, false, GWV, BSHV, 4>), dim3(grid_for(ws->cap_wave_many, want)), dim3(256), 0, st, D, b, od_many, o, ws->ctr, ws->ovf_list, force_block, dbg, sh, db->g)
-        if (gw) { if (b64) MCQ_LAUNCH_MANY(true, 2); else MCQ_LAUNCH_MANY(true, 0); }
-        else    { if (b64) MCQ_LAUNCH_MANY(false, 2); else MCQ_LAUNCH_MANY(false, 0); }
-#undef MCQ_LAUNCH_MANY
-    }
-    else if (db->d.compact) { if (gw) MCQ_LAUNCH_WAVE_L(u32, true); else MCQ_LAUNCH_WAVE_L(u32, false); }
-    else                    MCQ_LAUNCH_WAVE_L(u64, false);
-#undef MCQ_LAUNCH_WAVE_L
-#undef MCQ_LAUNCH_WAVE
-    rc = tm.mark(); if (rc) return rc;
-    if (db->d.compact) {   // second wave stage (back queue); no queue for 64-bit keys
-        const dim3 g16(grid_for(ws->cap_wave16, want));
-#define MCQ_LAUNCH_WAVE16(TAPV, SHV, GWV, BSHV) hipLaunchKernelGGL((k_query_wave16<TAPV, SHV, GWV, BSHV>), g16, dim3(256), 0, st, D, b, od, o, ws->ctr, ws->ovf_list, dbg, sh, db->g)
-        if (shp)      { if (gw) MCQ_LAUNCH_WAVE16(false, true, true, -1); else MCQ_LAUNCH_WAVE16(false, true, false, -1); }
-        else if (tap) { if (gw) MCQ_LAUNCH_WAVE16(true, false, true, -1); else MCQ_LAUNCH_WAVE16(true, false, false, -1); }
-        else if (gw)  { if (b64) MCQ_LAUNCH_WAVE16(false, false, true, 2); else MCQ_LAUNCH_WAVE16(false, false, true, 0); }
-        else          { if (b64) MCQ_LAUNCH_WAVE16(false, false, false, 2); else MCQ_LAUNCH_WAVE16(false, false, false, 0); }
-#undef MCQ_LAUNCH_WAVE16
-    }
-    if (with_tc) {          // third wave stage: front-queue entries of up to 2048 locations (see k_query_wave32); counts the narrow ones it leaves
-        const dim3 g32(grid_for(ws->cap_wave32, want));
-#define MCQ_LAUNCH_WAVE32(SHV, GWV, BSHV) hipLaunchKernelGGL((k_query_wave32<SHV, GWV, BSHV>), g32, dim3(256), 0, st, D, b, od, o, ws->ctr, ws->ovf_list, force_block, sh, db->g)
-        if (shp)     { if (gw) MCQ_LAUNCH_WAVE32(true, true, -1); else MCQ_LAUNCH_WAVE32(true, false, -1); }
-        else if (gw) { if (b64) MCQ_LAUNCH_WAVE32(false, true, 2); else MCQ_LAUNCH_WAVE32(false, true, 0); }
-        else         { if (b64) MCQ_LAUNCH_WAVE32(false, false, 2); else MCQ_LAUNCH_WAVE32(false, false, 0); }
-#undef MCQ_LAUNCH_WAVE32
-    }
-    rc = tm.mark(); if (rc) return rc;
-#define MCQ_LAUNCH_BLOCK(KT, LC, NTH, BIGV, SHV, GWV) hipLaunchKernelGGL((k_query_block<KT, LC, NTH, BIGV, SHV, GWV, false>), dim3(ws->n_block_wgs), dim3(NTH), 0, st, D, b, od, o, ws->ctr, \
-                                                             (const u32*)ws->ovf_list, ws->sc, dbg, sh, db->g)
-#define MCQ_LAUNCH_BLOCK2(KT, LC, NTH, SHV, GWV) do { if (od.lin) MCQ_LAUNCH_BLOCK(KT, LC, NTH, 2, SHV, GWV); else if (od.big) MCQ_LAUNCH_BLOCK(KT, LC, NTH, 1, SHV, GWV); \
-                                                      else MCQ_LAUNCH_BLOCK(KT, LC, NTH, 0, SHV, GWV); } while (0)
-#define MCQ_LAUNCH_BLOCK32(SHV) do { if (gw) MCQ_LAUNCH_BLOCK2(u32, MCQ_BLOCK_LCAP, MCQ_BLOCK_NT, SHV, true); else MCQ_LAUNCH_BLOCK2(u32, MCQ_BLOCK_LCAP, MCQ_BLOCK_NT, SHV, false); } while (0)
-    if (db->d.compact) { if (shp) MCQ_LAUNCH_BLOCK32(true); else MCQ_LAUNCH_BLOCK32(false); }
-    else               { if (shp) MCQ_LAUNCH_BLOCK2(u64, kLcapBlock, 1024, true, false); else MCQ_LAUNCH_BLOCK2(u64, kLcapBlock, 1024, false, false); }
-#undef MCQ_LAUNCH_BLOCK32
-#undef MCQ_LAUNCH_BLOCK2
-#undef MCQ_LAUNCH_BLOCK
-    if (with_tc) {
-#define MCQ_LAUNCH_TC1(FORMV, SHV, GWV) hipLaunchKernelGGL((k_query_block<u32, MCQ_BLOCK_LCAP, MCQ_BLOCK_NT, FORMV, SHV, GWV, true>), dim3(ws->n_block_wgs), dim3(MCQ_BLOCK_NT), 0, st, \
-                                                   D, b, od, o, ws->ctr, (const u32*)ws->ovf_list, ws->sc, dbg, sh, db->g)
-#define MCQ_LAUNCH_TC(SHV, GWV) do { if (od.lin) MCQ_LAUNCH_TC1(2, SHV, GWV); else MCQ_LAUNCH_TC1(0, SHV, GWV); } while (0)
-        if (shp) { if (gw) MCQ_LAUNCH_TC(true, true); else MCQ_LAUNCH_TC(true, false); }
-        else     { if (gw) MCQ_LAUNCH_TC(false, true); else MCQ_LAUNCH_TC(false, false); }
-#undef MCQ_LAUNCH_TC1
-#undef MCQ_LAUNCH_TC
-    }
+    using Yes = std::true_type; using No = std::false_type;
+    // the launch role as <TAP, SH, BSH>: the sharded home side and the debug tap read the layout at run time, plain launches
+    // take the table's
+    auto by_role = [&](auto f) {
+        if (shp) f(No{}, Yes{}, IntC<-1>{});
+        else if (tap) f(Yes{}, No{}, IntC<-1>{});
+        else with_layout(db, [&](auto BSH) { f(No{}, No{}, BSH); });
+    };
+    rc = with_loc_form(db, [&](auto L) -> int {
+        using Key = typename decltype(L)::Key;
+        constexpr bool GW = decltype(L)::gw;
+        if (many) {
+            if constexpr (sizeof(Key) == 4) with_layout(db, [&](auto BSH) {
+                hipLaunchKernelGGL((k_query_wave<u32, kLcapWave, false, false, GW, BSH, 4>), dim3(grid_for(ws->cap_wave_many, want)), dim3(256), 0, st,
+                                   D, b, od_many, o, ws->ctr, ws->ovf_list, force_block, dbg, sh, db->g);
+            });
+        } else by_role([&](auto TAP, auto SH, auto BSH) {
+            hipLaunchKernelGGL((k_query_wave<Key, kLcapWave, TAP, SH, GW, BSH>), dim3(grid), dim3(256), 0, st, D, b, od, o, ws->ctr, ws->ovf_list,
+                               force_block, dbg, sh, db->g);
+        });
+        rc = tm.mark(); if (rc) return rc;
+        if constexpr (sizeof(Key) == 4) {   // second wave stage (back queue); no queue for 64-bit keys
+            by_role([&](auto TAP, auto SH, auto BSH) {
+                hipLaunchKernelGGL((k_query_wave16<TAP, SH, GW, BSH>), dim3(grid_for(ws->cap_wave16, want)), dim3(256), 0, st, D, b, od, o, ws->ctr,
+                                   ws->ovf_list, dbg, sh, db->g);
+            });
+            // third wave stage: front-queue entries of up to 2048 locations (see k_query_wave32); counts the narrow ones it leaves
+            if (with_tc) by_role([&](auto TAP, auto SH, auto BSH) {     // (no tap form: with_tc excludes the tap)
+                if constexpr (!TAP) hipLaunchKernelGGL((k_query_wave32<SH, GW, BSH>), dim3(grid_for(ws->cap_wave32, want)), dim3(256), 0, st, D, b, od, o,
+                                                       ws->ctr, ws->ovf_list, force_block, sh, db->g);
+            });
+        }
+        rc = tm.mark(); if (rc) return rc;
+        // the workgroup kernel: list form BIG (2: od.lin, 1: od.big, else 0), plain or with the two-class tail (TC; 32-bit words)
+        constexpr int lcap = sizeof(Key) == 4 ? MCQ_BLOCK_LCAP : kLcapBlock, nt = sizeof(Key) == 4 ? MCQ_BLOCK_NT : 1024;
+        auto block = [&](auto TC, auto BIG) {
+            auto launch = [&](auto SH) {
+                hipLaunchKernelGGL((k_query_block<Key, lcap, nt, BIG, SH, GW, TC>), dim3(ws->n_block_wgs), dim3(nt), 0, st, D, b, od, o, ws->ctr,
+                                   (const u32*)ws->ovf_list, ws->sc, dbg, sh, db->g);
+            };
+            if (shp) launch(Yes{}); else launch(No{});
+        };
+        if (od.lin) block(No{}, IntC<2>{}); else if (od.big) block(No{}, IntC<1>{}); else block(No{}, IntC<0>{});
+        if constexpr (sizeof(Key) == 4) if (with_tc) { if (od.lin) block(Yes{}, IntC<2>{}); else block(Yes{}, IntC<0>{}); }
+        return MCQ_OK;
+    });
+    if (rc) return rc;
     rc = tm.end(); if (rc) return rc;
     if (db->d.compact && !tap && !many && !(force_block & 7) && !getenv("MCQ_NO_DIRECT_MODE")) hipLaunchKernelGGL(k_next_mode, dim3(1), dim3(1), 0, st, ws->ctr, b.nq);
     else HIPCHK(hipMemsetAsync(&ws->ctr->direct_mode, 0, 4, st));
@@ -3162,8 +3173,10 @@ extern "C" int mcq_lookup_gather(const mcq_db* db, const uint32_t* features, uin
     if (n_features == 0) return MCQ_OK;
     u64 groups = (n_features + 63) / 64;
     const u32 grid = (u32)std::min<u64>((groups + 3) / 4, 256ull * 32);
-    if (db->d.compact) hipLaunchKernelGGL(k_lookup_gather<u32>, dim3(grid), dim3(256), 0, (hipStream_t)stream, db->d, features, n_features, list_len, list_src, out_off, (u32*)out_locs);
-    else               hipLaunchKernelGGL(k_lookup_gather<u64>, dim3(grid), dim3(256), 0, (hipStream_t)stream, db->d, features, n_features, list_len, list_src, out_off, (u64*)out_locs);
+    with_loc_form(db, [&](auto L) {
+        using Key = typename decltype(L)::Key;
+        hipLaunchKernelGGL(k_lookup_gather<Key>, dim3(grid), dim3(256), 0, (hipStream_t)stream, db->d, features, n_features, list_len, list_src, out_off, (Key*)out_locs);
+    });
     HIPCHK(hipGetLastError());
     return MCQ_OK;
 }
@@ -3188,8 +3201,10 @@ extern "C" int mcq_assemble(const mcq_db* db, uint64_t n_lists, const uint32_t* 
     if (n_lists) {
         u64 groups = (n_lists + 63) / 64;
         const u32 grid = (u32)std::min<u64>((groups + 3) / 4, 256ull * 32);
-        if (db->d.compact) hipLaunchKernelGGL(k_scatter_lists<u32>, dim3(grid), dim3(256), 0, st, n_lists, (const u64*)src_off, src_slot, (const u64*)dst_off, (const u32*)src_locs, (u32*)dst_locs);
-        else               hipLaunchKernelGGL(k_scatter_lists<u64>, dim3(grid), dim3(256), 0, st, n_lists, (const u64*)src_off, src_slot, (const u64*)dst_off, (const u64*)src_locs, (u64*)dst_locs);
+        with_loc_form(db, [&](auto L) {
+            using Key = typename decltype(L)::Key;
+            hipLaunchKernelGGL(k_scatter_lists<Key>, dim3(grid), dim3(256), 0, st, n_lists, (const u64*)src_off, src_slot, (const u64*)dst_off, (const Key*)src_locs, (Key*)dst_locs);
+        });
     }
     hipLaunchKernelGGL(k_query_offsets, dim3((u32)((nq + 256) / 256)), dim3(256), 0, st, nq, in->paired ? 2u : 1u, db->d.s, win_off,
                        in->seq_off, (in->flags & MCQ_BATCH_RANGES) ? 1u : 0u, (const u64*)dst_off, n_slots, loc_off, query_len);
@@ -3215,30 +3230,24 @@ extern "C" int mcq_reduce(const mcq_db* db, mcq_ws* ws, uint64_t n_queries, cons
     const u32 grid = (u32)std::min<u64>((n_queries + 3) / 4, 256ull * 24);     // measured: 1.07 ms vs 1.25 ms at the resident 8 per CU
     LaunchTimer tm(ws, st);
     rc = tm.begin(); if (rc) return rc;
-#define MCQ_REDUCE32(GWV) do { \
-        hipLaunchKernelGGL((k_reduce_wave<u32, kLcapWave, GWV>), dim3(grid), dim3(256), 0, st, db->d, od, o, ws->ctr, ws->ovf_list, \
-                           n_queries, loc_off, (const u32*)locs, query_len, db->g); \
-        rc = tm.mark(); if (rc) return rc; \
-        hipLaunchKernelGGL(k_reduce_wave16<GWV>, dim3(grid_for(ws->cap_reduce16, (n_queries + 3) / 4)), dim3(256), 0, st, db->d, od, o, ws->ctr, \
-                           (const u32*)ws->ovf_list, n_queries, loc_off, (const u32*)locs, query_len, db->g); \
-        rc = tm.mark(); if (rc) return rc; \
-        if (od.big) hipLaunchKernelGGL((k_reduce_block<u32, kLcapBlock, 1, GWV>), dim3(ws->n_block_wgs), dim3(1024), 0, st, db->d, od, o, ws->ctr, \
-                                       (const u32*)ws->ovf_list, ws->sc, loc_off, (const u32*)locs, query_len, db->g); \
-        else        hipLaunchKernelGGL((k_reduce_block<u32, kLcapBlock, 0, GWV>), dim3(ws->n_block_wgs), dim3(1024), 0, st, db->d, od, o, ws->ctr, \
-                                       (const u32*)ws->ovf_list, ws->sc, loc_off, (const u32*)locs, query_len, db->g); } while (0)
-    if (db->d.compact) {
-        if (db->g.on) MCQ_REDUCE32(true); else MCQ_REDUCE32(false);
-    } else {
-        hipLaunchKernelGGL((k_reduce_wave<u64, kLcapWave>), dim3(grid), dim3(256), 0, st, db->d, od, o, ws->ctr, ws->ovf_list,
-                           n_queries, loc_off, (const u64*)locs, query_len, db->g);
+    rc = with_loc_form(db, [&](auto L) -> int {
+        using Key = typename decltype(L)::Key;
+        constexpr bool GW = decltype(L)::gw;
+        hipLaunchKernelGGL((k_reduce_wave<Key, kLcapWave, GW>), dim3(grid), dim3(256), 0, st, db->d, od, o, ws->ctr, ws->ovf_list,
+                           n_queries, loc_off, (const Key*)locs, query_len, db->g);
         rc = tm.mark(); if (rc) return rc;
+        if constexpr (sizeof(Key) == 4)     // (no second stage for 64-bit words: its timer slot stays empty)
+            hipLaunchKernelGGL(k_reduce_wave16<GW>, dim3(grid_for(ws->cap_reduce16, (n_queries + 3) / 4)), dim3(256), 0, st, db->d, od, o, ws->ctr,
+                               (const u32*)ws->ovf_list, n_queries, loc_off, (const u32*)locs, query_len, db->g);
         rc = tm.mark(); if (rc) return rc;
-        if (od.big) hipLaunchKernelGGL((k_reduce_block<u64, kLcapBlock, 1>), dim3(ws->n_block_wgs), dim3(1024), 0, st, db->d, od, o, ws->ctr,
-                                       (const u32*)ws->ovf_list, ws->sc, loc_off, (const u64*)locs, query_len, db->g);
-        else        hipLaunchKernelGGL((k_reduce_block<u64, kLcapBlock, 0>), dim3(ws->n_block_wgs), dim3(1024), 0, st, db->d, od, o, ws->ctr,
-                                       (const u32*)ws->ovf_list, ws->sc, loc_off, (const u64*)locs, query_len, db->g);
-    }
-#undef MCQ_REDUCE32
+        auto block = [&](auto BIG) {
+            hipLaunchKernelGGL((k_reduce_block<Key, kLcapBlock, BIG, GW>), dim3(ws->n_block_wgs), dim3(1024), 0, st, db->d, od, o, ws->ctr,
+                               (const u32*)ws->ovf_list, ws->sc, loc_off, (const Key*)locs, query_len, db->g);
+        };
+        if (od.big) block(IntC<1>{}); else block(IntC<0>{});
+        return MCQ_OK;
+    });
+    if (rc) return rc;
     rc = tm.end(); if (rc) return rc;
     HIPCHK(hipGetLastError());
     return MCQ_OK;

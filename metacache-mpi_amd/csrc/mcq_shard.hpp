@@ -583,10 +583,11 @@ static int shard_owner_round(mcq_shard* c, int k, hipStream_t st, bool exact) {
     auto lookup = [&](int count_only) {
         hipLaunchKernelGGL(k_shard_zero_headers, dim3(1), dim3(64), 0, st, b.sendR, rblk_words(c), n);
         const dim3 grid(n * c->capT);
-        if (c->db->d.compact) hipLaunchKernelGGL(k_shard_lookup<u32>, grid, dim3(256), 0, st, c->db->d, n, (const u32*)recvF, c->capF, capFx, c->capT,
-                                                 b.sendR, (u32*)b.sendL, c->capL, err, count_only);
-        else                  hipLaunchKernelGGL(k_shard_lookup<u64>, grid, dim3(256), 0, st, c->db->d, n, (const u32*)recvF, c->capF, capFx, c->capT,
-                                                 b.sendR, (u64*)b.sendL, c->capL, err, count_only);
+        with_loc_form(c->db, [&](auto L) {
+            using Key = typename decltype(L)::Key;
+            hipLaunchKernelGGL(k_shard_lookup<Key>, grid, dim3(256), 0, st, c->db->d, n, (const u32*)recvF, c->capF, capFx, c->capT,
+                               b.sendR, (Key*)b.sendL, c->capL, err, count_only);
+        });
     };
     lookup(exact && c->capL == 0);
     HIPCHK(hipGetLastError());
