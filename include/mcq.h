@@ -306,7 +306,7 @@ int mcq_ws_timing(mcq_ws* ws, int enable);
 int mcq_ws_kernel_times(mcq_ws* ws, double* ms /* [3] */, uint64_t* n_batches);
 int mcq_ws_kernel_time(mcq_ws* ws, double* total_ms, uint64_t* n_batches);
 
-/* ---- feature-sharded multi-GPU path behind one call (csrc/mcq_shard.hpp) ----------------------
+/* ---- feature-sharded multi-GPU path behind one call (csrc/mcq_shard.hip) ----------------------
  * One process per GPU.  Replaces, for a table that is partitioned over n_ranks GPUs, what mcq_query replaces on one:
  * the worker body of query_batched_parallel2 and the MPI tree merge (src/querying.h:792-825, :867-1073).  The table
  * is partitioned by hash range of h2(feature) (mcq_owner) instead of the reference's tgt % P

@@ -1,15 +1,20 @@
 """Builds csrc/ into libmcq_hip.so (in-tree, so it travels with gpurun snapshots)."""
 import os
 import subprocess
+from concurrent.futures import ThreadPoolExecutor
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 _HDR = os.path.join(os.path.dirname(_HERE), "include", "mcq.h")
-# translation unit -> what it depends on besides itself
+_CSRC = os.path.join(_HERE, "csrc")
+_INTERNAL = [os.path.join(_CSRC, h) for h in ("mcq_internal.hpp", "mcq_device.hpp", "mcq_classify.hpp")] + [_HDR]
+# translation unit -> what it depends on besides itself; the library is linked in this order
 _UNITS = {
-    os.path.join(_HERE, "csrc", "mcq_engine.hip"): [os.path.join(_HERE, "csrc", "mcq_device.hpp"), os.path.join(_HERE, "csrc", "mcq_shard.hpp"),
-                                                     os.path.join(_HERE, "csrc", "mcq_classify.hpp"), _HDR],
-    os.path.join(_HERE, "csrc", "mcq_build.hip"): [_HDR],       # table construction (rocPRIM sorts)
-    os.path.join(_HERE, "csrc", "mcq_classify.hip"): [os.path.join(_HERE, "csrc", "mcq_classify.hpp"), _HDR],   # classification + taxon counts
+    os.path.join(_CSRC, "mcq_engine.hip"): _INTERNAL,      # workspace, fused query, reduce
+    os.path.join(_CSRC, "mcq_table.hip"): _INTERNAL,       # mcq_db_*
+    os.path.join(_CSRC, "mcq_stages.hip"): _INTERNAL,      # staged and routing entry points, batch preparation
+    os.path.join(_CSRC, "mcq_shard.hip"): _INTERNAL,       # mcq_shard_*
+    os.path.join(_CSRC, "mcq_build.hip"): [_HDR],          # table construction (rocPRIM sorts)
+    os.path.join(_CSRC, "mcq_classify.hip"): [os.path.join(_CSRC, "mcq_classify.hpp"), _HDR],   # classification + taxon counts
 }
 _OBJ = os.path.join(_HERE, "csrc", "_obj")
 
@@ -102,7 +107,7 @@ def build_host(force=False, verbose=False):
 
 
 def build_hip(force=False, verbose=False):
-    """hipcc every unit of csrc/ for gfx950 into csrc/_obj/*.o, link libmcq_hip.so"""
+    """hipcc every stale unit of csrc/ for gfx950 into csrc/_obj/*.o, link libmcq_hip.so"""
     if os.environ.get("MCQ_HIP_LIB"):          # a prebuilt variant was asked for: nothing to build
         return lib_path()
     out = lib_path()
@@ -110,19 +115,23 @@ def build_hip(force=False, verbose=False):
     os.makedirs(_OBJ, exist_ok=True)
     extra = os.environ.get("MCQ_HIPCC_FLAGS", "").split()      # tuning experiments, e.g. -DMCQ_WAVE_OCC=7
     force = force or bool(extra)
-    objs, relink = [], force or not os.path.exists(out)
+    objs, stale, relink = [], [], force or not os.path.exists(out)
     for src, deps in _UNITS.items():
         obj = os.path.join(_OBJ, os.path.basename(src) + ".o")
         objs.append(obj)
         newest = max(os.path.getmtime(f) for f in [src] + deps)
         if force or not os.path.exists(obj) or os.path.getmtime(obj) < newest:
-            cmd = [hipcc, "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC"] + extra + ["-c", src, "-o", obj]
-            if verbose:
-                print(" ".join(cmd))
-            subprocess.check_call(cmd)
-            relink = True
+            stale.append([hipcc, "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC"] + extra + ["-c", src, "-o", obj])
         elif os.path.exists(out) and os.path.getmtime(out) < os.path.getmtime(obj):
             relink = True
+    if stale:       # the stale units side by side, each in its own compiler process
+        relink = True
+        if verbose:
+            for cmd in stale:
+                print(" ".join(cmd))
+        jobs = min(len(stale), int(os.environ.get("MAX_JOBS", 16)), 16)
+        with ThreadPoolExecutor(jobs) as pool:
+            list(pool.map(subprocess.check_call, stale))
     if relink:
         cmd = [hipcc, "--offload-arch=gfx950", "-shared", "-fPIC"] + objs + ["-o", out, "-ldl"]
         if verbose:

@@ -7,7 +7,7 @@
 // virtual rank) only the first max_locs = 254 locations in (target, window) order survive
 // (:1090-1092); the table is the union of the P rank tables, lists in (target, window) order.
 //
-// Only the public C ABI of mcq_engine.hip is used from here (mcq_count_windows, mcq_sketch,
+// Only the public C ABI of mcq_stages.hip and mcq_table.hip is used from here (mcq_count_windows, mcq_sketch,
 // mcq_db_create), plus rocPRIM's radix sort for the two global sorts -- a plain library sort of
 // ~3e8 pairs, run once per database, outside any timed region.
 #include <cstring>

@@ -1,6 +1,6 @@
 #pragma once
-// mcq_classify.hpp -- what mcq_engine.hip needs of the classify unit (mcq_classify.hip): the taxonomy handle and the
-// shared error text of mcq_last_error.
+// mcq_classify.hpp -- what the other units need of the classify unit (mcq_classify.hip): the taxonomy handle, and the
+// shared error text of mcq_last_error, which every unit sets through mcq::set_error.
 #include <stdint.h>
 
 #include "../../include/mcq.h"

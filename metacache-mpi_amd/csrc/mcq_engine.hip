@@ -1,4 +1,6 @@
-// mcq_engine.hip -- kernels + C ABI of the MI355X query-path engine (see include/mcq.h).
+// mcq_engine.hip -- the fused query path of the MI355X engine and its C ABI (see include/mcq.h): workspace, mcq_query,
+// mcq_query_pipelined, mcq_reduce, debug tap, timing.  Tables: mcq_table.hip; staged entry points and batch preparation:
+// mcq_stages.hip; the feature-sharded path: mcq_shard.hip; what they share on the host side: mcq_internal.hpp.
 //
 // Three kernels carry the whole per-query path (rows 1-11 of SURVEY.md 8a):
 //
@@ -16,31 +18,10 @@
 //
 // Queries that overflow the first stage are queued through device counters (two queues in
 // one array); the other kernels drain them, so no host round trip sits inside a batch.
-#include <hip/hip_runtime.h>
-#include <stdint.h>
-#include <stdio.h>
-#include <string.h>
-#include <string>
-#include <vector>
-#include <algorithm>
-#include <type_traits>
-
-#include "../../include/mcq.h"
-#include "mcq_device.hpp"
-#include "mcq_classify.hpp"
-
-using namespace mcq;
+#include "mcq_internal.hpp"
 
 // ------------------------------------------------------------------ error handling
 static thread_local std::string g_err;
-static int fail(int code, const std::string& msg) { g_err = msg; return code; }
-#define HIPCHK(expr) do { hipError_t e_ = (expr); if (e_ != hipSuccess) \
-    return fail(MCQ_E_HIP, std::string(#expr) + ": " + hipGetErrorString(e_)); } while (0)
-
-// like HIPCHK inside a constructor-like function: releases what the half-built object already holds before returning
-#define HIPCHK_OR(expr, cleanup) do { hipError_t e_ = (expr); if (e_ != hipSuccess) { cleanup; \
-    return fail(MCQ_E_HIP, std::string(#expr) + ": " + hipGetErrorString(e_)); } } while (0)
-
 extern "C" const char* mcq_last_error(void) { return g_err.c_str(); }
 int mcq::set_error(int code, const char* msg) { g_err = msg; return code; }
 extern "C" const char* mcq_version(void) { return "mcq 0.1 (gfx950)"; }
@@ -61,253 +42,6 @@ static u32 resident_blocks(Kernel kernel, int block_size, int device) {
 // (computed once per workspace for its device and kept in the handle: nothing static, so two devices or two
 // threads in one process do not disturb each other)
 static u32 grid_for(u32 cap, u64 want) { return (u32)std::min<u64>(want ? want : 1, cap ? cap : 1); }
-
-// ------------------------------------------------------------------ handles
-struct mcq_db {
-    DbDev d;
-    int device;
-    u64 nslots;
-    u64 n_keys_local, n_locs_local;
-    uint4* slots;             // one allocation: the buckets, then the lists too long for a bucket
-    u32* tgt2tax;
-    u32* gw_off; u32* gw_blk; // global-window form: first window of every target, block -> target (see LocGW)
-    GwDev g;                  // ... as the kernels take them
-    u32 n_shards, shard_id;
-    u32 bucket_bytes, slots_per_key;
-    u64 n_ext, n_windows;
-    u64 bytes;
-    bool seq_taxa;            // tgt2tax holds sequence-level taxa (bit 31; see make_opt)
-    u64 fmt_sig;              // what the location words of this handle mean (format, field widths, window offsets of the targets, sketch
-                              // parameters), hashed: the ranks of a sharded run compare it before the first words travel (mcq_shard.hpp)
-};
-
-struct ScratchDev {
-    u32* feat; u32* fpos; u64* foff; u64* gbuf; u64* ghits;
-    u32 fmax; u32 lmax;
-};
-
-struct DebugDev {
-    int mode;                 // 0 off, 1 = write match counts, 2 = write matches
-    u64* match_cnt;           // [nq]
-    const u64* match_off;     // [nq+1]
-    u64* matches;
-};
-
-#define MCQ_N_TIMED 3           // kernels of one batch that are timed separately: first wave stage, second wave stage, workgroup kernel
-struct TimedLaunch { hipEvent_t ev[MCQ_N_TIMED + 1]; };
-struct mcq_ws {
-    int device;
-    u64 max_queries, max_bases;
-    CountersDev* ctr;         // device
-    CountersDev* ctr_host;    // pinned
-    u32* ovf_list;            // [ovf_capacity(max_queries)]
-    unsigned long long* probe_buf;   // [(2 x max_queries + 3 x MCQ_OVF_TAIL) x 64]: rows of the back queue, then of the front queue; see CountersDev
-    ScratchDev sc;
-    int n_block_wgs;
-    u32 cap_wave, cap_wave16, cap_reduce16, cap_wave32, cap_wave_many;   // resident workgroups of the wave-per-query kernels on this device
-    // staging for host-pointer calls
-    char* d_bases; u64* d_seq_off; u32* d_cands; u32* d_ncand;
-    u64 last_nq;
-    // host-buffer pipeline (mcq_query_pipelined): two staging sets, copy streams on both sides of the compute stream
-    struct Pipe {
-        char* d_bases[2]; u64* d_seq_off[2]; u32* d_cands[2]; u32* d_ncand[2];
-        hipStream_t s_in, s_k, s_out;
-        hipEvent_t ev_in[2], ev_k[2], ev_out[2];
-        u64 issued;             // calls so far; call i uses set i & 1
-        bool ready;
-    } pipe;
-    // optional per-launch timing of the path's kernels (events between them on the call's stream)
-    int timing;
-    std::vector<TimedLaunch>* ev_used;
-    std::vector<TimedLaunch>* ev_free;
-    double timed_ms[MCQ_N_TIMED]; u64 timed_launches;
-    // classification of every batch while a taxonomy is attached (mcq_ws_set_classify): counts [cls_n] on the device,
-    // cls_ev recorded behind the last batch that added into them
-    const mcq_taxonomy* cls_tx;
-    mcq_classify_opts cls_opt;
-    unsigned long long* cls_counts;
-    u32 cls_n;
-    hipEvent_t cls_ev;
-};
-
-// ------------------------------------------------------------------ kernels: table build
-__global__ void k_fill_slots(uint4* slots, u64 n_uint4) {
-    const u64 stride = (u64)gridDim.x * blockDim.x;
-    for (u64 i = (u64)blockIdx.x * blockDim.x + threadIdx.x; i < n_uint4; i += stride) slots[i] = make_uint4(MCQ_EMPTY, 0, 0, 0);
-}
-
-// A table is handed over in one piece (mcq_db_create: offsets + public 64-bit locations) or in parts (mcq_db_create_parts:
-// list lengths + locations that are global-window words already).  PartView is what the build kernels see of either.
-struct PartView {
-    u64 n_keys, n_locs;
-    const u32* keys;
-    const u64* off;           // [n_keys + 1] exclusive offsets of the lists inside `locs`
-    const void* locs;         // u64 (tgt << 32) | win, or (gw_words) u32 global window indices
-    u32 gw_words;
-};
-// source location i of a part -> the handle's native word: bit fields (tgt << wb) | win, or, with gw_off, the global window index
-// gw_off[tgt] + win; a source that holds global-window words already is copied (the handle then keeps that form)
-template <class KeyT>
-__device__ __forceinline__ KeyT loc_native(const PartView& pv, u64 i, u32 wb, const u32* __restrict__ gw_off) {
-    if (pv.gw_words) return (KeyT)static_cast<const u32*>(pv.locs)[i];
-    const u64 l = static_cast<const u64*>(pv.locs)[i];
-    if (sizeof(KeyT) == 4 && gw_off) return (KeyT)(gw_off[(u32)(l >> 32)] + (u32)l);
-    return (KeyT)(((l >> 32) << wb) | (l & 0xFFFFFFFFull));
-}
-// one thread per key: claim a bucket with CAS on the key word, then fill it: length, and either the list itself
-// (64-B buckets: up to 14 compact / 7 wide locations) or the offset of the list among the long ones (ext_off + ext_base).
-// bq = uint4 per bucket (4 or 1); inl = longest inline list (0 with 16-B slots)
-template <class KeyT>
-__global__ void k_insert_keys(uint4* slots, u32 mask, u32 bq, u32 inl, PartView pv, const u64* own_len, const u64* ext_off, u64 ext_base,
-                              u32 wb, const u32* gw_off) {
-    u64 i = (u64)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= pv.n_keys) return;
-    const u32 len = (u32)own_len[i];
-    if (len == 0) return;                                 // foreign or empty
-    const u32 key = pv.keys[i];
-    u32 idx = tmh(key) & mask;
-    while (true) {
-        u32* w = reinterpret_cast<u32*>(&slots[(u64)idx * bq]);
-        const u32 prev = atomicCAS(w, MCQ_EMPTY, key);
-        if (prev == MCQ_EMPTY) {
-            w[1] = len;
-            if (len <= inl) {
-                KeyT* dst = reinterpret_cast<KeyT*>(w + 2);
-                const u64 src = pv.off[i];
-                for (u32 t = 0; t < len; ++t) dst[t] = loc_native<KeyT>(pv, src + t, wb, gw_off);
-            } else { const u64 b = ext_base + ext_off[i]; w[2] = (u32)b; w[3] = (u32)(b >> 32); }
-            return;
-        }
-        idx = (idx + 1) & mask;
-    }
-}
-
-// list length per key if owned by this shard, else 0
-__global__ void k_owned_len(PartView pv, u32 n_shards, u32 shard_id, u64* out_len) {
-    u64 i = (u64)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= pv.n_keys) return;
-    u32 own = (u32)(((u64)tmh(pv.keys[i]) * n_shards) >> 32);
-    out_len[i] = (own == shard_id) ? (pv.off[i + 1] - pv.off[i]) : 0;
-}
-// owned non-empty keys, owned locations, and of those the ones in lists longer than inl64 (what a 64-B bucket cannot hold): totals[3]
-__global__ void k_owned_totals(const u64* own_len, u64 n_keys, u32 inl64, unsigned long long* totals) {
-    unsigned long long k = 0, l = 0, x = 0;
-    const u64 stride = (u64)gridDim.x * blockDim.x;
-    for (u64 i = (u64)blockIdx.x * blockDim.x + threadIdx.x; i < n_keys; i += stride) { const u64 v = own_len[i]; k += v > 0; l += v; x += v > inl64 ? v : 0; }
-    for (int d = 32; d > 0; d >>= 1) { k += __shfl_xor(k, d, 64); l += __shfl_xor(l, d, 64); x += __shfl_xor(x, d, 64); }
-    if ((threadIdx.x & 63) == 0 && l) { atomicAdd(&totals[0], k); atomicAdd(&totals[1], l); if (x) atomicAdd(&totals[2], x); }
-}
-__global__ void k_ext_len(const u64* own_len, u64 n_keys, u32 inline_max, u64* ext_len) {
-    u64 i = (u64)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i < n_keys) { const u64 len = own_len[i]; ext_len[i] = len > inline_max ? len : 0; }
-}
-
-// copy the owned long lists behind the buckets
-template <class KeyT>
-__global__ void k_copy_lists(PartView pv, const u64* ext_off, KeyT* out, u32 wb, const u32* gw_off) {
-    // one wave per key, grid-stride (the grid is bounded: total threads must stay < 2^32)
-    const u32 lane = threadIdx.x & 63;
-    const u64 nwaves = ((u64)gridDim.x * blockDim.x) >> 6;
-    for (u64 key = ((u64)blockIdx.x * blockDim.x + threadIdx.x) >> 6; key < pv.n_keys; key += nwaves) {
-        u64 b = ext_off[key], n = ext_off[key + 1] - b, src = pv.off[key];
-        for (u64 t = lane; t < n; t += 64) out[b + t] = loc_native<KeyT>(pv, src + t, wb, gw_off);
-    }
-}
-
-// ---- global-window form: extents of the targets, offsets, block table
-// ext[t] = 1 + largest window id of target t among the locations (a racy read first: the maximum only grows, and most
-// locations lose against it without an atomic)
-__global__ void k_tgt_extent(const u64* locs, u64 n, u32 n_targets, u32* ext) {
-    const u64 stride = (u64)gridDim.x * blockDim.x;
-    for (u64 i = (u64)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) {
-        const u64 l = locs[i];
-        const u32 t = (u32)(l >> 32), w = (u32)l;
-        if (t < n_targets && w != 0xFFFFFFFFu && *reinterpret_cast<volatile const u32*>(&ext[t]) <= w) atomicMax(&ext[t], w + 1);
-    }
-}
-// gw_blk[b] = (last target t with gw_off[t] <= b << shift, gw_off[t]) (targets without windows are skipped)
-__global__ void k_gw_blocks(const u32* gw_off, u32 n_targets, u32 shift, u64 n_blk, uint2* blk) {
-    const u64 b = (u64)blockIdx.x * blockDim.x + threadIdx.x;
-    if (b >= n_blk) return;
-    const u64 w = b << shift;
-    u32 lo = 0, hi = n_targets ? n_targets - 1 : 0;
-    while (lo < hi) { const u32 mid = (lo + hi + 1) >> 1; if ((u64)gw_off[mid] <= w) lo = mid; else hi = mid - 1; }
-    blk[b] = make_uint2(lo, gw_off[lo]);
-}
-__global__ void k_u64_to_u32(const u64* in, u32* out, u64 n) {
-    const u64 i = (u64)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i < n) out[i] = (u32)in[i];
-}
-
-// largest window id over all locations (decides whether locations fit 32 bits)
-__global__ void k_max_win(const u64* locs, u64 n, u32* out) {
-    u32 m = 0;
-    const u64 stride = (u64)gridDim.x * blockDim.x;
-    for (u64 i = (u64)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) { u32 w = (u32)locs[i]; m = w > m ? w : m; }
-    for (int d = 32; d > 0; d >>= 1) { u32 o = __shfl_xor(m, d, 64); m = o > m ? o : m; }
-    if ((threadIdx.x & 63) == 0) atomicMax(out, m);
-}
-
-// exclusive scan of u64 array (single workgroup of 256 or 1024 threads)
-template <class InT>
-__global__ __launch_bounds__(1024) void k_scan_u64(const InT* in, u64* out, u64 n) {
-    __shared__ u64 s_w[16];
-    __shared__ u64 s_carry;
-    const u32 tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, NT = blockDim.x;
-    if (tid == 0) s_carry = 0;
-    __syncthreads();
-    for (u64 base = 0; base < n; base += NT) {
-        u64 i = base + tid;
-        u64 v = (i < n) ? in[i] : 0, x = v;
-        for (int d = 1; d < 64; d <<= 1) {
-            u64 t = __shfl_up(x, d, 64);
-            if (lane >= (u32)d) x += t;
-        }
-        if (lane == 63) s_w[wave] = x;
-        __syncthreads();
-        u64 woff = 0;
-        for (u32 w = 0; w < wave; ++w) woff += s_w[w];
-        u64 carry = s_carry;
-        if (i < n) out[i] = carry + woff + x - v;
-        __syncthreads();
-        if (tid == NT - 1) s_carry = carry + woff + x;
-        __syncthreads();
-    }
-    if (tid == 0) out[n] = s_carry;
-}
-
-// exclusive scan of n u64 values in three launches: per-tile scan + tile sums, scan of the
-// tile sums (one workgroup), add.  out has n + 1 entries (out[n] = total).
-#define MCQ_SCAN_TILE 8192
-template <class InT>
-__global__ __launch_bounds__(1024) void k_scan_tiles(const InT* in, u64* out, u64 n, u64* tile_sums) {
-    __shared__ u64 s_w[16];
-    __shared__ u64 s_carry;
-    const u32 tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, NT = blockDim.x;
-    if (tid == 0) s_carry = 0;
-    __syncthreads();
-    const u64 t0 = (u64)blockIdx.x * MCQ_SCAN_TILE;
-    for (u64 base = t0; base < t0 + MCQ_SCAN_TILE; base += NT) {
-        const u64 i = base + tid;
-        u64 v = (i < n) ? in[i] : 0, x = v;
-        for (int d = 1; d < 64; d <<= 1) { u64 t = __shfl_up(x, d, 64); if (lane >= (u32)d) x += t; }
-        if (lane == 63) s_w[wave] = x;
-        __syncthreads();
-        u64 woff = 0;
-        for (u32 w = 0; w < wave; ++w) woff += s_w[w];
-        const u64 carry = s_carry;
-        if (i < n) out[i] = carry + woff + x - v;
-        __syncthreads();
-        if (tid == NT - 1) s_carry = carry + woff + x;
-        __syncthreads();
-    }
-    if (tid == 0) tile_sums[blockIdx.x] = s_carry;
-}
-__global__ void k_scan_add(u64* out, u64 n, const u64* tile_off) {
-    const u64 i = (u64)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i < n) out[i] += tile_off[i / MCQ_SCAN_TILE];
-    if (i == 0) out[n] = tile_off[(n + MCQ_SCAN_TILE - 1) / MCQ_SCAN_TILE];
-}
 
 // ------------------------------------------------------------------ kernel: wave per query
 #define MCQ_LCAP_WAVE16 1024    // longest match list of the second wave stage (16 keys per lane)
@@ -1750,117 +1484,6 @@ __global__ __launch_bounds__(NT, sizeof(KeyT) == 4 ? 8 : 4) void k_query_block(D
 #endif
 }
 
-// ------------------------------------------------------------------ staged kernels (sharded path, DB build)
-__global__ void k_count_windows(const u64* seq_off, u32 ranges, u64 n_seqs, u32 W, u32 S, u64* cnt) {
-    u64 i = (u64)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i < n_seqs) { u64 bg, en; seq_bounds(seq_off, ranges, i, bg, en); cnt[i] = num_windows(en - bg, W, S); }
-}
-
-// one wave per window: window w belongs to the last sequence i with win_off[i] <= w
-__global__ __launch_bounds__(256) void k_sketch_windows(DbDev db, const char* bases, const u64* seq_off, u32 ranges, u64 n_seqs,
-                                                        const u64* win_off, u32* features, u32* n_feat) {
-    const u32 lane = threadIdx.x & 63;
-    const u32 wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    const u64 n_win = win_off[n_seqs];
-    const u64 nwaves = (u64)gridDim.x * 4;
-    __shared__ u32 s_sk[4][128];
-    u32* sk = s_sk[wave];
-    for (u64 w = (u64)blockIdx.x * 4 + wave; w < n_win; w += nwaves) {
-        u64 lo = 0, hi = n_seqs;
-        while (hi - lo > 1) { u64 mid = (lo + hi) >> 1; if (win_off[mid] <= w) lo = mid; else hi = mid; }
-        u64 o0, oe; seq_bounds(seq_off, ranges, lo, o0, oe);
-        const u64 n = oe - o0;
-        u64 beg; u32 wl;
-        window_of(n, db.winlen, db.winstride, (u32)(w - win_off[lo]), beg, wl);
-        u32 m = wave_sketch(bases + o0 + beg, wl, db.k, db.s, lane, sk, sk + 64);
-        if (lane < db.s) features[w * db.s + lane] = (lane < m) ? sk[64 + lane] : MCQ_EMPTY;
-        if (lane == 0) n_feat[w] = m;
-        wave_sync();
-    }
-}
-
-// one wave per sequence, looping over its (few) windows: no search, window math in 32 bits
-__global__ __launch_bounds__(256) void k_sketch_seqs(DbDev db, const char* bases, const u64* seq_off, u32 ranges, u64 n_seqs,
-                                                     const u64* win_off, u32* features, u32* n_feat) {
-    const u32 lane = threadIdx.x & 63;
-    const u32 wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    const u64 nwaves = (u64)gridDim.x * 4;
-    __shared__ u32 s_sk[4][128];
-    u32* sk = s_sk[wave];
-    for (u64 i = (u64)blockIdx.x * 4 + wave; i < n_seqs; i += nwaves) {
-        u64 o0, oe; seq_bounds(seq_off, ranges, i, o0, oe);
-        const u32 n = (u32)(oe - o0);
-        const u64 w0 = win_off[i];
-        const u32 nw = (u32)(win_off[i + 1] - w0);
-        for (u32 j = 0; j < nw; ++j) {
-            u32 beg, wl;
-            window_of32(n, db.winlen, db.winstride, db.magic_stride, j, beg, wl);
-            u32 m = wave_sketch(bases + o0 + beg, wl, db.k, db.s, lane, sk, sk + 64);
-            if (lane < db.s) features[(w0 + j) * db.s + lane] = (lane < m) ? sk[64 + lane] : MCQ_EMPTY;
-            if (lane == 0) n_feat[w0 + j] = m;
-            wave_sync();
-        }
-    }
-}
-
-__global__ void k_lookup_count(DbDev db, const u32* features, u64 n, u32* list_len, u64* list_src) {
-    u64 i = (u64)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n) return;
-    u64 off; u32 len;
-    probe(db, features[i], off, len);
-    list_len[i] = len;
-    if (list_src) list_src[i] = off;
-}
-
-// one wave per 64 consecutive features: (probe again unless the list starts were kept), then
-// copy the lists cooperatively, in the handle's native location width
-template <class KeyT>
-__global__ __launch_bounds__(256) void k_lookup_gather(DbDev db, const u32* features, u64 n, const u32* list_len,
-                                                       const u64* list_src, const u64* out_off, KeyT* out_locs) {
-    const u32 lane = threadIdx.x & 63;
-    const u32 wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    const u64 ngroups = (n + 63) / 64, nwaves = (u64)gridDim.x * 4;
-    const KeyT* __restrict__ locs = static_cast<const KeyT*>(db.locs);
-    for (u64 g = (u64)blockIdx.x * 4 + wave; g < ngroups; g += nwaves) {
-        const u64 i = g * 64 + lane;
-        u64 off = 0; u32 len = 0;
-        if (i < n) {
-            if (list_src) { off = list_src[i]; len = list_len[i]; }
-            else probe(db, features[i], off, len);
-        }
-        const u64 obase = out_off[g * 64];
-        u32 incl = wave_incl_scan_dpp(len);
-        u32 pos = incl - len;
-        const u32 T = bcast(incl, 63);
-        for (u32 base = 0; base < T; base += 256) {           // four 64-element chunks in flight per round trip
-            KeyT v[4];
-#pragma unroll
-            for (int u = 0; u < 4; ++u) {
-                v[u] = 0;
-                if (base + (u32)(u * 64) < T) {
-                    const u32 t = base + u * 64 + lane;
-                    const u32 tt = t < T ? t : T - 1;
-                    u32 lo = 0;
-#pragma unroll
-                    for (u32 step = 32; step > 0; step >>= 1) {
-                        u32 c = lo + step;
-                        u32 pc = __shfl(pos, (int)(c & 63), 64);
-                        if (c < 64 && pc <= tt) lo = c;
-                    }
-                    u32 pj = __shfl(pos, (int)lo, 64);
-                    u32 olo = __shfl((u32)off, (int)lo, 64), ohi = __shfl((u32)(off >> 32), (int)lo, 64);
-                    if (t < T) v[u] = locs[(((u64)ohi << 32) | olo) + (tt - pj)];
-                }
-            }
-#pragma unroll
-            for (int u = 0; u < 4; ++u) {
-                const u32 t = base + u * 64 + lane;
-                if (t < T) out_locs[obase + t] = v[u];
-            }
-        }
-    }
-}
-
 // rows 8-11 from per-query location segments in the handle's native width (home GPU of the sharded path)
 template <class KeyT, int E>
 __device__ __forceinline__ void load_sort_store(KeyT* buf, const KeyT* src, u32 T, u32 lane) {
@@ -1998,226 +1621,7 @@ __global__ __launch_bounds__(1024) void k_reduce_block(DbDev db, OptDev opt, Out
     }
 }
 
-// ------------------------------------------------------------------ sharded-path routing kernels
-// Bucket features by owning shard (mcq_owner); EMPTY features are dropped.  Counting sort
-// over workgroup tiles: (1) every workgroup counts its tile per shard, (2) one workgroup
-// turns the [shard][workgroup] counts into start offsets (shard-major), (3) every workgroup
-// places its features; waves of a workgroup claim their slice with an LDS atomic.
-#define MCQ_BUCKET_MAX_SHARDS 64
-__device__ __forceinline__ u32 owner_of(u32 f, u32 n_shards) {
-    return f == MCQ_EMPTY ? 0xFFFFFFFFu : (u32)(((u64)tmh(f) * n_shards) >> 32);
-}
-__global__ __launch_bounds__(256) void k_bucket_count(const u32* features, u64 n, u32 n_shards, u64 tile,
-                                                      unsigned long long* blk_counts /* [n_shards][gridDim.x] */) {
-    __shared__ u32 s_c[MCQ_BUCKET_MAX_SHARDS];
-    const u32 lane = threadIdx.x & 63;
-    if (threadIdx.x < MCQ_BUCKET_MAX_SHARDS) s_c[threadIdx.x] = 0;
-    __syncthreads();
-    const u64 t0 = (u64)blockIdx.x * tile, t1 = t0 + tile < n ? t0 + tile : n;
-    for (u64 i0 = t0 + (threadIdx.x & ~63u); i0 < t1; i0 += 256) {
-        const u64 i = i0 + lane;
-        const u32 own = owner_of(i < t1 ? features[i] : MCQ_EMPTY, n_shards);
-        for (u32 o = 0; o < n_shards; ++o) {
-            u32 c = (u32)__builtin_popcountll(__ballot(own == o));
-            if (lane == 0 && c) atomicAdd(&s_c[o], c);
-        }
-    }
-    __syncthreads();
-    if (threadIdx.x < n_shards) blk_counts[(u64)threadIdx.x * gridDim.x + blockIdx.x] = s_c[threadIdx.x];
-}
-// exclusive scan over the [shard][workgroup] matrix in shard-major order; totals per shard to counts[]
-__global__ __launch_bounds__(1024) void k_bucket_scan(unsigned long long* blk_counts, u32 n_shards, u32 n_blocks, unsigned long long* counts) {
-    __shared__ unsigned long long s_w[16];
-    __shared__ unsigned long long s_carry;
-    const u32 tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const u64 n = (u64)n_shards * n_blocks;
-    if (tid == 0) s_carry = 0;
-    __syncthreads();
-    for (u64 base = 0; base < n; base += 1024) {
-        const u64 i = base + tid;
-        unsigned long long v = i < n ? blk_counts[i] : 0, x = v;
-        for (int d = 1; d < 64; d <<= 1) { unsigned long long t = __shfl_up(x, d, 64); if (lane >= (u32)d) x += t; }
-        if (lane == 63) s_w[wave] = x;
-        __syncthreads();
-        unsigned long long woff = 0;
-        for (u32 w = 0; w < wave; ++w) woff += s_w[w];
-        const unsigned long long carry = s_carry;
-        if (i < n) blk_counts[i] = carry + woff + x - v;
-        __syncthreads();
-        if (tid == 1023) s_carry = carry + woff + x;
-        __syncthreads();
-    }
-    // per-shard totals = difference of the shard's first offsets
-    if (tid < n_shards) {
-        unsigned long long b0 = blk_counts[(u64)tid * n_blocks];
-        unsigned long long b1 = (tid + 1 < n_shards) ? blk_counts[(u64)(tid + 1) * n_blocks] : s_carry;
-        counts[tid] = b1 - b0;
-    }
-}
-__global__ __launch_bounds__(256) void k_bucket_fill(const u32* features, u64 n, u32 n_shards, u64 tile,
-                                                     const unsigned long long* blk_off, u32* bucketed, u32* src_index) {
-    __shared__ unsigned long long s_cur[MCQ_BUCKET_MAX_SHARDS];
-    const u32 lane = threadIdx.x & 63;
-    if (threadIdx.x < n_shards) s_cur[threadIdx.x] = blk_off[(u64)threadIdx.x * gridDim.x + blockIdx.x];
-    __syncthreads();
-    const u64 t0 = (u64)blockIdx.x * tile, t1 = t0 + tile < n ? t0 + tile : n;
-    for (u64 i0 = t0 + (threadIdx.x & ~63u); i0 < t1; i0 += 256) {
-        const u64 i = i0 + lane;
-        const u32 f = i < t1 ? features[i] : MCQ_EMPTY;
-        const u32 own = owner_of(f, n_shards);
-        for (u32 o = 0; o < n_shards; ++o) {
-            const u64 m = __ballot(own == o);
-            const u32 c = (u32)__builtin_popcountll(m);
-            unsigned long long start = 0;
-            if (lane == 0 && c) start = atomicAdd(&s_cur[o], (unsigned long long)c);
-            start = ((unsigned long long)__builtin_amdgcn_readfirstlane((u32)(start >> 32)) << 32) | __builtin_amdgcn_readfirstlane((u32)start);
-            if (own == o) {
-                const u64 d = start + lane_rank(m);
-                bucketed[d] = f; src_index[d] = (u32)i;
-            }
-        }
-    }
-}
-
-// list i = src_locs[src_off[i] .. src_off[i+1]) goes to dst_locs[dst_off[dst_slot[i]] ..); one wave per 64 lists
-template <class KeyT>
-__global__ __launch_bounds__(256) void k_scatter_lists(u64 n_lists, const u64* src_off, const u32* dst_slot, const u64* dst_off,
-                                                       const KeyT* src_locs, KeyT* dst_locs) {
-    const u32 lane = threadIdx.x & 63;
-    const u32 wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    const u64 ngroups = (n_lists + 63) / 64, nwaves = (u64)gridDim.x * 4;
-    for (u64 g = (u64)blockIdx.x * 4 + wave; g < ngroups; g += nwaves) {
-        const u64 i = g * 64 + lane;
-        u64 so = 0, d = 0; u32 len = 0;
-        if (i < n_lists) { so = src_off[i]; len = (u32)(src_off[i + 1] - so); d = dst_off[dst_slot[i]]; }
-        const u64 sbase = src_off[g * 64];
-        u32 incl = wave_incl_scan_dpp(len);
-        u32 pos = incl - len;
-        const u32 T = bcast(incl, 63);
-        for (u32 base = 0; base < T; base += 64) {
-            const u32 t = base + lane;
-            const u32 tt = t < T ? t : T - 1;
-            u32 lo = 0;
-#pragma unroll
-            for (u32 step = 32; step > 0; step >>= 1) {
-                u32 c = lo + step;
-                u32 pc = __shfl(pos, (int)(c & 63), 64);
-                if (c < 64 && pc <= tt) lo = c;
-            }
-            u32 pj = __shfl(pos, (int)lo, 64);
-            u32 dlo = __shfl((u32)d, (int)lo, 64), dhi = __shfl((u32)(d >> 32), (int)lo, 64);
-            if (t < T) dst_locs[(((u64)dhi << 32) | dlo) + (tt - pj)] = src_locs[sbase + t];
-        }
-    }
-}
-__global__ void k_scatter_len(const u32* list_len, const u32* slot, u64 n, u32* slot_len) {
-    const u64 i = (u64)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i < n) slot_len[slot[i]] = list_len[i];
-}
-// per query: location segment start = offset of its first feature slot; length = sum of its mates
-__global__ void k_query_offsets(u64 nq, u32 qstep, u32 s, const u64* win_off, const u64* seq_off, u32 ranges, const u64* dst_off, u64 n_slots,
-                                u64* loc_off, u32* query_len) {
-    const u64 q = (u64)blockIdx.x * blockDim.x + threadIdx.x;
-    if (q < nq) {
-        loc_off[q] = dst_off[win_off[q * qstep] * s];
-        u64 len = 0;
-        for (u32 m = 0; m < qstep; ++m) { u64 bg, en; seq_bounds(seq_off, ranges, q * qstep + m, bg, en); len += en - bg; }
-        query_len[q] = (u32)len;
-    }
-    if (q == 0) loc_off[nq] = dst_off[n_slots];
-}
-
-// ------------------------------------------------------------------ row f4: FASTQ text -> sequence ranges on the GPU
-// FASTQ is four lines per record and the reference reads it exactly so (fastq_reader::read_next,
-// src/sequence_io.cpp:251-285: getline header, getline data, getline '+', getline qualities), so
-// the sequence of record r is line 4r+1.  Workgroup tiles of 4 KiB count their newlines, a scan
-// gives every newline its line number, and the newline that ends line 4r (4r+1) writes the
-// begin (end) of sequence r.  The text is not copied: mcq_query reads the bases in place
-// (MCQ_BATCH_RANGES).  Like getline, a '\r' before the newline stays part of the line.
-#define MCQ_FQ_TILE 4096
-// 16-bit mask of the newlines among text[base .. base+16): one 16-B load and exact per-byte zero detection of
-// (word ^ 0x0A0A0A0A) when the address is aligned and inside the buffer, a byte loop otherwise
-__device__ __forceinline__ u32 fq_newline_mask(const char* __restrict__ text, u64 base, u64 n) {
-    u32 mask = 0;
-    if (base + 16 <= n && ((reinterpret_cast<uintptr_t>(text) + base) & 15) == 0) {
-        const uint4 v = *reinterpret_cast<const uint4*>(text + base);
-        const u32 w[4] = {v.x, v.y, v.z, v.w};
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-            const u32 m = w[i] ^ 0x0A0A0A0Au;
-            const u32 z = ~(((m & 0x7F7F7F7Fu) + 0x7F7F7F7Fu) | m) & 0x80808080u;     // bit 7 of every zero byte
-            mask |= (((z >> 7) & 1u) | ((z >> 14) & 2u) | ((z >> 21) & 4u) | ((z >> 28) & 8u)) << (4 * i);
-        }
-    } else {
-        for (u32 j = 0; j < 16; ++j) mask |= (u32)(base + j < n && text[base + j] == '\n') << j;
-    }
-    return mask;
-}
-__global__ __launch_bounds__(256) void k_fq_count(const char* text, u64 n, u64* tile_cnt) {
-    __shared__ u32 s_c;
-    if (threadIdx.x == 0) s_c = 0;
-    __syncthreads();
-    const u64 base = (u64)blockIdx.x * MCQ_FQ_TILE + (u64)threadIdx.x * 16;
-    u32 c = (u32)__builtin_popcount(fq_newline_mask(text, base, n));
-    for (int d = 32; d > 0; d >>= 1) c += __shfl_xor(c, d, 64);
-    if ((threadIdx.x & 63) == 0 && c) atomicAdd(&s_c, c);
-    __syncthreads();
-    if (threadIdx.x == 0) tile_cnt[blockIdx.x] = s_c;
-}
-// L: lines per record (4: FASTQ; 2: FASTA with the sequence on one line); the sequence is the record's second line
-__global__ __launch_bounds__(256) void k_fq_ranges(const char* text, u64 n, const u64* tile_off, u64 n_tiles, u64* ranges, u64 max_seqs,
-                                                   u64* n_seqs_out, u32 L) {
-    __shared__ u32 s_w[4];
-    const u32 tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const u64 base = (u64)blockIdx.x * MCQ_FQ_TILE + (u64)tid * 16;
-    u32 mask = fq_newline_mask(text, base, n);
-    const u32 c = (u32)__builtin_popcount(mask);
-    u32 incl = wave_incl_scan_dpp(c);
-    if (lane == 63) s_w[wave] = incl;
-    __syncthreads();
-    u32 woff = 0;
-    for (u32 w = 0; w < wave; ++w) woff += s_w[w];
-    u64 line = tile_off[blockIdx.x] + woff + incl - c;         // index of the line my first newline terminates
-    while (mask) {
-        const u32 j = (u32)__builtin_ctz(mask);
-        mask &= mask - 1;
-        const u64 p = base + j;
-        const u64 rec = L == 4 ? line >> 2 : line >> 1;
-        const u32 li = (u32)(line & (L - 1));
-        if (rec < max_seqs) {
-            if (li == 0) ranges[2 * rec] = p + 1;
-            else if (li == 1) ranges[2 * rec + 1] = p;
-        }
-        ++line;
-    }
-    if (blockIdx.x == 0 && tid == 0) {
-        const u64 total = tile_off[n_tiles];
-        u64 ns = total >= 2 ? (total - 2) / L + 1 : 0;          // records whose sequence line is complete
-        *n_seqs_out = ns < max_seqs ? ns : max_seqs;
-    }
-}
-
 // ------------------------------------------------------------------ host helpers
-static u64 pow2ceil64(u64 x) { u64 p = 1; while (p < x) p <<= 1; return p; }
-
-// nt: threads per workgroup, 256 or 1024.  A 1024-thread workgroup needs 16 free wave slots on ONE CU at once: enqueued
-// beside a grid of smaller workgroups that fills the GPU (the sharded path's second stream) it waits until that grid has
-// drained; 256-thread workgroups slip in as the others retire.
-template <class InT>
-static int device_exclusive_scan(const InT* in, u64* out, u64 n, hipStream_t st, u32 nt = 1024) {
-    const u64 ntiles = (n + MCQ_SCAN_TILE - 1) / MCQ_SCAN_TILE;
-    if (ntiles <= 1) { hipLaunchKernelGGL(k_scan_u64<InT>, dim3(1), dim3(nt), 0, st, in, out, n); return MCQ_OK; }
-    u64 *sums = nullptr, *offs = nullptr;
-    HIPCHK(hipMallocAsync((void**)&sums, ntiles * 8, st));
-    HIPCHK(hipMallocAsync((void**)&offs, (ntiles + 1) * 8, st));
-    hipLaunchKernelGGL(k_scan_tiles<InT>, dim3((u32)ntiles), dim3(nt), 0, st, in, out, n, sums);
-    hipLaunchKernelGGL(k_scan_u64<u64>, dim3(1), dim3(nt), 0, st, (const u64*)sums, offs, ntiles);
-    hipLaunchKernelGGL(k_scan_add, dim3((u32)((n + 255) / 256)), dim3(256), 0, st, out, n, (const u64*)offs);
-    HIPCHK(hipFreeAsync(sums, st));
-    HIPCHK(hipFreeAsync(offs, st));
-    return MCQ_OK;
-}
-
 // Fold schedule of the reference's merge loop (src/querying.h:867-1073): senders = odd
 // ranks, receivers = even ranks, i-th sender -> i-th receiver; used senders retire, every
 // second used receiver becomes a sender; floor(log2 P) rounds.
@@ -2244,7 +1648,7 @@ static void fold_schedule(u32 P, std::vector<std::pair<u32, u32>>& sched, std::v
 #else
 #define MCQ_OPT_FLAGS_KNOWN (MCQ_QUIRK_SEQ_DROP | MCQ_FORCE_BLOCK_PATH | MCQ_FORCE_RAW_SORT | MCQ_NO_WAVE16 | MCQ_NO_TWO_CLASS | MCQ_FOLD_BY_LISTS)
 #endif
-static int force_bits(u32 flags) {
+int mcq::force_bits(u32 flags) {
     int f = ((flags & MCQ_FORCE_BLOCK_PATH) ? 1 : 0) | ((flags & MCQ_FORCE_RAW_SORT) ? 2 : 0) | ((flags & MCQ_NO_WAVE16) ? 4 : 0);
 #ifdef MCQ_PROFILE_HOOKS
     f |= (int)((flags >> 12) & 0xFu) << 4;
@@ -2252,7 +1656,7 @@ static int force_bits(u32 flags) {
     return f;
 }
 
-static int make_opt(const mcq_query_opts* o, OptDev& d, const mcq_db* db) {
+int mcq::make_opt(const mcq_query_opts* o, OptDev& d, const mcq_db* db) {
     if (!o) return fail(MCQ_E_ARG, "opts is null");
     if (o->flags & ~(u32)MCQ_OPT_FLAGS_KNOWN) return fail(MCQ_E_ARG, "unknown bits in mcq_query_opts.flags");
     u32 P = o->emulate_ranks ? o->emulate_ranks : 1;
@@ -2290,297 +1694,6 @@ static int make_opt(const mcq_query_opts* o, OptDev& d, const mcq_db* db) {
     }
     return MCQ_OK;
 }
-
-extern "C" uint32_t mcq_owner(uint32_t feature, uint32_t n_shards) {
-    u32 x = feature;
-    x = ((x >> 16) ^ x) * 0x45d9f3bu; x = ((x >> 16) ^ x) * 0x45d9f3bu; x = (x >> 16) ^ x;
-    return (u32)(((u64)x * (n_shards ? n_shards : 1)) >> 32);
-}
-
-// ------------------------------------------------------------------ a handle's form as template arguments
-// The only code that turns d.compact, g.on and d.bsh into the template arguments of the kernels a handle launches.  The location
-// word: LocForm<u64, false> = 64-bit bit fields, <u32, false> = 32-bit bit fields, <u32, true> = the 32-bit global-window index.
-// The bucket layout BSH: 2 = 64-B buckets, 0 = 16-B slots.  f gets the form as a value of the tag type.
-template <class KeyT, bool GW> struct LocForm { using Key = KeyT; static constexpr bool gw = GW; };
-template <int V> using IntC = std::integral_constant<int, V>;
-template <class F> static auto with_loc_form(bool compact, bool gw, F&& f) {
-    if (!compact) return f(LocForm<u64, false>{});
-    return gw ? f(LocForm<u32, true>{}) : f(LocForm<u32, false>{});
-}
-template <class F> static auto with_loc_form(const mcq_db* db, F&& f) { return with_loc_form(db->d.compact != 0, db->g.on != 0, f); }
-template <class F> static auto with_layout(const mcq_db* db, F&& f) {
-    return db->d.bsh != 0 ? f(IntC<2>{}) : f(IntC<0>{});
-}
-
-// ------------------------------------------------------------------ db
-// temporaries are released on every way out; the handle itself by mcq_db_destroy on failure
-struct DevTemps {
-    std::vector<void*> p;
-    ~DevTemps() { for (void* x : p) (void)hipFree(x); }
-    hipError_t alloc(void** out, u64 bytes) { hipError_t e = hipMalloc(out, bytes ? bytes : 1); if (e == hipSuccess) p.push_back(*out); return e; }
-    void release(void* x) { for (auto& q : p) if (q == x) { (void)hipFree(x); q = nullptr; } }
-};
-static int check_params(const mcq_db_desc* desc) {
-    if (desc->k < 1 || desc->k > 16) return fail(MCQ_E_UNSUPPORTED, "k must be 1..16");
-    if (desc->sketch_size < 1 || desc->sketch_size > 32) return fail(MCQ_E_UNSUPPORTED, "sketch_size must be 1..32");
-    if (desc->winlen < desc->k || desc->winlen > 128) return fail(MCQ_E_UNSUPPORTED, "winlen must be k..128");
-    if (desc->winstride < 1) return fail(MCQ_E_ARG, "winstride must be >= 1");
-    if (desc->shard_id >= (desc->n_shards ? desc->n_shards : 1)) return fail(MCQ_E_ARG, "shard_id >= n_shards");
-    return MCQ_OK;
-}
-// windows per target -> gw_off (u32 [n_targets + 1]) and the block table; ext: device, u32 [n_targets]
-static int make_gw_tables(const u32* d_ext, u32 nt, DevTemps& tmp, u32** gw_off, u32** gw_blk, u32* gw_shift, u64* n_windows) {
-    const u32 TB = 256;
-    u64* d_off64 = nullptr;
-    HIPCHK(tmp.alloc((void**)&d_off64, ((u64)nt + 1) * 8));
-    { int rcs = device_exclusive_scan<u32>(d_ext, d_off64, nt, 0); if (rcs) return rcs; }
-    HIPCHK(hipMemcpy(n_windows, d_off64 + nt, 8, hipMemcpyDeviceToHost));
-    *gw_off = nullptr; *gw_blk = nullptr;
-    if (*n_windows >= 0xFFFFFFFFull) return MCQ_OK;       // does not fit 32 bits: the caller decides
-    // block table: at most 2^18 entries (2 MB: stays in L2), at least 64 windows per block
-    u32 sh = 6; while ((*n_windows >> sh) > (1ull << 18)) ++sh;
-    const u64 n_blk = (*n_windows >> sh) + 2;
-    HIPCHK(hipMalloc(gw_off, ((u64)nt + 1) * 4));
-    hipLaunchKernelGGL(k_u64_to_u32, dim3((u32)((nt + 1 + TB - 1) / TB)), dim3(TB), 0, 0, (const u64*)d_off64, *gw_off, (u64)nt + 1);
-    if (hipMalloc(gw_blk, n_blk * 8) != hipSuccess) { (void)hipFree(*gw_off); *gw_off = nullptr; return fail(MCQ_E_HIP, "hipMalloc of the window block table failed"); }
-    hipLaunchKernelGGL(k_gw_blocks, dim3((u32)((n_blk + TB - 1) / TB)), dim3(TB), 0, 0, (const u32*)*gw_off, nt, sh, n_blk, reinterpret_cast<uint2*>(*gw_blk));
-    *gw_shift = sh;
-    return MCQ_OK;
-}
-
-// the table itself, from one or several parts (device memory); format decided by the caller
-static int create_table(const mcq_db_desc* desc, const std::vector<PartView>& parts, u32 compact, u32 wb, u32 gw,
-                        u32* d_gwoff, u32* d_gwblk, u32 gw_shift, u64 n_windows, mcq_db** out) {
-    const u32 TB = 256;
-    const bool dev = (desc->flags & MCQ_DEVICE_PTRS) != 0;
-    const u32 n_shards = desc->n_shards ? desc->n_shards : 1;
-    const u64 locsz = compact ? 4 : 8;
-    mcq_db* db = new mcq_db();
-    memset(db, 0, sizeof(*db));
-    db->device = desc->device; db->n_shards = n_shards; db->shard_id = desc->shard_id;
-    db->gw_off = d_gwoff; db->gw_blk = d_gwblk;           // (released by mcq_db_destroy from here on)
-    DevTemps tmp;
-#define DBCHK(expr) HIPCHK_OR(expr, (void)mcq_db_destroy(db))
-#define DBRC(expr) do { int rc_ = (expr); if (rc_) { (void)mcq_db_destroy(db); return rc_; } } while (0)
-
-    // ---- pass 1 over the parts: owned non-empty keys, owned locations, locations of lists too long for a 64-B bucket
-    u64 nk_max = 0;
-    for (const auto& pv : parts) nk_max = std::max(nk_max, pv.n_keys);
-    u64 *d_len = nullptr, *d_ext = nullptr, *d_new = nullptr; unsigned long long* d_tot = nullptr;
-    DBCHK(tmp.alloc((void**)&d_len, std::max<u64>(1, nk_max) * 8));
-    DBCHK(tmp.alloc((void**)&d_tot, 24));
-    DBCHK(hipMemset(d_tot, 0, 24));
-    const u32 inl64 = bucket_inline_max(2u, compact);
-    for (const auto& pv : parts) {
-        if (!pv.n_keys) continue;
-        hipLaunchKernelGGL(k_owned_len, dim3((u32)((pv.n_keys + TB - 1) / TB)), dim3(TB), 0, 0, pv, n_shards, desc->shard_id, d_len);
-        hipLaunchKernelGGL(k_owned_totals, dim3(1024), dim3(TB), 0, 0, (const u64*)d_len, pv.n_keys, inl64, d_tot);
-    }
-    unsigned long long tot[3] = {0, 0, 0};
-    DBCHK(hipMemcpy(tot, d_tot, 24, hipMemcpyDeviceToHost));
-    const u64 nk_local = tot[0], nl_local = tot[1];
-
-    // ---- layout, per table.  64-B buckets hold a list of up to 14 (7) locations next to its key -- in the sector the
-    // probe has just brought in -- and pay with 64 B per slot; worth it while most lists are that short (2 Gbp: mean
-    // 2.9 locations per key).  On larger tables (>= 10 Gbp: mean >= 4.9) most lists sit behind the array anyway, and
-    // the r01 layout -- 16-B slots, every list behind them -- is 27-30 GB smaller and 1-3 % faster (profiles/r02_db_scale.txt).
-    u32 bucket_bytes = (nk_local == 0 || (double)nl_local / (double)nk_local <= 4.0) ? 64u : 16u;
-    if (desc->flags & MCQ_DB_SLOTS_16) bucket_bytes = 16;
-    if (desc->flags & MCQ_DB_BUCKETS_64) bucket_bytes = 64;
-    if (const char* e = getenv("MCQ_BUCKET_BYTES")) { const int v = atoi(e); if (v == 16 || v == 64) bucket_bytes = (u32)v; }   // tuning knob
-    const u32 bsh = bucket_bytes == 64 ? 2u : 0u;
-    const u32 inl = bucket_inline_max(bsh, compact);
-    const u64 nl_ext = bucket_bytes == 64 ? tot[2] : nl_local;
-
-    // load factor <= 0.25 (43 % of a read's features are not in the table, and every step of a linear probe is a new
-    // sector) while the slot array stays below 48 GB and a third of the free memory, else <= 0.5 -- also when the
-    // allocation at 0.25 fails.  MCQ_SLOTS_PER_KEY overrides.
-    size_t mem_free = 0, mem_total = 0;
-    DBCHK(hipMemGetInfo(&mem_free, &mem_total));
-    const u64 ext_bytes = std::max<u64>(1, nl_ext) * locsz;
-    u64 slots_per_key = 4;
-    { const u64 b4 = pow2ceil64(nk_local * 4) * bucket_bytes; if (b4 > (48ull << 30) || b4 + ext_bytes > mem_free / 3) slots_per_key = 2; }
-    bool spk_forced = false;
-    if (const char* e = getenv("MCQ_SLOTS_PER_KEY")) { slots_per_key = std::max<u64>(1, strtoull(e, nullptr, 10)); spk_forced = true; }   // tuning knob
-    u64 nslots = 0, table_bytes = 0;
-    for (;;) {
-        nslots = std::max<u64>(1024, pow2ceil64(nk_local * slots_per_key));
-        if (nslots > (1ull << 32)) { (void)mcq_db_destroy(db); return fail(MCQ_E_UNSUPPORTED, "table too large"); }
-        table_bytes = nslots * bucket_bytes + ext_bytes;
-        const hipError_t e = hipMalloc(&db->slots, table_bytes);
-        if (e == hipSuccess) break;
-        (void)hipGetLastError();
-        db->slots = nullptr;
-        if (slots_per_key > 2 && !spk_forced) { slots_per_key = 2; continue; }
-        (void)mcq_db_destroy(db);
-        return fail(MCQ_E_HIP, std::string("hipMalloc of the table (") + std::to_string(table_bytes >> 20) + " MiB): " + hipGetErrorString(e));
-    }
-    db->n_keys_local = nk_local; db->n_locs_local = nl_local; db->nslots = nslots;
-    db->bucket_bytes = bucket_bytes; db->slots_per_key = (u32)slots_per_key; db->n_ext = nl_ext; db->n_windows = n_windows;
-    DBCHK(hipMalloc(&db->tgt2tax, std::max<u32>(1, desc->n_targets) * 4));
-    if (desc->n_targets)
-        DBCHK(hipMemcpy(db->tgt2tax, desc->tgt2tax, (u64)desc->n_targets * 4, dev ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice));
-    {
-        std::vector<u32> t2t(desc->n_targets);
-        if (desc->n_targets) DBCHK(hipMemcpy(t2t.data(), db->tgt2tax, (u64)desc->n_targets * 4, hipMemcpyDeviceToHost));
-        db->seq_taxa = false;
-        for (u32 x : t2t) if (x != MCQ_EMPTY && (x & 0x80000000u)) { db->seq_taxa = true; break; }
-    }
-    const u32 bq = bucket_bytes / 16;
-    const u64 n_uint4 = nslots * bq;
-    hipLaunchKernelGGL(k_fill_slots, dim3((u32)std::min<u64>((n_uint4 + TB - 1) / TB, 1u << 20)), dim3(TB), 0, 0, db->slots, n_uint4);
-
-    // ---- pass 2: insert part by part; the long lists of part p start where those of part p - 1 end
-    DBCHK(tmp.alloc((void**)&d_ext, std::max<u64>(1, nk_max) * 8));
-    DBCHK(tmp.alloc((void**)&d_new, (nk_max + 1) * 8));
-    char* ext = reinterpret_cast<char*>(db->slots) + nslots * bucket_bytes;
-    u64 ext_base = 0;
-    for (const auto& pv : parts) {
-        if (!pv.n_keys) continue;
-        const dim3 ig((u32)((pv.n_keys + TB - 1) / TB));
-        hipLaunchKernelGGL(k_owned_len, ig, dim3(TB), 0, 0, pv, n_shards, desc->shard_id, d_len);
-        hipLaunchKernelGGL(k_ext_len, ig, dim3(TB), 0, 0, (const u64*)d_len, pv.n_keys, inl, d_ext);
-        DBRC(device_exclusive_scan<u64>(d_ext, d_new, pv.n_keys, 0));
-        u64 part_ext = 0;
-        DBCHK(hipMemcpy(&part_ext, d_new + pv.n_keys, 8, hipMemcpyDeviceToHost));
-        if (ext_base + part_ext > std::max<u64>(1, nl_ext)) { (void)mcq_db_destroy(db); return fail(MCQ_E_ARG, "the parts changed between the two passes"); }
-        // (64-bit words: wb = 32 and no window table)
-        with_loc_form(compact, gw, [&](auto L) {
-            hipLaunchKernelGGL(k_insert_keys<typename decltype(L)::Key>, ig, dim3(TB), 0, 0, db->slots, (u32)(nslots - 1), bq, inl, pv, (const u64*)d_len, (const u64*)d_new, ext_base, wb, (const u32*)d_gwoff);
-        });
-        DBCHK(hipGetLastError());
-        const dim3 cg((u32)std::min<u64>((pv.n_keys * 64 + TB - 1) / TB, 1u << 20));
-        with_loc_form(compact, gw, [&](auto L) {
-            using Key = typename decltype(L)::Key;
-            hipLaunchKernelGGL(k_copy_lists<Key>, cg, dim3(TB), 0, 0, pv, (const u64*)d_new, reinterpret_cast<Key*>(ext) + ext_base, wb, (const u32*)d_gwoff);
-        });
-        DBCHK(hipGetLastError());
-        ext_base += part_ext;
-    }
-    DBCHK(hipDeviceSynchronize());
-#undef DBCHK
-#undef DBRC
-
-    db->d.slots = db->slots; db->d.slot_mask = (u32)(db->nslots - 1); db->d.locs = db->slots;
-    db->d.bsh = bsh;
-    db->d.wb = wb; db->d.compact = compact;
-    db->g.on = gw; db->g.shift = gw_shift; db->g.off = d_gwoff; db->g.blk = d_gwblk;
-    db->d.tgt2tax = db->tgt2tax; db->d.n_targets = desc->n_targets;
-    db->d.k = desc->k; db->d.s = desc->sketch_size; db->d.winlen = desc->winlen; db->d.winstride = desc->winstride;
-    db->d.tgt_winstride = desc->tgt_winstride ? desc->tgt_winstride : desc->winstride;
-    db->d.magic_stride = (u32)std::min<u64>((1ull << 32) / db->d.winstride, 0xFFFFFFFFull);
-    db->d.magic_tgt_stride = (u32)std::min<u64>((1ull << 32) / db->d.tgt_winstride, 0xFFFFFFFFull);
-    db->bytes = table_bytes + (u64)desc->n_targets * 4 + (gw ? ((u64)desc->n_targets + 1) * 4 + ((n_windows >> gw_shift) + 2) * 4 : 0);
-    {   // FNV-1a over everything a peer must agree on to read this handle's location words
-        u64 h = 1469598103934665603ull;
-        auto mix = [&h](u64 v) { for (int i = 0; i < 8; ++i) { h ^= (v >> (8 * i)) & 0xFF; h *= 1099511628211ull; } };
-        mix(compact); mix(gw); mix(wb); mix(gw ? n_windows : 0); mix(desc->n_targets); mix(db->d.k); mix(db->d.s); mix(db->d.winlen); mix(db->d.winstride);
-        mix(db->d.tgt_winstride); mix(n_shards);
-        if (gw && desc->n_targets) {
-            std::vector<u32> go((u64)desc->n_targets + 1);
-            if (hipMemcpy(go.data(), d_gwoff, go.size() * 4, hipMemcpyDeviceToHost) != hipSuccess) { (void)mcq_db_destroy(db); return fail(MCQ_E_HIP, "reading back the window offsets failed"); }
-            for (u32 v : go) { h ^= v; h *= 1099511628211ull; }
-        }
-        db->fmt_sig = h;
-    }
-    *out = db;
-    return MCQ_OK;
-}
-
-extern "C" int mcq_db_create(const mcq_db_desc* desc, mcq_db** out) {
-    if (!desc || !out) return fail(MCQ_E_ARG, "null argument");
-    { int rc = check_params(desc); if (rc) return rc; }
-    HIPCHK(hipSetDevice(desc->device));
-
-    const bool dev = (desc->flags & MCQ_DEVICE_PTRS) != 0;
-    const u64 nk = desc->n_keys, nl = desc->n_locs;
-    const u32* d_keys = desc->keys; const u64* d_off = desc->list_off; const u64* d_locs = desc->locs;
-    DevTemps tmp;
-    u32* t_keys = nullptr; u64* t_off = nullptr; u64* t_locs = nullptr;
-    if (!dev) {
-        HIPCHK(tmp.alloc((void**)&t_keys, std::max<u64>(1, nk) * 4));
-        HIPCHK(tmp.alloc((void**)&t_off, (nk + 1) * 8));
-        HIPCHK(tmp.alloc((void**)&t_locs, std::max<u64>(1, nl) * 8));
-        if (nk) HIPCHK(hipMemcpy(t_keys, desc->keys, nk * 4, hipMemcpyHostToDevice));
-        HIPCHK(hipMemcpy(t_off, desc->list_off, (nk + 1) * 8, hipMemcpyHostToDevice));
-        if (nl) HIPCHK(hipMemcpy(t_locs, desc->locs, nl * 8, hipMemcpyHostToDevice));
-        d_keys = t_keys; d_off = t_off; d_locs = t_locs;
-    }
-
-    // ---- location format: 32-bit bit fields (tgt << wb) | win when target and window ids fit; else the 32-bit global
-    // window index (any table of fewer than 2^32 - 1 windows); else 64-bit words
-    u32 wb = 32, compact = 0, gw = 0;
-    u32 *d_gwoff = nullptr, *d_gwblk = nullptr; u32 gw_shift = 0; u64 n_windows = 0;
-    if ((desc->flags & MCQ_DB_LOCS_64) && (desc->flags & MCQ_DB_LOCS_GW)) return fail(MCQ_E_ARG, "MCQ_DB_LOCS_64 and MCQ_DB_LOCS_GW exclude each other");
-    if (!(desc->flags & MCQ_DB_LOCS_64)) {
-        u32* d_mw = nullptr; u32 maxwin = 0;
-        HIPCHK(tmp.alloc((void**)&d_mw, 4));
-        HIPCHK(hipMemset(d_mw, 0, 4));
-        if (nl) hipLaunchKernelGGL(k_max_win, dim3(1024), dim3(256), 0, 0, d_locs, nl, d_mw);
-        HIPCHK(hipMemcpy(&maxwin, d_mw, 4, hipMemcpyDeviceToHost));
-        u32 winbits = 1; while (winbits < 32 && (maxwin >> winbits)) ++winbits;
-        u32 maxtgt = desc->n_targets ? desc->n_targets - 1 : 0;
-        u32 tgtbits = 1; while (tgtbits < 32 && (maxtgt >> tgtbits)) ++tgtbits;
-        if (desc->loc_win_bits > winbits) winbits = desc->loc_win_bits;
-        if (!(desc->flags & MCQ_DB_LOCS_GW) && winbits + tgtbits <= 32 && winbits <= 31 &&
-            ((((u64)maxtgt << winbits) | maxwin) < 0xFFFFFFFFull)) { compact = 1; wb = winbits; }
-        else if (desc->n_targets) {
-            // global-window form: windows per target (given, or 1 + the largest window id among the locations), offsets
-            const u32 nt = desc->n_targets;
-            u32* d_ext = nullptr;
-            HIPCHK(tmp.alloc((void**)&d_ext, (u64)nt * 4));
-            if (desc->tgt_windows) HIPCHK(hipMemcpy(d_ext, desc->tgt_windows, (u64)nt * 4, dev ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice));
-            else {
-                HIPCHK(hipMemset(d_ext, 0, (u64)nt * 4));
-                if (nl) hipLaunchKernelGGL(k_tgt_extent, dim3(2048), dim3(256), 0, 0, d_locs, nl, nt, d_ext);
-            }
-            int rc = make_gw_tables(d_ext, nt, tmp, &d_gwoff, &d_gwblk, &gw_shift, &n_windows); if (rc) return rc;
-            if (d_gwoff) { compact = 1; gw = 1; wb = 0; }
-            else if (desc->flags & MCQ_DB_LOCS_GW) return fail(MCQ_E_UNSUPPORTED, "MCQ_DB_LOCS_GW: the table has 2^32 - 1 windows or more");
-        }
-    }
-    PartView pv; pv.n_keys = nk; pv.n_locs = nl; pv.keys = d_keys; pv.off = d_off; pv.locs = d_locs; pv.gw_words = 0;
-    return create_table(desc, std::vector<PartView>{pv}, compact, wb, gw, d_gwoff, d_gwblk, gw_shift, n_windows, out);
-}
-
-// The same for a table that is larger than the memory for its one-piece description (RefSeq scale: the 64-bit locations
-// alone would be 8 B x 1.7e10): handed over in parts -- e.g. one per feature-hash range, as mcq_build_parts makes them --
-// whose locations are 32-bit global-window words already.  Device memory only.
-extern "C" int mcq_db_create_parts(const mcq_db_desc* desc, const mcq_db_part* parts, uint32_t n_parts, mcq_db** out) {
-    if (!desc || !out || (n_parts && !parts)) return fail(MCQ_E_ARG, "null argument");
-    { int rc = check_params(desc); if (rc) return rc; }
-    if (!(desc->flags & MCQ_DEVICE_PTRS)) return fail(MCQ_E_ARG, "mcq_db_create_parts takes device pointers");
-    if (desc->flags & MCQ_DB_LOCS_64) return fail(MCQ_E_UNSUPPORTED, "parts hold global-window words: the handle keeps that form");
-    if (!desc->tgt_windows || !desc->n_targets) return fail(MCQ_E_ARG, "mcq_db_create_parts needs tgt_windows (the words of the parts are defined by it)");
-    HIPCHK(hipSetDevice(desc->device));
-    DevTemps tmp;
-    u32 *d_gwoff = nullptr, *d_gwblk = nullptr; u32 gw_shift = 0; u64 n_windows = 0;
-    int rc = make_gw_tables(desc->tgt_windows, desc->n_targets, tmp, &d_gwoff, &d_gwblk, &gw_shift, &n_windows); if (rc) return rc;
-    if (!d_gwoff) return fail(MCQ_E_UNSUPPORTED, "the table has 2^32 - 1 windows or more");
-    std::vector<PartView> pvs;
-    std::vector<u64*> offs;
-    for (u32 i = 0; i < n_parts; ++i) {
-        const mcq_db_part& p = parts[i];
-        if (p.n_keys && (!p.keys || !p.list_len || (p.n_locs && !p.locs))) { (void)hipFree(d_gwoff); (void)hipFree(d_gwblk); return fail(MCQ_E_ARG, "null pointer in a part"); }
-        u64* off = nullptr;
-        if (tmp.alloc((void**)&off, (p.n_keys + 1) * 8) != hipSuccess) { (void)hipFree(d_gwoff); (void)hipFree(d_gwblk); return fail(MCQ_E_HIP, "hipMalloc of a part's list offsets failed"); }
-        rc = device_exclusive_scan<u32>(p.list_len, off, p.n_keys, 0);
-        if (rc) { (void)hipFree(d_gwoff); (void)hipFree(d_gwblk); return rc; }
-        PartView pv; pv.n_keys = p.n_keys; pv.n_locs = p.n_locs; pv.keys = p.keys; pv.off = off; pv.locs = p.locs; pv.gw_words = 1;
-        pvs.push_back(pv);
-    }
-    return create_table(desc, pvs, 1, 0, 1, d_gwoff, d_gwblk, gw_shift, n_windows, out);
-}
-
-extern "C" int mcq_db_destroy(mcq_db* db) {
-    if (!db) return MCQ_OK;
-    (void)hipSetDevice(db->device);
-    (void)hipFree(db->slots); (void)hipFree(db->tgt2tax); (void)hipFree(db->gw_off); (void)hipFree(db->gw_blk);
-    delete db;
-    return MCQ_OK;
-}
-
-extern "C" uint64_t mcq_db_bytes(const mcq_db* db) { return db ? db->bytes : 0; }
 
 #ifndef MCQ_BLOCK_NT            // tuning knobs: shape of the 32-bit workgroup kernel (threads, keys of LDS, workgroups)
 #define MCQ_BLOCK_NT 1024
@@ -2675,70 +1788,6 @@ static int ensure_staging(mcq_ws* ws) {
 }
 
 // layout of an MCQ_BATCH_PACKED buffer for n bases (u32 words): [ceil(n/16) words of 2-bit codes][1 zero pad word]
-// [ceil(n/32) words of ambiguity bits][1 zero pad word]
-static u64 packed_words2(u64 n) { return (n + 15) / 16; }
-static u64 packed_wordsA(u64 n) { return (n + 31) / 32; }
-extern "C" uint64_t mcq_packed_bytes(uint64_t n_bases) { return (packed_words2(n_bases) + 1 + packed_wordsA(n_bases) + 1) * 4; }
-
-// device-side view of a batch whose buffers are (already) in device memory
-static int batch_dev(const mcq_batch* in, const char* d_bases, const u64* d_seq_off, BatchDev& b) {
-    memset(&b, 0, sizeof(b));
-    b.bases = d_bases; b.seq_off = d_seq_off; b.n_seq = in->n_seqs; b.nq = in->paired ? in->n_seqs / 2 : in->n_seqs;
-    b.paired = in->paired ? 1 : 0;
-    b.ranges = (in->flags & MCQ_BATCH_RANGES) ? 1 : 0;
-    if (in->flags & MCQ_BATCH_PACKED) {
-        if (b.ranges) return fail(MCQ_E_ARG, "MCQ_BATCH_PACKED and MCQ_BATCH_RANGES exclude each other");
-        if (in->n_bases >= (1ull << 35)) return fail(MCQ_E_UNSUPPORTED, "packed batches hold fewer than 2^35 bases");
-        b.packed = 1;
-        b.last_word = (u32)packed_words2(in->n_bases);
-        b.amb_off = b.last_word + 1;
-        b.amb_last = (u32)packed_wordsA(in->n_bases);
-    }
-    return MCQ_OK;
-}
-
-// ASCII bases -> MCQ_BATCH_PACKED words; one thread per 32 bases
-__global__ void k_pack_bases(const char* __restrict__ src, u64 n, u32* __restrict__ dst, u64 n2, u64 amb_off, u64 nA) {
-    const u64 g = (u64)blockIdx.x * blockDim.x + threadIdx.x;
-    if (g > nA) return;
-    u32 w0 = 0, w1 = 0, am = 0;
-    for (u32 j = 0; j < 32; ++j) {
-        const u64 i = g * 32 + j;
-        u32 code = 0, amb = 0;                                  // behind the end: code 0, not ambiguous (never looked at)
-        if (i < n) {
-            const u32 u = (u32)(unsigned char)src[i] & 0xDFu;
-            code = (u >> 1) & 3u; code ^= code >> 1;
-            amb = !(u == 'A' || u == 'C' || u == 'G' || u == 'T');
-            if (amb) code = 0;
-        }
-        if (j < 16) w0 |= code << (30 - 2 * j); else w1 |= code << (30 - 2 * (j - 16));
-        am |= amb << (31 - j);
-    }
-    if (2 * g <= n2) dst[2 * g] = (2 * g < n2) ? w0 : 0u;      // index n2 is the zero pad word
-    if (2 * g + 1 <= n2) dst[2 * g + 1] = (2 * g + 1 < n2) ? w1 : 0u;
-    dst[amb_off + g] = g < nA ? am : 0u;
-}
-
-extern "C" int mcq_pack_bases(const char* bases, uint64_t n_bases, void* out, uint32_t flags, void* stream) {
-    if (!out || (n_bases && !bases)) return fail(MCQ_E_ARG, "null argument");
-    const u64 n2 = packed_words2(n_bases), nA = packed_wordsA(n_bases), amb_off = n2 + 1;
-    if (flags & MCQ_DEVICE_PTRS) {
-        hipLaunchKernelGGL(k_pack_bases, dim3((u32)((nA + 1 + 255) / 256)), dim3(256), 0, (hipStream_t)stream, bases, n_bases, (u32*)out, n2, amb_off, nA);
-        HIPCHK(hipGetLastError());
-        return MCQ_OK;
-    }
-    u32* dst = (u32*)out;
-    memset(dst, 0, mcq_packed_bytes(n_bases));
-    for (u64 i = 0; i < n_bases; ++i) {
-        const u32 u = (u32)(unsigned char)bases[i] & 0xDFu;
-        u32 code = (u >> 1) & 3u; code ^= code >> 1;
-        const bool amb = !(u == 'A' || u == 'C' || u == 'G' || u == 'T');
-        if (amb) dst[amb_off + (i >> 5)] |= 1u << (31 - (i & 31));
-        else dst[i >> 4] |= code << (30 - 2 * (i & 15));
-    }
-    return MCQ_OK;
-}
-
 static const int kLcapWave = 512;
 static const int kLcapBlock = 8192;
 
@@ -2773,8 +1822,8 @@ __global__ void k_next_mode(CountersDev* ctr, u64 nq) {
 
 // sh != nullptr: the feature-sharded home side (SH instantiations; dbd = the handle's DbDev with `locs` pointing at the
 // received location buffer); the counters are then zeroed by the caller (the sketch kernel has already counted)
-static int launch_query(const mcq_db* db, mcq_ws* ws, const BatchDev& b, const OptDev& od_in, const OutDev& o,
-                        hipStream_t st, int force_block_in, const DebugDev& dbg, const ShardDev* shp = nullptr, const DbDev* dbd = nullptr) {
+int mcq::launch_query(const mcq_db* db, mcq_ws* ws, const BatchDev& b, const OptDev& od_in, const OutDev& o,
+                      hipStream_t st, int force_block_in, const DebugDev& dbg, const ShardDev* shp, const DbDev* dbd) {
     if (!shp) HIPCHK(hipMemsetAsync(ws->ctr, 0, MCQ_CTR_ZEROED, st));
     if (b.nq == 0) return MCQ_OK;
     ShardDev sh; memset(&sh, 0, sizeof(sh));
@@ -3103,116 +2152,6 @@ extern "C" int mcq_debug_matches(const mcq_db* db, mcq_ws* ws, const mcq_batch* 
     return MCQ_OK;
 }
 
-// ------------------------------------------------------------------ staged entry points (device pointers only)
-extern "C" int mcq_count_windows(const mcq_db* db, const mcq_batch* in, uint64_t* win_off, void* stream) {
-    if (!db || !in || !win_off) return fail(MCQ_E_ARG, "null argument");
-    if (!(in->flags & MCQ_DEVICE_PTRS)) return fail(MCQ_E_ARG, "staged entry points take device pointers");
-    HIPCHK(hipSetDevice(db->device));
-    hipStream_t st = (hipStream_t)stream;
-    const u64 n = in->n_seqs;
-    u64* cnt = nullptr;
-    HIPCHK(hipMallocAsync((void**)&cnt, std::max<u64>(1, n) * 8, st));
-    if (n) hipLaunchKernelGGL(k_count_windows, dim3((u32)((n + 255) / 256)), dim3(256), 0, st, in->seq_off, (in->flags & MCQ_BATCH_RANGES) ? 1u : 0u, n, db->d.winlen, db->d.winstride, cnt);
-    { int rcs = device_exclusive_scan<u64>((const u64*)cnt, win_off, n, st, 256); if (rcs) return rcs; }
-    HIPCHK(hipFreeAsync(cnt, st));
-    HIPCHK(hipGetLastError());
-    return MCQ_OK;
-}
-
-extern "C" int mcq_sketch(const mcq_db* db, const mcq_batch* in, const uint64_t* win_off,
-                          uint32_t* features, uint32_t* n_feat, void* stream) {
-    if (!db || !in || !win_off || !features || !n_feat) return fail(MCQ_E_ARG, "null argument");
-    if (!(in->flags & MCQ_DEVICE_PTRS)) return fail(MCQ_E_ARG, "staged entry points take device pointers");
-    if (in->flags & MCQ_BATCH_PACKED) return fail(MCQ_E_ARG, "mcq_sketch takes ASCII batches");
-    HIPCHK(hipSetDevice(db->device));
-    if (in->n_seqs == 0) return MCQ_OK;
-    // many short sequences (reads): one wave per sequence; few long ones (genomes): one wave per window
-    if (in->n_seqs >= 4096) {
-        const u32 grid = (u32)std::min<u64>((in->n_seqs + 3) / 4, 256ull * 32);    // short items: several rounds balance better
-        hipLaunchKernelGGL(k_sketch_seqs, dim3(grid), dim3(256), 0, (hipStream_t)stream, db->d, in->bases, in->seq_off,
-                           (in->flags & MCQ_BATCH_RANGES) ? 1u : 0u, in->n_seqs, win_off, features, n_feat);
-    } else {
-        hipLaunchKernelGGL(k_sketch_windows, dim3(256 * 16), dim3(256), 0, (hipStream_t)stream, db->d, in->bases, in->seq_off,
-                           (in->flags & MCQ_BATCH_RANGES) ? 1u : 0u, in->n_seqs, win_off, features, n_feat);
-    }
-    HIPCHK(hipGetLastError());
-    return MCQ_OK;
-}
-
-extern "C" uint32_t mcq_db_loc_bytes(const mcq_db* db) { return db && db->d.compact ? 4u : 8u; }
-extern "C" uint32_t mcq_db_win_bits(const mcq_db* db) { return db ? db->d.wb : 32u; }
-extern "C" int mcq_db_layout_get(const mcq_db* db, mcq_db_layout* out) {
-    if (!db || !out) return fail(MCQ_E_ARG, "null argument");
-    memset(out, 0, sizeof(*out));
-    out->loc_bytes = db->d.compact ? 4u : 8u;
-    out->loc_format = db->g.on ? MCQ_LOC_GLOBAL_WINDOW : db->d.compact ? MCQ_LOC_FIELDS32 : MCQ_LOC_FIELDS64;
-    out->win_bits = db->d.wb; out->bucket_bytes = db->bucket_bytes; out->slots_per_key = db->slots_per_key;
-    out->n_slots = db->nslots; out->n_keys = db->n_keys_local; out->n_locs = db->n_locs_local; out->n_ext_locs = db->n_ext;
-    out->n_windows = db->n_windows; out->bytes = db->bytes;
-    out->gw_offsets = db->gw_off;
-    return MCQ_OK;
-}
-
-extern "C" int mcq_lookup_count(const mcq_db* db, const uint32_t* features, uint64_t n_features,
-                                uint32_t* list_len, uint64_t* list_src, void* stream) {
-    if (!db || (n_features && (!features || !list_len))) return fail(MCQ_E_ARG, "null argument");
-    HIPCHK(hipSetDevice(db->device));
-    if (n_features == 0) return MCQ_OK;
-    hipLaunchKernelGGL(k_lookup_count, dim3((u32)((n_features + 255) / 256)), dim3(256), 0, (hipStream_t)stream, db->d, features,
-                       n_features, list_len, list_src);
-    HIPCHK(hipGetLastError());
-    return MCQ_OK;
-}
-
-extern "C" int mcq_lookup_gather(const mcq_db* db, const uint32_t* features, uint64_t n_features,
-                                 const uint32_t* list_len, const uint64_t* list_src,
-                                 const uint64_t* out_off, void* out_locs, void* stream) {
-    if (!db || (n_features && (!features || !out_off))) return fail(MCQ_E_ARG, "null argument");
-    if (list_src && !list_len) return fail(MCQ_E_ARG, "list_src needs list_len");
-    HIPCHK(hipSetDevice(db->device));
-    if (n_features == 0) return MCQ_OK;
-    u64 groups = (n_features + 63) / 64;
-    const u32 grid = (u32)std::min<u64>((groups + 3) / 4, 256ull * 32);
-    with_loc_form(db, [&](auto L) {
-        using Key = typename decltype(L)::Key;
-        hipLaunchKernelGGL(k_lookup_gather<Key>, dim3(grid), dim3(256), 0, (hipStream_t)stream, db->d, features, n_features, list_len, list_src, out_off, (Key*)out_locs);
-    });
-    HIPCHK(hipGetLastError());
-    return MCQ_OK;
-}
-
-extern "C" int mcq_assemble(const mcq_db* db, uint64_t n_lists, const uint32_t* list_len, const uint32_t* src_slot,
-                            uint64_t n_slots, const void* src_locs, const mcq_batch* in, const uint64_t* win_off,
-                            uint64_t* loc_off, uint32_t* query_len, void* dst_locs, void* stream) {
-    if (!db || !in || !win_off || !loc_off || !query_len) return fail(MCQ_E_ARG, "null argument");
-    if (!(in->flags & MCQ_DEVICE_PTRS)) return fail(MCQ_E_ARG, "staged entry points take device pointers");
-    if (n_lists && (!list_len || !src_slot)) return fail(MCQ_E_ARG, "null argument");
-    HIPCHK(hipSetDevice(db->device));
-    hipStream_t st = (hipStream_t)stream;
-    const u64 nq = in->paired ? in->n_seqs / 2 : in->n_seqs;
-    u32* slot_len = nullptr; u64 *dst_off = nullptr, *src_off = nullptr;
-    HIPCHK(hipMallocAsync((void**)&slot_len, std::max<u64>(1, n_slots) * 4, st));
-    HIPCHK(hipMallocAsync((void**)&dst_off, (n_slots + 1) * 8, st));
-    HIPCHK(hipMallocAsync((void**)&src_off, (n_lists + 1) * 8, st));
-    HIPCHK(hipMemsetAsync(slot_len, 0, std::max<u64>(1, n_slots) * 4, st));
-    if (n_lists) hipLaunchKernelGGL(k_scatter_len, dim3((u32)((n_lists + 255) / 256)), dim3(256), 0, st, list_len, src_slot, n_lists, slot_len);
-    int rc = device_exclusive_scan<u32>(slot_len, dst_off, n_slots, st); if (rc) return rc;
-    rc = device_exclusive_scan<u32>(list_len, src_off, n_lists, st); if (rc) return rc;
-    if (n_lists) {
-        u64 groups = (n_lists + 63) / 64;
-        const u32 grid = (u32)std::min<u64>((groups + 3) / 4, 256ull * 32);
-        with_loc_form(db, [&](auto L) {
-            using Key = typename decltype(L)::Key;
-            hipLaunchKernelGGL(k_scatter_lists<Key>, dim3(grid), dim3(256), 0, st, n_lists, (const u64*)src_off, src_slot, (const u64*)dst_off, (const Key*)src_locs, (Key*)dst_locs);
-        });
-    }
-    hipLaunchKernelGGL(k_query_offsets, dim3((u32)((nq + 256) / 256)), dim3(256), 0, st, nq, in->paired ? 2u : 1u, db->d.s, win_off,
-                       in->seq_off, (in->flags & MCQ_BATCH_RANGES) ? 1u : 0u, (const u64*)dst_off, n_slots, loc_off, query_len);
-    HIPCHK(hipFreeAsync(slot_len, st)); HIPCHK(hipFreeAsync(dst_off, st)); HIPCHK(hipFreeAsync(src_off, st));
-    HIPCHK(hipGetLastError());
-    return MCQ_OK;
-}
-
 extern "C" int mcq_reduce(const mcq_db* db, mcq_ws* ws, uint64_t n_queries, const uint64_t* loc_off,
                           const void* locs, const uint32_t* query_len, const mcq_query_opts* opt, mcq_result* out, void* stream) {
     if (!db || !ws || !opt || !out || (n_queries && (!loc_off || !query_len))) return fail(MCQ_E_ARG, "null argument");
@@ -3293,52 +2232,3 @@ extern "C" int mcq_ws_kernel_time(mcq_ws* ws, double* total_ms, uint64_t* n_batc
     if (total_ms) { *total_ms = 0; for (double m : ms) *total_ms += m; }
     return MCQ_OK;
 }
-
-// ------------------------------------------------------------------ sharded-path routing entry points
-extern "C" int mcq_bucket_features(const uint32_t* features, uint64_t n, uint32_t n_shards,
-                                   uint64_t* counts, uint32_t* bucketed, uint32_t* src_index, void* stream) {
-    if (!counts || (n && (!features || !bucketed || !src_index))) return fail(MCQ_E_ARG, "null argument");
-    if (n_shards < 1 || n_shards > MCQ_BUCKET_MAX_SHARDS) return fail(MCQ_E_ARG, "n_shards must be 1..64");
-    if (n >= (1ull << 32)) return fail(MCQ_E_UNSUPPORTED, "more than 2^32 feature slots in one batch");
-    hipStream_t st = (hipStream_t)stream;
-    if (n == 0) { HIPCHK(hipMemsetAsync(counts, 0, (u64)n_shards * 8, st)); return MCQ_OK; }
-    const u32 grid = (u32)std::min<u64>((n + 4095) / 4096, 2048);
-    const u64 tile = ((n + grid - 1) / grid + 255) / 256 * 256;
-    unsigned long long* blk = nullptr;
-    HIPCHK(hipMallocAsync((void**)&blk, (u64)n_shards * grid * 8, st));
-    hipLaunchKernelGGL(k_bucket_count, dim3(grid), dim3(256), 0, st, features, n, n_shards, tile, blk);
-    hipLaunchKernelGGL(k_bucket_scan, dim3(1), dim3(1024), 0, st, blk, n_shards, grid, (unsigned long long*)counts);
-    hipLaunchKernelGGL(k_bucket_fill, dim3(grid), dim3(256), 0, st, features, n, n_shards, tile, (const unsigned long long*)blk, bucketed, src_index);
-    HIPCHK(hipFreeAsync(blk, st));
-    HIPCHK(hipGetLastError());
-    return MCQ_OK;
-}
-
-// ------------------------------------------------------------------ row f4 entry point
-static int text_index(const char* text, uint64_t n_bytes, uint64_t* seq_ranges, uint64_t max_seqs, uint64_t* n_seqs_out, void* stream, u32 L);
-extern "C" int mcq_fastq_index(const char* text, uint64_t n_bytes, uint64_t* seq_ranges, uint64_t max_seqs,
-                               uint64_t* n_seqs_out, void* stream) {
-    return text_index(text, n_bytes, seq_ranges, max_seqs, n_seqs_out, stream, 4);
-}
-extern "C" int mcq_fasta_index(const char* text, uint64_t n_bytes, uint64_t* seq_ranges, uint64_t max_seqs,
-                               uint64_t* n_seqs_out, void* stream) {
-    return text_index(text, n_bytes, seq_ranges, max_seqs, n_seqs_out, stream, 2);
-}
-static int text_index(const char* text, uint64_t n_bytes, uint64_t* seq_ranges, uint64_t max_seqs, uint64_t* n_seqs_out, void* stream, u32 L) {
-    if (!seq_ranges || !n_seqs_out || (n_bytes && !text)) return fail(MCQ_E_ARG, "null argument");
-    hipStream_t st = (hipStream_t)stream;
-    const u64 n_tiles = std::max<u64>(1, (n_bytes + MCQ_FQ_TILE - 1) / MCQ_FQ_TILE);
-    if (n_tiles >= (1ull << 31)) return fail(MCQ_E_UNSUPPORTED, "text too large for one call");
-    u64 *cnt = nullptr, *off = nullptr;
-    HIPCHK(hipMallocAsync((void**)&cnt, n_tiles * 8, st));
-    HIPCHK(hipMallocAsync((void**)&off, (n_tiles + 1) * 8, st));
-    hipLaunchKernelGGL(k_fq_count, dim3((u32)n_tiles), dim3(256), 0, st, text, n_bytes, cnt);
-    int rc = device_exclusive_scan<u64>((const u64*)cnt, off, n_tiles, st); if (rc) return rc;
-    hipLaunchKernelGGL(k_fq_ranges, dim3((u32)n_tiles), dim3(256), 0, st, text, n_bytes, (const u64*)off, n_tiles, seq_ranges, max_seqs, n_seqs_out, L);
-    HIPCHK(hipFreeAsync(cnt, st)); HIPCHK(hipFreeAsync(off, st));
-    HIPCHK(hipGetLastError());
-    return MCQ_OK;
-}
-
-// ------------------------------------------------------------------ feature-sharded multi-GPU path (mcq_shard_*)
-#include "mcq_shard.hpp"

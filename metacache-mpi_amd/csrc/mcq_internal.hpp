@@ -1,0 +1,128 @@
+#pragma once
+// mcq_internal.hpp -- what more than one unit of libmcq_hip.so needs on the host side: the handle structs behind the
+// C ABI, error reporting, a few inline helpers, and the declarations of the functions that cross a unit boundary
+// (hidden visibility: none of them is part of the ABI).  The units: mcq_engine.hip (workspace, fused query, reduce),
+// mcq_table.hip (mcq_db_*), mcq_stages.hip (staged and routing entry points, batch preparation), mcq_shard.hip
+// (mcq_shard_*).  Kernels are not declared here: each is defined in the unit that launches it.
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+#include <stdio.h>
+#include <string.h>
+#include <string>
+#include <vector>
+#include <algorithm>
+#include <type_traits>
+
+#include "../../include/mcq.h"
+#include "mcq_device.hpp"
+#include "mcq_classify.hpp"
+
+using namespace mcq;
+
+// ------------------------------------------------------------------ error handling
+// one text per thread, kept in mcq_engine.hip behind mcq_last_error
+static inline int fail(int code, const std::string& msg) { return mcq::set_error(code, msg.c_str()); }
+#define HIPCHK(expr) do { hipError_t e_ = (expr); if (e_ != hipSuccess) \
+    return fail(MCQ_E_HIP, std::string(#expr) + ": " + hipGetErrorString(e_)); } while (0)
+
+// like HIPCHK inside a constructor-like function: releases what the half-built object already holds before returning
+#define HIPCHK_OR(expr, cleanup) do { hipError_t e_ = (expr); if (e_ != hipSuccess) { cleanup; \
+    return fail(MCQ_E_HIP, std::string(#expr) + ": " + hipGetErrorString(e_)); } } while (0)
+
+static u64 pow2ceil64(u64 x) { u64 p = 1; while (p < x) p <<= 1; return p; }
+
+// ------------------------------------------------------------------ handles
+struct mcq_db {
+    DbDev d;
+    int device;
+    u64 nslots;
+    u64 n_keys_local, n_locs_local;
+    uint4* slots;             // one allocation: the buckets, then the lists too long for a bucket
+    u32* tgt2tax;
+    u32* gw_off; u32* gw_blk; // global-window form: first window of every target, block -> target (see LocGW)
+    GwDev g;                  // ... as the kernels take them
+    u32 n_shards, shard_id;
+    u32 bucket_bytes, slots_per_key;
+    u64 n_ext, n_windows;
+    u64 bytes;
+    bool seq_taxa;            // tgt2tax holds sequence-level taxa (bit 31; see make_opt)
+    u64 fmt_sig;              // what the location words of this handle mean (format, field widths, window offsets of the targets, sketch
+                              // parameters), hashed: the ranks of a sharded run compare it before the first words travel (mcq_shard.hip)
+};
+
+struct ScratchDev {
+    u32* feat; u32* fpos; u64* foff; u64* gbuf; u64* ghits;
+    u32 fmax; u32 lmax;
+};
+
+struct DebugDev {
+    int mode;                 // 0 off, 1 = write match counts, 2 = write matches
+    u64* match_cnt;           // [nq]
+    const u64* match_off;     // [nq+1]
+    u64* matches;
+};
+
+#define MCQ_N_TIMED 3           // kernels of one batch that are timed separately: first wave stage, second wave stage, workgroup kernel
+struct TimedLaunch { hipEvent_t ev[MCQ_N_TIMED + 1]; };
+struct mcq_ws {
+    int device;
+    u64 max_queries, max_bases;
+    CountersDev* ctr;         // device
+    CountersDev* ctr_host;    // pinned
+    u32* ovf_list;            // [ovf_capacity(max_queries)]
+    unsigned long long* probe_buf;   // [(2 x max_queries + 3 x MCQ_OVF_TAIL) x 64]: rows of the back queue, then of the front queue; see CountersDev
+    ScratchDev sc;
+    int n_block_wgs;
+    u32 cap_wave, cap_wave16, cap_reduce16, cap_wave32, cap_wave_many;   // resident workgroups of the wave-per-query kernels on this device
+    // staging for host-pointer calls
+    char* d_bases; u64* d_seq_off; u32* d_cands; u32* d_ncand;
+    u64 last_nq;
+    // host-buffer pipeline (mcq_query_pipelined): two staging sets, copy streams on both sides of the compute stream
+    struct Pipe {
+        char* d_bases[2]; u64* d_seq_off[2]; u32* d_cands[2]; u32* d_ncand[2];
+        hipStream_t s_in, s_k, s_out;
+        hipEvent_t ev_in[2], ev_k[2], ev_out[2];
+        u64 issued;             // calls so far; call i uses set i & 1
+        bool ready;
+    } pipe;
+    // optional per-launch timing of the path's kernels (events between them on the call's stream)
+    int timing;
+    std::vector<TimedLaunch>* ev_used;
+    std::vector<TimedLaunch>* ev_free;
+    double timed_ms[MCQ_N_TIMED]; u64 timed_launches;
+    // classification of every batch while a taxonomy is attached (mcq_ws_set_classify): counts [cls_n] on the device,
+    // cls_ev recorded behind the last batch that added into them
+    const mcq_taxonomy* cls_tx;
+    mcq_classify_opts cls_opt;
+    unsigned long long* cls_counts;
+    u32 cls_n;
+    hipEvent_t cls_ev;
+};
+
+// ------------------------------------------------------------------ a handle's form as template arguments
+// The only code that turns d.compact, g.on and d.bsh into the template arguments of the kernels a handle launches.  The location
+// word: LocForm<u64, false> = 64-bit bit fields, <u32, false> = 32-bit bit fields, <u32, true> = the 32-bit global-window index.
+// The bucket layout BSH: 2 = 64-B buckets, 0 = 16-B slots.  f gets the form as a value of the tag type.
+template <class KeyT, bool GW> struct LocForm { using Key = KeyT; static constexpr bool gw = GW; };
+template <int V> using IntC = std::integral_constant<int, V>;
+template <class F> static auto with_loc_form(bool compact, bool gw, F&& f) {
+    if (!compact) return f(LocForm<u64, false>{});
+    return gw ? f(LocForm<u32, true>{}) : f(LocForm<u32, false>{});
+}
+template <class F> static auto with_loc_form(const mcq_db* db, F&& f) { return with_loc_form(db->d.compact != 0, db->g.on != 0, f); }
+template <class F> static auto with_layout(const mcq_db* db, F&& f) {
+    return db->d.bsh != 0 ? f(IntC<2>{}) : f(IntC<0>{});
+}
+
+// ------------------------------------------------------------------ defined in one unit, called from others
+namespace mcq {
+// mcq_engine.hip
+__attribute__((visibility("hidden"))) int force_bits(u32 flags);
+__attribute__((visibility("hidden"))) int make_opt(const mcq_query_opts* o, OptDev& d, const mcq_db* db);
+__attribute__((visibility("hidden"))) int launch_query(const mcq_db* db, mcq_ws* ws, const BatchDev& b, const OptDev& od_in, const OutDev& o,
+                                                       hipStream_t st, int force_block_in, const DebugDev& dbg, const ShardDev* shp = nullptr, const DbDev* dbd = nullptr);
+// mcq_stages.hip (instantiated for InT = u32 and u64)
+__attribute__((visibility("hidden"))) int batch_dev(const mcq_batch* in, const char* d_bases, const u64* d_seq_off, BatchDev& b);
+template <class InT>
+__attribute__((visibility("hidden"))) int device_exclusive_scan(const InT* in, u64* out, u64 n, hipStream_t st, u32 nt = 1024);
+}  // namespace mcq

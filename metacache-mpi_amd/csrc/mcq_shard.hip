@@ -1,5 +1,6 @@
-// mcq_shard.hpp -- the feature-sharded multi-GPU query path behind the C ABI (mcq_shard_* in include/mcq.h).
-// Included at the end of mcq_engine.hip (same translation unit: it launches the SH instantiations of the query kernels).
+// mcq_shard.hip -- the feature-sharded multi-GPU query path behind the C ABI (mcq_shard_* in include/mcq.h).
+// Its own stages are kernels of this unit; the home side goes through launch_query (mcq_engine.hip), which launches the
+// SH instantiations of the query kernels.
 //
 // One process per GPU, n_ranks of them.  The feature -> locations table is partitioned by hash range of h2(feature)
 // (mcq_owner); every rank keeps its shard (mcq_db with n_shards = n_ranks, shard_id = rank) and its own reads.  It
@@ -23,6 +24,8 @@
 // MCQ_E_CAPACITY).
 #include <dlfcn.h>
 #include <rccl/rccl.h>
+
+#include "mcq_internal.hpp"
 
 #define MCQ_SHARD_HDR 4u                  // u32 words in front of a feature block: [0] = number of feature positions in it
 

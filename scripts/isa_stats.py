@@ -1,6 +1,7 @@
 #!/usr/bin/env python3
-"""Static instruction statistics of one kernel of csrc/mcq_engine.hip (device ISA via hipcc -S): totals by class and the
+"""Static instruction statistics of one kernel of a unit of csrc/ (device ISA via hipcc -S): totals by class and the
 SGPR-spill traffic (v_readlane / v_writelane).  python3 scripts/isa_stats.py KERNEL_REGEX [--src FILE] [hipcc flags]
+FILE: a unit of csrc/ by name (mcq_stages.hip; default mcq_engine.hip), or a path to a source or .s file
 e.g.  scripts/isa_stats.py 'k_query_waveIjLi512ELb0ELb0ELb0E'      (mangled-name regex)"""
 import collections
 import re
@@ -14,6 +15,8 @@ pat = re.compile(args.pop(0))
 src = os.path.join(ROOT, "metacache-mpi_amd", "csrc", "mcq_engine.hip")
 if "--src" in args:
     i = args.index("--src"); src = args[i + 1]; del args[i:i + 2]
+    if os.sep not in src and not os.path.exists(src):
+        src = os.path.join(ROOT, "metacache-mpi_amd", "csrc", src)
 asm = src if src.endswith(".s") else "/tmp/isa_stats_%d.s" % os.getpid()
 if not src.endswith(".s"):
     subprocess.run(["/opt/rocm/bin/hipcc", "--offload-arch=gfx950", "-O3", "-std=c++17", "--cuda-device-only", "-S", src, "-o", asm] + args,

@@ -1,7 +1,8 @@
 #!/usr/bin/env python3
-"""Kernel resource usage of csrc/mcq_engine.hip as hipcc reports it (-Rpass-analysis=kernel-resource-usage):
-one line per kernel with VGPRs, spills, scratch, LDS, occupancy.  Runs in the build container (no GPU needed):
-  python3 scripts/resource_usage.py [--filter REGEX] [extra hipcc flags]
+"""Kernel resource usage of one unit of csrc/ (mcq_engine.hip unless --unit names another) as hipcc reports it
+(-Rpass-analysis=kernel-resource-usage): one line per kernel with VGPRs, spills, scratch, LDS, occupancy.  Runs in the
+build container (no GPU needed):
+  python3 scripts/resource_usage.py [--unit mcq_stages.hip] [--filter REGEX] [extra hipcc flags]
   python3 scripts/resource_usage.py --from saved_stderr.txt          (a compile's remarks kept in a file)"""
 import os
 import re
@@ -13,10 +14,13 @@ args = sys.argv[1:]
 flt = None
 if "--filter" in args:
     i = args.index("--filter"); flt = re.compile(args[i + 1]); del args[i:i + 2]
+unit = "mcq_engine.hip"
+if "--unit" in args:
+    i = args.index("--unit"); unit = args[i + 1]; del args[i:i + 2]
 if args[:1] == ["--from"]:
     err = open(args[1]).read()
 else:
-    src = os.path.join(ROOT, "metacache-mpi_amd", "csrc", "mcq_engine.hip")
+    src = os.path.join(ROOT, "metacache-mpi_amd", "csrc", unit)
     cmd = ["/opt/rocm/bin/hipcc", "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-Rpass-analysis=kernel-resource-usage",
            "-c", src, "-o", "/dev/null"] + args
     err = subprocess.run(cmd, stderr=subprocess.PIPE, text=True).stderr

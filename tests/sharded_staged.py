@@ -1,6 +1,6 @@
 """TEST CODE (moved out of the product package in round 3): the round-1 form of the feature-sharded query path, a
 torch.distributed loop over the engine's STAGED entry points.  The product path at N > 1 is mcq_shard_* behind the C ABI
-(csrc/mcq_shard.hpp); this loop is kept as an independent second implementation of the routing for the tests
+(csrc/mcq_shard.hip); this loop is kept as an independent second implementation of the routing for the tests
 (tests/test_sharded_gloo.py on CPU with an oracle backend, tests/test_gpu_sharded.py with the staged kernels).
 
 Feature-sharded multi-GPU query path over torch.distributed.

@@ -1,4 +1,4 @@
-"""The native sharded path (mcq_shard_*: csrc/mcq_shard.hpp) against the oracle.
+"""The native sharded path (mcq_shard_*: csrc/mcq_shard.hip) against the oracle.
 
 * n_ranks = 1 in-process (device-copy transport): exact and padded mode, prepared next batch, every query class, both
   location widths, capacity errors reported.
