@@ -398,6 +398,33 @@ int mcq_fastq_index(const char* text, uint64_t n_bytes, uint64_t* seq_ranges, ui
 int mcq_fasta_index(const char* text, uint64_t n_bytes, uint64_t* seq_ranges, uint64_t max_seqs,
                     uint64_t* n_seqs_out, void* stream);
 
+/* ---- reading files: one chunk of read text -> a compacted batch (mcq_query_cli's input stage) -----------------------
+ * text1 (and text2 for paired files; NULL: single-end): raw FASTQ or FASTA bytes in DEVICE memory, each chunk starting
+ * at a record; flags MCQ_READS_EOF1 / _EOF2: the chunk ends its file.  In one call on `stream`, with no host wait:
+ *   bases, seq_off   the sequences compacted as mcq_query takes them with MCQ_DEVICE_PTRS (mates of query q are
+ *                    sequences 2q, 2q+1; FASTA lines joined by dropping the '\n' only, a '\r' stays as getline keeps it);
+ *                    bases holds len1 + len2 bytes, seq_off 2 * max_queries + 1 entries
+ *   hdr              [2q], [2q+1]: byte range in text1 of query q's header after '@' / '>' up to its first ' ' or the line end
+ *   info             [MCQ_READS_INFO_WORDS] (device): queries taken, their bases, bytes of text1 / text2 used (the host
+ *                    carries the rest into the next chunk), status, complete records found in text1 / text2
+ * Records are taken in order while they are complete in the chunk (the next record has begun, or the file ends), n <
+ * max_queries, and the bases stay <= max_bases (a first query larger than that is taken alone); with two texts n is at
+ * most the smaller complete-record count.  Status MCQ_READS_NOT_STRICT: the chunk is not in the strict form -- FASTQ of
+ * 4-line records (line 1 '@', line 3 '+'), or FASTA of '>' header lines and non-empty sequence lines, one format per
+ * text -- and the outputs are not to be used: the host parses that chunk (mcq_reads_parse of include/mcq_host.h, the
+ * same contract).  scratch: device memory of mcq_reads_scratch_bytes(len1, len2, max_queries) bytes.  Chunks < 4 GiB. */
+#ifndef MCQ_READS_CONSTANTS             /* (the same in include/mcq_host.h) */
+#define MCQ_READS_CONSTANTS
+enum { MCQ_READS_EOF1 = 1u, MCQ_READS_EOF2 = 2u };
+enum { MCQ_READS_N = 0, MCQ_READS_BASES = 1, MCQ_READS_CUT1 = 2, MCQ_READS_CUT2 = 3, MCQ_READS_STATUS = 4,
+       MCQ_READS_COMPLETE1 = 5, MCQ_READS_COMPLETE2 = 6, MCQ_READS_INFO_WORDS = 8 };
+enum { MCQ_READS_NOT_STRICT = 1u };   /* info[MCQ_READS_STATUS] of the device step: parse this chunk on the host */
+#endif
+uint64_t mcq_reads_scratch_bytes(uint64_t len1, uint64_t len2, uint64_t max_queries);
+int mcq_reads_prepare(const char* text1, uint64_t len1, const char* text2, uint64_t len2, uint32_t flags,
+                      uint64_t max_queries, uint64_t max_bases, void* scratch, uint64_t scratch_bytes,
+                      char* bases, uint64_t* seq_off, uint64_t* hdr, uint64_t* info, void* stream);
+
 /* ---- row f2: building the table from reference sequences on the GPU -----------------
  * Replaces the build-side loop add_all_window_sketches (src/sketch_database.h:1079-1097) with
  * target t inserted on rank t % P (src/sketch_database.h:540-542): every window of every target is

@@ -127,6 +127,40 @@ int mcq_refdb_lineages(const mcq_refdb* db, uint32_t* lineage, uint8_t* rank);
 int64_t mcq_refdb_abundance_text(const mcq_refdb* db, const uint64_t* counts, uint64_t total, uint32_t est_rank,
                                  char* buf, size_t cap);
 
+/* ---- read files in chunks (mcq_query_cli's input stage) -------------------------------------------------------------
+ * mcq_read_stream_fill puts into buf (cap bytes) first the bytes that the last fill left unconsumed, then read()s of the
+ * file until buf holds `want` bytes (want <= cap) or the file ends: *len bytes, *eof = 1 when buf[0 .. *len) runs to the end
+ * of the file.  mcq_read_stream_consume(s, n) marks the first n bytes of the last fill as used; the rest stays in that
+ * buffer, which must stay valid until the next fill moves it to the front of the buffer given then (it may be the same
+ * buffer).  Host memory: none besides the caller's buffers.                                                           */
+typedef struct mcq_read_stream mcq_read_stream;
+int mcq_read_stream_open(const char* path, mcq_read_stream** out);
+int mcq_read_stream_fill(mcq_read_stream* s, char* buf, uint64_t cap, uint64_t want, uint64_t* len, int32_t* eof);
+int mcq_read_stream_consume(mcq_read_stream* s, uint64_t n_bytes);
+int mcq_read_stream_close(mcq_read_stream* s);
+
+/* One chunk of read text per file (text2 NULL: single-end), each starting at a record, parsed exactly as
+ * `metacache query` reads it with std::getline (src/sequence_io.cpp:122-285): '@' starts a record of header, sequence,
+ * '+' and quality lines; '>' starts a record whose following lines are joined; empty lines are skipped; other lines are
+ * appended to the record before them; a '\r' stays in its line.  A record is taken only once it is complete in its chunk
+ * (the next record has begun, or the chunk ends the file: flags MCQ_READS_EOF1 / _EOF2).  Records are taken in order while
+ * n < max_queries and the bases stay <= max_bases (a first query larger than that is taken alone); with two texts n is at
+ * most the smaller complete-record count.  Output, in the form mcq_reads_prepare (include/mcq.h) writes on the device:
+ *   bases      the sequences back to back (capacity len1 + len2), mates of query q as sequences 2q, 2q+1
+ *   seq_off    [n_seqs + 1] offsets into bases (capacity 2 * max_queries + 1)
+ *   hdr        [2 * n] (begin, end) byte range in text1 of query q's header up to its first ' ' (what the -out file prints)
+ *   info       [MCQ_READS_INFO_WORDS]: n queries, bases, bytes of text1 / text2 used (the rest is carried to the next
+ *              chunk), status (always 0 here), complete records found in text1 / text2 (at most max_queries)          */
+#ifndef MCQ_READS_CONSTANTS             /* (the same in include/mcq.h) */
+#define MCQ_READS_CONSTANTS
+enum { MCQ_READS_EOF1 = 1u, MCQ_READS_EOF2 = 2u };
+enum { MCQ_READS_N = 0, MCQ_READS_BASES = 1, MCQ_READS_CUT1 = 2, MCQ_READS_CUT2 = 3, MCQ_READS_STATUS = 4,
+       MCQ_READS_COMPLETE1 = 5, MCQ_READS_COMPLETE2 = 6, MCQ_READS_INFO_WORDS = 8 };
+enum { MCQ_READS_NOT_STRICT = 1u };   /* info[MCQ_READS_STATUS] of the device step: parse this chunk on the host */
+#endif
+int mcq_reads_parse(const char* text1, uint64_t len1, const char* text2, uint64_t len2, uint32_t flags,
+                    uint64_t max_queries, uint64_t max_bases, char* bases, uint64_t* seq_off, uint64_t* hdr, uint64_t* info);
+
 /* default of -hitmin when unset: src/mode_query.cpp:247-259 */
 uint32_t mcq_default_hits_min(uint32_t sketch_size);
 uint32_t mcq_rank_from_name(const char* name);

@@ -24,7 +24,10 @@
 // usage: mcq_query_cli <dbprefix> <n_ranks> <r1.fq> <r2.fq|-> [-lowest R] [-highest R] [-maxcand N] [-hitmin N]
 //            [-hitdiff X] [-insertsize N] [-threads N] [-tophits] [-taxids] [-taxids-only] [-omit-ranks] [-lineage]
 //            [-mapped-only] [-nomap] [-noquirks] [-abundances [FILE]] [-abundance-per R] [-out FILE] [-batch N] [-batch-bases N]
+//            [-read-chunk BYTES] [-reader gpu|host]
 // (-batch / -batch-bases: queries / bases per batch; the reads go through in batches, see mcq_query_cli.cpp;
+//  -read-chunk / -reader (mcq_query_cli only, written into no output): bytes per read() of each file, default 8 MiB, and
+//  who parses the chunks -- the GPU (mcq_reads_prepare; a chunk not in the strict form goes to the host) or always the host;
 //  -abundances [FILE] / -abundance-per R (aliases -abundances-per, -abundance_per, -abundances_per): src/query_options.cpp:310-323)
 #include <chrono>
 #include <cstdio>
@@ -127,6 +130,8 @@ struct Options {
     bool tax_counts() const { return abundances || abundance_rank != MCQ_RANK_NONE; }
     std::string transport = "rccl";      // mcq_query_mpi: rccl | mpi (blocks through the host and MPI_Alltoallv)
     uint64_t batch = 1u << 19, batch_bases = 256u << 20;   // mcq_query_mpi: queries / bases per rank and batch
+    uint64_t read_chunk = 8u << 20;      // mcq_query_cli: bytes per file and chunk (-read-chunk)
+    bool host_reader = false;            // mcq_query_cli: -reader host
     bool paired() const { return f2 != "-"; }
 };
 
@@ -155,6 +160,8 @@ static bool parse_options(int argc, char** argv, Options& o) {
         else if (a == "-batch") o.batch = std::max<uint64_t>(1, std::strtoull(next(), nullptr, 10));
         else if (a == "-batch-bases") o.batch_bases = std::max<uint64_t>(1024, std::strtoull(next(), nullptr, 10));
         else if (a == "-out") o.outfile = next();
+        else if (a == "-read-chunk") o.read_chunk = std::max<uint64_t>(1, std::strtoull(next(), nullptr, 10));
+        else if (a == "-reader") o.host_reader = std::string(next()) == "host";
         else if (a == "-abundances") {                                       // the FILE is the next token unless it is an option
             o.abundances = true;
             if (i + 1 < argc && argv[i + 1][0] != '-') o.abundance_file = argv[++i];
@@ -203,14 +210,15 @@ static void write_head(std::ostream& os, const Out& o, const Options& p, uint32_
 
 // one query: classification (src/classification.cpp:235-265), statistics (classification_statistics::assign,
 // src/classification_statistics.h:69-78) and its mapping line (show_query_mapping, src/classification.cpp:583-632)
-static void write_query(std::ostream& os, const Out& o, const Options& p, uint32_t hitmin, const std::string& header,
+// (token: the header up to its first ' ', what the line prints)
+static void write_query(std::ostream& os, const Out& o, const Options& p, uint32_t hitmin, const char* token, size_t token_len,
                         const mcq_cand* cands, uint32_t ncand, uint64_t* assigned /* [MCQ_RANK_NONE + 1] */) {
     mcq_refdb* rdb = o.db;
     const uint32_t best = mcq_refdb_classify(rdb, reinterpret_cast<const uint32_t*>(cands), ncand, hitmin, p.hitdiff, p.highest);
     if (best == MCQ_NO_TAXON) ++assigned[MCQ_RANK_NONE];
     else for (uint32_t r = mcq_refdb_taxon_rank(rdb, best); r <= MCQ_RANK_ROOT; ++r) ++assigned[r];
     if (p.nomap || (p.mapped_only && best == MCQ_NO_TAXON)) return;
-    os << header.substr(0, header.find(' ')) << o.col;
+    os.write(token, (std::streamsize)token_len) << o.col;
     if (p.tophits) {                                                         // show_matches, src/printing.cpp:333-360
         for (uint32_t i = 0; i < ncand && cands[i].hits > 0; ++i) {
             const mcq_cand& c = cands[i];
@@ -227,6 +235,10 @@ static void write_query(std::ostream& os, const Out& o, const Options& p, uint32
     }
     o.best(os, best);
     os << '\n';
+}
+static void write_query(std::ostream& os, const Out& o, const Options& p, uint32_t hitmin, const std::string& header,
+                        const mcq_cand* cands, uint32_t ncand, uint64_t* assigned) {
+    write_query(os, o, p, hitmin, header.data(), std::min(header.size(), header.find(' ')), cands, ncand, assigned);
 }
 
 // show_summary (src/printing.cpp:622-641) + show_taxon_statistics (:522-555)

@@ -505,3 +505,155 @@ extern "C" uint32_t mcq_rank_from_name(const char* name) {
     auto it = m.find(s);
     return it == m.end() ? MCQ_RANK_NONE : it->second;
 }
+
+// ------------------------------------------------------------------ read files in chunks (mcq_query_cli's input stage)
+#include <cerrno>
+#include <fcntl.h>
+#include <unistd.h>
+
+struct mcq_read_stream {
+    int fd = -1; bool eof = false;
+    const char* carry = nullptr; uint64_t carry_len = 0;        // the unconsumed tail of the last fill (in the caller's buffer)
+    const char* last = nullptr; uint64_t last_len = 0;
+};
+
+extern "C" int mcq_read_stream_open(const char* path, mcq_read_stream** out) {
+    if (!path || !out) return fail("null argument");
+    const int fd = ::open(path, O_RDONLY);
+    if (fd < 0) return fail(std::string("can't open file ") + path);
+#ifdef POSIX_FADV_SEQUENTIAL
+    (void)posix_fadvise(fd, 0, 0, POSIX_FADV_SEQUENTIAL);
+#endif
+    mcq_read_stream* s = new mcq_read_stream();
+    s->fd = fd;
+    *out = s;
+    return 0;
+}
+
+extern "C" int mcq_read_stream_fill(mcq_read_stream* s, char* buf, uint64_t cap, uint64_t want, uint64_t* len, int32_t* eof) {
+    if (!s || !buf || !len || !eof) return fail("null argument");
+    if (s->carry_len > cap) return fail("the carried bytes do not fit the buffer");
+    if (s->carry_len && s->carry != buf) std::memmove(buf, s->carry, s->carry_len);
+    uint64_t n = s->carry_len;
+    s->carry = nullptr; s->carry_len = 0;
+    want = std::max(std::min(want, cap), n);
+    while (n < want && !s->eof) {
+        const ssize_t r = ::read(s->fd, buf + n, (size_t)std::min<uint64_t>(want - n, 1ull << 30));
+        if (r < 0) { if (errno == EINTR) continue; return fail(std::string("read failed: ") + std::strerror(errno)); }
+        if (r == 0) s->eof = true;
+        n += (uint64_t)r;
+    }
+    s->last = buf; s->last_len = n;
+    *len = n; *eof = s->eof ? 1 : 0;
+    return 0;
+}
+
+extern "C" int mcq_read_stream_consume(mcq_read_stream* s, uint64_t n_bytes) {
+    if (!s || !s->last) return fail("no fill to consume from");
+    if (n_bytes > s->last_len) return fail("consumed more than the last fill holds");
+    s->carry = s->last + n_bytes; s->carry_len = s->last_len - n_bytes;
+    s->last = nullptr; s->last_len = 0;
+    return 0;
+}
+
+extern "C" int mcq_read_stream_close(mcq_read_stream* s) {
+    if (!s) return 0;
+    if (s->fd >= 0) ::close(s->fd);
+    delete s;
+    return 0;
+}
+
+namespace {
+// the records of one chunk as std::getline reads them (mcq_cli_common.hpp: read_records)
+struct ChunkRecs {
+    std::vector<uint64_t> start, hb, he, piece_at;     // per record: first byte, header line [hb, he) after '@' / '>', first piece
+    std::vector<uint64_t> pieces;                      // (begin, end) byte ranges of sequence text, record after record
+    uint64_t n_complete = 0, end = 0;                  // records [0, n_complete) are complete; `end` is just past the last one
+    uint64_t seq_len(uint64_t r) const {
+        uint64_t n = 0;
+        const uint64_t e = r + 1 < piece_at.size() ? piece_at[r + 1] : pieces.size() / 2;
+        for (uint64_t i = piece_at[r]; i < e; ++i) n += pieces[2 * i + 1] - pieces[2 * i];
+        return n;
+    }
+};
+
+void parse_chunk(const char* t, uint64_t L, bool eof, uint64_t max_recs, ChunkRecs& R) {
+    // one getline from p: 1 = line [p, *le), next line at *next; 0 = none (end of file); -1 = the line is not whole in the chunk
+    auto line = [&](uint64_t p, uint64_t* le, uint64_t* next) -> int {
+        if (p >= L) return eof ? 0 : -1;
+        const void* nl = std::memchr(t + p, '\n', L - p);
+        if (nl) { *le = (uint64_t)((const char*)nl - t); *next = *le + 1; return 1; }
+        if (!eof) return -1;
+        *le = L; *next = L; return 1;
+    };
+    uint64_t pos = 0, le = 0, next = 0;
+    auto last_incomplete = [&]() { R.n_complete = R.start.size() - 1; R.end = R.start.back(); };
+    for (;;) {
+        const int k = line(pos, &le, &next);
+        if (k == 0) { R.n_complete = R.start.size(); R.end = L; return; }
+        if (k < 0) {          // a line that goes on in the next chunk: if it starts a record, every record before it is complete
+            if (!R.start.empty() && !(pos < L && (t[pos] == '@' || t[pos] == '>'))) last_incomplete();
+            else { R.n_complete = R.start.size(); R.end = pos; }
+            return;
+        }
+        if (le == pos) { pos = next; continue; }                    // empty line
+        const char c = t[pos];
+        if (c == '@' || c == '>') {
+            if (R.start.size() == max_recs) { R.n_complete = max_recs; R.end = pos; return; }
+            R.start.push_back(pos); R.hb.push_back(pos + 1); R.he.push_back(le); R.piece_at.push_back(R.pieces.size() / 2);
+            pos = next;
+            if (c == '@') {                                          // getline sequence, '+' and qualities
+                for (int i = 0; i < 3; ++i) {
+                    const int k2 = line(pos, &le, &next);
+                    if (k2 < 0) { last_incomplete(); return; }
+                    if (k2 == 0) break;                              // end of file: the failed getlines leave the record as it is
+                    if (i == 0) { R.pieces.push_back(pos); R.pieces.push_back(le); }
+                    pos = next;
+                }
+            }
+            continue;
+        }
+        if (!R.start.empty()) { R.pieces.push_back(pos); R.pieces.push_back(le); }   // joined to the record before it
+        pos = next;
+    }
+}
+}  // namespace
+
+extern "C" int mcq_reads_parse(const char* text1, uint64_t len1, const char* text2, uint64_t len2, uint32_t flags,
+                               uint64_t max_queries, uint64_t max_bases, char* bases, uint64_t* seq_off, uint64_t* hdr, uint64_t* info) {
+    if ((len1 && !text1) || (len2 && !text2) || !bases || !seq_off || !hdr || !info) return fail("null argument");
+    if (max_queries < 1) return fail("max_queries must be >= 1");
+    const bool paired = text2 != nullptr;
+    ChunkRecs R[2];
+    parse_chunk(text1, len1, (flags & MCQ_READS_EOF1) != 0, max_queries, R[0]);
+    if (paired) parse_chunk(text2, len2, (flags & MCQ_READS_EOF2) != 0, max_queries, R[1]);
+    uint64_t nq = R[0].n_complete;
+    if (paired) nq = std::min(nq, R[1].n_complete);
+    const int mates = paired ? 2 : 1;
+    const char* text[2] = {text1, text2};
+    uint64_t n = 0, nb = 0;
+    seq_off[0] = 0;
+    for (; n < nq; ++n) {
+        uint64_t len = 0;
+        for (int m = 0; m < mates; ++m) len += R[m].seq_len(n);
+        if (n && nb + len > max_bases) break;
+        for (int m = 0; m < mates; ++m) {
+            const ChunkRecs& X = R[m];
+            const uint64_t e = n + 1 < X.piece_at.size() ? X.piece_at[n + 1] : X.pieces.size() / 2;
+            for (uint64_t i = X.piece_at[n]; i < e; ++i) {
+                const uint64_t b = X.pieces[2 * i], l = X.pieces[2 * i + 1] - b;
+                std::memcpy(bases + nb, text[m] + b, l); nb += l;
+            }
+            seq_off[n * mates + m + 1] = nb;
+        }
+        const char* sp = (const char*)std::memchr(text1 + R[0].hb[n], ' ', R[0].he[n] - R[0].hb[n]);
+        hdr[2 * n] = R[0].hb[n]; hdr[2 * n + 1] = sp ? (uint64_t)(sp - text1) : R[0].he[n];
+    }
+    std::memset(info, 0, MCQ_READS_INFO_WORDS * 8);
+    info[MCQ_READS_N] = n; info[MCQ_READS_BASES] = nb;
+    for (int m = 0; m < mates; ++m)        // the next chunk starts at record n, or behind everything this one held
+        info[MCQ_READS_CUT1 + m] = n < R[m].n_complete ? R[m].start[n] : R[m].end;
+    info[MCQ_READS_COMPLETE1] = R[0].n_complete;
+    info[MCQ_READS_COMPLETE2] = paired ? R[1].n_complete : 0;
+    return 0;
+}

@@ -1,7 +1,7 @@
 // mcq_stages.hip -- the query path as separate stages behind the C ABI (see include/mcq.h), and batch preparation:
 // mcq_count_windows, mcq_sketch, mcq_lookup_*, mcq_assemble (rows 1-7 one call each; mcq_reduce, rows 8-11, is in
-// mcq_engine.hip), feature routing for sharded runs (mcq_owner, mcq_bucket_features), FASTQ/FASTA indexing, base
-// packing, and the exclusive scan that these and table creation use.
+// mcq_engine.hip), feature routing for sharded runs (mcq_owner, mcq_bucket_features), FASTQ/FASTA indexing, chunks of
+// read files into compacted batches (mcq_reads_prepare), base packing, and the exclusive scan that these and table creation use.
 #include "mcq_internal.hpp"
 
 // ------------------------------------------------------------------ exclusive scan
@@ -604,6 +604,302 @@ static int text_index(const char* text, uint64_t n_bytes, uint64_t* seq_ranges, 
     int rc = device_exclusive_scan<u64>((const u64*)cnt, off, n_tiles, st); if (rc) return rc;
     hipLaunchKernelGGL(k_fq_ranges, dim3((u32)n_tiles), dim3(256), 0, st, text, n_bytes, (const u64*)off, n_tiles, seq_ranges, max_seqs, n_seqs_out, L);
     HIPCHK(hipFreeAsync(cnt, st)); HIPCHK(hipFreeAsync(off, st));
+    HIPCHK(hipGetLastError());
+    return MCQ_OK;
+}
+
+// ------------------------------------------------------------------ read files: one chunk of text -> a compacted batch
+// mcq_reads_prepare (include/mcq.h).  Per text: workgroup tiles of 4 KiB count their newlines and their header starts
+// (a line that begins with '>') from 16-B loads; two scans number them; a second pass over the tiles writes the position of
+// every newline and the line index of every header, and checks the strict form at every line start.  Then one thread per
+// record measures its sequence, one workgroup scans the lengths into seq_off and applies max_queries / max_bases, and one
+// wave per (query, mate) copies the sequence lines (a wave ballot finds the header's first ' ').  Byte positions are u32:
+// a chunk is below 4 GiB.
+struct RdText {
+    const char* t; u64 L; u32 eof, pad;
+    u64 n_tiles, rcap;
+    u64 *cnt_nl, *off_nl, *cnt_h, *off_h;   // [n_tiles] per-tile counts, [n_tiles + 1] exclusive offsets
+    u32* nl;                                // [L + 1]     byte position of newline l
+    u32* hl;                                // [L / 2 + 2] FASTA: line index of header r
+    u32* rlen;                              // [rcap]      sequence length of record r
+};
+struct RdPair { RdText x[2]; u32 mates; u64* info; };
+
+__device__ __forceinline__ u32 rd_zero_bytes(u32 m) {                  // bit i = byte i of m is zero (exact)
+    const u32 z = ~(((m & 0x7F7F7F7Fu) + 0x7F7F7F7Fu) | m) & 0x80808080u;
+    return ((z >> 7) & 1u) | ((z >> 14) & 2u) | ((z >> 21) & 4u) | ((z >> 28) & 8u);
+}
+// among t[base .. base+16): newlines (nlm), line starts (lsm) and line starts on a '>' (hsm)
+__device__ __forceinline__ void rd_masks(const char* __restrict__ t, u64 base, u64 n, u32& nlm, u32& lsm, u32& hsm) {
+    nlm = 0; hsm = 0;
+    if (base + 16 <= n && ((reinterpret_cast<uintptr_t>(t) + base) & 15) == 0) {
+        const uint4 v = *reinterpret_cast<const uint4*>(t + base);
+        const u32 w[4] = {v.x, v.y, v.z, v.w};
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+            nlm |= rd_zero_bytes(w[i] ^ 0x0A0A0A0Au) << (4 * i);
+            hsm |= rd_zero_bytes(w[i] ^ 0x3E3E3E3Eu) << (4 * i);
+        }
+    } else {
+        for (u32 j = 0; j < 16; ++j)
+            if (base + j < n) { const char c = t[base + j]; nlm |= (u32)(c == '\n') << j; hsm |= (u32)(c == '>') << j; }
+    }
+    const u32 valid = base >= n ? 0u : (n - base >= 16 ? 0xFFFFu : (1u << (n - base)) - 1u);
+    const u32 prev = base == 0 ? 1u : (base < n ? (u32)(t[base - 1] == '\n') : 0u);
+    lsm = ((nlm << 1) | prev) & valid;
+    hsm &= lsm;
+}
+__device__ __forceinline__ const RdText& rd_pick(const RdPair& P, u32 y) { return y ? P.x[1] : P.x[0]; }
+
+__global__ __launch_bounds__(256) void k_rd_count(RdPair P) {
+    const RdText X = rd_pick(P, blockIdx.y);
+    if (blockIdx.x >= X.n_tiles) return;
+    __shared__ u32 s_c[2];
+    if (threadIdx.x == 0) { s_c[0] = 0; s_c[1] = 0; }
+    __syncthreads();
+    u32 nlm, lsm, hsm;
+    rd_masks(X.t, (u64)blockIdx.x * MCQ_FQ_TILE + (u64)threadIdx.x * 16, X.L, nlm, lsm, hsm);
+    u32 a = (u32)__builtin_popcount(nlm), b = (u32)__builtin_popcount(hsm);
+    for (int d = 32; d > 0; d >>= 1) { a += __shfl_xor(a, d, 64); b += __shfl_xor(b, d, 64); }
+    if ((threadIdx.x & 63) == 0) { if (a) atomicAdd(&s_c[0], a); if (b) atomicAdd(&s_c[1], b); }
+    __syncthreads();
+    if (threadIdx.x == 0) { X.cnt_nl[blockIdx.x] = s_c[0]; X.cnt_h[blockIdx.x] = s_c[1]; }
+}
+
+__global__ __launch_bounds__(256) void k_rd_lines(RdPair P) {
+    const RdText X = rd_pick(P, blockIdx.y);
+    if (blockIdx.x >= X.n_tiles) return;
+    __shared__ u32 s_w[2][4];
+    const u32 tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const u64 base = (u64)blockIdx.x * MCQ_FQ_TILE + (u64)tid * 16;
+    u32 nlm, lsm, hsm;
+    rd_masks(X.t, base, X.L, nlm, lsm, hsm);
+    const u32 cn = (u32)__builtin_popcount(nlm), ch = (u32)__builtin_popcount(hsm);
+    const u32 in = wave_incl_scan_dpp(cn), ih = wave_incl_scan_dpp(ch);
+    if (lane == 63) { s_w[0][wave] = in; s_w[1][wave] = ih; }
+    __syncthreads();
+    u32 wn = 0, wh = 0;
+    for (u32 w = 0; w < wave; ++w) { wn += s_w[0][w]; wh += s_w[1][w]; }
+    const u64 line0 = X.off_nl[blockIdx.x] + wn + in - cn;             // the line that text[base] belongs to
+    const u64 hdr0 = X.off_h[blockIdx.x] + wh + ih - ch;
+    for (u32 m = nlm, l = 0; m; m &= m - 1, ++l) X.nl[line0 + l] = (u32)(base + (u32)__builtin_ctz(m));
+    const char f = X.L ? X.t[0] : 0;
+    bool bad = false;
+    for (u32 m = lsm; m; m &= m - 1) {
+        const u32 j = (u32)__builtin_ctz(m), below = (1u << j) - 1u;
+        const u64 li = line0 + (u32)__builtin_popcount(nlm & below);
+        const char c = X.t[base + j];
+        if (f == '@') {                                                 // FASTQ: line 4r starts with '@', line 4r+2 with '+'
+            const u32 role = (u32)(li & 3);
+            bad |= (role == 0 && c != '@') || (role == 2 && c != '+');
+        } else if (f == '>') {                                          // FASTA: no empty line, no FASTQ record
+            bad |= c == '\n' || c == '@';
+            if (c == '>') X.hl[hdr0 + (u32)__builtin_popcount(hsm & below)] = (u32)li;
+        } else bad = true;
+    }
+    if (bad) P.info[MCQ_READS_STATUS] = MCQ_READS_NOT_STRICT;
+}
+
+struct RdCounts { u64 nnl, n_lines, n_rec; bool fq; };
+__device__ __forceinline__ RdCounts rd_counts(const RdText& X) {
+    RdCounts c;
+    c.nnl = X.off_nl[X.n_tiles];
+    c.n_lines = c.nnl + (X.L && X.t[X.L - 1] != '\n' ? 1 : 0);
+    const char f = X.L ? X.t[0] : 0;
+    c.fq = f == '@';
+    c.n_rec = c.fq ? (c.n_lines + 3) / 4 : (f == '>' ? X.off_h[X.n_tiles] : 0);
+    return c;
+}
+__device__ __forceinline__ u64 rd_line_start(const RdText& X, u64 l) { return l ? (u64)X.nl[l - 1] + 1 : 0; }
+__device__ __forceinline__ u64 rd_line_end(const RdText& X, const RdCounts& c, u64 l) { return l < c.nnl ? (u64)X.nl[l] : X.L; }
+__device__ __forceinline__ u64 rd_hdr_line(const RdText& X, const RdCounts& c, u64 r) { return c.fq ? 4 * r : (u64)X.hl[r]; }
+// lines [a, b) that hold the sequence of record r
+__device__ __forceinline__ void rd_seq_lines(const RdText& X, const RdCounts& c, u64 r, u64& a, u64& b) {
+    if (c.fq) { a = 4 * r + 1; b = a + 1; }
+    else { a = (u64)X.hl[r] + 1; b = r + 1 < c.n_rec ? (u64)X.hl[r + 1] : c.n_lines; }
+    if (b > c.n_lines) b = c.n_lines;
+    if (a > b) a = b;
+}
+
+__global__ __launch_bounds__(256) void k_rd_recs(RdPair P) {
+    const RdText X = rd_pick(P, blockIdx.y);
+    const RdCounts c = rd_counts(X);
+    const u64 n = c.n_rec < X.rcap ? c.n_rec : X.rcap;
+    for (u64 r = (u64)blockIdx.x * blockDim.x + threadIdx.x; r < n; r += (u64)gridDim.x * blockDim.x) {
+        u64 a, b;
+        rd_seq_lines(X, c, r, a, b);
+        X.rlen[r] = b > a ? (u32)(rd_line_end(X, c, b - 1) - rd_line_start(X, a) - (b - 1 - a)) : 0u;
+    }
+}
+
+// one workgroup: complete records per text, the queries taken, seq_off, the cut points
+#define MCQ_RD_PER_THREAD 8
+__global__ __launch_bounds__(1024) void k_rd_offsets(RdPair P, u64 max_queries, u64 max_bases, u64* seq_off) {
+    __shared__ u64 s_w[16];
+    __shared__ u64 s_carry, s_endmax, s_end0;
+    __shared__ u32 s_k;
+    const u32 tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const u32 mates = P.mates;
+    RdCounts c[2];
+    u64 complete[2] = {0, 0};
+    bool bad = false;
+#pragma unroll
+    for (u32 m = 0; m < 2; ++m) {                                      // (unrolled: c[] and complete[] stay in registers)
+        if (m >= mates) break;
+        const RdText& X = P.x[m];
+        c[m] = rd_counts(X);
+        if (c[m].n_rec == 0) continue;
+        bool last = X.eof != 0;                                        // FASTA: the last record ends with the file
+        if (c[m].fq) {                                                 // FASTQ: its fourth line, and the byte after it, are here
+            const u64 l3 = 4 * (c[m].n_rec - 1) + 3;
+            last = X.eof ? l3 < c[m].n_lines : (l3 < c[m].nnl && (u64)X.nl[l3] + 1 < X.L);
+            bad |= X.eof && (c[m].n_lines & 3) != 0;                   // a cut last record
+        }
+        complete[m] = c[m].n_rec - (last ? 0 : 1);
+    }
+    u64 nq = complete[0];
+    if (mates == 2 && complete[1] < nq) nq = complete[1];
+    if (P.x[0].rcap < nq) nq = P.x[0].rcap;
+    if (mates == 2 && P.x[1].rcap < nq) nq = P.x[1].rcap;
+    if (max_queries < nq) nq = max_queries;
+    const u64 ns = nq * mates;
+    if (tid == 0) { s_carry = 0; s_endmax = 0; s_end0 = 0; s_k = 0; }
+    __syncthreads();
+    const u32* rlen0 = P.x[0].rlen;
+    const u32* rlen1 = P.x[1].rlen;
+    for (u64 base = 0; base < ns; base += 1024 * MCQ_RD_PER_THREAD) {
+        const u64 i0 = base + (u64)tid * MCQ_RD_PER_THREAD;
+        u32 len[MCQ_RD_PER_THREAD];
+        u64 tot = 0;
+#pragma unroll
+        for (int k = 0; k < MCQ_RD_PER_THREAD; ++k) {
+            const u64 i = i0 + k;
+            len[k] = i >= ns ? 0u : (mates == 1 ? rlen0[i] : ((i & 1) ? rlen1 : rlen0)[i >> 1]);
+            tot += len[k];
+        }
+        u64 x = tot;
+        for (int d = 1; d < 64; d <<= 1) { const u64 t = __shfl_up(x, d, 64); if (lane >= (u32)d) x += t; }
+        if (lane == 63) s_w[wave] = x;
+        __syncthreads();
+        u64 off = s_carry;
+        for (u32 w = 0; w < wave; ++w) off += s_w[w];
+        off += x - tot;
+        u32 k_fit = 0; u64 end_fit = 0;                                // this thread's last query that ends within max_bases
+#pragma unroll
+        for (int k = 0; k < MCQ_RD_PER_THREAD; ++k) {
+            const u64 i = i0 + k;
+            if (i < ns) {
+                seq_off[i] = off;
+                const u64 end = off + len[k];
+                if (i % mates == mates - 1) {                          // the end of query q
+                    const u64 q = i / mates;
+                    if (end <= max_bases) { k_fit = (u32)(q + 1); end_fit = end; }
+                    if (q == 0) s_end0 = end;
+                }
+            }
+            off += len[k];
+        }
+        for (int d = 32; d > 0; d >>= 1) {                             // (the ends grow with q: the largest q has the largest end)
+            const u32 ko = __shfl_xor(k_fit, d, 64);
+            const u64 eo = __shfl_xor(end_fit, d, 64);
+            if (ko > k_fit) { k_fit = ko; end_fit = eo; }
+        }
+        if (lane == 0 && k_fit) { atomicMax(&s_k, k_fit); atomicMax((unsigned long long*)&s_endmax, (unsigned long long)end_fit); }
+        __syncthreads();
+        if (tid == 1023) s_carry = off;
+        __syncthreads();
+    }
+    if (tid == 0) {
+        u64 n = s_k, nb = s_endmax;
+        if (n == 0 && nq) { n = 1; nb = s_end0; }                      // one query larger than max_bases goes alone
+        seq_off[n * mates] = nb;
+        u64* info = P.info;
+        info[MCQ_READS_N] = n; info[MCQ_READS_BASES] = nb;
+#pragma unroll
+        for (u32 m = 0; m < 2; ++m) {
+            if (m >= mates) break;
+            const RdText& X = P.x[m];
+            info[MCQ_READS_CUT1 + m] = n < c[m].n_rec ? rd_line_start(X, rd_hdr_line(X, c[m], n)) : X.L;
+            info[MCQ_READS_COMPLETE1 + m] = complete[m] < max_queries ? complete[m] : max_queries;
+        }
+        if (bad) info[MCQ_READS_STATUS] = MCQ_READS_NOT_STRICT;
+    }
+}
+
+// one wave per (query, mate): the sequence lines into bases, and (mate 0) the header's first token
+__global__ __launch_bounds__(256) void k_rd_copy(RdPair P, const u64* seq_off, char* bases, u64* hdr) {
+    const u32 m = blockIdx.y, lane = threadIdx.x & 63, mates = P.mates;
+    const RdText X = rd_pick(P, m);
+    const RdCounts c = rd_counts(X);
+    const u64 n = P.info[MCQ_READS_N];
+    for (u64 q = (u64)blockIdx.x * 4 + (threadIdx.x >> 6); q < n; q += (u64)gridDim.x * 4) {
+        char* dst = bases + seq_off[q * mates + m];
+        u64 a, b;
+        rd_seq_lines(X, c, q, a, b);
+        for (u64 l = a; l < b; ++l) {
+            const u64 s = rd_line_start(X, l), len = rd_line_end(X, c, l) - s;
+            for (u64 i = lane; i < len; i += 64) dst[i] = X.t[s + i];
+            dst += len;
+        }
+        if (m == 0) {
+            const u64 h = rd_hdr_line(X, c, q), hs = rd_line_start(X, h) + 1, he = rd_line_end(X, c, h);
+            u64 end = he;
+            for (u64 p = hs; p < he; p += 64) {
+                const unsigned long long sp = __ballot(p + lane < he && X.t[p + lane] == ' ');
+                if (sp) { end = p + (u64)__builtin_ctzll(sp); break; }
+            }
+            if (lane == 0) { hdr[2 * q] = hs; hdr[2 * q + 1] = end; }
+        }
+    }
+}
+
+static u64 rd_align(u64 x) { return (x + 255) & ~255ull; }
+static u64 rd_tiles(u64 L) { return std::max<u64>(1, (L + MCQ_FQ_TILE - 1) / MCQ_FQ_TILE); }
+static u64 rd_rcap(u64 L, u64 max_queries) { return std::min<u64>(max_queries, L / 2 + 2); }
+static u64 rd_text_bytes(u64 L, u64 max_queries) {
+    const u64 nt = rd_tiles(L);
+    return 2 * rd_align(nt * 8) + 2 * rd_align((nt + 1) * 8) + rd_align((L + 1) * 4) + rd_align((L / 2 + 2) * 4) + rd_align(rd_rcap(L, max_queries) * 4);
+}
+extern "C" uint64_t mcq_reads_scratch_bytes(uint64_t len1, uint64_t len2, uint64_t max_queries) {
+    return rd_text_bytes(len1, max_queries) + rd_text_bytes(len2, max_queries);
+}
+
+extern "C" int mcq_reads_prepare(const char* text1, uint64_t len1, const char* text2, uint64_t len2, uint32_t flags,
+                                 uint64_t max_queries, uint64_t max_bases, void* scratch, uint64_t scratch_bytes,
+                                 char* bases, uint64_t* seq_off, uint64_t* hdr, uint64_t* info, void* stream) {
+    if ((len1 && !text1) || (len2 && !text2) || !scratch || !bases || !seq_off || !hdr || !info) return fail(MCQ_E_ARG, "null argument");
+    if (max_queries < 1) return fail(MCQ_E_ARG, "max_queries must be >= 1");
+    if (len1 >= 0xFFFFFFFFull || len2 >= 0xFFFFFFFFull) return fail(MCQ_E_UNSUPPORTED, "a chunk of read text is below 4 GiB");
+    if (scratch_bytes < mcq_reads_scratch_bytes(len1, len2, max_queries)) return fail(MCQ_E_ARG, "scratch smaller than mcq_reads_scratch_bytes");
+    hipStream_t st = (hipStream_t)stream;
+    RdPair P; memset(&P, 0, sizeof(P));
+    P.mates = text2 ? 2 : 1; P.info = info;
+    char* s = (char*)scratch;
+    auto take = [&](u64 bytes) { char* p = s; s += rd_align(bytes); return p; };
+    const char* tx[2] = {text1, text2};
+    const u64 lx[2] = {len1, len2};
+    u64 tiles = 1, qcap = max_queries;
+    for (u32 m = 0; m < 2; ++m) {
+        RdText& X = P.x[m];
+        X.t = tx[m]; X.L = lx[m]; X.eof = (flags >> m) & 1u;
+        X.n_tiles = rd_tiles(X.L); X.rcap = rd_rcap(X.L, max_queries);
+        X.cnt_nl = (u64*)take(X.n_tiles * 8); X.cnt_h = (u64*)take(X.n_tiles * 8);
+        X.off_nl = (u64*)take((X.n_tiles + 1) * 8); X.off_h = (u64*)take((X.n_tiles + 1) * 8);
+        X.nl = (u32*)take((X.L + 1) * 4); X.hl = (u32*)take((X.L / 2 + 2) * 4); X.rlen = (u32*)take(X.rcap * 4);
+        if (m < P.mates) { tiles = std::max(tiles, X.n_tiles); qcap = std::min(qcap, X.rcap); }
+    }
+    if (tiles >= (1ull << 31)) return fail(MCQ_E_UNSUPPORTED, "text too large for one call");
+    HIPCHK(hipMemsetAsync(info, 0, MCQ_READS_INFO_WORDS * 8, st));
+    hipLaunchKernelGGL(k_rd_count, dim3((u32)tiles, P.mates), dim3(256), 0, st, P);
+    for (u32 m = 0; m < P.mates; ++m) {
+        int rc = device_exclusive_scan<u64>((const u64*)P.x[m].cnt_nl, P.x[m].off_nl, P.x[m].n_tiles, st); if (rc) return rc;
+        rc = device_exclusive_scan<u64>((const u64*)P.x[m].cnt_h, P.x[m].off_h, P.x[m].n_tiles, st); if (rc) return rc;
+    }
+    hipLaunchKernelGGL(k_rd_lines, dim3((u32)tiles, P.mates), dim3(256), 0, st, P);
+    const u64 rmax = std::max(P.x[0].rcap, P.mates == 2 ? P.x[1].rcap : 0);
+    hipLaunchKernelGGL(k_rd_recs, dim3((u32)std::min<u64>((rmax + 255) / 256, 1024), P.mates), dim3(256), 0, st, P);
+    hipLaunchKernelGGL(k_rd_offsets, dim3(1), dim3(1024), 0, st, P, max_queries, max_bases, seq_off);
+    hipLaunchKernelGGL(k_rd_copy, dim3((u32)std::min<u64>((qcap + 3) / 4, 2048), P.mates), dim3(256), 0, st, P, (const u64*)seq_off, bases, hdr);
     HIPCHK(hipGetLastError());
     return MCQ_OK;
 }

@@ -142,6 +142,9 @@ def lib():
                                    C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
         L.mcq_fastq_index.argtypes = [C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p]
         L.mcq_fasta_index.argtypes = [C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p]
+        L.mcq_reads_scratch_bytes.restype = C.c_uint64; L.mcq_reads_scratch_bytes.argtypes = [C.c_uint64, C.c_uint64, C.c_uint64]
+        L.mcq_reads_prepare.argtypes = [C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.c_uint32, C.c_uint64, C.c_uint64,
+                                        C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
         L.mcq_build_table.argtypes = [C.POINTER(BuildDesc), C.POINTER(C.c_void_p)]
         L.mcq_db_build.argtypes = [C.POINTER(BuildDesc), C.POINTER(C.c_void_p)]
         L.mcq_table_info.argtypes = [C.c_void_p] + [C.c_void_p] * 6
@@ -700,6 +703,22 @@ def fastq_index(text_ptr, n_bytes, ranges_ptr, max_seqs, n_seqs_ptr, stream=None
 def fasta_index(text_ptr, n_bytes, ranges_ptr, max_seqs, n_seqs_ptr, stream=None):
     """the same for FASTA text with one sequence line per record"""
     _chk(lib().mcq_fasta_index(text_ptr, n_bytes, ranges_ptr, max_seqs, n_seqs_ptr, stream))
+
+
+MCQ_READS_EOF1, MCQ_READS_EOF2, MCQ_READS_NOT_STRICT = 1, 2, 1
+MCQ_READS_INFO_WORDS = 8
+
+
+def reads_scratch_bytes(len1, len2, max_queries):
+    return int(lib().mcq_reads_scratch_bytes(len1, len2, max_queries))
+
+
+def reads_prepare(text1_ptr, len1, text2_ptr, len2, flags, max_queries, max_bases, scratch_ptr, scratch_bytes,
+                  bases_ptr, seq_off_ptr, hdr_ptr, info_ptr, stream=None):
+    """one chunk of FASTQ / FASTA text per file in HBM (text2_ptr None: single-end) -> compacted bases, seq_off, header
+    ranges and info[MCQ_READS_INFO_WORDS] (device buffers; include/mcq.h mcq_reads_prepare)"""
+    _chk(lib().mcq_reads_prepare(text1_ptr, len1, text2_ptr, len2, flags, max_queries, max_bases, scratch_ptr, scratch_bytes,
+                                 bases_ptr, seq_off_ptr, hdr_ptr, info_ptr, stream))
 
 
 def owner(feature, n_shards):

@@ -83,6 +83,12 @@ def lib():
         L.mcq_shard_stream_open.argtypes = [C.c_void_p, C.c_uint32, C.POINTER(C.c_void_p)]
         L.mcq_shard_stream_next.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64)]
         L.mcq_shard_stream_close.argtypes = [C.c_void_p]
+        L.mcq_read_stream_open.argtypes = [C.c_char_p, C.POINTER(C.c_void_p)]
+        L.mcq_read_stream_fill.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint64, C.POINTER(C.c_uint64), C.POINTER(C.c_int32)]
+        L.mcq_read_stream_consume.argtypes = [C.c_void_p, C.c_uint64]
+        L.mcq_read_stream_close.argtypes = [C.c_void_p]
+        L.mcq_reads_parse.argtypes = [C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.c_uint32, C.c_uint64, C.c_uint64,
+                                      C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
         _lib = L
     return _lib
 
@@ -195,3 +201,108 @@ class RefDb:
 
 def rank_from_name(name):
     return int(lib().mcq_rank_from_name(name.encode()))
+
+
+# ---- read files in chunks (mcq_read_stream_*, mcq_reads_parse): what mcq_query_cli's input stage does, for the tests
+READS_EOF1, READS_EOF2 = 1, 2
+READS_N, READS_BASES, READS_CUT1, READS_CUT2, READS_STATUS, READS_COMPLETE1, READS_COMPLETE2, READS_INFO_WORDS = 0, 1, 2, 3, 4, 5, 6, 8
+READS_NOT_STRICT = 1
+
+
+def parse_chunk(texts, flags, max_queries, max_bases):
+    """mcq_reads_parse on one chunk per file (texts: 1 or 2 bytes objects) -> (info, bases, seq_off, hdr) as numpy arrays"""
+    t1 = texts[0]
+    t2 = texts[1] if len(texts) > 1 else None
+    cap_q = max(1, min(max_queries, min(len(t) for t in texts) // 2 + 2))     # (no chunk holds more records: as mcq_query_cli sizes it)
+    bases = np.zeros(len(t1) + (len(t2) if t2 is not None else 0) + 1, np.uint8)
+    seq_off = np.zeros(2 * cap_q + 1, np.uint64)
+    hdr = np.zeros(2 * cap_q, np.uint64)
+    info = np.zeros(READS_INFO_WORDS, np.uint64)
+    rc = lib().mcq_reads_parse(t1, len(t1), t2, len(t2) if t2 is not None else 0, flags, cap_q, max_bases,
+                               bases.ctypes.data_as(C.c_void_p), seq_off.ctypes.data_as(C.c_void_p), hdr.ctypes.data_as(C.c_void_p),
+                               info.ctypes.data_as(C.c_void_p))
+    if rc != 0:
+        raise RuntimeError(lib().mcq_host_last_error().decode())
+    return info, bases, seq_off, hdr
+
+
+class ReadStream:
+    """mcq_read_stream_*: one file read in chunks, the unconsumed tail of a chunk carried into the next"""
+
+    def __init__(self, path):
+        h = C.c_void_p()
+        if lib().mcq_read_stream_open(str(path).encode(), C.byref(h)) != 0:
+            raise RuntimeError(lib().mcq_host_last_error().decode())
+        self.h = h
+
+    def fill(self, buf, want):
+        n, eof = C.c_uint64(), C.c_int32()
+        if lib().mcq_read_stream_fill(self.h, buf, len(buf), want, C.byref(n), C.byref(eof)) != 0:
+            raise RuntimeError(lib().mcq_host_last_error().decode())
+        return int(n.value), bool(eof.value)
+
+    def consume(self, n):
+        if lib().mcq_read_stream_consume(self.h, n) != 0:
+            raise RuntimeError(lib().mcq_host_last_error().decode())
+
+    def close(self):
+        if getattr(self, "h", None):
+            lib().mcq_read_stream_close(self.h); self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def read_batches(paths, chunk, max_queries=1 << 40, max_bases=1 << 62, prepare=None):
+    """The input stage of mcq_query_cli on 1 or 2 files: fill a chunk per file (three buffer sets in rotation, so the carry
+    moves from one buffer to another), prepare it (default: parse_chunk; the GPU tests pass the device step), consume what
+    it used; a file with no complete record in a full chunk gets a buffer twice as large, for that chunk only.  Yields
+    (texts, info, bases, seq_off, hdr, caps) per batch; caps = the buffer sizes used."""
+    prepare = prepare or parse_chunk
+    streams = [ReadStream(p) for p in paths]
+    sets = [[C.create_string_buffer(max(1, chunk)) for _ in paths] for _ in range(3)]
+    want = [max(1, chunk)] * len(paths)
+    carry = [0] * len(paths)
+    j = 0
+    try:
+        while True:
+            bufs = sets[j % 3]
+            texts, flags = [], 0
+            for m, s in enumerate(streams):
+                old = bufs[m]                                       # (may hold the carry: alive until the fill has moved it)
+                need = max(want[m], carry[m])
+                if len(bufs[m]) < need:
+                    bufs[m] = C.create_string_buffer(need)
+                n, eof = s.fill(bufs[m], need)
+                del old
+                texts.append(bufs[m].raw[:n])
+                flags |= (READS_EOF1 << m) if eof else 0
+            info, bases, seq_off, hdr = prepare(texts, flags, max_queries, max_bases)
+            n = int(info[READS_N])
+            if n == 0:
+                done = False
+                for m in range(len(paths)):
+                    if int(info[READS_COMPLETE1 + m]) == 0:
+                        if flags & (READS_EOF1 << m):
+                            done = True
+                        else:
+                            want[m] = 2 * len(texts[m])
+                for m, s in enumerate(streams):
+                    s.consume(0)
+                    carry[m] = len(texts[m])
+                if done:
+                    return
+                continue
+            caps = [len(b) for b in bufs]
+            for m, s in enumerate(streams):
+                s.consume(int(info[READS_CUT1 + m]))
+                carry[m] = len(texts[m]) - int(info[READS_CUT1 + m])
+                want[m] = max(1, chunk)
+            yield texts, info, bases, seq_off, hdr, caps
+            j += 1
+    finally:
+        for s in streams:
+            s.close()

@@ -1,0 +1,105 @@
+"""The chunked reader of the host library (mcq_read_stream_* + mcq_reads_parse, include/mcq_host.h): mcq_query_cli's input
+stage reads its files in chunks of -read-chunk bytes and carries a record that a chunk boundary cuts into the next chunk.
+Whatever the chunk size, the records must be exactly those the whole-file reader gives (tests/read_corpus.py restates
+read_records), the buffers must stay bounded by the chunk size and the longest record, and the batch limits must hold."""
+import importlib
+
+import numpy as np
+import pytest
+
+from read_corpus import corpus, read_records
+
+CHUNKS = list(range(1, 301)) + [4096, 1 << 16]
+
+
+@pytest.fixture(scope="module")
+def host():
+    pkg = importlib.import_module("metacache-mpi_amd")
+    pkg.build_host()
+    return importlib.import_module("metacache-mpi_amd.host")
+
+
+def _expected(files):
+    recs = [read_records(f) for f in files]
+    n = min(len(r) for r in recs)
+    return [tuple((r[q][0], r[q][1]) for r in recs) for q in range(n)], recs
+
+
+def _span_bound(data, recs):
+    """largest number of bytes from a record's start to just past the first byte of the next record (what must sit in one
+    buffer before the record counts as complete)"""
+    starts = [at for _, _, at in recs] + [len(data)]
+    return max([starts[i + 1] - starts[i] + 1 for i in range(len(recs))] + [starts[0] + 1])
+
+
+def _run(host, paths, chunk, max_q=1 << 40, max_b=1 << 62):
+    got, caps, sizes = [], [], []
+    for texts, info, bases, seq_off, hdr, cap in host.read_batches(paths, chunk, max_q, max_b):
+        n, mates = int(info[host.READS_N]), len(texts)
+        assert info[host.READS_STATUS] == 0
+        assert 1 <= n <= max_q
+        nb = int(seq_off[n * mates])
+        assert nb == info[host.READS_BASES]
+        sizes.append((n, nb, [int(seq_off[(q + 1) * mates] - seq_off[q * mates]) for q in range(n)]))
+        for q in range(n):
+            mate_seqs = [bytes(bases[int(seq_off[q * mates + m]):int(seq_off[q * mates + m + 1])]) for m in range(mates)]
+            h = texts[0][int(hdr[2 * q]):int(hdr[2 * q + 1])]
+            got.append(tuple([(h, mate_seqs[0])] + [(None, s) for s in mate_seqs[1:]]))
+        caps.append(cap)
+    return got, caps, sizes
+
+
+@pytest.mark.parametrize("name", sorted(corpus()))
+def test_chunked_reader_gives_the_records_of_the_whole_file_reader(host, name, tmp_path):
+    files, _strict = corpus()[name]
+    paths = []
+    for i, data in enumerate(files):
+        p = tmp_path / ("r%d.fq" % (i + 1))
+        p.write_bytes(data)
+        paths.append(p)
+    exp, recs = _expected(files)
+    exp = [tuple([(e[0][0], e[0][1])] + [(None, m[1]) for m in e[1:]]) for e in exp]
+    bound = [_span_bound(d, r) if r else len(d) + 1 for d, r in zip(files, recs)]
+    for chunk in CHUNKS:
+        got, caps, _ = _run(host, paths, chunk)
+        assert got == exp, (name, chunk)
+        for cap in caps:                       # memory: the chunk, or twice what one record needs
+            for m, c in enumerate(cap):
+                assert c <= max(chunk, 2 * bound[m]), (name, chunk, m, c, bound[m])
+
+
+@pytest.mark.parametrize("name", ["fq_lf", "fa_wrap60", "paired_fq", "paired_fa_fq", "long_record_fa"])
+@pytest.mark.parametrize("chunk", [97, 4096])
+@pytest.mark.parametrize("max_q,max_b", [(1, 1 << 62), (3, 1 << 62), (1 << 40, 150), (4, 400), (1 << 40, 1)])
+def test_batch_limits(host, name, chunk, max_q, max_b, tmp_path):
+    """n < max_queries; bases <= max_bases unless one query alone is larger; the records themselves unchanged"""
+    files, _ = corpus()[name]
+    paths = []
+    for i, data in enumerate(files):
+        p = tmp_path / ("r%d.fq" % (i + 1))
+        p.write_bytes(data)
+        paths.append(p)
+    exp, _ = _expected(files)
+    got, _, sizes = _run(host, paths, chunk, max_q, max_b)
+    assert [g[0][0] for g in got] == [e[0][0] for e in exp]
+    assert [tuple(x[1] for x in g) for g in got] == [tuple(x[1] for x in e) for e in exp]
+    for n, nb, qlen in sizes:
+        assert n <= max_q
+        assert nb <= max_b or n == 1, (n, nb, max_b)
+
+
+def test_parse_reports_carry_and_completeness(host):
+    """one chunk by hand: a cut record is not taken and is where the carry starts; at the end of the file it is taken"""
+    t = b"@a x\nAC\n+\nII\n@b\nGG"
+    info, bases, seq_off, hdr = host.parse_chunk([t], 0, 100, 1 << 30)
+    assert int(info[host.READS_N]) == 1 and int(info[host.READS_CUT1]) == t.index(b"@b") and int(info[host.READS_COMPLETE1]) == 1
+    assert bytes(bases[:2]) == b"AC" and t[int(hdr[0]):int(hdr[1])] == b"a"
+    info, bases, seq_off, hdr = host.parse_chunk([t], host.READS_EOF1, 100, 1 << 30)
+    assert int(info[host.READS_N]) == 2 and int(info[host.READS_CUT1]) == len(t)
+    assert bytes(bases[:int(info[host.READS_BASES])]) == b"ACGG"
+    # FASTA: complete only once the next header has begun
+    t = b">a\nAC\nGT\n>b\nTT\n"
+    info, *_ = host.parse_chunk([t], 0, 100, 1 << 30)
+    assert int(info[host.READS_N]) == 1 and int(info[host.READS_CUT1]) == t.index(b">b")
+    info, bases, _, _ = host.parse_chunk([t], host.READS_EOF1, 100, 1 << 30)
+    assert int(info[host.READS_N]) == 2 and bytes(bases[:6]) == b"ACGTTT"
