@@ -71,10 +71,11 @@ def build_host(force=False, verbose=False):
         subprocess.check_call(cmd)
     cli_src = os.path.join(_HERE, "csrc", "host", "mcq_query_cli.cpp")
     cli = cli_path()
-    open_hpp = os.path.join(os.path.dirname(_HERE), "include", "mcq_open.hpp")
-    if force or not os.path.exists(cli) or os.path.getmtime(cli) < max(os.path.getmtime(cli_src), os.path.getmtime(out), os.path.getmtime(lib_path()),
-                                                                         os.path.getmtime(os.path.join(_HERE, "csrc", "host", "mcq_cli_common.hpp")),
-                                                                         os.path.getmtime(open_hpp)):
+    # what both programs depend on besides their own source: the two libraries and every header they include
+    shared = [out, lib_path(), _HDR, hdr, os.path.join(os.path.dirname(_HERE), "include", "mcq_open.hpp")] + \
+             [os.path.join(_HERE, "csrc", "host", h) for h in ("mcq_cli_common.hpp", "mcq_cli_buffers.hpp")]
+    cli_deps = shared + [cli_src, os.path.join(_HERE, "csrc", "host", "mcq_read_batches.hpp")]
+    if force or not os.path.exists(cli) or os.path.getmtime(cli) < max(os.path.getmtime(f) for f in cli_deps):
         hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
         cmd = [hipcc, "-std=c++14", "-O2", "-pthread", cli_src, "-o", cli, "-L" + _HERE, "-lmcq_hip", "-lmcq_host", "-Wl,-rpath,$ORIGIN"]
         if verbose:
@@ -82,7 +83,6 @@ def build_host(force=False, verbose=False):
         subprocess.check_call(cmd)
     # the MPI program (multi-GPU host in C++): only where an MPI is installed
     mpi_src = os.path.join(_HERE, "csrc", "host", "mcq_query_mpi.cpp")
-    common = os.path.join(_HERE, "csrc", "host", "mcq_cli_common.hpp")
     mpi_h = os.path.join(_MPI_ROOT, "include", "mpi.h")
     mpi_so = os.path.join(_MPI_ROOT, "lib", _MPI_LIBS[0])
     if os.path.exists(mpi_h) and os.path.exists(mpi_so):
@@ -92,7 +92,7 @@ def build_host(force=False, verbose=False):
             if not os.path.lexists(dst) and os.path.exists(os.path.join(_MPI_ROOT, "lib", l)):
                 os.symlink(os.path.join(_MPI_ROOT, "lib", l), dst)
         mpi_cli = mpi_cli_path()
-        newest = max(os.path.getmtime(f) for f in (mpi_src, common, out, lib_path(), open_hpp))
+        newest = max(os.path.getmtime(f) for f in shared + [mpi_src])
         if force or not os.path.exists(mpi_cli) or os.path.getmtime(mpi_cli) < newest:
             rocm = os.environ.get("ROCM_PATH", "/opt/rocm")
             # plain g++ (host code only; hipcc would take libmpi.so.12 for a source file)

@@ -1,6 +1,6 @@
 #pragma once
 // mcq_cli_common.hpp -- what mcq_query_cli (one GPU) and mcq_query_mpi (one process per GPU under mpiexec) share: the
-// readers, the options and the writers of the reference's -out file.
+// options, the opening of the database and the writers of the reference's -out file.
 //
 // mcq_query_cli -- stand-in for `mpiexec -n P metacache query <db> r1.fq r2.fq -pairfiles ...`
 // (src/mode_query.cpp:404-458) around the engine: reads the reference's shard files, runs the per-read path on
@@ -25,7 +25,7 @@
 //            [-hitdiff X] [-insertsize N] [-threads N] [-tophits] [-taxids] [-taxids-only] [-omit-ranks] [-lineage]
 //            [-mapped-only] [-nomap] [-noquirks] [-abundances [FILE]] [-abundance-per R] [-out FILE] [-batch N] [-batch-bases N]
 //            [-read-chunk BYTES] [-reader gpu|host]
-// (-batch / -batch-bases: queries / bases per batch; the reads go through in batches, see mcq_query_cli.cpp;
+// (-batch / -batch-bases: queries / bases per batch; the reads go through in batches, see mcq_read_batches.hpp;
 //  -read-chunk / -reader (mcq_query_cli only, written into no output): bytes per read() of each file, default 8 MiB, and
 //  who parses the chunks -- the GPU (mcq_reads_prepare; a chunk not in the strict form goes to the host) or always the host;
 //  -abundances [FILE] / -abundance-per R (aliases -abundances-per, -abundance_per, -abundances_per): src/query_options.cpp:310-323)
@@ -42,30 +42,6 @@
 #include "../../../include/mcq_host.h"
 #include "../../../include/mcq_open.hpp"
 
-struct Rec { std::string header, seq; };
-
-// FASTA ('>') and FASTQ ('@') records; sequence may span lines in FASTA (src/sequence_io.cpp:122-285)
-static bool read_records(const std::string& path, std::vector<Rec>& out) {
-    std::ifstream is(path);
-    if (!is.good()) return false;
-    std::string line;
-    while (std::getline(is, line)) {
-        if (line.empty()) continue;
-        if (line[0] == '@') {
-            Rec r; r.header = line.substr(1);
-            std::getline(is, r.seq);
-            std::getline(is, line); std::getline(is, line);          // '+' and qualities
-            out.push_back(std::move(r));
-        } else if (line[0] == '>') {
-            Rec r; r.header = line.substr(1);
-            out.push_back(std::move(r));
-        } else if (!out.empty()) {
-            out.back().seq += line;
-        }
-    }
-    return true;
-}
-
 // How a taxon is written (the reference's taxon_print_mode, src/query_options.h:68-71; output of src/printing.cpp:117-176,
 // :243-300) as two independent choices: an optional "<rank>:" prefix, and one of three bodies -- name, id, name(id).
 struct Mode {
@@ -73,50 +49,6 @@ struct Mode {
     static constexpr Mode make(bool show_ranks, bool taxids, bool taxids_only) { return Mode{show_ranks, taxids_only ? 1 : (taxids ? 2 : 0)}; }
     bool ids_only() const { return body == 1; }
 };
-
-struct Out {
-    mcq_refdb* db;
-    Mode mode = Mode{true, 0};
-    uint32_t lowest = MCQ_RANK_SEQUENCE, highest = MCQ_RANK_DOMAIN;
-    bool lineage = false, tophits = false;
-    const char* comment = "# "; const char* none = "--"; const char* col = "\t|\t";
-
-    // one taxon column entry: [prefix ':'] body, the body built from a name text and an id text
-    template <class Name, class Id>
-    void entry(std::ostream& os, const char* prefix, const Name& name, const Id& id) const {
-        if (mode.rank_prefix) os << prefix << ':';
-        if (mode.body != 1) os << name;
-        if (mode.body == 2) os << '(';
-        if (mode.body != 0) os << id;
-        if (mode.body == 2) os << ')';
-    }
-    void taxon(std::ostream& os, uint32_t key) const {
-        entry(os, mcq_rank_name(mcq_refdb_taxon_rank(db, key)), mcq_refdb_taxon_name(db, key), mcq_refdb_taxon_id(db, key));
-    }
-    void no_taxon(std::ostream& os, uint32_t rank) const { entry(os, mcq_rank_name(rank), none, 0); }
-    // classification column: show_taxon(os, db, opt, tax), src/printing.cpp:305-330 (collapseUnclassified is on)
-    void best(std::ostream& os, uint32_t key) const {
-        if (key == MCQ_NO_TAXON || mcq_refdb_taxon_rank(db, key) > highest) {
-            if (mode.ids_only() && !mode.rank_prefix) os << 0; else os << none;
-            return;
-        }
-        const uint32_t tr = mcq_refdb_taxon_rank(db, key);
-        const uint32_t rmin = lowest < tr ? tr : lowest, rmax = lineage ? highest : rmin;
-        for (uint32_t r = rmin; r <= rmax; ++r) {                           // show_lineage, src/printing.cpp:181-201
-            const uint32_t a = mcq_refdb_ancestor(db, key, r);
-            if (a != MCQ_NO_TAXON) taxon(os, a); else no_taxon(os, r);
-            if (r < rmax) os << ',';
-        }
-    }
-    void header_taxon(std::ostream& os) const {          // the TABLE_LAYOUT line's taxon column: one entry per rank shown
-        const uint32_t rmax = lineage ? highest : lowest;
-        for (uint32_t r = lowest; r <= rmax; ++r) {
-            entry(os, lowest == rmax ? "rank" : mcq_rank_name(r), "taxname", "taxid");
-            if (r < rmax) os << ',';
-        }
-    }
-};
-
 
 struct Options {
     std::string prefix, f1, f2, outfile;
@@ -176,15 +108,53 @@ static bool parse_options(int argc, char** argv, Options& o) {
     return true;
 }
 
+struct Out {
+    mcq_refdb* db; const Options& p; Mode mode;
+    const char* comment = "# "; const char* none = "--"; const char* col = "\t|\t";
+
+    // one taxon column entry: [prefix ':'] body, the body built from a name text and an id text
+    template <class Name, class Id>
+    void entry(std::ostream& os, const char* prefix, const Name& name, const Id& id) const {
+        if (mode.rank_prefix) os << prefix << ':';
+        if (mode.body != 1) os << name;
+        if (mode.body == 2) os << '(';
+        if (mode.body != 0) os << id;
+        if (mode.body == 2) os << ')';
+    }
+    void taxon(std::ostream& os, uint32_t key) const {
+        entry(os, mcq_rank_name(mcq_refdb_taxon_rank(db, key)), mcq_refdb_taxon_name(db, key), mcq_refdb_taxon_id(db, key));
+    }
+    void no_taxon(std::ostream& os, uint32_t rank) const { entry(os, mcq_rank_name(rank), none, 0); }
+    // classification column: show_taxon(os, db, opt, tax), src/printing.cpp:305-330 (collapseUnclassified is on)
+    void best(std::ostream& os, uint32_t key) const {
+        if (key == MCQ_NO_TAXON || mcq_refdb_taxon_rank(db, key) > p.highest) {
+            if (mode.ids_only() && !mode.rank_prefix) os << 0; else os << none;
+            return;
+        }
+        const uint32_t tr = mcq_refdb_taxon_rank(db, key);
+        const uint32_t rmin = p.lowest < tr ? tr : p.lowest, rmax = p.lineage ? p.highest : rmin;
+        for (uint32_t r = rmin; r <= rmax; ++r) {                           // show_lineage, src/printing.cpp:181-201
+            const uint32_t a = mcq_refdb_ancestor(db, key, r);
+            if (a != MCQ_NO_TAXON) taxon(os, a); else no_taxon(os, r);
+            if (r < rmax) os << ',';
+        }
+    }
+    void header_taxon(std::ostream& os) const {          // the TABLE_LAYOUT line's taxon column: one entry per rank shown
+        const uint32_t rmax = p.lineage ? p.highest : p.lowest;
+        for (uint32_t r = p.lowest; r <= rmax; ++r) {
+            entry(os, p.lowest == rmax ? "rank" : mcq_rank_name(r), "taxname", "taxid");
+            if (r < rmax) os << ',';
+        }
+    }
+};
+
 static Out make_out(mcq_refdb* rdb, const Options& p) {
-    Out o; o.db = rdb; o.lowest = p.lowest; o.highest = p.highest; o.lineage = p.lineage; o.tophits = p.tophits;
-    o.mode = Mode::make(p.show_ranks, p.taxids, p.taxids_only);          // -taxids-only wins over -taxids (src/query_options.cpp:262-274)
-    return o;
+    return Out{rdb, p, Mode::make(p.show_ranks, p.taxids, p.taxids_only)};   // -taxids-only wins over -taxids (src/query_options.cpp:262-274)
 }
 
 // show_query_parameters (src/printing.cpp:40-113) + show_query_mapping_header (src/classification.cpp:486-512) + the file line
-static void write_head(std::ostream& os, const Out& o, const Options& p, uint32_t hitmin) {
-    const char* cm = o.comment;
+static void write_head(std::ostream& os, const Out& o, uint32_t hitmin) {
+    const Options& p = o.p; const char* cm = o.comment;
     if (!p.nomap) {
         os << cm << "Reporting per-read mappings (non-mapping lines start with '" << cm << "').\n";
         if (p.lineage) os << cm << "The complete lineage will be reported starting with the lowest match.\n";
@@ -211,9 +181,9 @@ static void write_head(std::ostream& os, const Out& o, const Options& p, uint32_
 // one query: classification (src/classification.cpp:235-265), statistics (classification_statistics::assign,
 // src/classification_statistics.h:69-78) and its mapping line (show_query_mapping, src/classification.cpp:583-632)
 // (token: the header up to its first ' ', what the line prints)
-static void write_query(std::ostream& os, const Out& o, const Options& p, uint32_t hitmin, const char* token, size_t token_len,
+static void write_query(std::ostream& os, const Out& o, uint32_t hitmin, const char* token, size_t token_len,
                         const mcq_cand* cands, uint32_t ncand, uint64_t* assigned /* [MCQ_RANK_NONE + 1] */) {
-    mcq_refdb* rdb = o.db;
+    mcq_refdb* rdb = o.db; const Options& p = o.p;
     const uint32_t best = mcq_refdb_classify(rdb, reinterpret_cast<const uint32_t*>(cands), ncand, hitmin, p.hitdiff, p.highest);
     if (best == MCQ_NO_TAXON) ++assigned[MCQ_RANK_NONE];
     else for (uint32_t r = mcq_refdb_taxon_rank(rdb, best); r <= MCQ_RANK_ROOT; ++r) ++assigned[r];
@@ -236,14 +206,14 @@ static void write_query(std::ostream& os, const Out& o, const Options& p, uint32
     o.best(os, best);
     os << '\n';
 }
-static void write_query(std::ostream& os, const Out& o, const Options& p, uint32_t hitmin, const std::string& header,
+static void write_query(std::ostream& os, const Out& o, uint32_t hitmin, const std::string& header,
                         const mcq_cand* cands, uint32_t ncand, uint64_t* assigned) {
-    write_query(os, o, p, hitmin, header.data(), std::min(header.size(), header.find(' ')), cands, ncand, assigned);
+    write_query(os, o, hitmin, header.data(), std::min(header.size(), header.find(' ')), cands, ncand, assigned);
 }
 
 // show_summary (src/printing.cpp:622-641) + show_taxon_statistics (:522-555)
-static void write_summary(std::ostream& os, const Out& o, const Options& p, const uint64_t* assigned, double ms) {
-    const char* cm = o.comment;
+static void write_summary(std::ostream& os, const Out& o, const uint64_t* assigned, double ms) {
+    const Options& p = o.p; const char* cm = o.comment;
     const uint64_t total = assigned[MCQ_RANK_ROOT] + assigned[MCQ_RANK_NONE];
     const uint64_t num_queries = p.paired() ? 2 * total : total;             // paired reads count twice (:626-627)
     os << cm << "queries: " << num_queries << '\n'
@@ -276,9 +246,27 @@ static mcq_taxonomy* make_taxonomy(mcq_refdb* rdb, int device) {
     if (mcq_taxonomy_create(lin.data(), rank.data(), info.n_taxa, device, &tx)) { std::fprintf(stderr, "ABORT: %s\n", mcq_last_error()); return nullptr; }
     return tx;
 }
+static mcq_query_opts query_opts(const Options& p) {
+    mcq_query_opts qo; qo.max_cand = p.maxcand; qo.emulate_ranks = p.P; qo.insert_size_max = p.insertsize; qo.flags = p.quirks ? MCQ_QUIRK_SEQ_DROP : 0;
+    return qo;
+}
 static mcq_classify_opts classify_opts(const Options& p, uint32_t hitmin) {
     mcq_classify_opts co; co.hits_min = hitmin; co.hits_diff_fraction = p.hitdiff; co.highest_rank = p.highest; co.flags = 0;
     return co;
+}
+
+// where the mapping lines go: the -out file (`file`, opened here) if one was named, else stdout
+static std::ostream& open_out(const Options& p, std::ofstream& file) {
+    if (!p.outfile.empty()) file.open(p.outfile);
+    return p.outfile.empty() ? std::cout : file;
+}
+
+// counts += the per-taxon counts that ws has gathered since it was made ([n_taxa + 1])
+static bool add_taxon_counts(mcq_ws* ws, std::vector<uint64_t>& counts) {
+    std::vector<uint64_t> c(counts.size(), 0);
+    if (mcq_ws_taxon_counts(ws, c.data(), 0)) { std::fprintf(stderr, "ABORT: %s\n", mcq_last_error()); return false; }
+    for (size_t i = 0; i < c.size(); ++i) counts[i] += c[i];
+    return true;
 }
 
 // the abundance tables (src/classification.cpp:744-757) from the device's counts ([n_taxa + 1], the last slot the unclassified
@@ -318,14 +306,17 @@ static bool write_abundances(std::ostream& os, mcq_refdb* rdb, const Options& p,
 // The reference's shard files -> the queryable handle of shard `shard_id` of `n_shards` (include/mcq_open.hpp: the host-side union
 // for small databases, the streaming route -- heads on the host, tables merged on the GPU -- from MCQ_STREAM_LOAD_MIN_MB, default
 // 1024, MB of shard files on)
-static bool open_database(const Options& p, mcq_refdb** rdb, std::vector<uint32_t>& t2t, mcq_db** edb, uint32_t& hitmin,
-                          uint32_t n_shards, uint32_t shard_id, int device) {
+struct Database {
+    mcq_refdb* rdb = nullptr; mcq_db* edb = nullptr; std::vector<uint32_t> t2t; uint32_t hitmin = 0;     // hitmin: -hitmin or its default
+    ~Database() { mcq_db_destroy(edb); mcq_refdb_close(rdb); }
+};
+static bool open_database(const Options& p, Database& db, uint32_t n_shards, uint32_t shard_id, int device) {
     std::string err; bool streamed = false;
-    if (mcq_open_refdb(p.prefix, p.P, mcq_stream_load_min_bytes(), rdb, &streamed, err)) { std::fprintf(stderr, "ABORT: %s\n", err.c_str()); return false; }
-    mcq_refdb_info info; mcq_refdb_get_info(*rdb, &info);
-    hitmin = p.hitmin < 1 ? mcq_default_hits_min(info.sketch_size) : p.hitmin;
-    t2t.resize(info.n_targets);
-    if (mcq_refdb_tgt2tax(*rdb, p.lowest, t2t.data())) { std::fprintf(stderr, "ABORT: %s\n", mcq_host_last_error()); return false; }
-    if (mcq_make_db(*rdb, streamed, t2t.data(), n_shards, shard_id, device, edb, err)) { std::fprintf(stderr, "ABORT: %s\n", err.c_str()); return false; }
+    if (mcq_open_refdb(p.prefix, p.P, mcq_stream_load_min_bytes(), &db.rdb, &streamed, err)) { std::fprintf(stderr, "ABORT: %s\n", err.c_str()); return false; }
+    mcq_refdb_info info; mcq_refdb_get_info(db.rdb, &info);
+    db.hitmin = p.hitmin < 1 ? mcq_default_hits_min(info.sketch_size) : p.hitmin;
+    db.t2t.resize(info.n_targets);
+    if (mcq_refdb_tgt2tax(db.rdb, p.lowest, db.t2t.data())) { std::fprintf(stderr, "ABORT: %s\n", mcq_host_last_error()); return false; }
+    if (mcq_make_db(db.rdb, streamed, db.t2t.data(), n_shards, shard_id, device, &db.edb, err)) { std::fprintf(stderr, "ABORT: %s\n", err.c_str()); return false; }
     return true;
 }

@@ -564,7 +564,7 @@ extern "C" int mcq_read_stream_close(mcq_read_stream* s) {
 }
 
 namespace {
-// the records of one chunk as std::getline reads them (mcq_cli_common.hpp: read_records)
+// the records of one chunk as std::getline reads them (mcq_query_mpi.cpp: read_records)
 struct ChunkRecs {
     std::vector<uint64_t> start, hb, he, piece_at;     // per record: first byte, header line [hb, he) after '@' / '>', first piece
     std::vector<uint64_t> pieces;                      // (begin, end) byte ranges of sequence text, record after record

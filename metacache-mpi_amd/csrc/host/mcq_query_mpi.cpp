@@ -25,12 +25,42 @@
 
 #include <sstream>
 
+#include "mcq_cli_buffers.hpp"
 #include "mcq_cli_common.hpp"
 
-#define HIP_OR_DIE(expr) do { hipError_t e_ = (expr); if (e_ != hipSuccess) { \
-    std::fprintf(stderr, "ABORT: %s: %s\n", #expr, hipGetErrorString(e_)); MPI_Abort(MPI_COMM_WORLD, 1); } } while (0)
+#define HIP_OR_DIE(expr) MCQ_HIP_AS("ABORT", expr, MPI_Abort(MPI_COMM_WORLD, 1))
 #define MCQ_OR_DIE(expr) do { if ((expr) != MCQ_OK) { \
     std::fprintf(stderr, "ABORT: %s: %s\n", #expr, mcq_last_error()); MPI_Abort(MPI_COMM_WORLD, 1); } } while (0)
+
+struct Rec { std::string header, seq; };
+
+// FASTA ('>') and FASTQ ('@') records; sequence may span lines in FASTA (src/sequence_io.cpp:122-285)
+static bool read_records(const std::string& path, std::vector<Rec>& out) {
+    std::ifstream is(path);
+    if (!is.good()) return false;
+    std::string line;
+    while (std::getline(is, line)) {
+        if (line.empty()) continue;
+        if (line[0] == '@') {
+            Rec r; r.header = line.substr(1);
+            std::getline(is, r.seq);
+            std::getline(is, line); std::getline(is, line);          // '+' and qualities
+            out.push_back(std::move(r));
+        } else if (line[0] == '>') {
+            Rec r; r.header = line.substr(1);
+            out.push_back(std::move(r));
+        } else if (!out.empty()) {
+            out.back().seq += line;
+        }
+    }
+    return true;
+}
+
+// one of the three sets of device inputs / outputs
+struct DevSet {
+    DeviceBuf<char> bases; DeviceBuf<uint64_t> off; DeviceBuf<mcq_cand> d_cands; DeviceBuf<uint32_t> d_ncand;
+    PinnedBuf<mcq_cand> cands; PinnedBuf<uint32_t> ncand; Event out;
+};
 
 // mcq_exchange_fn over MPI: device blocks -> host, MPI_Alltoallv, host -> device
 static int exchange_over_mpi(void*, const void* send_base, const uint64_t* send_off, const uint64_t* send_bytes,
@@ -65,9 +95,8 @@ int main(int argc, char** argv) {
     HIP_OR_DIE(hipSetDevice(device));
 
     // this rank's hash range of the table
-    mcq_refdb* rdb = nullptr; std::vector<uint32_t> t2t; uint32_t hitmin = 0;
-    mcq_db* shard = nullptr;
-    if (!open_database(p, &rdb, t2t, &shard, hitmin, (uint32_t)N, (uint32_t)rank, device)) MPI_Abort(MPI_COMM_WORLD, 1);
+    Database db;
+    if (!open_database(p, db, (uint32_t)N, (uint32_t)rank, device)) MPI_Abort(MPI_COMM_WORLD, 1);
 
     // the context for a fixed batch shape and the communicator: set up before the clock starts, like the reference's
     // database load and MPI_Init (identical capacities on every rank)
@@ -76,7 +105,7 @@ int main(int argc, char** argv) {
     cfg.n_ranks = (uint32_t)N; cfg.rank = (uint32_t)rank;
     cfg.max_queries = B; cfg.max_seqs = 2 * B; cfg.max_bases = MB;
     mcq_shard* ctx = nullptr;
-    MCQ_OR_DIE(mcq_shard_create(shard, &cfg, &ctx));
+    MCQ_OR_DIE(mcq_shard_create(db.edb, &cfg, &ctx));
     if (p.transport == "mpi") MCQ_OR_DIE(mcq_shard_set_exchange(ctx, exchange_over_mpi, nullptr));
     else if (N > 1 || std::getenv("MCQ_SHARD_FORCE_RCCL")) {
         char id[MCQ_SHARD_UNIQUE_ID_BYTES];
@@ -87,28 +116,21 @@ int main(int argc, char** argv) {
     // three sets of device inputs / outputs: batch j+1 is staged while batch j-1 may still run (its set is the one batch
     // j+2 will take), results come back on the stream behind the kernels
     constexpr int NS = 3;
-    hipStream_t st = nullptr;
-    HIP_OR_DIE(hipStreamCreateWithFlags(&st, hipStreamNonBlocking));
-    char* d_bases[NS]; uint64_t* d_off[NS]; mcq_cand* d_cands[NS]; uint32_t* d_ncand[NS];
-    mcq_cand* h_cands[NS]; uint32_t* h_ncand[NS]; hipEvent_t ev_out[NS];
-    for (int s = 0; s < NS; ++s) {
-        HIP_OR_DIE(hipMalloc(&d_bases[s], MB + 64));
-        HIP_OR_DIE(hipMalloc(&d_off[s], (2 * B + 1) * 8));
-        HIP_OR_DIE(hipMalloc(&d_cands[s], B * p.maxcand * sizeof(mcq_cand)));
-        HIP_OR_DIE(hipMalloc(&d_ncand[s], B * 4));
-        HIP_OR_DIE(hipHostMalloc(&h_cands[s], B * p.maxcand * sizeof(mcq_cand)));
-        HIP_OR_DIE(hipHostMalloc(&h_ncand[s], B * 4));
-        HIP_OR_DIE(hipEventCreateWithFlags(&ev_out[s], hipEventDisableTiming));
-    }
+    Stream st; DevSet set[NS];
+    bool made = st.create();
+    for (DevSet& S : set)
+        made = made && S.bases.grow(MB + 64) && S.off.grow(2 * B + 1) && S.d_cands.grow(B * p.maxcand) && S.d_ncand.grow(B) &&
+               S.cands.grow(B * p.maxcand) && S.ncand.grow(B) && S.out.create();
 
     // -abundances / -abundance-per: every batch's device results are classified on the GPU into per-taxon counts (reduced to rank 0)
-    mcq_taxonomy* tx = nullptr; uint64_t* d_counts = nullptr; uint32_t n_taxa = 0;
-    const mcq_classify_opts co = classify_opts(p, hitmin);
+    mcq_taxonomy* tx = nullptr; DeviceBuf<uint64_t> d_counts; uint32_t n_taxa = 0;
+    const mcq_classify_opts co = classify_opts(p, db.hitmin);
     if (p.tax_counts()) {
-        mcq_refdb_info info; mcq_refdb_get_info(rdb, &info); n_taxa = info.n_taxa;
-        if (!(tx = make_taxonomy(rdb, device))) MPI_Abort(MPI_COMM_WORLD, 1);
-        HIP_OR_DIE(hipMalloc(&d_counts, ((size_t)n_taxa + 1) * 8));
+        mcq_refdb_info info; mcq_refdb_get_info(db.rdb, &info); n_taxa = info.n_taxa;
+        if (!(tx = make_taxonomy(db.rdb, device))) MPI_Abort(MPI_COMM_WORLD, 1);
+        made = made && d_counts.grow((size_t)n_taxa + 1);
     }
+    if (!made) MPI_Abort(MPI_COMM_WORLD, 1);
 
     MPI_Barrier(MPI_COMM_WORLD);                                            // src/mode_query.cpp:129
     const auto t_start = std::chrono::steady_clock::now();
@@ -136,51 +158,50 @@ int main(int argc, char** argv) {
     auto lo = [&](size_t j) { return j < cut.size() - 1 ? cut[j] : q1; };
     auto hi = [&](size_t j) { return j < cut.size() - 1 ? cut[j + 1] : q1; };
 
-    mcq_query_opts qo; qo.max_cand = p.maxcand; qo.emulate_ranks = p.P; qo.insert_size_max = p.insertsize;
-    qo.flags = p.quirks ? MCQ_QUIRK_SEQ_DROP : 0;
-    const Out o = make_out(rdb, p);
+    const mcq_query_opts qo = query_opts(p);
+    const Out o = make_out(db.rdb, p);
     std::ostringstream lines;
     uint64_t assigned[MCQ_RANK_NONE + 1] = {0};
     std::vector<mcq_batch> in(nb ? nb : 1);
     std::string bases; std::vector<uint64_t> off;
     auto stage = [&](size_t j) {                                           // batch j of this rank to its device set
-        const int s = (int)(j % NS);
+        DevSet& S = set[j % NS];
         bases.clear(); off.assign(1, 0);
         for (size_t q = lo(j); q < hi(j); ++q) {
             bases += r1[q].seq; off.push_back(bases.size());
             if (paired) { bases += r2[q].seq; off.push_back(bases.size()); }
         }
-        if (!bases.empty()) HIP_OR_DIE(hipMemcpy(d_bases[s], bases.data(), bases.size(), hipMemcpyHostToDevice));
-        HIP_OR_DIE(hipMemcpy(d_off[s], off.data(), off.size() * 8, hipMemcpyHostToDevice));
+        if (!bases.empty()) HIP_OR_DIE(hipMemcpy(S.bases.p, bases.data(), bases.size(), hipMemcpyHostToDevice));
+        HIP_OR_DIE(hipMemcpy(S.off.p, off.data(), off.size() * 8, hipMemcpyHostToDevice));
         std::memset(&in[j], 0, sizeof(mcq_batch));
-        in[j].n_seqs = off.size() - 1; in[j].bases = d_bases[s]; in[j].seq_off = d_off[s]; in[j].paired = paired ? 1 : 0; in[j].flags = MCQ_DEVICE_PTRS;
+        in[j].n_seqs = off.size() - 1; in[j].bases = S.bases.p; in[j].seq_off = S.off.p; in[j].paired = paired ? 1 : 0; in[j].flags = MCQ_DEVICE_PTRS;
     };
     auto finish = [&](size_t j) {                                          // results of batch j: wait, write its mapping lines
-        const int s = (int)(j % NS);
-        HIP_OR_DIE(hipEventSynchronize(ev_out[s]));
+        const DevSet& S = set[j % NS];
+        HIP_OR_DIE(hipEventSynchronize(S.out));
         for (size_t q = lo(j); q < hi(j); ++q)
-            write_query(lines, o, p, hitmin, r1[q].header, &h_cands[s][(q - lo(j)) * p.maxcand], h_ncand[s][q - lo(j)], assigned);
+            write_query(lines, o, db.hitmin, r1[q].header, &S.cands.p[(q - lo(j)) * p.maxcand], S.ncand.p[q - lo(j)], assigned);
     };
     // the first batch of a context exchanges exact sizes and learns the block sizes the others travel at; should a later
     // batch not fit them (MCQ_E_CAPACITY at the end), everything is repeated with exact sizes
     for (int attempt = 0; attempt < 2; ++attempt) {
         const uint32_t flags = attempt ? MCQ_SHARD_EXACT : 0;
         lines.str(""); std::memset(assigned, 0, sizeof(assigned));
-        if (d_counts) HIP_OR_DIE(hipMemsetAsync(d_counts, 0, ((size_t)n_taxa + 1) * 8, st));
+        if (tx) HIP_OR_DIE(hipMemsetAsync(d_counts.p, 0, ((size_t)n_taxa + 1) * 8, st));
         if (nb) stage(0);
         for (size_t j = 0; j < nb; ++j) {
-            const int s = (int)(j % NS);
+            DevSet& S = set[j % NS];
             if (j >= 2) finish(j - 2);                                      // (its device set is the one batch j+1 takes)
             if (j + 1 < nb) stage(j + 1);
-            mcq_result res; res.cands = d_cands[s]; res.n_cand = d_ncand[s]; res.flags = MCQ_DEVICE_PTRS;
+            mcq_result res; res.cands = S.d_cands.p; res.n_cand = S.d_ncand.p; res.flags = MCQ_DEVICE_PTRS;
             MCQ_OR_DIE(mcq_shard_query(ctx, &in[j], &qo, &res, st, flags, j + 1 < nb ? &in[j + 1] : nullptr));
             const size_t nqj = hi(j) - lo(j);
-            if (tx && nqj) MCQ_OR_DIE(mcq_classify(tx, &res, nqj, p.maxcand, &co, nullptr, d_counts, st));
+            if (tx && nqj) MCQ_OR_DIE(mcq_classify(tx, &res, nqj, p.maxcand, &co, nullptr, d_counts.p, st));
             if (nqj) {
-                HIP_OR_DIE(hipMemcpyAsync(h_cands[s], d_cands[s], nqj * p.maxcand * sizeof(mcq_cand), hipMemcpyDeviceToHost, st));
-                HIP_OR_DIE(hipMemcpyAsync(h_ncand[s], d_ncand[s], nqj * 4, hipMemcpyDeviceToHost, st));
+                HIP_OR_DIE(hipMemcpyAsync(S.cands.p, S.d_cands.p, nqj * p.maxcand * sizeof(mcq_cand), hipMemcpyDeviceToHost, st));
+                HIP_OR_DIE(hipMemcpyAsync(S.ncand.p, S.d_ncand.p, nqj * 4, hipMemcpyDeviceToHost, st));
             }
-            HIP_OR_DIE(hipEventRecord(ev_out[s], st));
+            HIP_OR_DIE(hipEventRecord(S.out, st));
         }
         if (nb >= 2) finish(nb - 2);
         if (nb >= 1) finish(nb - 1);
@@ -208,27 +229,21 @@ int main(int argc, char** argv) {
     if (tx) {
         counts.resize((size_t)n_taxa + 1); counts_all.resize((size_t)n_taxa + 1);
         HIP_OR_DIE(hipStreamSynchronize(st));
-        HIP_OR_DIE(hipMemcpy(counts.data(), d_counts, counts.size() * 8, hipMemcpyDeviceToHost));
+        HIP_OR_DIE(hipMemcpy(counts.data(), d_counts.p, counts.size() * 8, hipMemcpyDeviceToHost));
         static_assert(sizeof(unsigned long long) == sizeof(uint64_t), "u64 counts travel as MPI_UNSIGNED_LONG_LONG");
         MPI_Reduce(counts.data(), counts_all.data(), (int)counts.size(), MPI_UNSIGNED_LONG_LONG, MPI_SUM, 0, MPI_COMM_WORLD);
     }
     if (rank == 0) {
-        std::ofstream fout; if (!p.outfile.empty()) fout.open(p.outfile);
-        std::ostream& os = p.outfile.empty() ? std::cout : fout;
-        write_head(os, o, p, hitmin);
+        std::ofstream fout;
+        std::ostream& os = open_out(p, fout);
+        write_head(os, o, db.hitmin);
         os << all;
         for (int i = 0; i <= (int)MCQ_RANK_NONE; ++i) assigned[i] = a_all[i];
-        if (tx && !write_abundances(os, rdb, p, counts_all, assigned)) MPI_Abort(MPI_COMM_WORLD, 1);
-        write_summary(os, o, p, assigned, std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_start).count());
+        if (tx && !write_abundances(os, db.rdb, p, counts_all, assigned)) MPI_Abort(MPI_COMM_WORLD, 1);
+        write_summary(os, o, assigned, std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_start).count());
     }
-    for (int s = 0; s < NS; ++s) {
-        (void)hipFree(d_bases[s]); (void)hipFree(d_off[s]); (void)hipFree(d_cands[s]); (void)hipFree(d_ncand[s]);
-        (void)hipHostFree(h_cands[s]); (void)hipHostFree(h_ncand[s]); (void)hipEventDestroy(ev_out[s]);
-    }
-    (void)hipStreamDestroy(st);
-    if (d_counts) (void)hipFree(d_counts);
     mcq_taxonomy_destroy(tx);
-    mcq_shard_destroy(ctx); mcq_db_destroy(shard); mcq_refdb_close(rdb);
+    mcq_shard_destroy(ctx);
     MPI_Finalize();
-    return 0;
+    return 0;                                                               // (the owners give back the rest)
 }

@@ -167,6 +167,9 @@ def main():
                   "reads_per_s_median": round(2 * a.pairs / (statistics.median(r["ms"]) / 1000.0))}
     t, pa = res["this"]["time_ms"], res["parent"]["time_ms"]
     res["faster_beyond_spread"] = pa["median"] - t["median"] > max(t["spread"], pa["spread"])
+    tr, pr = res["this"]["peak_rss_mb"], res["parent"]["peak_rss_mb"]         # the same rule turned round: a change meant to cost nothing
+    res["slower_beyond_spread"] = t["median"] - pa["median"] > max(t["spread"], pa["spread"])
+    res["more_rss_beyond_spread"] = tr["median"] - pr["median"] > max(tr["spread"], pr["spread"])
     res["identical_out_files"] = all(all(res[k]["out_identical_to_parent_first_run"]) for k in trees)
     text = json.dumps(res, indent=1)
     print(text)

@@ -1,5 +1,5 @@
 """Read files for the chunked input stage of mcq_query_cli (tests/test_host_read_stream.py, tests/test_gpu_read_stream.py),
-and a Python restatement of the reader they must agree with: read_records of metacache-mpi_amd/csrc/host/mcq_cli_common.hpp,
+and a Python restatement of the reader they must agree with: read_records of metacache-mpi_amd/csrc/host/mcq_query_mpi.cpp,
 which reads as the reference does (std::getline, src/sequence_io.cpp:122-285)."""
 import random
 
