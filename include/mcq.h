@@ -453,6 +453,15 @@ int mcq_build_table(const mcq_build_desc* desc, mcq_table** out);
 int mcq_table_info(const mcq_table* t, uint64_t* n_keys, uint64_t* n_locs, const uint32_t** keys,
                    const uint64_t** list_off, const uint64_t** locs, const uint64_t** win_off);
 int mcq_table_free(mcq_table* t);
+/* One reference rank's table out of a union table built with emulate_ranks = n_ranks: rank r of the reference holds the targets
+ * with tgt % n_ranks == r (src/sketch_database.h:540-542), so its table is the union table without the other targets' locations
+ * and without the keys whose list becomes empty (the per-(feature, rank) limit and -remove-overpopulated-features were applied
+ * by the build).  Done on the device (count per key, scans, scatter; lists keep their order); *out is a table of its own --
+ * mcq_table_info gives its device arrays (win_off: the union's), mcq_table_free releases it.  A rank without targets gives an
+ * empty table (n_keys = 0), not an error.  What mcq_refdb_write_shard (include/mcq_host.h) takes, one rank at a time.        */
+int mcq_table_rank_split(const mcq_table* t, uint32_t n_ranks, uint32_t rank, mcq_table** out);
+/* windows of every target (the `windows` field of its sequence-level taxon, src/taxonomy.h:326-335) to host memory [n_targets] */
+int mcq_table_tgt_windows(const mcq_table* t, uint32_t* out);
 /* mcq_build_table + mcq_db_create in one call; the queryable handle is the only thing left in HBM */
 int mcq_db_build(const mcq_build_desc* desc, mcq_db** out);
 /* The build in parts, for tables whose one-piece temporaries do not fit the GPU (RefSeq scale: ~60 B per feature slot of

@@ -14,6 +14,10 @@
  *   mcq_rank_from_name  taxonomy::rank_from_name          src/taxonomy.h:173-213
  *   mcq_refdb_write_shard  sketch_database::write         src/sketch_database.h:959-998
  *   mcq_refdb_open_meta + mcq_shard_stream_*   the same reader, streaming (no host-side table)
+ *   mcq_taxdump_read    make_taxonomic_hierarchy         src/taxonomy_io.cpp:56-185
+ *   mcq_target_name / mcq_target_parent_taxid   extract_accession_string / extract_taxon_id   src/sequence_io.cpp:705-748
+ *   mcq_genome_files    sequence_filenames               src/args_handling.cpp:50-90, src/filesys_utility.cpp:32-73
+ *   mcq_genome_reader_* fasta_reader + add_targets_to_database   src/sequence_io.cpp:121-170, src/mode_build.cpp:559-647
  *
  * A taxon *key* is the index of the taxon in the database's taxon list; bit 31 marks a
  * sequence-level taxon (rank Sequence), 0xFFFFFFFF is "no taxon".  These are the keys
@@ -102,6 +106,13 @@ int mcq_refdb_tgt2tax(const mcq_refdb* db, uint32_t merge_below_rank, uint32_t* 
 int64_t mcq_refdb_taxon_id(const mcq_refdb* db, uint32_t key);       /* 0 for MCQ_NO_TAXON        */
 uint32_t mcq_refdb_taxon_rank(const mcq_refdb* db, uint32_t key);
 const char* mcq_refdb_taxon_name(const mcq_refdb* db, uint32_t key);
+/* the rest of a taxon record as the shard file holds it (src/taxonomy.h:312-335): parent id, and the source of a sequence-level
+ * taxon -- file name, index of the record in that file (from 1), windows (non-zero on the rank that owns the target; the
+ * handle keeps the taxa of rank 0's file)                                                                             */
+int64_t mcq_refdb_taxon_parent(const mcq_refdb* db, uint32_t key);
+const char* mcq_refdb_taxon_file(const mcq_refdb* db, uint32_t key);
+uint64_t mcq_refdb_taxon_index(const mcq_refdb* db, uint32_t key);
+uint64_t mcq_refdb_taxon_windows(const mcq_refdb* db, uint32_t key);
 /* taxon index at `rank` in the ranked lineage of `key`, MCQ_NO_TAXON if none */
 uint32_t mcq_refdb_ancestor(const mcq_refdb* db, uint32_t key, uint32_t rank);
 
@@ -160,6 +171,49 @@ enum { MCQ_READS_NOT_STRICT = 1u };   /* info[MCQ_READS_STATUS] of the device st
 #endif
 int mcq_reads_parse(const char* text1, uint64_t len1, const char* text2, uint64_t len2, uint32_t flags,
                     uint64_t max_queries, uint64_t max_bases, char* bases, uint64_t* seq_off, uint64_t* hdr, uint64_t* info);
+
+/* ---- the inputs of a build (mcq_build_cli): taxonomy dump, genome files, targets ---------------------------------------
+ * mcq_taxdump_read: nodes.dmp, names.dmp (scientific names) and, if there, merged.dmp of `dir`, as make_taxonomic_hierarchy
+ * (src/taxonomy_io.cpp:56-185) reads them: every old id of merged.dmp becomes a taxon of rank none below its new id and is
+ * replaced by it in nodes.dmp; of several records with one id the first stays; taxon 1 gets rank root.  The records come in
+ * the order the reference writes them (ascending id; the sequence-level taxa, id -(target + 1), go before them).  `name`
+ * points into the handle; file is "", index and windows 0.                                                              */
+typedef struct mcq_taxdump mcq_taxdump;
+int mcq_taxdump_read(const char* dir, mcq_taxdump** out);
+uint64_t mcq_taxdump_count(const mcq_taxdump* t);
+const mcq_taxon_rec* mcq_taxdump_taxa(const mcq_taxdump* t);
+int mcq_taxdump_free(mcq_taxdump* t);
+/* name of the sequence-level taxon of a sequence with this header (the '>' line without the '>'): accession.version, else
+ * accession, else the gi number, else the whole header (src/sequence_io.cpp:705-719, src/mode_build.cpp:591-596).  Written to
+ * buf (NUL-terminated, cut to cap - 1 bytes); returns the length.  mcq_target_parent_taxid: the N of "taxid|N" in the header,
+ * 0 if there is none (src/sequence_io.cpp:724-748) -- the parent a target gets when no mapping file names one.  Mapping files
+ * (assembly_summary.txt, *.accession2taxid) are not read.                                                               */
+int64_t mcq_target_name(const char* header, uint64_t len, char* buf, size_t cap);
+int64_t mcq_target_parent_taxid(const char* header, uint64_t len);
+/* the files named by the arguments of a build, every directory expanded (recursively, 10 levels), then sorted: the order in
+ * which the reference reads them (src/args_handling.cpp:50-90, src/filesys_utility.cpp:32-73, src/mode_build.cpp:570-575)   */
+typedef struct mcq_file_list mcq_file_list;
+int mcq_genome_files(const char* const* args, uint32_t n_args, mcq_file_list** out);
+uint32_t mcq_file_list_count(const mcq_file_list* l);
+const char* mcq_file_list_get(const mcq_file_list* l, uint32_t i);
+int mcq_file_list_free(mcq_file_list* l);
+/* Multi-line FASTA files read in order through one buffer of io_bytes.  mcq_genome_reader_next appends up to `cap` bases to
+ * `bases`: the sequences of the targets back to back, in target order, a sequence going on in the next call when the buffer is
+ * full (*done = 1: all files are read).  A target is a record with sequence text whose name is not taken yet (target ids
+ * count only those); mcq_genome_reader_target gives target t's taxon record (id -(t + 1), parent from the header, rank
+ * sequence, name, file, index of the record in its file from 1; windows 0: the build counts them) and its length so far,
+ * for every target begun.  Lines are joined by dropping the '\n' only.  A file that does not start with '>' and a record
+ * without sequence text end the reading of that file, as they do in the reference.  The extension decides how the reference
+ * reads a file, its first character only without a known one (src/sequence_io.cpp:534-571): FASTA text under a FASTQ
+ * extension is left as its FASTQ reader leaves it, a file or directory that cannot be read is passed over; a file the
+ * reference would read as FASTQ is an error.
+ * Host memory: io_bytes, one header line, and name + file + length per target.                                        */
+typedef struct mcq_genome_reader mcq_genome_reader;
+int mcq_genome_reader_open(const char* const* files, uint32_t n_files, uint64_t io_bytes, mcq_genome_reader** out);
+int mcq_genome_reader_next(mcq_genome_reader* r, char* bases, uint64_t cap, uint64_t* n_bases, int32_t* done);
+uint32_t mcq_genome_reader_n_targets(const mcq_genome_reader* r);
+int mcq_genome_reader_target(const mcq_genome_reader* r, uint32_t target, mcq_taxon_rec* rec, uint64_t* length);
+int mcq_genome_reader_close(mcq_genome_reader* r);
 
 /* default of -hitmin when unset: src/mode_query.cpp:247-259 */
 uint32_t mcq_default_hits_min(uint32_t sketch_size);

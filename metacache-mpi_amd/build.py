@@ -32,6 +32,10 @@ def cli_path():
     return os.path.join(_HERE, "mcq_query_cli")
 
 
+def build_cli_path():
+    return os.path.join(_HERE, "mcq_build_cli")
+
+
 def mpi_cli_path():
     """mcq_query_mpi (one process per GPU under mpiexec); built only where an MPI is installed (/opt/conda: MPICH)"""
     return os.path.join(_HERE, "mcq_query_mpi")
@@ -59,13 +63,13 @@ def source_digest():
 
 
 def build_host(force=False, verbose=False):
-    """libmcq_host.so (shard reader, taxonomy keys, classify; g++, no GPU) and the
-    mcq_query_cli binary (links both libraries)."""
-    src = os.path.join(_HERE, "csrc", "host", "mcq_host.cpp")
+    """libmcq_host.so (shard reader and writer, taxonomy, classify, build inputs; g++, no GPU) and the
+    mcq_query_cli and mcq_build_cli binaries (they link both libraries)."""
+    srcs = [os.path.join(_HERE, "csrc", "host", f) for f in ("mcq_host.cpp", "mcq_host_build.cpp")]     # query side, build side
     hdr = os.path.join(os.path.dirname(_HERE), "include", "mcq_host.h")
     out = host_lib_path()
-    if force or not os.path.exists(out) or os.path.getmtime(out) < max(os.path.getmtime(src), os.path.getmtime(hdr)):
-        cmd = ["g++", "-std=c++14", "-O2", "-ffp-contract=off", "-Wall", "-shared", "-fPIC", src, "-o", out]   # (no contraction: the abundance estimate is float arithmetic restated op for op)
+    if force or not os.path.exists(out) or os.path.getmtime(out) < max(os.path.getmtime(f) for f in srcs + [hdr, os.path.join(_HERE, "csrc", "host", "mcq_host_internal.hpp")]):
+        cmd = ["g++", "-std=c++14", "-O2", "-ffp-contract=off", "-Wall", "-shared", "-fPIC"] + srcs + ["-o", out]   # (no contraction: the abundance estimate is float arithmetic restated op for op)
         if verbose:
             print(" ".join(cmd))
         subprocess.check_call(cmd)
@@ -78,6 +82,15 @@ def build_host(force=False, verbose=False):
     if force or not os.path.exists(cli) or os.path.getmtime(cli) < max(os.path.getmtime(f) for f in cli_deps):
         hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
         cmd = [hipcc, "-std=c++14", "-O2", "-pthread", cli_src, "-o", cli, "-L" + _HERE, "-lmcq_hip", "-lmcq_host", "-Wl,-rpath,$ORIGIN"]
+        if verbose:
+            print(" ".join(cmd))
+        subprocess.check_call(cmd)
+    # mcq_build_cli: genome files + taxonomy dump -> the reference's shard files
+    bcli_src = os.path.join(_HERE, "csrc", "host", "mcq_build_cli.cpp")
+    bcli = build_cli_path()
+    if force or not os.path.exists(bcli) or os.path.getmtime(bcli) < max(os.path.getmtime(f) for f in shared + [bcli_src]):
+        hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
+        cmd = [hipcc, "-std=c++14", "-O2", "-pthread", bcli_src, "-o", bcli, "-L" + _HERE, "-lmcq_hip", "-lmcq_host", "-Wl,-rpath,$ORIGIN"]
         if verbose:
             print(" ".join(cmd))
         subprocess.check_call(cmd)

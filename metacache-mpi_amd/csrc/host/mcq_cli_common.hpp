@@ -34,6 +34,7 @@
 #include <cstdlib>
 #include <cstring>
 #include <fstream>
+#include <initializer_list>
 #include <iostream>
 #include <string>
 #include <vector>
@@ -66,6 +67,12 @@ struct Options {
     bool host_reader = false;            // mcq_query_cli: -reader host
     bool paired() const { return f2 != "-"; }
 };
+
+// an option under any of its spellings (the reference's args.get / args.contains take a list of them, e.g. src/mode_build.cpp:113-122)
+static inline bool opt_named(const std::string& a, std::initializer_list<const char*> names) {
+    for (const char* n : names) if (a == n) return true;
+    return false;
+}
 
 static bool parse_options(int argc, char** argv, Options& o) {
     if (argc < 5) { std::fprintf(stderr, "usage: %s <dbprefix> <n_ranks> <r1> <r2|-> [options]\n", argv[0]); return false; }

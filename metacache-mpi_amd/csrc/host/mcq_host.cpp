@@ -1,6 +1,7 @@
 // mcq_host.cpp -- host companions of the engine: reference shard reader, taxonomy keys,
 // classification (include/mcq_host.h).  Plain C++14, no GPU, no MPI.
 #include "../../../include/mcq_host.h"
+#include "mcq_host_internal.hpp"
 
 #include <algorithm>
 #include <cstdio>
@@ -18,7 +19,7 @@ int fail(const std::string& m) { g_err = m; return -1; }
 const uint64_t kDbVersion = 20181001;      // MC_DB_VERSION
 const int kNumRanks = 21;                  // taxonomy::num_ranks; rank::root == 20, rank::none == 21
 
-struct Taxon { int64_t id, parent; uint8_t rank; std::string name; uint64_t windows; };
+struct Taxon { int64_t id, parent; uint8_t rank; std::string name, file; uint64_t index, windows; };
 
 struct Reader {
     std::vector<unsigned char> buf; size_t pos = 0; bool ok = true;
@@ -116,6 +117,7 @@ static bool read_file(const std::string& path, std::vector<unsigned char>& out) 
 }
 
 extern "C" const char* mcq_host_last_error(void) { return g_err.c_str(); }
+int mcq_host_set_error(const char* text) { return fail(text ? text : ""); }
 
 extern "C" int mcq_refdb_open(const char* prefix, uint32_t n_ranks, mcq_refdb** out) {
     if (!prefix || !out || n_ranks < 1) return fail("bad argument");
@@ -137,7 +139,7 @@ extern "C" int mcq_refdb_open(const char* prefix, uint32_t n_ranks, mcq_refdb** 
         std::vector<Taxon> taxa; taxa.reserve(ntaxa);
         for (uint64_t i = 0; i < ntaxa && rd.ok; ++i) {
             Taxon t; t.id = rd.get<int64_t>(); t.parent = rd.get<int64_t>(); t.rank = rd.get<uint8_t>();
-            t.name = rd.str(); rd.str(); rd.get<uint64_t>(); t.windows = rd.get<uint64_t>();
+            t.name = rd.str(); t.file = rd.str(); t.index = rd.get<uint64_t>(); t.windows = rd.get<uint64_t>();
             taxa.push_back(std::move(t));
         }
         const uint32_t ntargets = rd.get<uint32_t>();
@@ -205,7 +207,7 @@ extern "C" int mcq_refdb_open_meta(const char* prefix, uint32_t n_ranks, mcq_ref
         std::vector<Taxon> taxa;
         for (uint64_t i = 0; i < ntaxa && rd.ok; ++i) {
             Taxon t; t.id = rd.get<int64_t>(); t.parent = rd.get<int64_t>(); t.rank = rd.get<uint8_t>();
-            t.name = rd.str(); rd.str(); rd.get<uint64_t>(); t.windows = rd.get<uint64_t>();
+            t.name = rd.str(); t.file = rd.str(); t.index = rd.get<uint64_t>(); t.windows = rd.get<uint64_t>();
             taxa.push_back(std::move(t));
         }
         const uint32_t ntargets = rd.get<uint32_t>();
@@ -370,6 +372,10 @@ static inline bool valid_key(const mcq_refdb* db, uint32_t key) { return key != 
 extern "C" int64_t mcq_refdb_taxon_id(const mcq_refdb* db, uint32_t key) { return valid_key(db, key) ? db->taxa[key & 0x7FFFFFFFu].id : 0; }
 extern "C" uint32_t mcq_refdb_taxon_rank(const mcq_refdb* db, uint32_t key) { return valid_key(db, key) ? db->taxa[key & 0x7FFFFFFFu].rank : MCQ_RANK_NONE; }
 extern "C" const char* mcq_refdb_taxon_name(const mcq_refdb* db, uint32_t key) { return valid_key(db, key) ? db->taxa[key & 0x7FFFFFFFu].name.c_str() : "--"; }
+extern "C" int64_t mcq_refdb_taxon_parent(const mcq_refdb* db, uint32_t key) { return valid_key(db, key) ? db->taxa[key & 0x7FFFFFFFu].parent : 0; }
+extern "C" const char* mcq_refdb_taxon_file(const mcq_refdb* db, uint32_t key) { return valid_key(db, key) ? db->taxa[key & 0x7FFFFFFFu].file.c_str() : ""; }
+extern "C" uint64_t mcq_refdb_taxon_index(const mcq_refdb* db, uint32_t key) { return valid_key(db, key) ? db->taxa[key & 0x7FFFFFFFu].index : 0; }
+extern "C" uint64_t mcq_refdb_taxon_windows(const mcq_refdb* db, uint32_t key) { return valid_key(db, key) ? db->taxa[key & 0x7FFFFFFFu].windows : 0; }
 extern "C" uint32_t mcq_refdb_ancestor(const mcq_refdb* db, uint32_t key, uint32_t rank) {
     if (!valid_key(db, key) || rank >= (uint32_t)kNumRanks) return MCQ_NO_TAXON;
     return db->lineage[(size_t)(key & 0x7FFFFFFFu) * kNumRanks + rank];

@@ -854,3 +854,109 @@ extern "C" int mcq_db_build(const mcq_build_desc* d, mcq_db** out) {
     mcq_table_free(T);
     return rc;
 }
+
+// ---- one reference rank's table out of the union table (mcq_table_rank_split of include/mcq.h) ----------------------------------
+// The reference's rank r holds the targets with tgt % P == r (src/sketch_database.h:540-542), so its table is the union table with
+// every other target's locations taken out and the keys that lose their whole list dropped.  The per-(feature, rank) limit and
+// -remove-overpopulated-features were applied when the union was built.  Count per key, two scans, scatter: lists keep their
+// (target, window) order, keys their order, nothing is written through an atomic.
+// A group of 16 lanes works on one key (lists are short: a few locations on average, at most 254 x P), four keys per wave; a group
+// reads 16 consecutive locations per step.  All loops are uniform over the wave (the ballots need every lane): the trip count is
+// the longest of the wave's four lists.
+namespace {
+const u32 SPLIT_GROUP = 16;
+struct SplitKey { u64 kx, beg; u32 len, steps; };
+// key of this lane's group in the wave's round `base` and the wave-uniform number of 16-location steps
+__device__ __forceinline__ SplitKey split_key(const u64* list_off, u64 n_keys, u64 base, u32 lane) {
+    SplitKey s; s.kx = base + lane / SPLIT_GROUP; s.beg = 0; s.len = 0;
+    if (s.kx < n_keys) { s.beg = list_off[s.kx]; s.len = (u32)(list_off[s.kx + 1] - s.beg); }
+    u32 m = s.len;
+    m = max(m, (u32)__shfl_xor((int)m, 16, 64));
+    m = max(m, (u32)__shfl_xor((int)m, 32, 64));
+    s.steps = (m + SPLIT_GROUP - 1) / SPLIT_GROUP;
+    return s;
+}
+__global__ void __launch_bounds__(256) k_split_count(const u64* list_off, const u64* locs, u64 n_keys, u32 P, u32 rank, u32* cnt, u32* alive) {
+    const u32 lane = threadIdx.x & 63, sub = lane % SPLIT_GROUP, shift = lane - sub;
+    const u64 wave = ((u64)blockIdx.x * blockDim.x + threadIdx.x) >> 6, n_waves = ((u64)gridDim.x * blockDim.x) >> 6;
+    for (u64 base = wave * 4; base < n_keys; base += n_waves * 4) {
+        const SplitKey s = split_key(list_off, n_keys, base, lane);
+        u32 n = 0;
+        for (u32 i = 0; i < s.steps; ++i) {
+            const u32 j = i * SPLIT_GROUP + sub;
+            const bool mine = j < s.len && (u32)(locs[s.beg + j] >> 32) % P == rank;
+            n += (u32)__builtin_popcountll((__ballot(mine) >> shift) & 0xFFFFull);
+        }
+        if (sub == 0 && s.kx < n_keys) { cnt[s.kx] = n; alive[s.kx] = n ? 1u : 0u; }
+    }
+}
+__global__ void __launch_bounds__(256) k_split_scatter(const u32* keys, const u64* list_off, const u64* locs, u64 n_keys, u32 P, u32 rank,
+                                                      const u32* alive, const u64* key_pos, const u64* loc_pos, u64 n_keys_out, u64 n_locs_out,
+                                                      u32* okeys, u64* ooff, u64* olocs) {
+    const u32 lane = threadIdx.x & 63, sub = lane % SPLIT_GROUP, shift = lane - sub;
+    const u64 wave = ((u64)blockIdx.x * blockDim.x + threadIdx.x) >> 6, n_waves = ((u64)gridDim.x * blockDim.x) >> 6;
+    if (blockIdx.x == 0 && threadIdx.x == 0) ooff[n_keys_out] = n_locs_out;
+    for (u64 base = wave * 4; base < n_keys; base += n_waves * 4) {
+        const SplitKey s = split_key(list_off, n_keys, base, lane);
+        const bool live = s.kx < n_keys && alive[s.kx];
+        const u64 out = live ? loc_pos[s.kx] : 0;
+        if (live && sub == 0) { const u64 ko = key_pos[s.kx]; if (ko < n_keys_out) { okeys[ko] = keys[s.kx]; ooff[ko] = out; } }
+        u32 done = 0;
+        for (u32 i = 0; i < s.steps; ++i) {
+            const u32 j = i * SPLIT_GROUP + sub;
+            u64 w = 0;
+            bool mine = false;
+            if (live && j < s.len) { w = locs[s.beg + j]; mine = (u32)(w >> 32) % P == rank; }
+            const u32 bits = (u32)((__ballot(mine) >> shift) & 0xFFFFull);
+            const u64 o = out + done + (u32)__builtin_popcount(bits & ((1u << sub) - 1u));
+            if (mine && o < n_locs_out) olocs[o] = w;
+            done += (u32)__builtin_popcount(bits);
+        }
+    }
+}
+}  // namespace
+
+extern "C" int mcq_table_rank_split(const mcq_table* t, uint32_t n_ranks, uint32_t rank, mcq_table** out) {
+    if (!t || !out) return bfail(MCQ_E_ARG, "null argument");
+    if (n_ranks < 1 || rank >= n_ranks) return bfail(MCQ_E_ARG, "rank >= n_ranks");
+    BCHK(hipSetDevice(t->device));
+    const u64 nk = t->n_keys;
+    mcq_table* R = new mcq_table();
+    std::memset(R, 0, sizeof(*R));
+    R->device = t->device; R->n_targets = t->n_targets;
+    struct TableGuard { mcq_table*& t; ~TableGuard() { if (t) mcq_table_free(t); } } guard{R};
+    BCHK(hipMalloc(&R->win_off, ((u64)t->n_targets + 1) * 8));
+    BCHK(hipMemcpy(R->win_off, t->win_off, ((u64)t->n_targets + 1) * 8, hipMemcpyDeviceToDevice));
+    u32 *cnt = nullptr, *alive = nullptr; u64 *key_pos = nullptr, *loc_pos = nullptr;
+    struct Tmp { void** p; ~Tmp() { (void)hipFree(*p); } };
+    BCHK(hipMalloc(&cnt, (nk ? nk : 1) * 4)); Tmp f1{(void**)&cnt};
+    BCHK(hipMalloc(&alive, (nk ? nk : 1) * 4)); Tmp f2{(void**)&alive};
+    BCHK(hipMalloc(&key_pos, (nk ? nk : 1) * 8)); Tmp f3{(void**)&key_pos};
+    BCHK(hipMalloc(&loc_pos, (nk ? nk : 1) * 8)); Tmp f4{(void**)&loc_pos};
+    const dim3 grid = grid_for((nk + 3) / 4 * 64);               // four keys per wave of 64 lanes
+    u64 n_keys_out = 0, n_locs_out = 0;
+    if (nk) hipLaunchKernelGGL(k_split_count, grid, dim3(TB), 0, 0, (const u64*)t->list_off, (const u64*)t->locs, nk, n_ranks, rank, cnt, alive);
+    MCHK(excl_scan(cnt, loc_pos, nk, &n_locs_out));
+    MCHK(excl_scan(alive, key_pos, nk, &n_keys_out));
+    R->n_keys = n_keys_out; R->n_locs = n_locs_out;
+    BCHK(hipMalloc(&R->keys, (n_keys_out ? n_keys_out : 1) * 4));
+    BCHK(hipMalloc(&R->list_off, (n_keys_out + 1) * 8));
+    BCHK(hipMalloc(&R->locs, (n_locs_out ? n_locs_out : 1) * 8));
+    if (nk) hipLaunchKernelGGL(k_split_scatter, grid, dim3(TB), 0, 0, (const u32*)t->keys, (const u64*)t->list_off, (const u64*)t->locs, nk, n_ranks, rank,
+                               (const u32*)alive, (const u64*)key_pos, (const u64*)loc_pos, n_keys_out, n_locs_out, R->keys, R->list_off, R->locs);
+    else BCHK(hipMemset(R->list_off, 0, 8));
+    BCHK(hipDeviceSynchronize());
+    BCHK(hipGetLastError());
+    *out = R;
+    R = nullptr;
+    return MCQ_OK;
+}
+
+extern "C" int mcq_table_tgt_windows(const mcq_table* t, uint32_t* out) {
+    if (!t || !out) return bfail(MCQ_E_ARG, "null argument");
+    BCHK(hipSetDevice(t->device));
+    std::vector<u64> w((size_t)t->n_targets + 1);
+    BCHK(hipMemcpy(w.data(), t->win_off, w.size() * 8, hipMemcpyDeviceToHost));
+    for (u32 i = 0; i < t->n_targets; ++i) out[i] = (u32)(w[i + 1] - w[i]);
+    return MCQ_OK;
+}

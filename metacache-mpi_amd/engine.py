@@ -149,6 +149,8 @@ def lib():
         L.mcq_db_build.argtypes = [C.POINTER(BuildDesc), C.POINTER(C.c_void_p)]
         L.mcq_table_info.argtypes = [C.c_void_p] + [C.c_void_p] * 6
         L.mcq_table_free.argtypes = [C.c_void_p]
+        L.mcq_table_rank_split.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.POINTER(C.c_void_p)]
+        L.mcq_table_tgt_windows.argtypes = [C.c_void_p, C.c_void_p]
         L.mcq_build_last_error.restype = C.c_char_p
         L.mcq_build_parts.argtypes = [C.POINTER(BuildDesc), C.POINTER(C.c_void_p)]
         L.mcq_parts_info.argtypes = [C.c_void_p, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_uint32), C.POINTER(C.c_uint64)]
@@ -573,6 +575,9 @@ class Table:
         rc = lib().mcq_build_table(C.byref(d), C.byref(h))
         if rc != 0:
             raise McqError(rc, (lib().mcq_build_last_error() or b"").decode())
+        self._adopt(h, n_targets, device)
+
+    def _adopt(self, h, n_targets, device):
         self.h, self.n_targets, self.device = h, n_targets, device
         nk, nl = C.c_uint64(), C.c_uint64()
         pk, po, pl, pw = C.c_void_p(), C.c_void_p(), C.c_void_p(), C.c_void_p()
@@ -594,6 +599,23 @@ class Table:
             return out
         return (pull(self.keys_ptr, self.n_keys, np.uint32), pull(self.list_off_ptr, self.n_keys + 1, np.uint64),
                 pull(self.locs_ptr, self.n_locs, np.uint64), pull(self.win_off_ptr, self.n_targets + 1, np.uint64))
+
+    def rank_split(self, n_ranks, rank):
+        """mcq_table_rank_split: the table of reference rank `rank` of `n_ranks` (targets with tgt % n_ranks == rank), cut out of
+        this union table on the device -- a Table of its own"""
+        h = C.c_void_p()
+        rc = lib().mcq_table_rank_split(self.h, n_ranks, rank, C.byref(h))
+        if rc != 0:
+            raise McqError(rc, (lib().mcq_build_last_error() or b"").decode())
+        t = Table.__new__(Table)
+        t._adopt(h, self.n_targets, self.device)
+        return t
+
+    def tgt_windows(self):
+        """windows of every target (u32 [n_targets])"""
+        out = np.zeros(self.n_targets, np.uint32)
+        _chk(lib().mcq_table_tgt_windows(self.h, _np_ptr(out)))
+        return out
 
     def close(self):
         if getattr(self, "h", None):

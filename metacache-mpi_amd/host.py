@@ -89,6 +89,25 @@ def lib():
         L.mcq_read_stream_close.argtypes = [C.c_void_p]
         L.mcq_reads_parse.argtypes = [C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.c_uint32, C.c_uint64, C.c_uint64,
                                       C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.mcq_refdb_taxon_parent.restype = C.c_int64; L.mcq_refdb_taxon_parent.argtypes = [C.c_void_p, C.c_uint32]
+        L.mcq_refdb_taxon_file.restype = C.c_char_p; L.mcq_refdb_taxon_file.argtypes = [C.c_void_p, C.c_uint32]
+        L.mcq_refdb_taxon_index.restype = C.c_uint64; L.mcq_refdb_taxon_index.argtypes = [C.c_void_p, C.c_uint32]
+        L.mcq_refdb_taxon_windows.restype = C.c_uint64; L.mcq_refdb_taxon_windows.argtypes = [C.c_void_p, C.c_uint32]
+        L.mcq_taxdump_read.argtypes = [C.c_char_p, C.POINTER(C.c_void_p)]
+        L.mcq_taxdump_count.restype = C.c_uint64; L.mcq_taxdump_count.argtypes = [C.c_void_p]
+        L.mcq_taxdump_taxa.restype = C.POINTER(TaxonRec); L.mcq_taxdump_taxa.argtypes = [C.c_void_p]
+        L.mcq_taxdump_free.argtypes = [C.c_void_p]
+        L.mcq_target_name.restype = C.c_int64; L.mcq_target_name.argtypes = [C.c_char_p, C.c_uint64, C.c_char_p, C.c_size_t]
+        L.mcq_target_parent_taxid.restype = C.c_int64; L.mcq_target_parent_taxid.argtypes = [C.c_char_p, C.c_uint64]
+        L.mcq_genome_files.argtypes = [C.POINTER(C.c_char_p), C.c_uint32, C.POINTER(C.c_void_p)]
+        L.mcq_file_list_count.restype = C.c_uint32; L.mcq_file_list_count.argtypes = [C.c_void_p]
+        L.mcq_file_list_get.restype = C.c_char_p; L.mcq_file_list_get.argtypes = [C.c_void_p, C.c_uint32]
+        L.mcq_file_list_free.argtypes = [C.c_void_p]
+        L.mcq_genome_reader_open.argtypes = [C.POINTER(C.c_char_p), C.c_uint32, C.c_uint64, C.POINTER(C.c_void_p)]
+        L.mcq_genome_reader_next.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64), C.POINTER(C.c_int32)]
+        L.mcq_genome_reader_n_targets.restype = C.c_uint32; L.mcq_genome_reader_n_targets.argtypes = [C.c_void_p]
+        L.mcq_genome_reader_target.argtypes = [C.c_void_p, C.c_uint32, C.POINTER(TaxonRec), C.POINTER(C.c_uint64)]
+        L.mcq_genome_reader_close.argtypes = [C.c_void_p]
         _lib = L
     return _lib
 
@@ -173,6 +192,14 @@ class RefDb:
 
     def taxon_name(self, key):
         return lib().mcq_refdb_taxon_name(self.h, int(key)).decode("latin-1")
+
+    def taxon_parent(self, key):
+        return int(lib().mcq_refdb_taxon_parent(self.h, int(key)))
+
+    def taxon_source(self, key):
+        """(file, index, windows) of a taxon record: the source of a sequence-level taxon"""
+        return (lib().mcq_refdb_taxon_file(self.h, int(key)).decode("latin-1"), int(lib().mcq_refdb_taxon_index(self.h, int(key))),
+                int(lib().mcq_refdb_taxon_windows(self.h, int(key))))
 
     def ancestor(self, key, rank):
         return int(lib().mcq_refdb_ancestor(self.h, int(key), int(rank)))
@@ -306,3 +333,76 @@ def read_batches(paths, chunk, max_queries=1 << 40, max_bases=1 << 62, prepare=N
     finally:
         for s in streams:
             s.close()
+
+
+# ---- the inputs of a build (mcq_taxdump_*, mcq_target_*, mcq_genome_files, mcq_genome_reader_*): what mcq_build_cli reads
+def _err():
+    return RuntimeError(lib().mcq_host_last_error().decode())
+
+
+def _rec(r):
+    return dict(id=int(r.id), parent=int(r.parent), rank=int(r.rank), name=(r.name or b"").decode("latin-1"),
+                file=(r.file or b"").decode("latin-1"), index=int(r.index), windows=int(r.windows))
+
+
+def read_taxdump(directory):
+    """mcq_taxdump_read: the taxon records (dicts as write_shard takes them) of nodes.dmp / names.dmp / merged.dmp, in ascending id"""
+    h = C.c_void_p()
+    if lib().mcq_taxdump_read(str(directory).encode(), C.byref(h)) != 0:
+        raise _err()
+    try:
+        arr = lib().mcq_taxdump_taxa(h)
+        return [_rec(arr[i]) for i in range(lib().mcq_taxdump_count(h))]
+    finally:
+        lib().mcq_taxdump_free(h)
+
+
+def target_name(header):
+    """name of the sequence-level taxon of a sequence with this header (bytes, without the '>')"""
+    n = lib().mcq_target_name(header, len(header), None, 0)
+    buf = C.create_string_buffer(n + 1)
+    lib().mcq_target_name(header, len(header), buf, n + 1)
+    return buf.raw[:n]
+
+
+def target_parent_taxid(header):
+    return int(lib().mcq_target_parent_taxid(header, len(header)))
+
+
+def genome_files(args):
+    """the files a build reads for these command-line arguments, in the order it reads them"""
+    arr = (C.c_char_p * len(args))(*[str(a).encode() for a in args])
+    h = C.c_void_p()
+    if lib().mcq_genome_files(arr, len(args), C.byref(h)) != 0:
+        raise _err()
+    try:
+        return [lib().mcq_file_list_get(h, i).decode() for i in range(lib().mcq_file_list_count(h))]
+    finally:
+        lib().mcq_file_list_free(h)
+
+
+def read_genomes(files, cap, io_bytes=1 << 20):
+    """mcq_genome_reader_* over `files` with a buffer of `cap` bases: (bases of all targets back to back as bytes, taxon records of
+    the targets as dicts, lengths, number of fills)"""
+    arr = (C.c_char_p * len(files))(*[str(f).encode() for f in files])
+    h = C.c_void_p()
+    if lib().mcq_genome_reader_open(arr, len(files), io_bytes, C.byref(h)) != 0:
+        raise _err()
+    try:
+        buf = C.create_string_buffer(max(1, cap))
+        out, fills = [], 0
+        n, done = C.c_uint64(), C.c_int32()
+        while not done.value:
+            if lib().mcq_genome_reader_next(h, buf, cap, C.byref(n), C.byref(done)) != 0:
+                raise _err()
+            assert n.value <= cap
+            out.append(buf.raw[:n.value]); fills += 1
+        recs, lens = [], []
+        for t in range(lib().mcq_genome_reader_n_targets(h)):
+            r, ln = TaxonRec(), C.c_uint64()
+            if lib().mcq_genome_reader_target(h, t, C.byref(r), C.byref(ln)) != 0:
+                raise _err()
+            recs.append(_rec(r)); lens.append(int(ln.value))
+        return b"".join(out), recs, lens, fills
+    finally:
+        lib().mcq_genome_reader_close(h)
