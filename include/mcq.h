@@ -67,6 +67,11 @@ enum {
     MCQ_FOLD_BY_LISTS = 0x8000u,   /* test hook: emulate_ranks > 1 builds the P bounded lists and folds them level by level (the form
                                       MCQ_QUIRK_SEQ_DROP needs on a table with sequence-level taxa) instead of the one selection
                                       in the order (hits, rank, position) that gives the same list        */
+    MCQ_FORCE_LEAN_WAVE = 0x20000u, /* test hook / A-B: the first wave stage in its lean form: it answers the
+                                      reads of at most 256 locations and queues every other one for the later stages.  Only where that form exists (32-bit location words, P x M within a wave's
+                                      lanes, not with another MCQ_FORCE_* / MCQ_NO_WAVE16 hook): MCQ_E_UNSUPPORTED otherwise   */
+    MCQ_FORCE_FULL_WAVE = 0x40000u, /* test hook / A-B: the first wave stage in its full form, whatever the batch before it
+                                      suggests.  Same results with either flag and with neither                      */
     MCQ_BUILD_REMOVE_OVERPOPULATED = 0x1000u, /* mcq_build_desc.flags: the build option
                                    -remove-overpopulated-features (src/mode_build.cpp:847-1074): a feature whose
                                    per-rank location counts (after the per-rank limit) sum to more than
@@ -156,7 +161,7 @@ typedef struct {
                                    pow2ceil(P) x max_cand <= 64, in four registers per lane up to 256 list slots, beyond
                                    that in the LDS of the workgroup kernel (every query, several times slower)          */
     uint64_t insert_size_max;   /* insertSizeMax                                         */
-    uint32_t flags;             /* MCQ_QUIRK_SEQ_DROP and the MCQ_FORCE_* / MCQ_NO_WAVE16 / MCQ_NO_TWO_CLASS / MCQ_FOLD_BY_LISTS test hooks; any other
+    uint32_t flags;             /* MCQ_QUIRK_SEQ_DROP and the MCQ_FORCE_* (_LEAN_WAVE / _FULL_WAVE included) / MCQ_NO_WAVE16 / MCQ_NO_TWO_CLASS / MCQ_FOLD_BY_LISTS test hooks; any other
                                    bit is rejected with MCQ_E_ARG                         */
 } mcq_query_opts;
 
@@ -190,6 +195,8 @@ typedef struct {
     uint64_t n_narrow_queued;   /* queries with narrow window ranges (short reads, pairs) counted in the workgroup kernels' queue:
                                    from 4096 on they get the workgroup kernel with the two-class tail (an upper bound: an
                                    entry may be counted twice)                                            */
+    uint64_t n_lean_queued;     /* queries the lean first wave stage handed to the second one that the full stage would have
+                                   answered itself (not part of n_overflow, which is the same on both routes)         */
 } mcq_stats;
 
 /* replaces sketch_database::read -> hash_multimap::deserialize (the table build) */

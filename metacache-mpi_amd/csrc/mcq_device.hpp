@@ -180,7 +180,8 @@ struct CountersDev {         // one block of u64/u32 words, zeroed per call
     unsigned long long n_short;       // direct mode: queued queries whose list the first wave stage would have kept (<= 512 locations)
     unsigned long long n_geom;        // queries with more than 128 features: the workgroup kernels' by their geometry alone
     u32 blk_cursor[4];                // the workgroup kernels' shared cursors over the front queue ([0,1] plain kernel: long queries first, then the rest; [2,3] two-class kernel)
-    u32 w_cursor[2];                  // unused (reserved: keeps the offsets of the fields behind it)
+    u32 n_lean;                       // lean first wave stage: queries handed to the back queue that the full stage would have answered itself
+    u32 n_lean_would;                 // full first wave stage: queries it answered that the lean stage would have handed on
     unsigned long long n_long;        // queries of MCQ_BLOCK_LONG_FIRST bases and more (the workgroup kernels take those first: a pass of its own)
     unsigned long long pad_[17];      // (diagnostic builds, -DMCQ_PHASE_CLOCK: phase clocks of the workgroup kernel)
     unsigned long long* probe_buf;
@@ -193,10 +194,13 @@ struct CountersDev {         // one block of u64/u32 words, zeroed per call
     // lists: RefSeq scale, 99 %) -- taken by the sharded home side only, whose first stage has no sketch to lose: on the fused
     // path the second stage (4 waves per SIMD) sketches and probes no faster than the first (8), measured +-2 %.  Results are
     // the same either way; only the path differs.
+    // bit 2 (MCQ_MODE_LEAN): the next batch's first stage runs in its lean form (k_query_wave<LEAN>): few of this batch's queries
+    // were, or would have been, handed on by it.
     u32 direct_mode;
 };
 static_assert(offsetof(CountersDev, probe_buf) == 256, "probe_buf sits 256 bytes into the block");
 #define MCQ_CTR_ZEROED offsetof(CountersDev, probe_buf)
+#define MCQ_MODE_LEAN 4u
 
 // ---- feature-sharded path: what a home rank's reduce kernels read instead of sketching and probing ------------
 // The home rank sent every feature slot of the batch (slot = global window index x s + i) to the rank that owns the
@@ -268,6 +272,16 @@ __device__ __forceinline__ void ovf_push(u32* st, int back, CountersDev* ctr, u3
     if (left == 0) { next = atomicAdd(back ? &ctr->ovf_mid_count : &ctr->ovf_count, MCQ_OVF_CHUNK); left = MCQ_OVF_CHUNK; }
     list[ovf_slot(nq, back, next)] = q;
     st[back] = next + 1; st[2 + back] = left - 1; st[4] += 1;
+}
+// The first stage's hand-over of a query it has probed (<= 64 features) to the second stage: a back-queue entry and, in the row of
+// that slot, the 64 probe results (list offset << 16 | list length), so that the second stage neither sketches nor probes again.
+// By the whole wave.
+__device__ __forceinline__ void wave_sync();
+__device__ __forceinline__ void ovf_hand_over(u32* st, CountersDev* ctr, u32* list, u64 nq, u32 q, u64 off, u32 len, u32 lane) {
+    if (lane == 0) ovf_push(st, 1, ctr, list, nq, q);
+    wave_sync();                                       // the slot lane 0 just took: next - 1 of the back queue
+    const u32 slot = st[1] - 1;
+    ctr->probe_buf[(u64)slot * 64 + lane] = (off << 16) | len;
 }
 __device__ __forceinline__ void ovf_flush(u32* st, CountersDev* ctr, u32* list, u64 nq) {                    // one lane
     for (int back = 0; back < 2; ++back) {
