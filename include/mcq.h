@@ -419,10 +419,20 @@ int mcq_fasta_index(const char* text, uint64_t n_bytes, uint64_t* seq_ranges, ui
  * most the smaller complete-record count.  Status MCQ_READS_NOT_STRICT: the chunk is not in the strict form -- FASTQ of
  * 4-line records (line 1 '@', line 3 '+'), or FASTA of '>' header lines and non-empty sequence lines, one format per
  * text -- and the outputs are not to be used: the host parses that chunk (mcq_reads_parse of include/mcq_host.h, the
- * same contract).  scratch: device memory of mcq_reads_scratch_bytes(len1, len2, max_queries) bytes.  Chunks < 4 GiB. */
+ * same contract).  scratch: device memory of mcq_reads_scratch_bytes(len1, len2, max_queries) bytes.  Chunks < 4 GiB.
+ * Flag MCQ_READS_INTERLEAVED (text2 NULL, len2 0): records 2r, 2r+1 of text1 are the mates of one query, as the reference's
+ * sequence_pair_reader::next pairs the records of one file under -pairseq (src/sequence_io.cpp:442-462: two next() of the
+ * same reader; the second returns an empty sequence once the file has run out).  The outputs have the paired form (mates
+ * of query q are sequences 2q, 2q+1; hdr is the first mate's).  A query is complete once both its records are; a chunk
+ * that ends between two mates takes neither and the cut falls in front of the first.  A last record without a mate, in
+ * a chunk that ends the file, is a query whose second mate is empty.  max_queries and max_bases count pairs and the
+ * bases of both mates; info[MCQ_READS_COMPLETE1] counts complete queries; info[MCQ_READS_CUT2] and _COMPLETE2 are 0.
+ * The scratch is mcq_reads_scratch_bytes(len1, 0, max_queries): the record array holds one length per pair.  In this
+ * mode a line that ends in '\r' (CRLF text) also makes the chunk MCQ_READS_NOT_STRICT.                             */
 #ifndef MCQ_READS_CONSTANTS             /* (the same in include/mcq_host.h) */
 #define MCQ_READS_CONSTANTS
-enum { MCQ_READS_EOF1 = 1u, MCQ_READS_EOF2 = 2u };
+enum { MCQ_READS_EOF1 = 1u, MCQ_READS_EOF2 = 2u,
+       MCQ_READS_INTERLEAVED = 4u };   /* text2 NULL: records 2q, 2q+1 of text1 are the mates of query q (see above) */
 enum { MCQ_READS_N = 0, MCQ_READS_BASES = 1, MCQ_READS_CUT1 = 2, MCQ_READS_CUT2 = 3, MCQ_READS_STATUS = 4,
        MCQ_READS_COMPLETE1 = 5, MCQ_READS_COMPLETE2 = 6, MCQ_READS_INFO_WORDS = 8 };
 enum { MCQ_READS_NOT_STRICT = 1u };   /* info[MCQ_READS_STATUS] of the device step: parse this chunk on the host */

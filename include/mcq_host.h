@@ -161,10 +161,17 @@ int mcq_read_stream_close(mcq_read_stream* s);
  *   seq_off    [n_seqs + 1] offsets into bases (capacity 2 * max_queries + 1)
  *   hdr        [2 * n] (begin, end) byte range in text1 of query q's header up to its first ' ' (what the -out file prints)
  *   info       [MCQ_READS_INFO_WORDS]: n queries, bases, bytes of text1 / text2 used (the rest is carried to the next
- *              chunk), status (always 0 here), complete records found in text1 / text2 (at most max_queries)          */
+ *              chunk), status (always 0 here), complete records found in text1 / text2 (at most max_queries)
+ * Flag MCQ_READS_INTERLEAVED (text2 NULL): records 2r, 2r+1 of text1 are the mates of one query, as sequence_pair_reader::next
+ * pairs them under -pairseq (src/sequence_io.cpp:442-462: first = reader1_->next(), second = reader1_->next(), the second an
+ * empty sequence once the file has run out).  Output in the paired form; a query is complete once both its records are (a
+ * chunk that ends between two mates takes neither, the cut falls in front of the first mate); a last record without a mate,
+ * in a chunk that ends the file, is a query with an empty second mate; max_queries / max_bases count pairs and the bases
+ * of both mates; info[MCQ_READS_COMPLETE1] counts complete queries, _CUT2 and _COMPLETE2 are 0.                        */
 #ifndef MCQ_READS_CONSTANTS             /* (the same in include/mcq.h) */
 #define MCQ_READS_CONSTANTS
-enum { MCQ_READS_EOF1 = 1u, MCQ_READS_EOF2 = 2u };
+enum { MCQ_READS_EOF1 = 1u, MCQ_READS_EOF2 = 2u,
+       MCQ_READS_INTERLEAVED = 4u };   /* text2 NULL: records 2q, 2q+1 of text1 are the mates of query q (see above) */
 enum { MCQ_READS_N = 0, MCQ_READS_BASES = 1, MCQ_READS_CUT1 = 2, MCQ_READS_CUT2 = 3, MCQ_READS_STATUS = 4,
        MCQ_READS_COMPLETE1 = 5, MCQ_READS_COMPLETE2 = 6, MCQ_READS_INFO_WORDS = 8 };
 enum { MCQ_READS_NOT_STRICT = 1u };   /* info[MCQ_READS_STATUS] of the device step: parse this chunk on the host */

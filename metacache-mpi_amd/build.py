@@ -77,7 +77,7 @@ def build_host(force=False, verbose=False):
     cli = cli_path()
     # what both programs depend on besides their own source: the two libraries and every header they include
     shared = [out, lib_path(), _HDR, hdr, os.path.join(os.path.dirname(_HERE), "include", "mcq_open.hpp")] + \
-             [os.path.join(_HERE, "csrc", "host", h) for h in ("mcq_cli_common.hpp", "mcq_cli_buffers.hpp")]
+             [os.path.join(_HERE, "csrc", "host", h) for h in ("mcq_cli_common.hpp", "mcq_cli_buffers.hpp", "mcq_read_unit.hpp")]
     cli_deps = shared + [cli_src, os.path.join(_HERE, "csrc", "host", "mcq_read_batches.hpp")]
     if force or not os.path.exists(cli) or os.path.getmtime(cli) < max(os.path.getmtime(f) for f in cli_deps):
         hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")

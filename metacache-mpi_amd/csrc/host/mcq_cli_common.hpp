@@ -21,14 +21,27 @@
 // "# speed:" lines (tests/test_gpu_cli.py).  Not reproduced: the reference prints nothing for a thread's chunk in which
 // no read was classified (src/querying.h:1091, :1129).
 //
-// usage: mcq_query_cli <dbprefix> <n_ranks> <r1.fq> <r2.fq|-> [-lowest R] [-highest R] [-maxcand N] [-hitmin N]
-//            [-hitdiff X] [-insertsize N] [-threads N] [-tophits] [-taxids] [-taxids-only] [-omit-ranks] [-lineage]
-//            [-mapped-only] [-nomap] [-noquirks] [-abundances [FILE]] [-abundance-per R] [-out FILE] [-batch N] [-batch-bases N]
-//            [-read-chunk BYTES] [-reader gpu|host]
-// (-batch / -batch-bases: queries / bases per batch; the reads go through in batches, see mcq_read_batches.hpp;
+// usage: mcq_query_cli <dbprefix> <n_ranks> <file|directory>... [-pairfiles | -pairseq] [-splitout PREFIX] [-lowest R] [-highest R]
+//            [-maxcand N] [-hitmin N] [-hitdiff X] [-insertsize N] [-threads N] [-tophits] [-taxids] [-taxids-only] [-omit-ranks]
+//            [-lineage] [-mapped-only] [-nomap] [-noquirks] [-abundances [FILE]] [-abundance-per R] [-out FILE] [-batch N]
+//            [-batch-bases N] [-read-chunk BYTES] [-reader gpu|host]
+// (inputs: every argument up to the first option; a directory stands for the files in it (files_in_directory below).  -pairseq
+//  without -pairfiles comes first: every file is interleaved pairs, also the two of `r1 r2` and the one of `r1 -`.  Without it,
+//  `r1 r2` alone is one pair of files in the given order and `r1 -` one single-end file.  Otherwise -pairfiles sorts the names and pairs
+//  consecutive ones (src/mode_query.cpp:409-411, src/querying.h:1329-1340; an odd count is an error), -pairseq takes every file
+//  as interleaved pairs (sequence_pair_reader::next, src/sequence_io.cpp:442-462), and without either every file is single-end,
+//  in the given order.  Each unit's mapping lines follow its "# f1 + f2" / "# f1" line; statistics and abundances add up over
+//  all units.  -splitout PREFIX (-split-out): one output per unit instead, PREFIX_<name1>[_<name2>].txt, each with its own
+//  head, summary and abundance tables, src/mode_query.cpp:170-229; -out FILE, if given, is the prefix: src/query_options.cpp:343-351;
+//  -list-inputs (written into no output): print the pairing mode and one line per unit -- its "f1 + f2" / "f1" text, under -splitout a
+//  tab and its output file -- and leave before the database is opened;
+//  -batch / -batch-bases: queries / bases per batch; the reads go through in batches, see mcq_read_batches.hpp;
 //  -read-chunk / -reader (mcq_query_cli only, written into no output): bytes per read() of each file, default 8 MiB, and
 //  who parses the chunks -- the GPU (mcq_reads_prepare; a chunk not in the strict form goes to the host) or always the host;
 //  -abundances [FILE] / -abundance-per R (aliases -abundances-per, -abundance_per, -abundances_per): src/query_options.cpp:310-323)
+#include <dirent.h>
+
+#include <algorithm>
 #include <chrono>
 #include <cstdio>
 #include <cstdlib>
@@ -42,6 +55,7 @@
 #include "../../../include/mcq.h"
 #include "../../../include/mcq_host.h"
 #include "../../../include/mcq_open.hpp"
+#include "mcq_read_unit.hpp"
 
 // How a taxon is written (the reference's taxon_print_mode, src/query_options.h:68-71; output of src/printing.cpp:117-176,
 // :243-300) as two independent choices: an optional "<rank>:" prefix, and one of three bodies -- name, id, name(id).
@@ -52,7 +66,11 @@ struct Mode {
 };
 
 struct Options {
-    std::string prefix, f1, f2, outfile;
+    std::string prefix, outfile;
+    std::vector<ReadUnit> units;         // the inputs, in the order they are read and written (make_units)
+    enum Pairing { NONE, FILES, SEQUENCES } pairing = NONE;   // the reference's pairing_mode (src/query_options.cpp:82-97)
+    bool split = false;                  // -splitout: one output per unit
+    bool list_inputs = false;            // -list-inputs: print the units and leave
     uint32_t P = 1;                      // ranks of the reference build / run whose results are reproduced
     uint32_t lowest = MCQ_RANK_SEQUENCE, highest = MCQ_RANK_DOMAIN, maxcand = 2, hitmin = 0, threads = 1;
     float hitdiff = 1.0f; uint64_t insertsize = 0; bool quirks = true;
@@ -65,7 +83,7 @@ struct Options {
     uint64_t batch = 1u << 19, batch_bases = 256u << 20;   // mcq_query_mpi: queries / bases per rank and batch
     uint64_t read_chunk = 8u << 20;      // mcq_query_cli: bytes per file and chunk (-read-chunk)
     bool host_reader = false;            // mcq_query_cli: -reader host
-    bool paired() const { return f2 != "-"; }
+    bool paired() const { return pairing != NONE; }
 };
 
 // an option under any of its spellings (the reference's args.get / args.contains take a list of them, e.g. src/mode_build.cpp:113-122)
@@ -74,10 +92,68 @@ static inline bool opt_named(const std::string& a, std::initializer_list<const c
     return false;
 }
 
+// The files a directory stands for: files_in_directory (src/filesys_utility.cpp:32-73), which sequence_filenames
+// (src/args_handling.cpp:50-90) applies to every input name -- every entry but "." and "..", a subdirectory (10 levels) replaced
+// by what it holds, an entry that holds nothing (a file, an empty directory) by its own path.  The reference keeps readdir's
+// order, which no two file systems share; here the entries of a directory go in the order of their names.
+static std::vector<std::string> files_in_directory(std::string dir, int recurse = 10) {
+    if (!dir.empty() && (dir.back() == '/' || dir.back() == '\\')) dir.pop_back();
+    std::vector<std::string> files, names;
+    if (DIR* d = opendir(dir.c_str())) {
+        while (struct dirent* e = readdir(d))
+            if (std::strcmp(e->d_name, ".") != 0 && std::strcmp(e->d_name, "..") != 0) names.push_back(e->d_name);
+        closedir(d);
+    }
+    std::sort(names.begin(), names.end());
+    for (const std::string& n : names) {
+        std::vector<std::string> below;
+        if (recurse > 0) below = files_in_directory(dir + "/" + n, recurse - 1);
+        if (below.empty()) files.push_back(dir + "/" + n);
+        else files.insert(files.end(), below.begin(), below.end());
+    }
+    return files;
+}
+
+// The input names of the command line -> the units, in the order they are read.  false (reported): no input, or an odd
+// number of files to pair.
+static bool make_units(const std::vector<std::string>& named, bool pairfiles, bool pairseq, Options& o) {
+    o.units.clear(); o.pairing = Options::NONE;
+    auto unit = [&](const std::string& a, const std::string& b, bool inter) { ReadUnit u; u.f1 = a; u.f2 = b; u.interleaved = inter; o.units.push_back(u); };
+    bool expanded = false;
+    std::vector<std::string> files;
+    for (const std::string& n : named) {
+        if (n == "-" && named.size() == 2 && &n == &named[1]) continue;                 // `r1 -`
+        const std::vector<std::string> in = files_in_directory(n);
+        if (in.empty()) files.push_back(n); else { files.insert(files.end(), in.begin(), in.end()); expanded = true; }
+    }
+    if (files.empty()) { std::fprintf(stderr, "ABORT: no read files given\n"); return false; }
+    pairseq = pairseq && !pairfiles;                                                    // -pairfiles comes first: src/query_options.cpp:83-97
+    const bool two_named = named.size() == 2 && files.size() == 2 && !expanded && !pairseq;   // `r1 r2`: one pair, in the given order
+    if ((pairfiles && files.size() > 1) || two_named) {
+        o.pairing = Options::FILES;
+        if (!two_named) std::sort(files.begin(), files.end());                          // src/mode_query.cpp:409-411
+        if (files.size() & 1) { std::fprintf(stderr, "ABORT: -pairfiles needs an even number of read files, %zu were given\n", files.size()); return false; }
+        for (size_t i = 0; i < files.size(); i += 2) unit(files[i], files[i + 1], false);
+    } else if (pairseq) {
+        o.pairing = Options::SEQUENCES;
+        for (const std::string& f : files) unit(f, "", true);
+    } else
+        for (const std::string& f : files) unit(f, "", false);
+    return true;
+}
+
 static bool parse_options(int argc, char** argv, Options& o) {
-    if (argc < 5) { std::fprintf(stderr, "usage: %s <dbprefix> <n_ranks> <r1> <r2|-> [options]\n", argv[0]); return false; }
-    o.prefix = argv[1]; o.P = (uint32_t)std::atoi(argv[2]); o.f1 = argv[3]; o.f2 = argv[4];
-    for (int i = 5; i < argc; ++i) {
+    std::vector<std::string> named;                      // argv[3 ..] up to the first option
+    int i = 3;
+    for (; i < argc && !(argv[i][0] == '-' && argv[i][1] != '\0'); ++i) named.push_back(argv[i]);
+    if (argc < 4 || named.empty()) {
+        std::fprintf(stderr, "usage: %s <dbprefix> <n_ranks> <file|directory>... [-pairfiles | -pairseq] [-splitout PREFIX] [options]\n"
+                             "       %s <dbprefix> <n_ranks> <r1> <r2|-> [options]\n", argv[0], argv[0]);
+        return false;
+    }
+    o.prefix = argv[1]; o.P = (uint32_t)std::atoi(argv[2]);
+    bool pairfiles = false, pairseq = false; std::string split_prefix;
+    for (; i < argc; ++i) {
         std::string a = argv[i];
         auto next = [&]() -> const char* { return (i + 1 < argc) ? argv[++i] : ""; };
         if (a == "-lowest") { uint32_t r = mcq_rank_from_name(next()); if (r < MCQ_RANK_ROOT) o.lowest = r; }
@@ -95,6 +171,11 @@ static bool parse_options(int argc, char** argv, Options& o) {
         else if (a == "-mapped-only" || a == "-mappedonly") o.mapped_only = true;
         else if (a == "-nomap" || a == "-no-map") o.nomap = true;
         else if (a == "-noquirks") o.quirks = false;
+        else if (opt_named(a, {"-paired_files", "-paired-files", "-pair_files", "-pair-files", "-pairfiles"})) pairfiles = true;   // src/query_options.cpp:83-84
+        else if (opt_named(a, {"-paired_sequences", "-paired-sequences", "-pair_sequences", "-pair-sequences", "-pair_sequ", "-pair-sequ",
+                               "-pair_seq", "-pair-seq", "-pairsequ", "-pairseq", "-paired"})) pairseq = true;                      // :90-94
+        else if (a == "-list-inputs") o.list_inputs = true;
+        else if (a == "-splitout" || a == "-split-out") { o.split = true; if (i + 1 < argc && argv[i + 1][0] != '-') split_prefix = argv[++i]; }
         else if (a == "-transport") o.transport = next();
         else if (a == "-batch") o.batch = std::max<uint64_t>(1, std::strtoull(next(), nullptr, 10));
         else if (a == "-batch-bases") o.batch_bases = std::max<uint64_t>(1024, std::strtoull(next(), nullptr, 10));
@@ -109,7 +190,9 @@ static bool parse_options(int argc, char** argv, Options& o) {
             const uint32_t r = mcq_rank_from_name(next()); if (r < MCQ_RANK_ROOT) o.abundance_rank = r;
         }
     }
+    if (o.split && o.outfile.empty()) o.outfile = split_prefix;              // src/query_options.cpp:346-351
     if (o.abundance_file == o.outfile) o.abundance_file.clear();
+    if (!make_units(named, pairfiles, pairseq, o)) return false;
     if (o.lowest > o.highest) o.lowest = o.highest;
     if (o.nomap && o.tophits) { o.nomap = false; o.mapped_only = true; }   // "showing hits changes the mapping mode", src/query_options.cpp:289-292
     return true;
@@ -159,7 +242,7 @@ static Out make_out(mcq_refdb* rdb, const Options& p) {
     return Out{rdb, p, Mode::make(p.show_ranks, p.taxids, p.taxids_only)};   // -taxids-only wins over -taxids (src/query_options.cpp:262-274)
 }
 
-// show_query_parameters (src/printing.cpp:40-113) + show_query_mapping_header (src/classification.cpp:486-512) + the file line
+// show_query_parameters (src/printing.cpp:40-113) + show_query_mapping_header (src/classification.cpp:486-512)
 static void write_head(std::ostream& os, const Out& o, uint32_t hitmin) {
     const Options& p = o.p; const char* cm = o.comment;
     if (!p.nomap) {
@@ -170,8 +253,10 @@ static void write_head(std::ostream& os, const Out& o, uint32_t hitmin) {
     os << cm << "Classification will be constrained to ranks from '" << mcq_rank_name(p.lowest) << "' to '" << mcq_rank_name(p.highest) << "'.\n";
     os << cm << "Classification hit threshold is " << hitmin << " per query\n";
     os << cm << "At maximum " << p.maxcand << " classification candidates will be considered per query.\n";
-    if (p.paired()) os << cm << "File based paired-end mode:\n" << cm << "  Reads from two consecutive files will be interleaved.\n"
-                       << cm << "  Max insert size considered " << p.insertsize << ".\n";
+    if (p.pairing == Options::FILES) os << cm << "File based paired-end mode:\n" << cm << "  Reads from two consecutive files will be interleaved.\n"
+                                        << cm << "  Max insert size considered " << p.insertsize << ".\n";
+    else if (p.pairing == Options::SEQUENCES) os << cm << "Per file paired-end mode:\n" << cm << "  Reads from two consecutive sequences in each file will be paired up.\n"
+                                                 << cm << "  Max insert size considered " << p.insertsize << ".\n";
     if (p.abundance_rank != MCQ_RANK_NONE)                                  // (the reference keys the -abundances line on -hits-per-seq, :100-103)
         os << cm << "A list of absolute and relative abundances for each '" << mcq_rank_name(p.abundance_rank)
            << "' will be generated after the read mapping.\n";
@@ -182,7 +267,43 @@ static void write_head(std::ostream& os, const Out& o, uint32_t hitmin) {
         o.header_taxon(os);
         os << '\n';
     }
-    os << cm << (p.paired() ? p.f1 + " + " + p.f2 : p.f1) << '\n';          // src/querying.h:1337
+}
+// the line in front of a unit's mapping lines (showInfo, src/querying.h:1336-1340)
+static void write_unit_line(std::ostream& os, const Out& o, const ReadUnit& u) { os << o.comment << u.display() << '\n'; }
+
+// -splitout: the options of the run over `u` alone, its outputs named as src/mode_query.cpp:176-228 names them
+static std::string extract_filename(const std::string& path) { return path.substr(path.find_last_of("/\\") + 1); }   // src/filesys_utility.cpp:94-101
+static Options split_options(const Options& p, const ReadUnit& u) {
+    Options s = p;
+    s.units.assign(1, u); s.split = false;
+    const std::string tail = "_" + extract_filename(u.f1) + (u.f2.empty() ? std::string() : "_" + extract_filename(u.f2)) + ".txt";
+    if (!p.outfile.empty()) s.outfile = p.outfile + tail;
+    if (!p.abundance_file.empty()) s.abundance_file = p.abundance_file + tail;
+    return s;
+}
+// -list-inputs
+static void list_inputs(std::ostream& os, const Options& p) {
+    static const char* mode[] = {"none", "files", "sequences"};
+    os << "pairing: " << mode[p.pairing] << '\n';
+    for (const ReadUnit& u : p.units) {
+        os << u.display();
+        if (p.split) os << '\t' << split_options(p, u).outfile;
+        os << '\n';
+    }
+}
+// every file of every unit opens: asked before the first output is written, whichever run reads the file
+static bool inputs_readable(const Options& p) {
+    for (const ReadUnit& u : p.units)
+        for (const std::string* f : {&u.f1, &u.f2})
+            if (!f->empty() && !std::ifstream(*f).good()) { std::fprintf(stderr, "FAIL: can't open file %s\n", f->c_str()); return false; }
+    return true;
+}
+// the runs a command line asks for: one over all units, or (-splitout) one per unit
+static std::vector<Options> output_runs(const Options& p) {
+    std::vector<Options> runs;
+    if (!p.split) runs.push_back(p);
+    else for (const ReadUnit& u : p.units) runs.push_back(split_options(p, u));
+    return runs;
 }
 
 // one query: classification (src/classification.cpp:235-265), statistics (classification_statistics::assign,

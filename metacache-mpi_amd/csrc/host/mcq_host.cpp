@@ -629,37 +629,47 @@ extern "C" int mcq_reads_parse(const char* text1, uint64_t len1, const char* tex
                                uint64_t max_queries, uint64_t max_bases, char* bases, uint64_t* seq_off, uint64_t* hdr, uint64_t* info) {
     if ((len1 && !text1) || (len2 && !text2) || !bases || !seq_off || !hdr || !info) return fail("null argument");
     if (max_queries < 1) return fail("max_queries must be >= 1");
-    const bool paired = text2 != nullptr;
+    const bool paired = text2 != nullptr, inter = (flags & MCQ_READS_INTERLEAVED) != 0;
+    if (inter && paired) return fail("MCQ_READS_INTERLEAVED is given with text2 == NULL");
+    const bool eof1 = (flags & MCQ_READS_EOF1) != 0;
     ChunkRecs R[2];
-    parse_chunk(text1, len1, (flags & MCQ_READS_EOF1) != 0, max_queries, R[0]);
+    parse_chunk(text1, len1, eof1, inter ? (max_queries > (UINT64_MAX >> 1) ? UINT64_MAX : 2 * max_queries) : max_queries, R[0]);
     if (paired) parse_chunk(text2, len2, (flags & MCQ_READS_EOF2) != 0, max_queries, R[1]);
+    // query q is record q of each text, or (interleaved) records 2q and 2q+1 of text1: sequence_pair_reader::next,
+    // src/sequence_io.cpp:442-462.  There the second next() of a file that has run out gives an empty sequence, so an
+    // unpaired last record (an odd count, which under eof1 only the end of the text leaves: max_recs is even) is a query.
     uint64_t nq = R[0].n_complete;
     if (paired) nq = std::min(nq, R[1].n_complete);
-    const int mates = paired ? 2 : 1;
-    const char* text[2] = {text1, text2};
+    if (inter) nq = nq / 2 + ((eof1 && (nq & 1)) ? 1 : 0);
+    const int mates = (paired || inter) ? 2 : 1;
+    const char* text[2] = {text1, inter ? text1 : text2};
+    auto rec = [&](uint64_t q, int m) { return inter ? 2 * q + (uint64_t)m : q; };
+    auto has = [&](uint64_t q, int m) { return !inter || rec(q, m) < R[0].n_complete; };
     uint64_t n = 0, nb = 0;
     seq_off[0] = 0;
     for (; n < nq; ++n) {
         uint64_t len = 0;
-        for (int m = 0; m < mates; ++m) len += R[m].seq_len(n);
+        for (int m = 0; m < mates; ++m) if (has(n, m)) len += R[inter ? 0 : m].seq_len(rec(n, m));
         if (n && nb + len > max_bases) break;
         for (int m = 0; m < mates; ++m) {
-            const ChunkRecs& X = R[m];
-            const uint64_t e = n + 1 < X.piece_at.size() ? X.piece_at[n + 1] : X.pieces.size() / 2;
-            for (uint64_t i = X.piece_at[n]; i < e; ++i) {
+            const ChunkRecs& X = R[inter ? 0 : m];
+            const uint64_t r = rec(n, m);
+            const uint64_t e = r + 1 < X.piece_at.size() ? X.piece_at[r + 1] : X.pieces.size() / 2;
+            for (uint64_t i = has(n, m) ? X.piece_at[r] : e; i < e; ++i) {
                 const uint64_t b = X.pieces[2 * i], l = X.pieces[2 * i + 1] - b;
                 std::memcpy(bases + nb, text[m] + b, l); nb += l;
             }
             seq_off[n * mates + m + 1] = nb;
         }
-        const char* sp = (const char*)std::memchr(text1 + R[0].hb[n], ' ', R[0].he[n] - R[0].hb[n]);
-        hdr[2 * n] = R[0].hb[n]; hdr[2 * n + 1] = sp ? (uint64_t)(sp - text1) : R[0].he[n];
+        const uint64_t r0 = rec(n, 0);
+        const char* sp = (const char*)std::memchr(text1 + R[0].hb[r0], ' ', R[0].he[r0] - R[0].hb[r0]);
+        hdr[2 * n] = R[0].hb[r0]; hdr[2 * n + 1] = sp ? (uint64_t)(sp - text1) : R[0].he[r0];
     }
     std::memset(info, 0, MCQ_READS_INFO_WORDS * 8);
     info[MCQ_READS_N] = n; info[MCQ_READS_BASES] = nb;
-    for (int m = 0; m < mates; ++m)        // the next chunk starts at record n, or behind everything this one held
-        info[MCQ_READS_CUT1 + m] = n < R[m].n_complete ? R[m].start[n] : R[m].end;
-    info[MCQ_READS_COMPLETE1] = R[0].n_complete;
+    for (int m = 0; m < (inter ? 1 : mates); ++m)        // the next chunk starts at the first record not taken, or behind everything this one held
+        info[MCQ_READS_CUT1 + m] = rec(n, 0) < R[m].n_complete ? R[m].start[rec(n, 0)] : R[m].end;
+    info[MCQ_READS_COMPLETE1] = inter ? nq : R[0].n_complete;
     info[MCQ_READS_COMPLETE2] = paired ? R[1].n_complete : 0;
     return 0;
 }

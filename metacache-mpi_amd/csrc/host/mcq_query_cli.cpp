@@ -1,8 +1,8 @@
-// mcq_query_cli -- `metacache query <db> r1.fq r2.fq -pairfiles ...` on one GPU: see mcq_cli_common.hpp for what is
-// written and which reference code each part stands in for.
+// mcq_query_cli -- `metacache query <db> <files and directories> [-pairfiles | -pairseq] ...` on one GPU: see mcq_cli_common.hpp
+// for what is written and which reference code each part stands in for.
 //
 // The reads stream through three slots in rotation.  For batch j, ReadBatcher::next (mcq_read_batches.hpp)
-// fills slot j % 3 from a chunk of each file and leaves the batch on the device; mcq_query runs on it on a second stream, the
+// fills slot j % 3 from a chunk of each file of the unit it is in and leaves the batch on the device; mcq_query runs on it on a second stream, the
 // candidates copied back behind it, while -threads host threads format the mapping lines of batch j - 2.  Host memory is fixed by
 // -read-chunk and -batch.  All that is held has an owner (mcq_cli_buffers.hpp, Database, Run): every `return` of main frees it.
 #include "mcq_cli_common.hpp"
@@ -30,6 +30,7 @@ struct Run {
     Slot slot[NS];
     uint64_t assigned[MCQ_RANK_NONE + 1] = {0};
     size_t issued = 0, retired = 0;                              // batches enqueued; batches whose lines are written or being written
+    size_t announced = 0;                                        // units whose "# f1 + f2" line is written (by finish, in batch order)
     std::future<bool> pending;                                   // the formatting of batch `retired - 1`, beside the reading of the next
 
     Run(const Options& p_, const Database& db_) : p(p_), db(db_), o(make_out(db_.rdb, p_)), co(classify_opts(p_, db_.hitmin)) {}
@@ -52,6 +53,7 @@ struct Run {
     bool finish(size_t j) {
         Slot& S = slot[j % NS];
         if (hipEventSynchronize(S.done) != hipSuccess) { std::fprintf(stderr, "FAIL: batch %zu did not complete\n", j); return false; }
+        announce(S.unit + 1);
         const uint64_t n = S.n;
         const unsigned T = (unsigned)std::min<uint64_t>(std::max(1u, p.threads), std::max<uint64_t>(1, n / 64));
         std::vector<std::string> out(T);
@@ -76,6 +78,8 @@ struct Run {
         }
         return true;
     }
+    // the lines of the units before `end` that have none yet: a batch's own unit, and units without records before it
+    void announce(size_t end) { for (; announced < end; ++announced) write_unit_line(*os, o, p.units[announced]); }
     bool join() { return !pending.valid() || pending.get(); }
     void finish_next_beside() { const size_t r = retired++; pending = std::async(std::launch::async, [this, r] { return finish(r); }); }
     bool drain() {
@@ -101,14 +105,10 @@ struct Run {
 
 }  // namespace
 
-int main(int argc, char** argv) {
-    Options p;
-    if (!parse_options(argc, argv, p)) return 2;
-    Database db;
-    if (!open_database(p, db, 1, 0, 0)) return 1;
-
+// one output: the units of p through the GPU, head, mapping lines, tables and summary into p's -out file
+static int run_queries(const Options& p, const Database& db) {
     const auto t_start = std::chrono::steady_clock::now();                  // the reference times map_queries_to_targets, readers included (src/mode_query.cpp:130-132)
-    ReadBatcher reads(p.f1, p.paired() ? p.f2 : std::string(), p.read_chunk, p.batch, p.batch_bases, p.host_reader, 0);
+    ReadBatcher reads(p.units, p.read_chunk, p.batch, p.batch_bases, p.host_reader, 0);
     Run run(p, db);
     if (!reads.ok() || !run.init()) return 1;
     const mcq_query_opts qo = query_opts(p);
@@ -135,10 +135,23 @@ int main(int argc, char** argv) {
         ++run.issued;
     }
     if (!run.drain()) return 1;
+    run.announce(p.units.size());
     if (run.tx) {
         if (run.ws && !add_taxon_counts(run.ws, run.tax_counts)) return 1;
         if (!write_abundances(*run.os, db.rdb, p, run.tax_counts, run.assigned)) return 1;
     }
     write_summary(*run.os, run.o, run.assigned, std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_start).count());
+    return 0;
+}
+
+int main(int argc, char** argv) {
+    Options p;
+    if (!parse_options(argc, argv, p)) return 2;
+    if (p.list_inputs) { list_inputs(std::cout, p); return 0; }
+    Database db;
+    if (!open_database(p, db, 1, 0, 0)) return 1;
+    if (p.split && !inputs_readable(p)) return 1;               // (one run: its ReadBatcher tries them all)
+    for (const Options& r : output_runs(p))
+        if (const int rc = run_queries(r, db)) return rc;
     return 0;
 }

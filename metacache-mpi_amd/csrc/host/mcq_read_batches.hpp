@@ -1,7 +1,13 @@
 #pragma once
-// mcq_read_batches.hpp -- the input stage of mcq_query_cli: one or two read files -> batches of queries on
-// the device.  ReadBatcher owns the files (mcq_read_stream_* of the host library), what is asked of and carried between their
-// chunks, and the stream the batches are prepared on; the caller owns the slots it fills, as many as it keeps in flight.
+// mcq_read_batches.hpp -- the input stage of mcq_query_cli: a list of units (mcq_read_unit.hpp: a file, a
+// pair of files, an interleaved file) -> batches of queries on the device.  ReadBatcher owns the files of the unit it is in
+// (mcq_read_stream_* of the host library; only they are open), what is asked of and carried between their chunks, and the stream
+// the batches are prepared on; the caller owns the slots it fills, as many as it keeps in flight.
+//
+// The units go through in order and A BATCH NEVER MIXES UNITS: the end of a unit ends the batch, and slot.unit is the index of
+// the unit all of the batch's queries come from.  It never decreases; a caller that writes a line per unit writes, in front of
+// a batch, the lines of every unit up to slot.unit it has not written yet (a unit without records has no batch), and after
+// END those of the rest.  Every unit of a list has the same number of mates.
 //
 // next(slot) returns BATCH, END (from then on always) or ERROR (reported on stderr).  After BATCH, slot.n > 0 queries lie in
 // slot.d_bases / .d_seq_off as mcq_query takes them with MCQ_DEVICE_PTRS, ordered on stream(); query q's header is the pinned
@@ -15,6 +21,7 @@
 #include "../../../include/mcq.h"
 #include "../../../include/mcq_host.h"
 #include "mcq_cli_buffers.hpp"
+#include "mcq_read_unit.hpp"
 
 struct ReadSlot {
     PinnedBuf<char> text[2]; uint64_t len[2] = {0, 0};              // a chunk per file: the bytes the last batch left, then read()s
@@ -23,32 +30,51 @@ struct ReadSlot {
     PinnedBuf<uint64_t> hdr, info;
     std::vector<char> h_bases; std::vector<uint64_t> h_seq_off;     // a chunk parsed on the host
     uint64_t n = 0; bool host_parsed = false;
+    size_t unit = 0;                                                // the unit the batch comes from
 };
 
 class ReadBatcher {
 public:
     enum Status { BATCH, END, ERROR };
-    // f2 empty: single-end.  read_chunk: bytes per file and chunk; batch / batch_bases: most queries / bases of a batch;
-    // host_reader: every chunk is parsed on the host.  A file that does not open or a stream that cannot be made: !ok().
-    ReadBatcher(const std::string& f1, const std::string& f2, uint64_t read_chunk, uint64_t batch, uint64_t batch_bases, bool host_reader, int device)
-        : mates_(f2.empty() ? 1 : 2), chunk_(read_chunk), batch_(batch), batch_bases_(batch_bases), host_reader_(host_reader) {
-        for (int m = 0; m < mates_; ++m)
-            if (mcq_read_stream_open((m ? f2 : f1).c_str(), &rs_[m])) { std::fprintf(stderr, "FAIL: can't open file %s\n", (m ? f2 : f1).c_str()); return; }
+    // read_chunk: bytes per file and chunk; batch / batch_bases: most queries / bases of a batch; host_reader: every chunk is
+    // parsed on the host.  A file of any unit that does not open (all are tried here, before anything is read) or a stream that
+    // cannot be made: !ok().
+    ReadBatcher(const std::vector<ReadUnit>& units, uint64_t read_chunk, uint64_t batch, uint64_t batch_bases, bool host_reader, int device)
+        : units_(units), chunk_(read_chunk), batch_(batch), batch_bases_(batch_bases), host_reader_(host_reader) {
+        for (size_t u = units_.size(); u-- > 0;) { if (!open_unit(u)) return; }       // (ends with the first unit open)
         MCQ_HIP(hipSetDevice(device), return);
         ok_ = s_in_.create();
     }
-    ~ReadBatcher() { for (mcq_read_stream* s : rs_) if (s) mcq_read_stream_close(s); }
+    ~ReadBatcher() { close_unit(); }
     bool ok() const { return ok_; }
     hipStream_t stream() const { return s_in_; }
     Status next(ReadSlot& S) {
-        if (at_end_) return END;
-        do {
-            if (!ok_ || !fill(S) || !prepare(S) || !take_or_enlarge(S)) return ERROR;
-        } while (S.n == 0 && !at_end_);
-        return S.n ? BATCH : END;
+        for (;;) {
+            if (!ok_) return ERROR;
+            if (unit_ >= units_.size()) return END;
+            while (!at_end_) {
+                if (!fill(S) || !prepare(S) || !take_or_enlarge(S)) { ok_ = false; return ERROR; }
+                if (S.n) { S.unit = unit_; return BATCH; }
+            }
+            if (++unit_ < units_.size() && !open_unit(unit_)) { ok_ = false; return ERROR; }
+        }
     }
 
 private:
+    void close_unit() { for (mcq_read_stream*& s : rs_) { if (s) mcq_read_stream_close(s); s = nullptr; } }
+    // the files of unit u instead of those open now; chunks start over
+    bool open_unit(size_t u) {
+        close_unit();
+        const ReadUnit& U = units_[u];
+        mates_ = U.files(); inter_ = U.interleaved;
+        for (int m = 0; m < mates_; ++m) {
+            const std::string& f = m ? U.f2 : U.f1;
+            if (mcq_read_stream_open(f.c_str(), &rs_[m])) { std::fprintf(stderr, "FAIL: can't open file %s\n", f.c_str()); return false; }
+            want_[m] = chunk_; carry_[m] = 0; eof_[m] = 0;
+        }
+        at_end_ = false;
+        return true;
+    }
     // a chunk of each file into the slot's pinned text, the two files side by side.  A buffer too small for what is asked is
     // replaced; the one it replaces may hold the carried bytes, so it lives until the fill has moved them (the end of this function).
     bool fill(ReadSlot& S) {
@@ -70,7 +96,8 @@ private:
     bool prepare(ReadSlot& S) {
         const bool paired = mates_ == 2;
         const uint64_t L1 = S.len[0], L2 = paired ? S.len[1] : 0;
-        const uint32_t flags = (eof_[0] ? MCQ_READS_EOF1 : 0) | (paired && eof_[1] ? MCQ_READS_EOF2 : 0);
+        const uint32_t flags = (eof_[0] ? MCQ_READS_EOF1 : 0) | (paired && eof_[1] ? MCQ_READS_EOF2 : 0) | (inter_ ? MCQ_READS_INTERLEAVED : 0);
+        const int out_mates = (paired || inter_) ? 2 : 1;
         const uint64_t qcap = std::min<uint64_t>(batch_, std::min(L1, paired ? L2 : L1) / 2 + 2);
         if (!S.hdr.grow(2 * qcap) || !S.info.grow(MCQ_READS_INFO_WORDS) || !S.d_bases.grow(L1 + L2 + 1) || !S.d_seq_off.grow(2 * qcap + 1)) return false;
         S.host_parsed = host_reader_;
@@ -93,7 +120,7 @@ private:
                                 S.h_seq_off.data(), S.hdr.p, S.info.p)) { std::fprintf(stderr, "FAIL: %s\n", mcq_host_last_error()); return false; }
             if (const uint64_t n = S.info.p[MCQ_READS_N]) {
                 MCQ_HIP(hipMemcpyAsync(S.d_bases.p, S.h_bases.data(), S.info.p[MCQ_READS_BASES] + 1, hipMemcpyHostToDevice, s_in_), return false);
-                MCQ_HIP(hipMemcpyAsync(S.d_seq_off.p, S.h_seq_off.data(), (n * mates_ + 1) * 8, hipMemcpyHostToDevice, s_in_), return false);
+                MCQ_HIP(hipMemcpyAsync(S.d_seq_off.p, S.h_seq_off.data(), (n * out_mates + 1) * 8, hipMemcpyHostToDevice, s_in_), return false);
                 MCQ_HIP(hipStreamSynchronize(s_in_), return false);
             }
         }
@@ -114,7 +141,9 @@ private:
         return true;
     }
 
-    const int mates_; const uint64_t chunk_, batch_, batch_bases_; const bool host_reader_;
+    const std::vector<ReadUnit> units_; const uint64_t chunk_, batch_, batch_bases_; const bool host_reader_;
+    size_t unit_ = 0;                                              // the unit whose files are open
+    int mates_ = 1; bool inter_ = false;                           // its files; its file is interleaved
     mcq_read_stream* rs_[2] = {nullptr, nullptr}; Stream s_in_;
     uint64_t want_[2] = {chunk_, chunk_}, carry_[2] = {0, 0};      // bytes asked of the next fill; bytes the last batch left
     int32_t eof_[2] = {0, 0};                                      // the last fill reached the end of its file

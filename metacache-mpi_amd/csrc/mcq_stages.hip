@@ -615,6 +615,9 @@ static int text_index(const char* text, uint64_t n_bytes, uint64_t* seq_ranges, 
 // record measures its sequence, one workgroup scans the lengths into seq_off and applies max_queries / max_bases, and one
 // wave per (query, mate) copies the sequence lines (a wave ballot finds the header's first ' ').  Byte positions are u32:
 // a chunk is below 4 GiB.
+// MCQ_READS_INTERLEAVED (P.inter): one text, numbered as above; record 2q + m is mate m of query q.  rlen then holds one
+// length per PAIR (so the scratch of the single-text call is enough), the scan runs over pairs and writes seq_off[2q], and
+// the copy kernel, which walks the mates' lines anyway, places mate 1 behind mate 0 and writes seq_off[2q + 1].
 struct RdText {
     const char* t; u64 L; u32 eof, pad;
     u64 n_tiles, rcap;
@@ -623,7 +626,7 @@ struct RdText {
     u32* hl;                                // [L / 2 + 2] FASTA: line index of header r
     u32* rlen;                              // [rcap]      sequence length of record r
 };
-struct RdPair { RdText x[2]; u32 mates; u64* info; };
+struct RdPair { RdText x[2]; u32 mates, inter; u64* info; };   // mates: texts; inter: mates are records 2q, 2q+1 of x[0]
 
 __device__ __forceinline__ u32 rd_zero_bytes(u32 m) {                  // bit i = byte i of m is zero (exact)
     const u32 z = ~(((m & 0x7F7F7F7Fu) + 0x7F7F7F7Fu) | m) & 0x80808080u;
@@ -682,9 +685,13 @@ __global__ __launch_bounds__(256) void k_rd_lines(RdPair P) {
     for (u32 w = 0; w < wave; ++w) { wn += s_w[0][w]; wh += s_w[1][w]; }
     const u64 line0 = X.off_nl[blockIdx.x] + wn + in - cn;             // the line that text[base] belongs to
     const u64 hdr0 = X.off_h[blockIdx.x] + wh + ih - ch;
-    for (u32 m = nlm, l = 0; m; m &= m - 1, ++l) X.nl[line0 + l] = (u32)(base + (u32)__builtin_ctz(m));
-    const char f = X.L ? X.t[0] : 0;
     bool bad = false;
+    for (u32 m = nlm, l = 0; m; m &= m - 1, ++l) {
+        const u64 at = base + (u32)__builtin_ctz(m);
+        X.nl[line0 + l] = (u32)at;
+        bad |= P.inter && at > 0 && X.t[at - 1] == '\r';               // (interleaved: a line that ends in '\r' goes to the host, include/mcq.h)
+    }
+    const char f = X.L ? X.t[0] : 0;
     for (u32 m = lsm; m; m &= m - 1) {
         const u32 j = (u32)__builtin_ctz(m), below = (1u << j) - 1u;
         const u64 li = line0 + (u32)__builtin_popcount(nlm & below);
@@ -721,15 +728,22 @@ __device__ __forceinline__ void rd_seq_lines(const RdText& X, const RdCounts& c,
     if (a > b) a = b;
 }
 
+// sequence length of record r (0 for a record the text does not hold)
+__device__ __forceinline__ u32 rd_rec_len(const RdText& X, const RdCounts& c, u64 r) {
+    if (r >= c.n_rec) return 0u;
+    u64 a, b;
+    rd_seq_lines(X, c, r, a, b);
+    return b > a ? (u32)(rd_line_end(X, c, b - 1) - rd_line_start(X, a) - (b - 1 - a)) : 0u;
+}
+
+// rlen[i]: the length of record i, or (interleaved) of the pair of records 2i, 2i+1
 __global__ __launch_bounds__(256) void k_rd_recs(RdPair P) {
     const RdText X = rd_pick(P, blockIdx.y);
     const RdCounts c = rd_counts(X);
-    const u64 n = c.n_rec < X.rcap ? c.n_rec : X.rcap;
-    for (u64 r = (u64)blockIdx.x * blockDim.x + threadIdx.x; r < n; r += (u64)gridDim.x * blockDim.x) {
-        u64 a, b;
-        rd_seq_lines(X, c, r, a, b);
-        X.rlen[r] = b > a ? (u32)(rd_line_end(X, c, b - 1) - rd_line_start(X, a) - (b - 1 - a)) : 0u;
-    }
+    const u64 items = P.inter ? (c.n_rec + 1) / 2 : c.n_rec;
+    const u64 n = items < X.rcap ? items : X.rcap;
+    for (u64 r = (u64)blockIdx.x * blockDim.x + threadIdx.x; r < n; r += (u64)gridDim.x * blockDim.x)
+        X.rlen[r] = P.inter ? rd_rec_len(X, c, 2 * r) + rd_rec_len(X, c, 2 * r + 1) : rd_rec_len(X, c, r);
 }
 
 // one workgroup: complete records per text, the queries taken, seq_off, the cut points
@@ -739,7 +753,8 @@ __global__ __launch_bounds__(1024) void k_rd_offsets(RdPair P, u64 max_queries, 
     __shared__ u64 s_carry, s_endmax, s_end0;
     __shared__ u32 s_k;
     const u32 tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const u32 mates = P.mates;
+    const u32 mates = P.mates;                                         // items of the scan per query (interleaved: one, a pair's length)
+    const u32 ostride = P.inter ? 2u : 1u;                             // ... and seq_off entries per item
     RdCounts c[2];
     u64 complete[2] = {0, 0};
     bool bad = false;
@@ -755,8 +770,12 @@ __global__ __launch_bounds__(1024) void k_rd_offsets(RdPair P, u64 max_queries, 
             last = X.eof ? l3 < c[m].n_lines : (l3 < c[m].nnl && (u64)X.nl[l3] + 1 < X.L);
             bad |= X.eof && (c[m].n_lines & 3) != 0;                   // a cut last record
         }
+        bad |= P.inter && X.eof && X.t[X.L - 1] == '\r';                // (interleaved: a last line that ends in '\r' as well, see k_rd_lines)
         complete[m] = c[m].n_rec - (last ? 0 : 1);
     }
+    // interleaved: a query is two complete records, or the last record alone where the file ends (the second next() of
+    // sequence_pair_reader::next, src/sequence_io.cpp:442-462, then gives an empty sequence)
+    if (P.inter) complete[0] = complete[0] / 2 + ((P.x[0].eof && complete[0] == c[0].n_rec) ? (complete[0] & 1) : 0);
     u64 nq = complete[0];
     if (mates == 2 && complete[1] < nq) nq = complete[1];
     if (P.x[0].rcap < nq) nq = P.x[0].rcap;
@@ -789,7 +808,7 @@ __global__ __launch_bounds__(1024) void k_rd_offsets(RdPair P, u64 max_queries, 
         for (int k = 0; k < MCQ_RD_PER_THREAD; ++k) {
             const u64 i = i0 + k;
             if (i < ns) {
-                seq_off[i] = off;
+                seq_off[i * ostride] = off;
                 const u64 end = off + len[k];
                 if (i % mates == mates - 1) {                          // the end of query q
                     const u64 q = i / mates;
@@ -812,14 +831,15 @@ __global__ __launch_bounds__(1024) void k_rd_offsets(RdPair P, u64 max_queries, 
     if (tid == 0) {
         u64 n = s_k, nb = s_endmax;
         if (n == 0 && nq) { n = 1; nb = s_end0; }                      // one query larger than max_bases goes alone
-        seq_off[n * mates] = nb;
+        seq_off[n * mates * ostride] = nb;
         u64* info = P.info;
         info[MCQ_READS_N] = n; info[MCQ_READS_BASES] = nb;
 #pragma unroll
         for (u32 m = 0; m < 2; ++m) {
             if (m >= mates) break;
             const RdText& X = P.x[m];
-            info[MCQ_READS_CUT1 + m] = n < c[m].n_rec ? rd_line_start(X, rd_hdr_line(X, c[m], n)) : X.L;
+            const u64 rn = n * ostride;                                 // the first record not taken
+            info[MCQ_READS_CUT1 + m] = rn < c[m].n_rec ? rd_line_start(X, rd_hdr_line(X, c[m], rn)) : X.L;
             info[MCQ_READS_COMPLETE1 + m] = complete[m] < max_queries ? complete[m] : max_queries;
         }
         if (bad) info[MCQ_READS_STATUS] = MCQ_READS_NOT_STRICT;
@@ -827,22 +847,28 @@ __global__ __launch_bounds__(1024) void k_rd_offsets(RdPair P, u64 max_queries, 
 }
 
 // one wave per (query, mate): the sequence lines into bases, and (mate 0) the header's first token
-__global__ __launch_bounds__(256) void k_rd_copy(RdPair P, const u64* seq_off, char* bases, u64* hdr) {
-    const u32 m = blockIdx.y, lane = threadIdx.x & 63, mates = P.mates;
-    const RdText X = rd_pick(P, m);
+__global__ __launch_bounds__(256) void k_rd_copy(RdPair P, u64* seq_off, char* bases, u64* hdr) {
+    const u32 m = blockIdx.y, lane = threadIdx.x & 63, inter = P.inter, mates = inter ? 2u : P.mates;
+    const RdText X = rd_pick(P, inter ? 0u : m);
     const RdCounts c = rd_counts(X);
     const u64 n = P.info[MCQ_READS_N];
     for (u64 q = (u64)blockIdx.x * 4 + (threadIdx.x >> 6); q < n; q += (u64)gridDim.x * 4) {
-        char* dst = bases + seq_off[q * mates + m];
-        u64 a, b;
-        rd_seq_lines(X, c, q, a, b);
+        const u64 r = inter ? 2 * q + m : q;                           // the record that is mate m of query q
+        char* dst;
+        if (inter) {                                                   // the scan placed the pair: mate 1 lies behind mate 0
+            const u64 o1 = seq_off[2 * q] + rd_rec_len(X, c, 2 * q);
+            if (m == 0 && lane == 0) seq_off[2 * q + 1] = o1;
+            dst = bases + (m ? o1 : seq_off[2 * q]);
+        } else dst = bases + seq_off[q * mates + m];
+        u64 a = 0, b = 0;
+        if (r < c.n_rec) rd_seq_lines(X, c, r, a, b);                  // (an unpaired last record has no second mate)
         for (u64 l = a; l < b; ++l) {
             const u64 s = rd_line_start(X, l), len = rd_line_end(X, c, l) - s;
             for (u64 i = lane; i < len; i += 64) dst[i] = X.t[s + i];
             dst += len;
         }
         if (m == 0) {
-            const u64 h = rd_hdr_line(X, c, q), hs = rd_line_start(X, h) + 1, he = rd_line_end(X, c, h);
+            const u64 h = rd_hdr_line(X, c, r), hs = rd_line_start(X, h) + 1, he = rd_line_end(X, c, h);
             u64 end = he;
             for (u64 p = hs; p < he; p += 64) {
                 const unsigned long long sp = __ballot(p + lane < he && X.t[p + lane] == ' ');
@@ -871,9 +897,11 @@ extern "C" int mcq_reads_prepare(const char* text1, uint64_t len1, const char* t
     if (max_queries < 1) return fail(MCQ_E_ARG, "max_queries must be >= 1");
     if (len1 >= 0xFFFFFFFFull || len2 >= 0xFFFFFFFFull) return fail(MCQ_E_UNSUPPORTED, "a chunk of read text is below 4 GiB");
     if (scratch_bytes < mcq_reads_scratch_bytes(len1, len2, max_queries)) return fail(MCQ_E_ARG, "scratch smaller than mcq_reads_scratch_bytes");
+    const bool inter = (flags & MCQ_READS_INTERLEAVED) != 0;
+    if (inter && (text2 || len2)) return fail(MCQ_E_ARG, "MCQ_READS_INTERLEAVED is given with text2 == NULL");
     hipStream_t st = (hipStream_t)stream;
     RdPair P; memset(&P, 0, sizeof(P));
-    P.mates = text2 ? 2 : 1; P.info = info;
+    P.mates = text2 ? 2 : 1; P.inter = inter ? 1 : 0; P.info = info;
     char* s = (char*)scratch;
     auto take = [&](u64 bytes) { char* p = s; s += rd_align(bytes); return p; };
     const char* tx[2] = {text1, text2};
@@ -899,7 +927,7 @@ extern "C" int mcq_reads_prepare(const char* text1, uint64_t len1, const char* t
     const u64 rmax = std::max(P.x[0].rcap, P.mates == 2 ? P.x[1].rcap : 0);
     hipLaunchKernelGGL(k_rd_recs, dim3((u32)std::min<u64>((rmax + 255) / 256, 1024), P.mates), dim3(256), 0, st, P);
     hipLaunchKernelGGL(k_rd_offsets, dim3(1), dim3(1024), 0, st, P, max_queries, max_bases, seq_off);
-    hipLaunchKernelGGL(k_rd_copy, dim3((u32)std::min<u64>((qcap + 3) / 4, 2048), P.mates), dim3(256), 0, st, P, (const u64*)seq_off, bases, hdr);
+    hipLaunchKernelGGL(k_rd_copy, dim3((u32)std::min<u64>((qcap + 3) / 4, 2048), inter ? 2 : P.mates), dim3(256), 0, st, P, seq_off, bases, hdr);
     HIPCHK(hipGetLastError());
     return MCQ_OK;
 }

@@ -731,6 +731,7 @@ def fasta_index(text_ptr, n_bytes, ranges_ptr, max_seqs, n_seqs_ptr, stream=None
 
 
 MCQ_READS_EOF1, MCQ_READS_EOF2, MCQ_READS_NOT_STRICT = 1, 2, 1
+MCQ_READS_INTERLEAVED = 4
 MCQ_READS_INFO_WORDS = 8
 
 

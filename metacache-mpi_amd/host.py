@@ -231,7 +231,7 @@ def rank_from_name(name):
 
 
 # ---- read files in chunks (mcq_read_stream_*, mcq_reads_parse): what mcq_query_cli's input stage does, for the tests
-READS_EOF1, READS_EOF2 = 1, 2
+READS_EOF1, READS_EOF2, READS_INTERLEAVED = 1, 2, 4
 READS_N, READS_BASES, READS_CUT1, READS_CUT2, READS_STATUS, READS_COMPLETE1, READS_COMPLETE2, READS_INFO_WORDS = 0, 1, 2, 3, 4, 5, 6, 8
 READS_NOT_STRICT = 1
 
@@ -283,11 +283,12 @@ class ReadStream:
             pass
 
 
-def read_batches(paths, chunk, max_queries=1 << 40, max_bases=1 << 62, prepare=None):
+def read_batches(paths, chunk, max_queries=1 << 40, max_bases=1 << 62, prepare=None, interleaved=False):
     """The input stage of mcq_query_cli on 1 or 2 files: fill a chunk per file (three buffer sets in rotation, so the carry
     moves from one buffer to another), prepare it (default: parse_chunk; the GPU tests pass the device step), consume what
     it used; a file with no complete record in a full chunk gets a buffer twice as large, for that chunk only.  Yields
-    (texts, info, bases, seq_off, hdr, caps) per batch; caps = the buffer sizes used."""
+    (texts, info, bases, seq_off, hdr, caps) per batch; caps = the buffer sizes used.  interleaved: one file whose records
+    2q, 2q+1 are the mates of query q (READS_INTERLEAVED is passed on to prepare)."""
     prepare = prepare or parse_chunk
     streams = [ReadStream(p) for p in paths]
     sets = [[C.create_string_buffer(max(1, chunk)) for _ in paths] for _ in range(3)]
@@ -297,7 +298,7 @@ def read_batches(paths, chunk, max_queries=1 << 40, max_bases=1 << 62, prepare=N
     try:
         while True:
             bufs = sets[j % 3]
-            texts, flags = [], 0
+            texts, flags = [], (READS_INTERLEAVED if interleaved else 0)
             for m, s in enumerate(streams):
                 old = bufs[m]                                       # (may hold the carry: alive until the fill has moved it)
                 need = max(want[m], carry[m])

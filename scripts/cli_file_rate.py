@@ -10,6 +10,11 @@ child), and whether its -out file equals the first run of the other tree once "#
 
 The parent: --parent-cli PATH (a prebuilt mcq_query_cli with its libraries beside it), or --parent REV: a git worktree of
 REV is built here.  Writes profiles/cli_file_rate.json, or the file --out names.
+
+--interleaved: the same reads also as ONE interleaved file (il.fq: records 2q, 2q+1 are the mates of pair q) through this
+tree's `-pairseq`, a third run in every round; its mapping lines (the lines that are no comments) are compared with the
+parent's.  --kernel-stats: one more run of each form of this tree under `rocprofv3 --kernel-trace --stats`; the share of
+the reader kernels (k_rd_*) in the kernel time goes into the result.
 """
 import argparse
 import hashlib
@@ -99,10 +104,53 @@ RSS_HELPER = ("import json, os, subprocess, sys\n"
               "print(json.dumps([os.waitstatus_to_exitcode(status), ru.ru_maxrss * 1024]))\n")
 
 
-def run(cli, a, out, timeout_s):
-    cmd = ["timeout", "-k", "10", str(timeout_s), cli, os.path.join(a.workdir, "db"), str(a.ranks), os.path.join(a.workdir, "r1.fq"),
-           os.path.join(a.workdir, "r2.fq"), "-lowest", "species", "-maxcand", "2", "-hitmin", "4", "-hitdiff", "80", "-tophits",
-           "-taxids-only", "-omit-ranks", "-threads", "16", "-out", out]
+def write_interleaved(a):
+    """il.fq from r1.fq / r2.fq (records of one fixed size)"""
+    rec = 11 + a.read_len + 3 + a.read_len + 1
+    with open(os.path.join(a.workdir, "r1.fq"), "rb") as f1, open(os.path.join(a.workdir, "r2.fq"), "rb") as f2, \
+            open(os.path.join(a.workdir, "il.fq"), "wb") as fo:
+        while True:
+            b1, b2 = f1.read(rec << 16), f2.read(rec << 16)
+            if not b1:
+                break
+            m = len(b1) // rec
+            both = np.empty((m, 2, rec), np.uint8)
+            both[:, 0, :] = np.frombuffer(b1, np.uint8).reshape(m, rec)
+            both[:, 1, :] = np.frombuffer(b2, np.uint8).reshape(m, rec)
+            fo.write(both.tobytes())
+
+
+def inputs(a, interleaved):
+    if interleaved:
+        return [os.path.join(a.workdir, "il.fq"), "-pairseq"]
+    return [os.path.join(a.workdir, "r1.fq"), os.path.join(a.workdir, "r2.fq")]
+
+
+def command(cli, a, out, interleaved=False):
+    return [cli, os.path.join(a.workdir, "db"), str(a.ranks)] + inputs(a, interleaved) + ["-lowest", "species", "-maxcand", "2", "-hitmin", "4",
+            "-hitdiff", "80", "-tophits", "-taxids-only", "-omit-ranks", "-threads", "16", "-out", out]
+
+
+def kernel_stats(cli, a, interleaved, timeout_s):
+    """one run under rocprofv3 --kernel-trace --stats -> (reader kernels' ns, all kernels' ns)"""
+    import csv
+    import glob
+    d = os.path.join(a.workdir, "prof_il" if interleaved else "prof_files")
+    subprocess.check_call(["timeout", "-k", "10", str(timeout_s), "rocprofv3", "--kernel-trace", "--stats", "-d", d, "-o", "run", "--output-format", "csv",
+                           "--"] + command(cli, a, os.path.join(a.workdir, "prof.out"), interleaved), stdout=subprocess.DEVNULL, stderr=subprocess.DEVNULL)
+    rd = total = 0
+    for path in glob.glob(os.path.join(d, "**", "*kernel_stats.csv"), recursive=True):
+        with open(path) as f:
+            for row in csv.DictReader(f):
+                ns = int(float(row["TotalDurationNs"]))
+                total += ns
+                if "k_rd_" in row["Name"]:
+                    rd += ns
+    return rd, total
+
+
+def run(cli, a, out, timeout_s, interleaved=False):
+    cmd = ["timeout", "-k", "10", str(timeout_s)] + command(cli, a, out, interleaved)
     r = subprocess.run([sys.executable, "-c", RSS_HELPER, out + ".err"] + cmd, stdout=subprocess.PIPE, text=True)
     rc, rss = json.loads(r.stdout)
     if rc != 0:
@@ -110,6 +158,8 @@ def run(cli, a, out, timeout_s):
     text = open(out).read()
     ms = int(re.search(r"^# time:    (\d+) ms$", text, flags=re.M).group(1))
     masked = re.sub(r"^# (time|speed): .*$", "# masked", text, flags=re.M)
+    if interleaved:                                               # (its parameter lines and file line differ: the mapping lines)
+        masked = "".join(l + "\n" for l in text.split("\n") if l and not l.startswith("#"))
     return ms, rss, hashlib.sha256(masked.encode()).hexdigest()
 
 
@@ -132,6 +182,8 @@ def main():
     ap.add_argument("--parent", default="HEAD~1", help="git revision of the parent commit (built in a worktree)")
     ap.add_argument("--parent-cli", default="", help="a prebuilt mcq_query_cli of the parent instead")
     ap.add_argument("--timeout", type=int, default=300)
+    ap.add_argument("--interleaved", action="store_true", help="also run this tree on one interleaved file (-pairseq)")
+    ap.add_argument("--kernel-stats", action="store_true", help="the reader kernels' share, from one rocprofv3 run of each form")
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "cli_file_rate.json"))
     a = ap.parse_args()
 
@@ -153,13 +205,24 @@ def main():
             while fh.read(1 << 26):
                 pass
     trees = {"this": pkg.cli_path(), "parent": parent}
+    if a.interleaved:
+        if not os.path.exists(os.path.join(a.workdir, "il.fq")):
+            write_interleaved(a)
+        with open(os.path.join(a.workdir, "il.fq"), "rb") as fh:
+            while fh.read(1 << 26):
+                pass
+        trees["this_interleaved"] = pkg.cli_path()
     runs = {k: {"ms": [], "rss": [], "digest": []} for k in trees}
     for i in range(a.runs):
         for k, cli in trees.items():
-            ms, rss, dg = run(cli, a, os.path.join(a.workdir, "%s_%d.out" % (k, i)), a.timeout)
+            ms, rss, dg = run(cli, a, os.path.join(a.workdir, "%s_%d.out" % (k, i)), a.timeout, k == "this_interleaved")
             runs[k]["ms"].append(ms); runs[k]["rss"].append(rss); runs[k]["digest"].append(dg)
             print("%-6s run %d: %d ms, peak RSS %.0f MB" % (k, i, ms, rss / 1e6), flush=True)
     ref = runs["parent"]["digest"][0]
+    if a.interleaved:
+        with open(os.path.join(a.workdir, "parent_0.out")) as f:
+            ref_lines = hashlib.sha256("".join(l + "\n" for l in f.read().split("\n") if l and not l.startswith("#")).encode()).hexdigest()
+        res["interleaved_mapping_lines_identical_to_parent"] = [d == ref_lines for d in runs["this_interleaved"]["digest"]]
     for k in trees:
         r = runs[k]
         res[k] = {"time_ms": summary(r["ms"]), "peak_rss_mb": summary([round(x / 1e6, 1) for x in r["rss"]]),
@@ -170,7 +233,12 @@ def main():
     tr, pr = res["this"]["peak_rss_mb"], res["parent"]["peak_rss_mb"]         # the same rule turned round: a change meant to cost nothing
     res["slower_beyond_spread"] = t["median"] - pa["median"] > max(t["spread"], pa["spread"])
     res["more_rss_beyond_spread"] = tr["median"] - pr["median"] > max(tr["spread"], pr["spread"])
-    res["identical_out_files"] = all(all(res[k]["out_identical_to_parent_first_run"]) for k in trees)
+    res["identical_out_files"] = all(all(res[k]["out_identical_to_parent_first_run"]) for k in ("this", "parent"))
+    if a.kernel_stats:
+        for k in trees:
+            if k != "parent":
+                rd, total = kernel_stats(trees[k], a, k == "this_interleaved", a.timeout)
+                res.setdefault("reader_kernels", {})[k] = {"k_rd_ns": rd, "all_kernels_ns": total, "share": round(rd / max(1, total), 4)}
     text = json.dumps(res, indent=1)
     print(text)
     with open(a.out, "w") as f:
