@@ -144,7 +144,7 @@ struct OptDev {
     u32 big;                 // pow2ceil(P) x M > 64: the P lists do not fit one wave's lanes -- every query takes the
                              // workgroup kernel, which keeps them in LDS (MCQ_BIGLIST_MAX entries)
     u32 quirk_seq_drop;
-    u32 hooks;               // 8 = no two-class tail; staged reduce kernel: 1 = no de-duplicating pass, 2 = no second wave stage, 4 = workgroup kernel only
+    u32 hooks;               // MCQ_HOOK_*: the test hooks of mcq_query_opts.flags as the kernels read them
     u64 insert_size_max;
     u32 n_fold;              // fold schedule: (snd -> rcv) in the reference's order
     u32 n_levels;            // rounds of the tree; the edges of one round touch disjoint ranks
@@ -157,6 +157,21 @@ struct OptDev {
                              // that has sequence-level taxa
     u32 keep;                // lin: the ranks the tree routes to rank 0 = [0, keep), keep = 2^floor(log2 P)
 };
+// OptDev::hooks: the one word in which "run this path, not that one" reaches a kernel (make_opt: the flags; plan_launch: per stage)
+enum : u32 {
+    MCQ_HOOK_BLOCK_ONLY   = 1u,       // every query takes the workgroup kernel (MCQ_FORCE_BLOCK_PATH; lists beyond a wave's registers)
+    MCQ_HOOK_RAW_SORT     = 2u,       // the raw match list is sorted, no de-duplicating pass (MCQ_FORCE_RAW_SORT)
+    MCQ_HOOK_NO_WAVE16    = 4u,       // no second wave stage: its queries take the workgroup kernel (MCQ_NO_WAVE16; the NL > 1 first stage)
+    MCQ_HOOK_ROUTE        = MCQ_HOOK_BLOCK_ONLY | MCQ_HOOK_RAW_SORT | MCQ_HOOK_NO_WAVE16,     // those that change a query's route: no direct entry, no lean form
+    MCQ_HOOK_ONLY_LAUNCH  = 8u,       // k_query_wave: this is the first stage's only launch, whatever MCQ_MODE_LEAN says
+    MCQ_HOOK_NO_TWO_CLASS = 16u,      // no two-class tail (MCQ_NO_TWO_CLASS)
+    MCQ_HOOK_STOP_SHIFT   = 8u,       // profiling builds (-DMCQ_PROFILE_HOOKS): hooks >> this = stop k_query_wave after stage 1..5, 0 = run everything
+};
+// the lists for which the two-class tail is attempted: beyond P x M = 16 the light prefix rarely fills them (as one selection: P = 8;
+// ~40 / P of the light prefix are rank-0 words)
+__device__ __host__ __forceinline__ bool two_class_lists(const OptDev& opt) {
+    return (opt.lin ? opt.P <= 8u : opt.P * opt.max_cand <= 16u) && !(opt.hooks & MCQ_HOOK_NO_TWO_CLASS);
+}
 
 struct OutDev {
     u32* cands;              // nq * M * 4
@@ -189,17 +204,19 @@ struct CountersDev {         // one block of u64/u32 words, zeroed per call
                                       // a feature holds 0xFFFF
     // not zeroed per call either: how the NEXT batch on this workspace enters (k_next_mode, after the last kernel of a batch).
     // Direct entry: the next batch's first stage only looks at the geometry of its queries -- one LANE per query -- and queues all
-    // of them.  bit 1: most of this batch's queries had more than 128 features (long reads: the first stage did nothing for them
-    // but push one queue entry per wave).  bit 0: most of them left the first stage one way or the other (a table with long
-    // lists: RefSeq scale, 99 %) -- taken by the sharded home side only, whose first stage has no sketch to lose: on the fused
-    // path the second stage (4 waves per SIMD) sketches and probes no faster than the first (8), measured +-2 %.  Results are
-    // the same either way; only the path differs.
-    // bit 2 (MCQ_MODE_LEAN): the next batch's first stage runs in its lean form (k_query_wave<LEAN>): few of this batch's queries
+    // of them.  MCQ_MODE_DIRECT_GEOM: most of this batch's queries had more than 128 features (long reads: the first stage did
+    // nothing for them but push one queue entry per wave).  MCQ_MODE_DIRECT_QUEUED: most of them left the first stage one way or
+    // the other (a table with long lists: RefSeq scale, 99 %) -- taken by the sharded home side only, whose first stage has no
+    // sketch to lose: on the fused path the second stage (4 waves per SIMD) sketches and probes no faster than the first (8),
+    // measured +-2 %.  Results are the same either way; only the path differs.
+    // MCQ_MODE_LEAN: the next batch's first stage runs in its lean form (k_query_wave<LEAN>): few of this batch's queries
     // were, or would have been, handed on by it.
     u32 direct_mode;
 };
 static_assert(offsetof(CountersDev, probe_buf) == 256, "probe_buf sits 256 bytes into the block");
 #define MCQ_CTR_ZEROED offsetof(CountersDev, probe_buf)
+#define MCQ_MODE_DIRECT_QUEUED 1u
+#define MCQ_MODE_DIRECT_GEOM 2u
 #define MCQ_MODE_LEAN 4u
 
 // ---- feature-sharded path: what a home rank's reduce kernels read instead of sketching and probing ------------

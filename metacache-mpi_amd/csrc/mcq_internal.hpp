@@ -114,13 +114,16 @@ template <class F> static auto with_layout(const mcq_db* db, F&& f) {
     return db->d.bsh != 0 ? f(IntC<2>{}) : f(IntC<0>{});
 }
 
+// which form of the first wave stage a caller asked for (MCQ_FORCE_FULL_WAVE / MCQ_FORCE_LEAN_WAVE; make_opt rejects both at once)
+enum class LeanReq { Auto, FullOnly, LeanOnly };
+static inline LeanReq lean_request(u32 flags) { return (flags & MCQ_FORCE_LEAN_WAVE) ? LeanReq::LeanOnly : (flags & MCQ_FORCE_FULL_WAVE) ? LeanReq::FullOnly : LeanReq::Auto; }
+
 // ------------------------------------------------------------------ defined in one unit, called from others
 namespace mcq {
 // mcq_engine.hip
-__attribute__((visibility("hidden"))) int force_bits(u32 flags);
 __attribute__((visibility("hidden"))) int make_opt(const mcq_query_opts* o, OptDev& d, const mcq_db* db);
 __attribute__((visibility("hidden"))) int launch_query(const mcq_db* db, mcq_ws* ws, const BatchDev& b, const OptDev& od_in, const OutDev& o,
-                                                       hipStream_t st, int force_block_in, const DebugDev& dbg, const ShardDev* shp = nullptr, const DbDev* dbd = nullptr);
+                                                       hipStream_t st, LeanReq lean_req, const DebugDev& dbg, const ShardDev* shp = nullptr, const DbDev* dbd = nullptr);
 // mcq_stages.hip (instantiated for InT = u32 and u64)
 __attribute__((visibility("hidden"))) int batch_dev(const mcq_batch* in, const char* d_bases, const u64* d_seq_off, BatchDev& b);
 template <class InT>
