@@ -551,6 +551,36 @@ int mcq_ws_set_classify(mcq_ws* ws, const mcq_taxonomy* tx, const mcq_classify_o
  * to host_out; reset != 0 zeroes them afterwards                                                                      */
 int mcq_ws_taxon_counts(mcq_ws* ws, uint64_t* host_out, int reset);
 
+/* ---- clade exclusion: the reference's `-exclude RANK` (prepare_evaluation / remove_hits_on_rank, src/classification.cpp:141-183) ----
+ * For a read with a ground truth the reference drops, before the candidates are made, every match on a target whose ancestor
+ * at RANK equals the ancestor at RANK of the read's truth.  Either ancestor may be missing, and missing equals missing: a truth
+ * above RANK removes the targets that have no ancestor at RANK.  A match goes because of its target alone, so the engine takes
+ * the two ancestors as opaque 32-bit keys (mcq_refdb_clade_keys / mcq_refdb_taxon_clade of include/mcq_host.h make them):
+ *   tgt_clade[t]    key of target t's ancestor at RANK, MCQ_CLADE_NONE if it has none
+ *   query_clade[q]  key of the truth's ancestor at RANK, MCQ_CLADE_NONE if it has none, MCQ_CLADE_KEEP_ALL for a read without
+ *                   a ground truth: nothing is excluded for it
+ * and retires the excluded targets' candidates before the top lists are built: the same lists as from the match list without
+ * those targets' locations (tests/test_gpu_exclusion.py).
+ * mcq_ws_set_exclusion attaches the table (copied; host pointer, or device with MCQ_DEVICE_PTRS) to a workspace, NULL detaches;
+ * it waits for the device.  While a table is attached, every mcq_query / mcq_query_pipelined on the workspace needs the keys
+ * of its batch: mcq_ws_set_query_clades hands them over for the NEXT such call, which consumes them (none handed over, or
+ * another count than the batch's queries: MCQ_E_ARG).  A host array is copied by the call; a device array (MCQ_DEVICE_PTRS) is
+ * read by that batch's kernels and stays untouched until they are done.  Two pipelined batches in flight each keep their own.
+ * Queries under exclusion take the full first wave stage, the second one and the plain workgroup kernel (never the lean stage:
+ * MCQ_FORCE_LEAN_WAVE gives MCQ_E_UNSUPPORTED; never the two-class tail, which proves its cut from targets it would then lose).
+ * A workspace without a table behaves as ever.  mcq_reduce and mcq_shard_query do not look at it.
+ * Not checked: a table given as a device array is not searched for MCQ_CLADE_KEEP_ALL (a host table holding it is MCQ_E_ARG); a
+ * target that carried it would be dropped for every read without a truth, so the caller keeps it out.
+ * The keys are consumed when the query call takes them, before its kernels are planned: a call that then fails (MCQ_E_UNSUPPORTED
+ * of MCQ_FORCE_LEAN_WAVE, a HIP error) has used them up, and the keys are handed over again for the next attempt.  In
+ * mcq_query_pipelined such a failure comes after the batch's input copies are queued; they are harmless, the staging set is
+ * written again by the next call.  MCQ_QUIRK_SEQ_DROP works as ever: it acts where the emulated ranks' lists are merged, after
+ * the excluded targets are gone (tests/test_gpu_exclusion_device.py).                                                      */
+static const uint32_t MCQ_CLADE_NONE = 0xFFFFFFFFu;       /* no ancestor at RANK (a target's, or a truth's)      */
+static const uint32_t MCQ_CLADE_KEEP_ALL = 0xFFFFFFFEu;   /* query_clade only: no ground truth, exclude nothing */
+int mcq_ws_set_exclusion(mcq_ws* ws, const uint32_t* tgt_clade, uint32_t n_targets, uint32_t flags);
+int mcq_ws_set_query_clades(mcq_ws* ws, const uint32_t* query_clade, uint64_t n_queries, uint32_t flags);
+
 /* ---- debug / parity taps ------------------------------------------------------------
  * Row 5 in isolation is mcq_count_windows + mcq_sketch above (the sketches of every window).
  * Rows 7-8 in isolation: the sorted match list of every query (what merge_sort returns,

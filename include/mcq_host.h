@@ -116,6 +116,58 @@ uint64_t mcq_refdb_taxon_windows(const mcq_refdb* db, uint32_t key);
 /* taxon index at `rank` in the ranked lineage of `key`, MCQ_NO_TAXON if none */
 uint32_t mcq_refdb_ancestor(const mcq_refdb* db, uint32_t key, uint32_t rank);
 
+/* ---- ground truth and clade exclusion (`-ground-truth`, `-precision`, `-exclude RANK` of the reference's query mode) ----
+ * mcq_refdb_ground_truth: the taxon a read's header names, as ground_truth (src/classification.cpp:111-131) resolves it -- the
+ * first that succeeds of 1. the sequence-level taxon named by the header's accession.version (extract_ncbi_accession_version_number,
+ * src/sequence_io.cpp:600-642), 2. the first one whose name goes on from the header's accession without version
+ * (taxon_with_similar_name, src/sketch_database.h:631-639; the two-letter prefixes of src/sequence_io.cpp:43-58), 3. the taxon
+ * with the id behind "taxid" + one separator character (:724-748), 4. the sequence-level taxon named by the whole header --
+ * and then its next ranked ancestor (src/sketch_database.h:724-737: of a sequence-level taxon the first ranked taxon above
+ * it).  Returns the taxon index or MCQ_NO_TAXON.  Resolved against the WHOLE database: the handle holds every target's taxon
+ * (each rank of the reference's MPI program asks its own shard).
+ * mcq_refdb_clade_keys: per target the key of its ancestor at `rank` -- db.ancestor(hit.tax, rank) of remove_hits_on_rank
+ * (src/classification.cpp:141-157) -- or MCQ_CLADE_NONE of include/mcq.h (= MCQ_NO_TAXON) where it has none: what
+ * mcq_ws_set_exclusion takes.  mcq_refdb_taxon_clade: the same for a read's truth: its ancestor at `rank`, MCQ_CLADE_NONE if
+ * it has none (the truth sits above `rank`), MCQ_CLADE_KEEP_ALL (0xFFFFFFFE) for truth == MCQ_NO_TAXON: one entry of
+ * mcq_ws_set_query_clades.                                                                                          */
+uint32_t mcq_refdb_ground_truth(const mcq_refdb* db, const char* header, uint64_t len);
+int mcq_refdb_clade_keys(const mcq_refdb* db, uint32_t rank, uint32_t* out /* [n_targets] */);
+uint32_t mcq_refdb_taxon_clade(const mcq_refdb* db, uint32_t truth, uint32_t rank);
+
+/* ---- evaluation statistics (`-precision`): classification_statistics (src/classification_statistics.h:40-235) restated
+ * type for type.  The four arrays are indexed by rank, [MCQ_RANK_NONE] counting the queries without: assigned[r] = queries
+ * classified at rank r or below it, known[r] = queries whose truth is known at r or below, correct[r] = of those the ones whose
+ * classification is right from r up, wrong[r] = known wrong assignments at r.
+ * mcq_eval_stats_assign is assign (:70-78); mcq_eval_stats_assign_known_correct is assign_known_correct (:91-120) with the rank
+ * of the classification, of the truth, and of their ranked LCA (mcq_refdb_ranked_lca; MCQ_RANK_NONE where there is none):
+ * evaluate_classification (src/classification.cpp:329-353).  The accessors with a rank are known(r), correct(r), wrong(r),
+ * assigned(r); the reference's forms without one are the value at MCQ_RANK_ROOT, unknown() / unassigned() the value at
+ * MCQ_RANK_NONE, total() = assigned(root) + unassigned().  The rates and precision(r) = correct / (correct + wrong),
+ * sensitivity(r) = correct / known are doubles, 0 over an empty denominator (:201-224).
+ * mcq_eval_stats_text: show_taxon_statistics (src/printing.cpp:522-600) in ostream default formatting, every line behind
+ * `prefix`: the "unclassified" / "classified" block, and once a truth is known the "ground truth ..." blocks.  The coverage
+ * block (:601-611, -taxon-coverage) is not reproduced.  Text to buf as mcq_refdb_abundance_text does; returns its length. */
+typedef struct { uint64_t assigned[22], known[22], correct[22], wrong[22]; } mcq_eval_stats;
+void mcq_eval_stats_assign(mcq_eval_stats* s, uint32_t assigned);
+void mcq_eval_stats_assign_known_correct(mcq_eval_stats* s, uint32_t assigned, uint32_t known, uint32_t correct);
+void mcq_eval_stats_add(mcq_eval_stats* into, const mcq_eval_stats* from);
+uint64_t mcq_eval_stats_total(const mcq_eval_stats* s);
+uint64_t mcq_eval_stats_assigned(const mcq_eval_stats* s, uint32_t rank);
+uint64_t mcq_eval_stats_known(const mcq_eval_stats* s, uint32_t rank);
+uint64_t mcq_eval_stats_unknown(const mcq_eval_stats* s);
+uint64_t mcq_eval_stats_correct(const mcq_eval_stats* s, uint32_t rank);
+uint64_t mcq_eval_stats_wrong(const mcq_eval_stats* s, uint32_t rank);
+double mcq_eval_stats_known_rate(const mcq_eval_stats* s, uint32_t rank);
+double mcq_eval_stats_unknown_rate(const mcq_eval_stats* s);
+double mcq_eval_stats_classification_rate(const mcq_eval_stats* s, uint32_t rank);
+double mcq_eval_stats_unclassified_rate(const mcq_eval_stats* s);
+double mcq_eval_stats_precision(const mcq_eval_stats* s, uint32_t rank);
+double mcq_eval_stats_sensitivity(const mcq_eval_stats* s, uint32_t rank);
+int64_t mcq_eval_stats_text(const mcq_eval_stats* s, const char* prefix, char* buf, size_t cap);
+/* ranked_lca (src/taxonomy.h:531-537): the first rank at which both ranked lineages hold the same taxon; MCQ_NO_TAXON if
+ * either key is MCQ_NO_TAXON (src/sketch_database.h:751-753) or they share none */
+uint32_t mcq_refdb_ranked_lca(const mcq_refdb* db, uint32_t a, uint32_t b);
+
 /* cands: n x {tax key, hits, (2 ignored words)} as mcq_query returns them.
  * hits_diff_fraction as the reference stores it (-hitdiff 80 -> 0.8f).
  * Returns the taxon index of the classification or MCQ_NO_TAXON.                      */

@@ -16,7 +16,13 @@
 //         after the mapping lines, into the -out file or the -abundances FILE (src/mode_query.cpp:59-117); the counts come
 //         from the device (mcq_classify), checked against the host classification's total
 //   * the summary                              show_summary             src/printing.cpp:622-641,
-//                                              show_taxon_statistics    src/printing.cpp:522-555
+//                                              show_taxon_statistics    src/printing.cpp:522-600 (mcq_eval_stats_text)
+//   * -exclude RANK / -ground-truth / -precision (mcq_query_cli only; get_evaluation_options, src/query_options.cpp:190-213):
+//         the read's truth from its whole header (mcq_refdb_ground_truth, against the whole database), the "Clade Exclusion on
+//         Rank" parameter line (src/printing.cpp:75-78, which ends without a newline), the truth_ column of the TABLE_LAYOUT and
+//         of every mapping line (src/classification.cpp:499-502, :611-614), assign_known_correct and the "ground truth" blocks of
+//         the summary.  The truth stays with the read up to its evaluation; the reference's MPI program loses it on rank 0
+//         (DESIGN.md section 16).  -taxon-coverage is rejected; mcq_query_mpi rejects all of them.
 // After sorting, the file equals the reference's byte for byte except for the measured values of the "# time:" and
 // "# speed:" lines (tests/test_gpu_cli.py).  Not reproduced: the reference prints nothing for a thread's chunk in which
 // no read was classified (src/querying.h:1091, :1129).
@@ -24,7 +30,7 @@
 // usage: mcq_query_cli <dbprefix> <n_ranks> <file|directory>... [-pairfiles | -pairseq] [-splitout PREFIX] [-lowest R] [-highest R]
 //            [-maxcand N] [-hitmin N] [-hitdiff X] [-insertsize N] [-threads N] [-tophits] [-taxids] [-taxids-only] [-omit-ranks]
 //            [-lineage] [-mapped-only] [-nomap] [-noquirks] [-abundances [FILE]] [-abundance-per R] [-out FILE] [-batch N]
-//            [-batch-bases N] [-read-chunk BYTES] [-reader gpu|host]
+//            [-batch-bases N] [-read-chunk BYTES] [-reader gpu|host] [-exclude RANK] [-ground-truth] [-precision] [-help]
 // (inputs: every argument up to the first option; a directory stands for the files in it (files_in_directory below).  -pairseq
 //  without -pairfiles comes first: every file is interleaved pairs, also the two of `r1 r2` and the one of `r1 -`.  Without it,
 //  `r1 r2` alone is one pair of files in the given order and `r1 -` one single-end file.  Otherwise -pairfiles sorts the names and pairs
@@ -79,6 +85,9 @@ struct Options {
     std::string abundance_file;          // ... its FILE (cleared when it names the -out file: src/query_options.cpp:355)
     uint32_t abundance_rank = MCQ_RANK_NONE;   // -abundance-per R: the estimate to rank R (< root)
     bool tax_counts() const { return abundances || abundance_rank != MCQ_RANK_NONE; }
+    uint32_t exclude_rank = MCQ_RANK_NONE;     // -exclude R (< root): drop the hits on the read's own clade at R
+    bool ground_truth = false, precision = false;   // -ground-truth: the truth_ column; -precision: the evaluation statistics
+    bool wants_truth() const { return ground_truth || precision || exclude_rank != MCQ_RANK_NONE; }   // prepare_evaluation, src/classification.cpp:172-177
     std::string transport = "rccl";      // mcq_query_mpi: rccl | mpi (blocks through the host and MPI_Alltoallv)
     uint64_t batch = 1u << 19, batch_bases = 256u << 20;   // mcq_query_mpi: queries / bases per rank and batch
     uint64_t read_chunk = 8u << 20;      // mcq_query_cli: bytes per file and chunk (-read-chunk)
@@ -142,7 +151,27 @@ static bool make_units(const std::vector<std::string>& named, bool pairfiles, bo
     return true;
 }
 
+// -help of mcq_query_cli and mcq_query_mpi
+static const char* const kQueryUsage =
+    "usage: mcq_query_cli <dbprefix> <n_ranks> <file|directory>... [-pairfiles | -pairseq] [-splitout PREFIX] [options]\n"
+    "       mcq_query_cli <dbprefix> <n_ranks> <r1> <r2|-> [options]\n"
+    "       mpiexec -n N mcq_query_mpi <dbprefix> <n_ranks> <file|directory>... [options] [-transport rccl|mpi]\n"
+    "classification:  -lowest R  -highest R  -maxcand N  -hitmin N  -hitdiff X  -insertsize N  -noquirks\n"
+    "output:          -out FILE  -splitout PREFIX  -tophits  -taxids  -taxids-only  -omit-ranks  -lineage  -mapped-only  -nomap\n"
+    "                 -abundances [FILE]  -abundance-per R  -list-inputs\n"
+    "running:         -threads N  -batch N  -batch-bases N  -read-chunk BYTES  -reader gpu|host\n"
+    "evaluation (mcq_query_cli only; mcq_query_mpi rejects these three and names mcq_query_cli):\n"
+    "  -exclude RANK    clade exclusion: a read whose header names its ground truth (accession, or taxid|N) loses every\n"
+    "                   database hit on the truth's clade at RANK before its candidates are made; a truth without an\n"
+    "                   ancestor at RANK loses the hits on targets that have none either\n"
+    "  -ground-truth    (-ground_truth, -groundtruth) a truth_ column in front of the classification\n"
+    "  -precision       known / correct / precision / sensitivity per rank in the summary\n"
+    "                   The truth is resolved against the whole database and kept up to the evaluation (the reference's\n"
+    "                   MPI program resolves it per shard and evaluates without it).\n"
+    "rejected:        -taxon-coverage (both programs): the coverage statistics are not reproduced\n";
+
 static bool parse_options(int argc, char** argv, Options& o) {
+    for (int a = 1; a < argc; ++a) if (std::string(argv[a]) == "-help" || std::string(argv[a]) == "--help" || std::string(argv[a]) == "-h") { std::fputs(kQueryUsage, stdout); return false; }
     std::vector<std::string> named;                      // argv[3 ..] up to the first option
     int i = 3;
     for (; i < argc && !(argv[i][0] == '-' && argv[i][1] != '\0'); ++i) named.push_back(argv[i]);
@@ -189,6 +218,14 @@ static bool parse_options(int argc, char** argv, Options& o) {
         else if (a == "-abundance-per" || a == "-abundances-per" || a == "-abundance_per" || a == "-abundances_per") {
             const uint32_t r = mcq_rank_from_name(next()); if (r < MCQ_RANK_ROOT) o.abundance_rank = r;
         }
+        else if (a == "-exclude") { const uint32_t r = mcq_rank_from_name(next()); if (r < MCQ_RANK_ROOT) o.exclude_rank = r; }   // src/query_options.cpp:205-210
+        else if (opt_named(a, {"-ground-truth", "-ground_truth", "-groundtruth"})) o.ground_truth = true;                       // :196-198
+        else if (a == "-precision") o.precision = true;                                                                         // :203
+        else if (a == "-taxon-coverage") {                                                                                      // :201
+            std::fprintf(stderr, "ABORT: -taxon-coverage is not supported: the coverage statistics (a scan over all taxa per read) are not reproduced; "
+                                 "-precision alone gives the other statistics\n");
+            return false;
+        }
     }
     if (o.split && o.outfile.empty()) o.outfile = split_prefix;              // src/query_options.cpp:346-351
     if (o.abundance_file == o.outfile) o.abundance_file.clear();
@@ -229,10 +266,11 @@ struct Out {
             if (r < rmax) os << ',';
         }
     }
-    void header_taxon(std::ostream& os) const {          // the TABLE_LAYOUT line's taxon column: one entry per rank shown
+    // the TABLE_LAYOUT line's taxon column: one entry per rank shown, every word behind `pre` (show_taxon_header, src/printing.cpp:240-300)
+    void header_taxon(std::ostream& os, const std::string& pre = "") const {
         const uint32_t rmax = p.lineage ? p.highest : p.lowest;
         for (uint32_t r = p.lowest; r <= rmax; ++r) {
-            entry(os, p.lowest == rmax ? "rank" : mcq_rank_name(r), "taxname", "taxid");
+            entry(os, (pre + (p.lowest == rmax ? "rank" : mcq_rank_name(r))).c_str(), pre + "taxname", pre + "taxid");
             if (r < rmax) os << ',';
         }
     }
@@ -253,6 +291,7 @@ static void write_head(std::ostream& os, const Out& o, uint32_t hitmin) {
     os << cm << "Classification will be constrained to ranks from '" << mcq_rank_name(p.lowest) << "' to '" << mcq_rank_name(p.highest) << "'.\n";
     os << cm << "Classification hit threshold is " << hitmin << " per query\n";
     os << cm << "At maximum " << p.maxcand << " classification candidates will be considered per query.\n";
+    if (p.exclude_rank != MCQ_RANK_NONE) os << cm << "Clade Exclusion on Rank: " << mcq_rank_name(p.exclude_rank);   // (no newline: src/printing.cpp:75-78)
     if (p.pairing == Options::FILES) os << cm << "File based paired-end mode:\n" << cm << "  Reads from two consecutive files will be interleaved.\n"
                                         << cm << "  Max insert size considered " << p.insertsize << ".\n";
     else if (p.pairing == Options::SEQUENCES) os << cm << "Per file paired-end mode:\n" << cm << "  Reads from two consecutive sequences in each file will be paired up.\n"
@@ -263,6 +302,7 @@ static void write_head(std::ostream& os, const Out& o, uint32_t hitmin) {
     os << cm << "Using " << p.threads << " threads\n";
     if (!p.nomap) {
         os << cm << "TABLE_LAYOUT: query_header" << o.col;
+        if (p.ground_truth) { o.header_taxon(os, "truth_"); os << o.col; }
         if (p.tophits) os << "top_hits" << o.col;
         o.header_taxon(os);
         os << '\n';
@@ -308,15 +348,20 @@ static std::vector<Options> output_runs(const Options& p) {
 
 // one query: classification (src/classification.cpp:235-265), statistics (classification_statistics::assign,
 // src/classification_statistics.h:69-78) and its mapping line (show_query_mapping, src/classification.cpp:583-632)
-// (token: the header up to its first ' ', what the line prints)
+// (token: the header up to its first ' ', what the line prints; truth: the read's ground truth or MCQ_NO_TAXON, for the truth_
+//  column and, with `ev`, evaluate_classification's assign_known_correct, src/classification.cpp:329-353)
 static void write_query(std::ostream& os, const Out& o, uint32_t hitmin, const char* token, size_t token_len,
-                        const mcq_cand* cands, uint32_t ncand, uint64_t* assigned /* [MCQ_RANK_NONE + 1] */) {
+                        const mcq_cand* cands, uint32_t ncand, uint64_t* assigned /* [MCQ_RANK_NONE + 1] */,
+                        uint32_t truth = MCQ_NO_TAXON, mcq_eval_stats* ev = nullptr) {
     mcq_refdb* rdb = o.db; const Options& p = o.p;
     const uint32_t best = mcq_refdb_classify(rdb, reinterpret_cast<const uint32_t*>(cands), ncand, hitmin, p.hitdiff, p.highest);
     if (best == MCQ_NO_TAXON) ++assigned[MCQ_RANK_NONE];
     else for (uint32_t r = mcq_refdb_taxon_rank(rdb, best); r <= MCQ_RANK_ROOT; ++r) ++assigned[r];
+    if (ev) mcq_eval_stats_assign_known_correct(ev, mcq_refdb_taxon_rank(rdb, best), mcq_refdb_taxon_rank(rdb, truth),
+                                                mcq_refdb_taxon_rank(rdb, mcq_refdb_ranked_lca(rdb, best, truth)));
     if (p.nomap || (p.mapped_only && best == MCQ_NO_TAXON)) return;
     os.write(token, (std::streamsize)token_len) << o.col;
+    if (p.ground_truth) { o.best(os, truth); os << o.col; }                  // show_taxon(os, db, opt, query.groundTruth), :611-614
     if (p.tophits) {                                                         // show_matches, src/printing.cpp:333-360
         for (uint32_t i = 0; i < ncand && cands[i].hits > 0; ++i) {
             const mcq_cand& c = cands[i];
@@ -340,7 +385,7 @@ static void write_query(std::ostream& os, const Out& o, uint32_t hitmin, const s
 }
 
 // show_summary (src/printing.cpp:622-641) + show_taxon_statistics (:522-555)
-static void write_summary(std::ostream& os, const Out& o, const uint64_t* assigned, double ms) {
+static void write_summary(std::ostream& os, const Out& o, const uint64_t* assigned, double ms, const mcq_eval_stats* ev = nullptr) {
     const Options& p = o.p; const char* cm = o.comment;
     const uint64_t total = assigned[MCQ_RANK_ROOT] + assigned[MCQ_RANK_NONE];
     const uint64_t num_queries = p.paired() ? 2 * total : total;             // paired reads count twice (:626-627)
@@ -348,20 +393,12 @@ static void write_summary(std::ostream& os, const Out& o, const uint64_t* assign
        << cm << "time:    " << (long long)ms << " ms\n"
        << cm << "speed:   " << num_queries / (ms / 60000.0) << " queries/min\n";
     if (total > 0) {
-        if (assigned[MCQ_RANK_ROOT] < 1) os << "None of the input sequences could be classified.\n";
-        else {
-            if (assigned[MCQ_RANK_NONE] > 0)
-                os << cm << "unclassified: " << (100 * (assigned[MCQ_RANK_NONE] / double(total))) << "% (" << assigned[MCQ_RANK_NONE] << ")\n";
-            os << cm << "classified:\n";
-            static const uint32_t ranks[] = {0 /*sequence*/, 3 /*subspecies*/, 4 /*species*/, 6 /*genus*/, 10 /*family*/, 12 /*order*/,
-                                             14 /*class*/, 16 /*phylum*/, 18 /*kingdom*/, 19 /*domain*/, 20 /*root*/};
-            for (uint32_t r : ranks) {
-                if (assigned[r] == 0) continue;
-                std::string rn = mcq_rank_name(r);
-                rn.resize(11, ' ');
-                os << cm << "  " << rn << (100 * (assigned[r] / double(total))) << "% (" << assigned[r] << ")\n";
-            }
-        }
+        mcq_eval_stats st; std::memset(&st, 0, sizeof(st));                  // without -precision: the assignments alone
+        if (ev) st = *ev; else std::copy(assigned, assigned + MCQ_RANK_NONE + 1, st.assigned);
+        std::string text((size_t)mcq_eval_stats_text(&st, cm, nullptr, 0) + 1, '\0');
+        mcq_eval_stats_text(&st, cm, &text[0], text.size());
+        text.pop_back();
+        os << text;
     } else std::cerr << cm << "No valid query sequences found.\n";
 }
 

@@ -7,6 +7,7 @@
 #include <cstdio>
 #include <cstring>
 #include <map>
+#include <sstream>
 #include <string>
 #include <unordered_map>
 #include <vector>
@@ -44,6 +45,7 @@ struct mcq_refdb {
     std::vector<Taxon> taxa;
     std::unordered_map<int64_t, uint32_t> by_id;
     std::vector<uint32_t> lineage;          // n_taxa x 21, taxon indices or MCQ_NO_TAXON
+    std::map<std::string, uint32_t> seq_names;   // name2tax_ (src/sketch_database.h:938-943): names of the sequence-level taxa, the first of a name stays
     std::vector<uint32_t> keys; std::vector<uint64_t> off, locs;
     // mcq_refdb_open_meta: no table in host memory; per shard file where its key records begin, how many there are
     std::string prefix;
@@ -103,6 +105,8 @@ void build_lineages(mcq_refdb* db) {
             cur = (t.parent != cur) ? t.parent : 0;
         }
     }
+    for (uint32_t i = 0; i < db->taxa.size(); ++i)
+        if (db->taxa[i].rank == MCQ_RANK_SEQUENCE) db->seq_names.insert({db->taxa[i].name, i});
 }
 }  // namespace
 
@@ -379,6 +383,157 @@ extern "C" uint64_t mcq_refdb_taxon_windows(const mcq_refdb* db, uint32_t key) {
 extern "C" uint32_t mcq_refdb_ancestor(const mcq_refdb* db, uint32_t key, uint32_t rank) {
     if (!valid_key(db, key) || rank >= (uint32_t)kNumRanks) return MCQ_NO_TAXON;
     return db->lineage[(size_t)(key & 0x7FFFFFFFu) * kNumRanks + rank];
+}
+
+// ---- ground truth of a read and clade keys: ground_truth (src/classification.cpp:111-131), next_ranked_ancestor
+// (src/sketch_database.h:724-737, src/taxonomy.h:550-566), remove_hits_on_rank's db.ancestor(., rank) (src/classification.cpp:141-157)
+namespace {
+uint32_t next_ranked_ancestor(const mcq_refdb* db, uint32_t i) {
+    const Taxon& t = db->taxa[i];
+    if (t.rank == MCQ_RANK_SEQUENCE) {                           // the first entry of its ranked lineage above the sequence level
+        for (int r = 1; r < kNumRanks; ++r) { const uint32_t a = db->lineage[(size_t)i * kNumRanks + r]; if (a != MCQ_NO_TAXON) return a; }
+        return MCQ_NO_TAXON;
+    }
+    if (t.rank != MCQ_RANK_NONE) return i;
+    int64_t id = t.id;
+    while (id != 0) {
+        auto it = db->by_id.find(id);
+        if (it == db->by_id.end()) return MCQ_NO_TAXON;
+        const Taxon& a = db->taxa[it->second];
+        if (a.rank != MCQ_RANK_NONE) return it->second;
+        if (a.parent == id) return MCQ_NO_TAXON;
+        id = a.parent;
+    }
+    return MCQ_NO_TAXON;
+}
+uint32_t taxon_with_name(const mcq_refdb* db, const std::string& name) {           // src/sketch_database.h:620-626
+    if (name.empty()) return MCQ_NO_TAXON;
+    auto i = db->seq_names.find(name);
+    return i == db->seq_names.end() ? MCQ_NO_TAXON : i->second;
+}
+uint32_t taxon_with_similar_name(const mcq_refdb* db, const std::string& name) {   // :631-639: the first name AFTER `name` that begins with it
+    if (name.empty()) return MCQ_NO_TAXON;
+    auto i = db->seq_names.upper_bound(name);
+    if (i == db->seq_names.end()) return MCQ_NO_TAXON;
+    if (0 != i->first.compare(0, name.size(), name)) return MCQ_NO_TAXON;
+    return i->second;
+}
+}  // namespace
+
+extern "C" uint32_t mcq_refdb_ground_truth(const mcq_refdb* db, const char* header, uint64_t len) {
+    if (!db || (len && !header)) return MCQ_NO_TAXON;
+    const std::string h(header ? header : "", (size_t)len);
+    uint32_t t = taxon_with_name(db, mcq_header_accession_version(h));              // src/classification.cpp:116
+    if (t == MCQ_NO_TAXON) t = taxon_with_similar_name(db, mcq_header_accession(h));   // :119
+    if (t == MCQ_NO_TAXON) {                                                         // :123 (taxon id 0 is "none")
+        const int64_t id = mcq_header_taxid(h);
+        if (id != 0) { auto it = db->by_id.find(id); if (it != db->by_id.end()) t = it->second; }
+    }
+    if (t == MCQ_NO_TAXON) t = taxon_with_name(db, h);                               // :127
+    return t == MCQ_NO_TAXON ? MCQ_NO_TAXON : next_ranked_ancestor(db, t);
+}
+
+extern "C" uint32_t mcq_refdb_taxon_clade(const mcq_refdb* db, uint32_t truth, uint32_t rank) {
+    if (!db || !valid_key(db, truth)) return 0xFFFFFFFEu;                            // no ground truth: MCQ_CLADE_KEEP_ALL
+    return mcq_refdb_ancestor(db, truth, rank);                                      // MCQ_NO_TAXON == MCQ_CLADE_NONE: no ancestor there
+}
+
+extern "C" int mcq_refdb_clade_keys(const mcq_refdb* db, uint32_t rank, uint32_t* out) {
+    if (!db || !out) return fail("bad argument");
+    if (rank >= (uint32_t)kNumRanks) return fail("clade keys need a rank from sequence to root");
+    for (uint32_t t = 0; t < db->info.n_targets; ++t) {
+        auto it = db->by_id.find(-(int64_t)t - 1);
+        if (it == db->by_id.end()) return fail("target " + std::to_string(t) + " has no sequence-level taxon");
+        out[t] = db->lineage[(size_t)it->second * kNumRanks + rank];
+    }
+    return 0;
+}
+
+extern "C" uint32_t mcq_refdb_ranked_lca(const mcq_refdb* db, uint32_t a, uint32_t b) {
+    if (!valid_key(db, a) || !valid_key(db, b)) return MCQ_NO_TAXON;
+    const uint32_t* la = &db->lineage[(size_t)(a & 0x7FFFFFFFu) * kNumRanks];
+    const uint32_t* lb = &db->lineage[(size_t)(b & 0x7FFFFFFFu) * kNumRanks];
+    for (int r = 0; r <= (int)MCQ_RANK_ROOT; ++r) if (la[r] != MCQ_NO_TAXON && la[r] == lb[r]) return la[r];
+    return MCQ_NO_TAXON;
+}
+
+// ---- evaluation statistics: classification_statistics (src/classification_statistics.h) and its summary (src/printing.cpp:522-600)
+extern "C" void mcq_eval_stats_assign(mcq_eval_stats* s, uint32_t assigned) {               // :70-78
+    if (assigned >= MCQ_RANK_NONE) ++s->assigned[MCQ_RANK_NONE];
+    else for (uint32_t r = assigned; r <= MCQ_RANK_ROOT; ++r) ++s->assigned[r];
+}
+extern "C" void mcq_eval_stats_assign_known_correct(mcq_eval_stats* s, uint32_t assigned, uint32_t known, uint32_t correct) {   // :91-120
+    assigned = std::min<uint32_t>(assigned, MCQ_RANK_NONE); known = std::min<uint32_t>(known, MCQ_RANK_NONE); correct = std::min<uint32_t>(correct, MCQ_RANK_NONE);
+    mcq_eval_stats_assign(s, assigned);
+    if (correct < assigned) correct = assigned;                  // plausibility check
+    if (correct < known) correct = known;
+    if (known == MCQ_RANK_NONE) { ++s->known[MCQ_RANK_NONE]; return; }
+    for (uint32_t r = known; r <= MCQ_RANK_ROOT; ++r) ++s->known[r];
+    if (correct == MCQ_RANK_NONE) ++s->correct[MCQ_RANK_NONE];
+    else for (uint32_t r = correct; r <= MCQ_RANK_ROOT; ++r) ++s->correct[r];
+    if (correct > known && correct > assigned)                   // all ranks below the correct one are wrong
+        for (uint32_t r = MCQ_RANK_SEQUENCE; r < correct; ++r) ++s->wrong[r];
+}
+extern "C" void mcq_eval_stats_add(mcq_eval_stats* into, const mcq_eval_stats* from) {
+    for (int r = 0; r <= (int)MCQ_RANK_NONE; ++r) {
+        into->assigned[r] += from->assigned[r]; into->known[r] += from->known[r]; into->correct[r] += from->correct[r]; into->wrong[r] += from->wrong[r];
+    }
+}
+static inline uint32_t stat_rank(uint32_t r) { return std::min<uint32_t>(r, MCQ_RANK_NONE); }
+extern "C" uint64_t mcq_eval_stats_assigned(const mcq_eval_stats* s, uint32_t r) { return s->assigned[stat_rank(r)]; }
+extern "C" uint64_t mcq_eval_stats_total(const mcq_eval_stats* s) { return s->assigned[MCQ_RANK_ROOT] + s->assigned[MCQ_RANK_NONE]; }
+extern "C" uint64_t mcq_eval_stats_known(const mcq_eval_stats* s, uint32_t r) { return s->known[stat_rank(r)]; }
+extern "C" uint64_t mcq_eval_stats_unknown(const mcq_eval_stats* s) { return s->known[MCQ_RANK_NONE]; }
+extern "C" uint64_t mcq_eval_stats_correct(const mcq_eval_stats* s, uint32_t r) { return s->correct[stat_rank(r)]; }
+extern "C" uint64_t mcq_eval_stats_wrong(const mcq_eval_stats* s, uint32_t r) { return s->wrong[stat_rank(r)]; }
+static inline double over_total(const mcq_eval_stats* s, uint64_t n) { const uint64_t t = mcq_eval_stats_total(s); return t > 0 ? n / double(t) : 0; }   // :201-215
+extern "C" double mcq_eval_stats_known_rate(const mcq_eval_stats* s, uint32_t r) { return over_total(s, mcq_eval_stats_known(s, r)); }
+extern "C" double mcq_eval_stats_unknown_rate(const mcq_eval_stats* s) { return over_total(s, mcq_eval_stats_unknown(s)); }
+extern "C" double mcq_eval_stats_classification_rate(const mcq_eval_stats* s, uint32_t r) { return over_total(s, mcq_eval_stats_assigned(s, r)); }
+extern "C" double mcq_eval_stats_unclassified_rate(const mcq_eval_stats* s) { return over_total(s, s->assigned[MCQ_RANK_NONE]); }
+extern "C" double mcq_eval_stats_sensitivity(const mcq_eval_stats* s, uint32_t r) {         // :217-219
+    const uint64_t k = mcq_eval_stats_known(s, r);
+    return k > 0 ? mcq_eval_stats_correct(s, r) / double(k) : 0;
+}
+extern "C" double mcq_eval_stats_precision(const mcq_eval_stats* s, uint32_t r) {           // :220-224
+    const double tot = mcq_eval_stats_correct(s, r) + mcq_eval_stats_wrong(s, r);
+    return tot > 0 ? mcq_eval_stats_correct(s, r) / tot : 0;
+}
+extern "C" int64_t mcq_eval_stats_text(const mcq_eval_stats* s, const char* prefix, char* buf, size_t cap) {   // src/printing.cpp:522-600
+    if (!s || !prefix || (cap && !buf)) return fail("bad argument");
+    static const uint32_t ranks[] = {0 /*sequence*/, 3 /*subspecies*/, 4 /*species*/, 6 /*genus*/, 10 /*family*/, 12 /*order*/,
+                                     14 /*class*/, 16 /*phylum*/, 18 /*kingdom*/, 19 /*domain*/, 20 /*root*/};
+    std::ostringstream os;
+    auto per_rank = [&](auto&& value) {                          // one line per rank that has assignments
+        for (uint32_t r : ranks) {
+            if (s->assigned[r] == 0) continue;
+            std::string rn = mcq_rank_name(r);
+            rn.resize(11, ' ');
+            os << prefix << "  " << rn; value(r); os << '\n';
+        }
+    };
+    if (s->assigned[MCQ_RANK_ROOT] < 1) os << "None of the input sequences could be classified.\n";
+    else {
+        if (s->assigned[MCQ_RANK_NONE] > 0)
+            os << prefix << "unclassified: " << (100 * mcq_eval_stats_unclassified_rate(s)) << "% (" << s->assigned[MCQ_RANK_NONE] << ")\n";
+        os << prefix << "classified:\n";
+        per_rank([&](uint32_t r) { os << (100 * mcq_eval_stats_classification_rate(s, r)) << "% (" << s->assigned[r] << ")"; });
+        if (s->known[MCQ_RANK_ROOT] > 0) {
+            if (s->known[MCQ_RANK_NONE] > 0)
+                os << prefix << "ground truth unknown: " << (100 * mcq_eval_stats_unknown_rate(s)) << "% (" << s->known[MCQ_RANK_NONE] << ")\n";
+            os << prefix << "ground truth known:\n";
+            per_rank([&](uint32_t r) { os << (100 * mcq_eval_stats_known_rate(s, r)) << "% (" << s->known[r] << ")"; });
+            os << prefix << "correctly classified:\n";
+            per_rank([&](uint32_t r) { os << s->correct[r]; });
+            os << prefix << "precision (correctly classified / classified) if ground truth known:\n";
+            per_rank([&](uint32_t r) { os << (100 * mcq_eval_stats_precision(s, r)) << "%"; });
+            os << prefix << "sensitivity (correctly classified / all) if ground truth known:\n";
+            per_rank([&](uint32_t r) { os << (100 * mcq_eval_stats_sensitivity(s, r)) << "%"; });
+        }
+    }
+    const std::string t = os.str();
+    if (cap) { const size_t n = std::min(cap - 1, t.size()); std::memcpy(buf, t.data(), n); buf[n] = 0; }
+    return (int64_t)t.size();
 }
 
 extern "C" uint32_t mcq_refdb_classify(const mcq_refdb* db, const uint32_t* c, uint32_t n,

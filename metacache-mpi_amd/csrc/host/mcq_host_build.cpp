@@ -237,6 +237,10 @@ int64_t header_taxid(const std::string& t) {
 }
 }  // namespace
 
+std::string mcq_header_accession_version(const std::string& header) { return accession_version(header); }
+std::string mcq_header_accession(const std::string& header) { return accession_plain(header); }
+int64_t mcq_header_taxid(const std::string& header) { return header_taxid(header); }
+
 extern "C" int64_t mcq_target_name(const char* header, uint64_t len, char* buf, size_t cap) {
     if ((len && !header) || (cap && !buf)) return fail("null argument");
     const std::string s = target_name(std::string(header ? header : "", (size_t)len));

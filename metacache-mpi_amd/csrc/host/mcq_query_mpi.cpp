@@ -23,6 +23,7 @@
 //
 // usage: mpiexec -n N mcq_query_mpi <dbprefix> <P> <file|directory>... [options of mcq_query_cli] [-transport rccl|mpi]
 //                                   [-batch N] [-batch-bases N]
+// -exclude, -ground-truth and -precision are rejected with a line that names mcq_query_cli: the sharded kernels have no exclusion.
 #include <mpi.h>
 #include <hip/hip_runtime_api.h>
 
@@ -111,6 +112,10 @@ int main(int argc, char** argv) {
     Options p;                                                              // the command line; `run` below: one output's part of it
     if (!parse_options(argc, argv, p)) { MPI_Finalize(); return 2; }
     if (p.list_inputs) { if (rank == 0) list_inputs(std::cout, p); MPI_Finalize(); return 0; }
+    if (p.wants_truth()) {                                                  // (before any GPU work)
+        if (rank == 0) std::fprintf(stderr, "ABORT: -exclude, -ground-truth and -precision are options of mcq_query_cli; mcq_query_mpi does not evaluate against a ground truth\n");
+        MPI_Finalize(); return 2;
+    }
     int n_dev = 0;
     HIP_OR_DIE(hipGetDeviceCount(&n_dev));
     if (n_dev < 1) { std::fprintf(stderr, "ABORT: no GPU\n"); MPI_Abort(MPI_COMM_WORLD, 1); }

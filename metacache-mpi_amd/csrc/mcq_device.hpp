@@ -64,6 +64,30 @@ struct GwDev {
     u32 on;
 };
 
+// ---- clade exclusion (mcq_ws_set_exclusion; the EXCL instantiations of the query kernels only) -------------------------------
+// The reference's -exclude RANK (remove_hits_on_rank, src/classification.cpp:141-157) drops every match on a target whose
+// ancestor at RANK is the query's own.  A match goes because of its target alone, and rows 8-9 sort and sweep inside one
+// target's run: dropping a target's locations from the list and retiring that target's run heads before row 10 leave the
+// same candidates in the same order.  So the gather, the sorts and the sweep stay as they are, and the top-list routines
+// read a head's taxon through head_tax(): with a DbExcl an excluded target has no taxon, which is what retires a head.
+// A kernel argument of its own behind GwDev, read by the EXCL instantiations only (see GwDev for why not inside DbDev).
+struct ExclDev {
+    const u32* tgt_clade;    // [n_targets] key of the target's ancestor at RANK, MCQ_CLADE_NONE = it has none
+    const u32* query_clade;  // [nq] key of the truth's ancestor at RANK (MCQ_CLADE_NONE: none -- null equals null, such targets go),
+                             // MCQ_CLADE_KEEP_ALL = no ground truth: nothing is excluded (no target carries that key)
+};
+struct DbExcl : DbDev { const u32* tgt_clade; u32 qkey; };      // what the top-list routines of ONE query get in place of DbDev
+__device__ __forceinline__ u32 head_tax(const DbDev& db, u32 tgt) { return db.tgt2tax[tgt]; }
+__device__ __forceinline__ u32 head_tax(const DbExcl& db, u32 tgt) {
+    const u32 tax = db.tgt2tax[tgt], clade = db.tgt_clade[tgt];
+    return clade == db.qkey ? MCQ_EMPTY : tax;
+}
+template <bool EXCL>
+__device__ __forceinline__ decltype(auto) heads_db(const DbDev& db, const ExclDev& ex, u64 q) {
+    if constexpr (EXCL) { DbExcl d; static_cast<DbDev&>(d) = db; d.tgt_clade = ex.tgt_clade; d.qkey = ex.query_clade[q]; return d; }
+    else return (db);
+}
+
 // ---- location formats -----------------------------------------------------------------------------------------------
 // Everything behind the gather works on location words that sort like (target, window) and needs of a word k only
 //   tbeg(k)  the smallest word of k's target (so: same target <=> prev >= tbeg(k) for prev <= k; window = k - tbeg(k))
@@ -1249,8 +1273,8 @@ __device__ __forceinline__ u64 wave_max(u64 v) {
     return v;
 }
 
-template <class KeyT, class HT, int JB, class LF>
-__device__ __forceinline__ u32 topk_fold_write(const DbDev& db, const OptDev& opt, const OutDev& out,
+template <class KeyT, class HT, int JB, class LF, class DB>
+__device__ __forceinline__ u32 topk_fold_write(const DB& db, const OptDev& opt, const OutDev& out,
                                                const KeyT* buf, HT* H, u32 T, u32 numWindows, const LF& lf,
                                                u64 q, u32 lane) {
     const u32 M = opt.max_cand, P = opt.P, seg = opt.seg;
@@ -1278,7 +1302,7 @@ __device__ __forceinline__ u32 topk_fold_write(const DbDev& db, const OptDev& op
         const u32 jb = (u32)(JMASK - (cv & JMASK));
         const u32 tgt = lf.tgt(buf[cv ? jb : 0]);
         u32 ctax = MCQ_EMPTY;
-        if (cv != 0 && tgt < db.n_targets) ctax = db.tgt2tax[tgt];
+        if (cv != 0 && tgt < db.n_targets) ctax = head_tax(db, tgt);
         if (ctax == MCQ_EMPTY) cv = 0;
         const u32 cr = (P > 1) ? (p2 ? (tgt & (P - 1)) : (tgt % P)) : 0;
         u32 Ntax = MCQ_EMPTY; HT Nhv = 0;
@@ -1353,8 +1377,8 @@ __device__ __forceinline__ u32 lin_rank(const OptDev& opt, u32 tgt) {
     return (P & (P - 1)) == 0 ? (tgt & (P - 1)) : (tgt % P);
 }
 // H[0..nheads): the compacted packed words (hits << JB | JMASK - j) of the run heads, j indexing buf; REGT as below
-template <class KeyT, int JB, bool REGT = false, class LF>
-__device__ __forceinline__ u32 topk_lin_write(const DbDev& db, const OptDev& opt, const OutDev& out, const KeyT* buf, const u32* H, u32 nheads,
+template <class KeyT, int JB, bool REGT = false, class LF, class DB>
+__device__ __forceinline__ u32 topk_lin_write(const DB& db, const OptDev& opt, const OutDev& out, const KeyT* buf, const u32* H, u32 nheads,
                                               const LF& lf, u64 q, u32 lane, u32 t1 = 0) {
     const u32 M = opt.max_cand;
     const u32 JMASK = (1u << JB) - 1;
@@ -1367,7 +1391,7 @@ __device__ __forceinline__ u32 topk_lin_write(const DbDev& db, const OptDev& opt
         if constexpr (REGT) tgt = __shfl(t1, (int)(cv ? jb : 0), 64);
         else tgt = lf.tgt(buf[cv ? jb : 0]);
         u32 ctax = MCQ_EMPTY;
-        if (cv != 0 && tgt < db.n_targets) ctax = db.tgt2tax[tgt];
+        if (cv != 0 && tgt < db.n_targets) ctax = head_tax(db, tgt);
         const u32 cr = lin_rank(opt, tgt);
         u32 ck = (ctax == MCQ_EMPTY || cr >= opt.keep) ? 0u : lin_word<u32, JB>(cv, cr);
         u32 lk = Lk, Ntax = MCQ_EMPTY, Nk = 0;
@@ -1403,8 +1427,8 @@ __device__ __forceinline__ unsigned long long wave_max_pair(unsigned long long v
 // final write of list 0: one round of the tree at a time -- its edges touch disjoint ranks, so every receiver
 // selects from receiver-list ++ sender-list in the same M rounds (positions decide ties).  One wave; mx, wt:
 // 64 words of LDS each.
-template <class KeyT, class HT, int JB, class LF>
-__device__ __forceinline__ u32 fold_lists_write(const DbDev& db, const OptDev& opt, const OutDev& out, const KeyT* buf,
+template <class KeyT, class HT, int JB, class LF, class DB>
+__device__ __forceinline__ u32 fold_lists_write(const DB& db, const OptDev& opt, const OutDev& out, const KeyT* buf,
                                                 u32 Ltax, HT Lhv, u32 numWindows, const LF& lf, u64 q, u32 lane, u32* mx, u32* wt) {
     const u32 M = opt.max_cand, P = opt.P, seg = opt.seg;
     const u32 rl = lane / seg, li = lane - rl * seg;
@@ -1464,8 +1488,8 @@ __device__ __forceinline__ u32 fold_lists_write(const DbDev& db, const OptDev& o
 // VALU instructions.  scr: 128 words of this wave's LDS segment (scr[0..64) maxima, scr[64..128) winner taxa).
 // REGT (T <= 64 only): the target of entry j sits in lane j's t1 (the caller looked it up once, for the sweep) and
 // comes by shuffle instead of a second lookup -- for formats whose target is a memory access away (LocGW)
-template <int JB = 9, bool REGT = false, class LF>
-__device__ __forceinline__ u32 topk_fold_write_lds(const DbDev& db, const OptDev& opt, const OutDev& out,
+template <int JB = 9, bool REGT = false, class LF, class DB>
+__device__ __forceinline__ u32 topk_fold_write_lds(const DB& db, const OptDev& opt, const OutDev& out,
                                                    const u32* buf, u32* H, u32 T, u32 numWindows, const LF& lf,
                                                    u64 q, u32 lane, u32* scr, u32 t1 = 0) {
     const u32 M = opt.max_cand, P = opt.P, seg = opt.seg;
@@ -1496,7 +1520,7 @@ __device__ __forceinline__ u32 topk_fold_write_lds(const DbDev& db, const OptDev
         if constexpr (REGT) tgt = __shfl(t1, (int)(cv ? jb : 0), 64);
         else tgt = lf.tgt(buf[cv ? jb : 0]);
         u32 ctax = MCQ_EMPTY;
-        if (cv != 0 && tgt < db.n_targets) ctax = db.tgt2tax[tgt];
+        if (cv != 0 && tgt < db.n_targets) ctax = head_tax(db, tgt);
         if (ctax == MCQ_EMPTY) cv = 0;
         const u32 cr = (P > 1) ? (p2 ? (tgt & (P - 1)) : (tgt % P)) : 0;
         u32 Ntax = MCQ_EMPTY, Nhv = 0;
@@ -1529,8 +1553,8 @@ __device__ __forceinline__ u32 topk_fold_write_lds(const DbDev& db, const OptDev
 // into the word of its rank, the winners publish their taxa, every candidate of a winning taxon retires.  The
 // closed form is the same (first M distinct taxa by hits descending, position ascending); the taxon keys of all
 // heads are loaded in one go.  scr: 128 words of LDS.
-template <int JB, int NC, class LF>
-__device__ __forceinline__ u32 topk_all_lds(const DbDev& db, const OptDev& opt, const OutDev& out, const u32* buf,
+template <int JB, int NC, class LF, class DB>
+__device__ __forceinline__ u32 topk_all_lds(const DB& db, const OptDev& opt, const OutDev& out, const u32* buf,
                                             const u32* H, u32 nheads, u32 numWindows, const LF& lf, u64 q, u32 lane, u32* scr) {
     static_assert(JB <= 10, "hits << JB stays below bit 26");
     const u32 M = opt.max_cand, P = opt.P, seg = opt.seg;
@@ -1545,7 +1569,7 @@ __device__ __forceinline__ u32 topk_all_lds(const DbDev& db, const OptDev& opt, 
         const u32 k = c * 64 + lane;
         const u32 v = (k < nheads) ? H[k] : 0;
         const u32 tgt = lf.tgt(buf[v ? JMASK - (v & JMASK) : 0]);
-        if (v != 0 && tgt < db.n_targets) ctax[c] = db.tgt2tax[tgt];
+        if (v != 0 && tgt < db.n_targets) ctax[c] = head_tax(db, tgt);
         const u32 cr = (P > 1) ? (p2 ? (tgt & (P - 1)) : (tgt % P)) : 0;
         cv[c] = v | (cr << 26);
         if (v == 0) cv[c] = 0;
@@ -1581,8 +1605,8 @@ template <int NL>
 struct ListSlots {
     u32 tax[NL]; u32 hv[NL];
 };
-template <class KeyT, int JB, int NL, class LF>
-__device__ __forceinline__ u32 fold_lists_write_n(const DbDev& db, const OptDev& opt, const OutDev& out, const KeyT* buf, ListSlots<NL>& L,
+template <class KeyT, int JB, int NL, class LF, class DB>
+__device__ __forceinline__ u32 fold_lists_write_n(const DB& db, const OptDev& opt, const OutDev& out, const KeyT* buf, ListSlots<NL>& L,
                                                   u32 numWindows, const LF& lf, u64 q, u32 lane, u32* mx, u32* wt) {
     const u32 M = opt.max_cand, P = opt.P, seg = opt.seg;
     u32 rl[NL], li[NL]; bool lslot[NL];
@@ -1645,8 +1669,8 @@ __device__ __forceinline__ u32 fold_lists_write_n(const DbDev& db, const OptDev&
     return n;
 }
 // all run heads at once (as topk_all_lds): H[0..nheads) compacted packed words, nheads <= 64 * NC
-template <int JB, int NC, int NL, class LF>
-__device__ __forceinline__ u32 topk_all_lds_n(const DbDev& db, const OptDev& opt, const OutDev& out, const u32* buf, const u32* H, u32 nheads,
+template <int JB, int NC, int NL, class LF, class DB>
+__device__ __forceinline__ u32 topk_all_lds_n(const DB& db, const OptDev& opt, const OutDev& out, const u32* buf, const u32* H, u32 nheads,
                                               u32 numWindows, const LF& lf, u64 q, u32 lane, u32* scr) {
     static_assert(JB <= 10, "hits << JB stays below bit 26");
     const u32 M = opt.max_cand, P = opt.P, seg = opt.seg;
@@ -1661,7 +1685,7 @@ __device__ __forceinline__ u32 topk_all_lds_n(const DbDev& db, const OptDev& opt
         const u32 k = c * 64 + lane;
         const u32 v = (k < nheads) ? H[k] : 0;
         const u32 tgt = lf.tgt(buf[v ? JMASK - (v & JMASK) : 0]);
-        if (v != 0 && tgt < db.n_targets) ctax[c] = db.tgt2tax[tgt];
+        if (v != 0 && tgt < db.n_targets) ctax[c] = head_tax(db, tgt);
         const u32 cr = (P > 1) ? (p2 ? (tgt & (P - 1)) : (tgt % P)) : 0;
         cv[c] = v | (cr << 26);
         if (v == 0 || ctax[c] == MCQ_EMPTY) cv[c] = 0;
@@ -1992,8 +2016,8 @@ __device__ __forceinline__ u32 fold_lists_block(const OptDev& opt, const OutDev&
 // OptDev::lin in the workgroup kernels: one list (see topk_lin_write).  The workgroup kernels of the query path are
 // instantiated per form (lists / lists in LDS / one selection: they are compiled for 64 VGPRs and 1024 threads, and either
 // form's code inside the other's kernel cost the long reads 8 % in spills whether it ran or not).
-template <class KeyT, class HT, int JB, class LF>
-__device__ __forceinline__ u32 topk_block_lin(const DbDev& db, const OptDev& opt, const OutDev& out, const KeyT* B, HT* H, u32 T,
+template <class KeyT, class HT, int JB, class LF, class DB>
+__device__ __forceinline__ u32 topk_block_lin(const DB& db, const OptDev& opt, const OutDev& out, const KeyT* B, HT* H, u32 T,
                                               const LF& lf, u64 q, u32 tid, u32 NTB, TopkBlockScratch<HT>* scr) {
     const u32 M = opt.max_cand;
     // one list (see topk_lin_write): per round every thread offers its best live head as (hits, 63 - rank, position) in 64
@@ -2009,7 +2033,7 @@ __device__ __forceinline__ u32 topk_block_lin(const DbDev& db, const OptDev& opt
             const HT hv = H[j];
             if (hv == 0) continue;
             const u32 tgt = lf.tgt(B[j]);
-            const u32 tax = tgt < db.n_targets ? db.tgt2tax[tgt] : MCQ_EMPTY;
+            const u32 tax = tgt < db.n_targets ? head_tax(db, tgt) : MCQ_EMPTY;
             const u32 r = lin_rank(opt, tgt);
             if (tax == MCQ_EMPTY || r >= opt.keep) { H[j] = 0; continue; }
             const unsigned long long k = ((unsigned long long)(hv >> JB) << 38) | ((unsigned long long)(63u - r) << 32) | ((unsigned long long)hv & JM);
@@ -2035,8 +2059,8 @@ __device__ __forceinline__ u32 topk_block_lin(const DbDev& db, const OptDev& opt
     return n;
 }
 
-template <class KeyT, class HT, int JB, class LF>
-__device__ __attribute__((noinline)) u32 topk_block_lin_call(const DbDev& db, const OptDev& opt, const OutDev& out, const KeyT* B, HT* H, u32 T,
+template <class KeyT, class HT, int JB, class LF, class DB>
+__device__ __attribute__((noinline)) u32 topk_block_lin_call(const DB& db, const OptDev& opt, const OutDev& out, const KeyT* B, HT* H, u32 T,
                                                              const LF& lf, u64 q, u32 tid, u32 NTB, TopkBlockScratch<HT>* scr) {
     return topk_block_lin<KeyT, HT, JB>(db, opt, out, B, H, T, lf, q, tid, NTB, scr);
 }
@@ -2044,8 +2068,8 @@ __device__ __attribute__((noinline)) u32 topk_block_lin_call(const DbDev& db, co
 // FORM (separate instantiations of the workgroup kernels, so that each carries only its own): 0 = the P lists in the lanes
 // of a wave, 1 = OptDev::big, 2 = OptDev::lin.  RTLIN (staged reduce kernels, forms 0 / 1): OptDev::lin is looked at at run
 // time and served by a call.
-template <class KeyT, class HT, int JB, int FORM, bool RTLIN = false, class LF, class Sync>
-__device__ __forceinline__ u32 topk_block(const DbDev& db, const OptDev& opt, const OutDev& out, const KeyT* B, HT* H,
+template <class KeyT, class HT, int JB, int FORM, bool RTLIN = false, class LF, class Sync, class DB>
+__device__ __forceinline__ u32 topk_block(const DB& db, const OptDev& opt, const OutDev& out, const KeyT* B, HT* H,
                                           u32 T, u32 numWindows, const LF& lf, u64 q, u32 tid, u32 NTB,
                                           TopkBlockScratch<HT>* scr, u32* bl, Sync sync) {
     if constexpr (FORM == 2) return topk_block_lin<KeyT, HT, JB>(db, opt, out, B, H, T, lf, q, tid, NTB, scr);
@@ -2062,7 +2086,7 @@ __device__ __forceinline__ u32 topk_block(const DbDev& db, const OptDev& opt, co
             const HT v = H[j];
             if (v == 0) continue;
             const u32 tgt = lf.tgt(B[j]);
-            const u32 tax = tgt < db.n_targets ? db.tgt2tax[tgt] : MCQ_EMPTY;
+            const u32 tax = tgt < db.n_targets ? head_tax(db, tgt) : MCQ_EMPTY;
             if (tax == MCQ_EMPTY) { H[j] = 0; continue; }
             const u32 r = (P > 1) ? (p2 ? (tgt & (P - 1)) : (tgt % P)) : 0;
             atomicMax(&scr->mx[r], v);

@@ -200,8 +200,8 @@ __device__ __forceinline__ void gather_sort_store(const DbDev& db, KeyT* buf, u3
 #endif
 // top lists of the dedup path: more than 64 distinct keys (two to four rounds of 64 run heads) take all heads at once
 // t1 (D <= 64): the target of sorted key j in lane j, as dedup_finish looked it up
-template <class LF>
-__device__ __forceinline__ u32 topk_dedup(const DbDev& db, const OptDev& opt, const OutDev& out, const u32* sk, u32* H, u32 D,
+template <class LF, class DB>
+__device__ __forceinline__ u32 topk_dedup(const DB& db, const OptDev& opt, const OutDev& out, const u32* sk, u32* H, u32 D,
                                           u32 numWindows, const LF& lf, u64 q, u32 lane, u32 t1) {
     // one selection for all ranks (zero words among the heads do no harm).  (Tried: the taxon keys of the <= 64 sorted words
     // loaded before the sweep and shuffled in here -- one more live register in the 64-VGPR kernel, +1.5 % on configs[1].)
@@ -528,8 +528,8 @@ __device__ __forceinline__ void window_span(const DbDev& db, const ReadGeom& g, 
 // leave the last 128 of the CAP hit words free, those serve the LDS maxima of topk_all_lds (up to CAP / 2 heads at
 // once, all virtual ranks in the same round) or topk_fold_write_lds (64 heads at a time), else the DPP reductions per
 // rank and 64 heads.
-template <int JB, int CAP, class LF>
-__device__ __forceinline__ u32 topk_heads(const DbDev& db, const OptDev& opt, const OutDev& out, const u32* buf, u32* hits,
+template <int JB, int CAP, class LF, class DB>
+__device__ __forceinline__ u32 topk_heads(const DB& db, const OptDev& opt, const OutDev& out, const u32* buf, u32* hits,
                                           u32 T, u32 numWindows, const LF& lf, u64 q, u32 lane) {
     u32 nheads = 0;
     for (u32 base = 0; base < T; base += 64) {                      // in place: writes trail reads
@@ -550,8 +550,8 @@ __device__ __forceinline__ u32 topk_heads(const DbDev& db, const OptDev& opt, co
 }
 
 // 64-bit keys: the lists by DPP reductions per rank (topk_fold_write compacts the heads itself), or the one selection
-template <class KeyT, class LF>
-__device__ __forceinline__ u32 topk_heads64(const DbDev& db, const OptDev& opt, const OutDev& out, const KeyT* buf, u32* hits,
+template <class KeyT, class LF, class DB>
+__device__ __forceinline__ u32 topk_heads64(const DB& db, const OptDev& opt, const OutDev& out, const KeyT* buf, u32* hits,
                                             u32 T, u32 numWindows, const LF& lf, u64 q, u32 lane) {
     if (opt.lin != 0) return topk_lin_write<KeyT, 9>(db, opt, out, buf, hits, T, lf, q, lane);
     return topk_fold_write<KeyT, u32, 9>(db, opt, out, buf, hits, T, numWindows, lf, q, lane);
@@ -609,12 +609,13 @@ __device__ __forceinline__ void tap_distinct(const DebugDev& dbg, const u32* SK,
 // wide top lists go too -- costs more in the second stage than it saves here: DESIGN.md section 15.)
 // Which form runs is the batch before's word (CountersDev::direct_mode bit MCQ_MODE_LEAN; both are launched and the other one
 // returns at once) unless MCQ_HOOK_ONLY_LAUNCH says this launch is the only one.
-template <class KeyT, int LCAP, bool TAP = false, bool SH = false, bool GW = false, int BSH = -1, int NL = 1, bool LEAN = false>
+template <class KeyT, int LCAP, bool TAP = false, bool SH = false, bool GW = false, int BSH = -1, int NL = 1, bool LEAN = false, bool EXCL = false>
 __global__ __launch_bounds__(256, sizeof(KeyT) == 4 ? (NL > 1 ? 5 : MCQ_WAVE_OCC) : 5) void k_query_wave(DbDev db, BatchDev b, OptDev opt, OutDev out,
-                                                    CountersDev* ctr, u32* ovf_list, DebugDev dbg, ShardDev sh, GwDev gwd) {
+                                                    CountersDev* ctr, u32* ovf_list, DebugDev dbg, ShardDev sh, GwDev gwd, ExclDev exd) {
     static_assert(LCAP == 512, "wave path: 8 keys per lane at most, entry index packed into 9 bits");
     static_assert(!GW || sizeof(KeyT) == 4, "the global-window form is a 32-bit word");
     static_assert(!LEAN || (sizeof(KeyT) == 4 && !TAP && !SH && NL == 1), "the lean form: 32-bit words, plain launches");
+    static_assert(!EXCL || (!TAP && !SH && NL == 1 && !LEAN), "clade exclusion: plain launches of the full form, lists in a wave's lanes");
     constexpr u32 kKeepT = LEAN ? 256u : (u32)LCAP;   // the longest list this stage answers itself
     if (!(opt.hooks & MCQ_HOOK_ONLY_LAUNCH) && ((ctr->direct_mode & MCQ_MODE_LEAN) != 0) != LEAN) return;     // the other form's batch
     using LF = typename LocOf<KeyT, GW>::type;
@@ -736,6 +737,7 @@ __global__ __launch_bounds__(256, sizeof(KeyT) == 4 ? (NL > 1 ? 5 : MCQ_WAVE_OCC
 
         wave_sync();                                   // feat[] (aliasing hits) has been consumed
         const u32 numWindows = range_width(g.qlen, opt.insert_size_max, db.tgt_winstride, db.magic_tgt_stride);
+        const auto& hdb = heads_db<EXCL>(db, exd, q);  // what the top lists read the heads' taxa from (EXCL: without the query's own clade)
         if constexpr (sizeof(KeyT) == 4) {
             if (LEAN || (T <= MCQ_DEDUP_MAX_T && !(hooks & MCQ_HOOK_RAW_SORT))) {
                 u32 D = 0, k1 = MCQ_EMPTY, incl1 = 0, t1 = 0, tb1 = 0;
@@ -770,7 +772,7 @@ __global__ __launch_bounds__(256, sizeof(KeyT) == 4 ? (NL > 1 ? 5 : MCQ_WAVE_OCC
                             st_hit -= (u32)__builtin_popcountll(__ballot(len > 0)); st_loc -= T;
                         } else st_cand += nc;
                     } else
-                    st_cand += topk_dedup(db, opt, out, dedup_sk(hits), reinterpret_cast<u32*>(buf), D, numWindows, lf, q, lane, t1);
+                    st_cand += topk_dedup(hdb, opt, out, dedup_sk(hits), reinterpret_cast<u32*>(buf), D, numWindows, lf, q, lane, t1);
                     wave_sync();
                     continue;
                 }
@@ -796,8 +798,8 @@ __global__ __launch_bounds__(256, sizeof(KeyT) == 4 ? (NL > 1 ? 5 : MCQ_WAVE_OCC
                     st_hit -= (u32)__builtin_popcountll(__ballot(len > 0)); st_loc -= T;
                 } else st_cand += nc;
             } else
-            if constexpr (sizeof(KeyT) == 4) st_cand += topk_heads<9, LCAP>(db, opt, out, reinterpret_cast<const u32*>(buf), hits, T, numWindows, lf, q, lane);
-            else st_cand += topk_heads64<KeyT>(db, opt, out, buf, hits, T, numWindows, lf, q, lane);
+            if constexpr (sizeof(KeyT) == 4) st_cand += topk_heads<9, LCAP>(hdb, opt, out, reinterpret_cast<const u32*>(buf), hits, T, numWindows, lf, q, lane);
+            else st_cand += topk_heads64<KeyT>(hdb, opt, out, buf, hits, T, numWindows, lf, q, lane);
             wave_sync();
         }
     }
@@ -822,9 +824,9 @@ __global__ __launch_bounds__(256, sizeof(KeyT) == 4 ? (NL > 1 ? 5 : MCQ_WAVE_OCC
 #ifndef MCQ_WAVE16_OCC
 #define MCQ_WAVE16_OCC 4        // waves per SIMD it is compiled for: 5 fit the LDS, but then 10 VGPRs spill (+30 % time)
 #endif
-template <bool TAP = false, bool SH = false, bool GW = false, int BSH = -1>
+template <bool TAP = false, bool SH = false, bool GW = false, int BSH = -1, bool EXCL = false>
 __global__ __launch_bounds__(256, MCQ_WAVE16_OCC) void k_query_wave16(DbDev db, BatchDev b, OptDev opt, OutDev out,
-                                                                      CountersDev* ctr, u32* ovf_list, DebugDev dbg, ShardDev sh, GwDev gwd) {
+                                                                      CountersDev* ctr, u32* ovf_list, DebugDev dbg, ShardDev sh, GwDev gwd, ExclDev exd) {
     constexpr int LCAP = MCQ_LCAP_WAVE16, JB = 10;
     const typename LocOf<u32, GW>::type lf = loc_format<u32, GW>(db, gwd);
     __shared__ u32 s_buf[4][LCAP];
@@ -910,6 +912,7 @@ __global__ __launch_bounds__(256, MCQ_WAVE16_OCC) void k_query_wave16(DbDev db, 
         if (T == 0) { if (lane == 0) out.ncand[q] = 0; continue; }
         wave_sync();                                   // feat[] (aliasing hits) has been consumed
         const u32 numWindows = range_width(g.qlen, opt.insert_size_max, db.tgt_winstride, db.magic_tgt_stride);
+        const auto& hdb = heads_db<EXCL>(db, exd, q);  // (see k_query_wave)
         if (T <= MCQ_DEDUP_MAX_T && (qe & MCQ_Q_UNPROBED) && !g.wide) st_short += 1;       // (direct mode: the first stage would have kept this one)
         if (T <= MCQ_DEDUP_MAX_T) {                    // a short list (a wide read, or direct mode): the distinct-key tail of the first stage
             u32 D, k1 = MCQ_EMPTY, incl1 = 0, t1 = 0, tb1 = 0;
@@ -921,7 +924,7 @@ __global__ __launch_bounds__(256, MCQ_WAVE16_OCC) void k_query_wave16(DbDev db, 
                 if constexpr (TAP) { if (dbg.mode == 2) tap_distinct(dbg, dedup_sk(hits), dedup_wp(hits), D, lf, q, lane); }
                 if (D <= 64 && numWindows <= 8) sweep_targets_regs(k1, incl1, tb1, buf, D, numWindows, lf, lane);
                 else sweep_targets_weighted(dedup_sk(hits), dedup_wp(hits), buf, D, numWindows, lf, lane);
-                st_cand += topk_dedup(db, opt, out, dedup_sk(hits), buf, D, numWindows, lf, q, lane, t1);
+                st_cand += topk_dedup(hdb, opt, out, dedup_sk(hits), buf, D, numWindows, lf, q, lane, t1);
                 wave_sync();
                 continue;
             }
@@ -931,7 +934,8 @@ __global__ __launch_bounds__(256, MCQ_WAVE16_OCC) void k_query_wave16(DbDev db, 
             u32 r[16];
             gather_regs2<16>(db, r, T, pos0, len0, off0, pos1, len1, off1, two, lane, hits);
             WCLK(1);
-            if constexpr (!TAP) {                       // (the taps want the whole sorted list)
+            if constexpr (!TAP && !EXCL) {              // (the taps want the whole sorted list; the two-class tail proves its cut from the
+                                                        // light targets it has seen: retiring heads afterwards would break that proof)
                 const u32 n2 = two_class_tail<16>(db, opt, out, r, T, numWindows, word_space, lf, q, lane, buf, hits);
                 if (n2 == ~1u) {                        // given up after the registers were spent: the workgroup kernel takes it
                     st_loc -= T; st_retry += 1;
@@ -962,7 +966,7 @@ __global__ __launch_bounds__(256, MCQ_WAVE16_OCC) void k_query_wave16(DbDev db, 
         wave_sync();
         if constexpr (TAP) { if (dbg.mode == 2) tap_sorted<u32>(dbg, buf, T, lf, q, lane); }
         sweep_targets_wave<u32, JB>(buf, hits, T, numWindows, lf, lane);
-        st_cand += topk_heads<JB, LCAP>(db, opt, out, buf, hits, T, numWindows, lf, q, lane);
+        st_cand += topk_heads<JB, LCAP>(hdb, opt, out, buf, hits, T, numWindows, lf, q, lane);
         wave_sync();
     }
 #ifdef MCQ_PHASE_CLOCK
@@ -1151,8 +1155,8 @@ __device__ __forceinline__ u32 block_excl_scan4(u32* a, u32 n, u32 tid) {
 // HT/JB: packed (hits << JB | index) word of the sweep: u32 with JB = 13 when the list fits the workgroup's LDS
 // (<= 8192 entries, hits <= 8192), u64 with JB = 32 in global scratch
 // filled: B[0..T) holds the unsorted list already
-template <class KeyT, class HT, int JB, int BIG, bool RTLIN = false, class LF, class Fill, bool HGLOBAL = false>
-__device__ __forceinline__ void block_tail(const DbDev& db, const OptDev& opt, const OutDev& out, CountersDev* ctr,
+template <class KeyT, class HT, int JB, int BIG, bool RTLIN = false, class LF, class Fill, bool HGLOBAL = false, class DB>
+__device__ __forceinline__ void block_tail(const DB& db, const OptDev& opt, const OutDev& out, CountersDev* ctr,
                                            KeyT* B, HT* H, u32 T, u32 numWindows, const LF& lf, u64 q, u32 tid,
                                            const DebugDev& dbg, u32* biglist, Fill fill, bool filled = false) {
     const u32 n2p = pow2ceil(T), NTB = blockDim.x;
@@ -1278,10 +1282,11 @@ __device__ __forceinline__ int block_two_class(const DbDev& db, const OptDev& op
 // allocation: 20 spilled VGPRs around the query loop), which never take it -- so it is a kernel of its own, launched behind the
 // plain one over the same queue: queries with narrow window ranges (numWindows <= 16: short reads and pairs whose lists
 // outgrew the wave stages) are left to it (OptDev::tc_limit != 0 tells the plain kernel that it is there), everything else to the plain one.
-template <class KeyT, int LCAPB, int NT, int BIG = 0, bool SH = false, bool GW = false, bool TC = false>
+template <class KeyT, int LCAPB, int NT, int BIG = 0, bool SH = false, bool GW = false, bool TC = false, bool EXCL = false>
 __global__ __launch_bounds__(NT, sizeof(KeyT) == 4 ? 8 : 4) void k_query_block(DbDev db, BatchDev b, OptDev opt, OutDev out,
-                                                      CountersDev* ctr, const u32* ovf_list, ScratchDev sc, DebugDev dbg, ShardDev sh, GwDev gwd) {
+                                                      CountersDev* ctr, const u32* ovf_list, ScratchDev sc, DebugDev dbg, ShardDev sh, GwDev gwd, ExclDev exd) {
     static_assert(LCAPB <= 8192, "packed sweep word: 13 index bits");
+    static_assert(!EXCL || (!TC && !SH), "clade exclusion: the plain workgroup kernel");
     const typename LocOf<KeyT, GW>::type lf = loc_format<KeyT, GW>(db, gwd);
     constexpr u32 NW16 = NT / 64;
     // the key segment and the hit words behind it, in ONE allocation: lists of 8193 .. 16384 32-bit words sort across both (r04)
@@ -1416,6 +1421,7 @@ __global__ __launch_bounds__(NT, sizeof(KeyT) == 4 ? 8 : 4) void k_query_block(D
             continue;
         }
         const u32 numWindows = range_width(n1 + n2, opt.insert_size_max, db.tgt_winstride, db.magic_tgt_stride);
+        const auto& hdb = heads_db<EXCL>(db, exd, q);  // (see k_query_wave)
         // every wave copies the lists of 64 features at a time (fpos = exclusive scan of the list lengths): list of
         // an element by a shuffle search inside the group, four 64-element chunks of loads in flight
         auto fill = [&](KeyT* B) {
@@ -1481,7 +1487,7 @@ __global__ __launch_bounds__(NT, sizeof(KeyT) == 4 ? 8 : 4) void k_query_block(D
                 } else if (tc_skip) --tc_skip;
             }
             const bool done = tc == TC_DONE, filled = tc == TC_HEAVY;
-            if (!done) { block_tail<KeyT, u32, 13, BIG>(db, opt, out, ctr, s_buf, s_hits, T, numWindows, lf, q, tid, dbg, s_biglist, fill, filled); PHCLK(ph, 10); }
+            if (!done) { block_tail<KeyT, u32, 13, BIG>(hdb, opt, out, ctr, s_buf, s_hits, T, numWindows, lf, q, tid, dbg, s_biglist, fill, filled); PHCLK(ph, 10); }
         }
         // 8193 .. 16384 words (ONT-like reads of 27 .. 55 kb: one in a hundred, and until r04 a sixth of the kernel's time -- a workgroup
         // took 23-27 us per kb of such a read against 6.5 below, everything in global scratch): the list sorts in the LDS of BOTH
@@ -1489,9 +1495,9 @@ __global__ __launch_bounds__(NT, sizeof(KeyT) == 4 ? 8 : 4) void k_query_block(D
         // the lists' scans go through global memory, the atomics reduced per run inside a wave first (sweep_targets<..., true>)
         else if (sizeof(KeyT) == 4 && BIG == 2 && !f_lds && dbg.mode == 0 && ((T + 127u) & ~127u) <= 2u * (u32)LCAPB) {
             if constexpr (sizeof(KeyT) == 4 && BIG == 2)          // (instantiated for those only)
-                block_tail<KeyT, u32, 14, BIG, false, decltype(lf), decltype(fill), true>(db, opt, out, ctr, s_buf, reinterpret_cast<u32*>(ghits), T, numWindows, lf, q, tid, dbg, s_biglist, fill);
+                block_tail<KeyT, u32, 14, BIG, false, decltype(lf), decltype(fill), true>(hdb, opt, out, ctr, s_buf, reinterpret_cast<u32*>(ghits), T, numWindows, lf, q, tid, dbg, s_biglist, fill);
         }
-        else                           block_tail<KeyT, u64, 32, BIG>(db, opt, out, ctr, gbuf, ghits, T, numWindows, lf, q, tid, dbg, s_biglist, fill);
+        else                           block_tail<KeyT, u64, 32, BIG>(hdb, opt, out, ctr, gbuf, ghits, T, numWindows, lf, q, tid, dbg, s_biglist, fill);
     }
     }
     }
@@ -1783,6 +1789,13 @@ extern "C" int mcq_ws_destroy(mcq_ws* ws) {
     }
     if (ws->cls_counts) (void)hipFree(ws->cls_counts);
     if (ws->cls_ev) (void)hipEventDestroy(ws->cls_ev);
+    if (ws->excl_tgt) (void)hipFree(ws->excl_tgt);
+    for (auto& sl : ws->qc_slot) {
+        if (sl.pinned) (void)hipHostFree(sl.pinned);
+        if (sl.dev) (void)hipFree(sl.dev);
+        if (sl.ev) (void)hipEventDestroy(sl.ev);
+    }
+    delete ws->qc_host;
     for (auto* v : {ws->ev_used, ws->ev_free}) {
         if (!v) continue;
         for (auto& t : *v) for (auto e : t.ev) (void)hipEventDestroy(e);
@@ -1851,7 +1864,16 @@ struct LaunchPlan {          // what launch_query launches for one batch, decide
     OptDev first, rest;     // what the first stage gets, and every later one
     bool next_mode;         // k_next_mode runs behind the batch (else the mode word is zeroed); it may choose the lean form when both were launched
 };
-static int plan_launch(const mcq_db* db, const OptDev& od_in, bool tap, bool sharded, LeanReq req, LaunchPlan& p) {
+static int plan_launch(const mcq_db* db, const OptDev& od_req, bool tap, bool sharded, bool excl, LeanReq req, LaunchPlan& p) {
+    // Clade exclusion (EXCL instantiations: the full first wave stage, the second one and the plain workgroup kernel) routes around what
+    // has no such form: the two-class tail, the lean first stage, and the lists in four registers per lane (those take the workgroup kernel)
+    OptDev od_in = od_req;
+    if (excl) {
+        if (tap || sharded) return fail(MCQ_E_UNSUPPORTED, "clade exclusion: not on the tap or the sharded path");
+        if (req == LeanReq::LeanOnly) return fail(MCQ_E_UNSUPPORTED, "clade exclusion has no lean first wave stage (MCQ_FORCE_LEAN_WAVE)");
+        req = LeanReq::FullOnly;
+        od_in.hooks |= MCQ_HOOK_NO_TWO_CLASS;
+    }
     const bool compact = db->d.compact != 0;
     const bool route_hook = (od_in.hooks & MCQ_HOOK_ROUTE) != 0;
     // The workgroup kernel exists twice: plain, and with the two-class tail for queries with narrow window ranges (short reads
@@ -1864,7 +1886,7 @@ static int plan_launch(const mcq_db* db, const OptDev& od_in, bool tap, bool sha
     // the first wave stage keeps the lists in four registers per lane (NL instantiation; 32-bit words) and has no second stage behind
     // it; what overflows it, and every other case, takes the workgroup kernel with the lists in its LDS (`big`)
     const u32 pm_slots = (u32)pow2ceil64(od_in.P) * (u32)pow2ceil64(od_in.max_cand);
-    p.many = od_in.big && compact && !tap && !sharded && pm_slots <= 256 && !(od_in.hooks & MCQ_HOOK_BLOCK_ONLY);
+    p.many = od_in.big && compact && !tap && !sharded && !excl && pm_slots <= 256 && !(od_in.hooks & MCQ_HOOK_BLOCK_ONLY);
     p.rest = od_in;
     p.rest.tc_limit = p.with_tc ? tc_len : 0;
     if (od_in.big && !p.many) p.rest.hooks |= MCQ_HOOK_BLOCK_ONLY;
@@ -1885,7 +1907,7 @@ static int plan_launch(const mcq_db* db, const OptDev& od_in, bool tap, bool sha
 // sh != nullptr: the feature-sharded home side (SH instantiations; dbd = the handle's DbDev with `locs` pointing at the
 // received location buffer); the counters are then zeroed by the caller (the sketch kernel has already counted)
 int mcq::launch_query(const mcq_db* db, mcq_ws* ws, const BatchDev& b, const OptDev& od_in, const OutDev& o,
-                      hipStream_t st, LeanReq lean_req, const DebugDev& dbg, const ShardDev* shp, const DbDev* dbd) {
+                      hipStream_t st, LeanReq lean_req, const DebugDev& dbg, const ShardDev* shp, const DbDev* dbd, const ExclDev* exp) {
     if (!shp) HIPCHK(hipMemsetAsync(ws->ctr, 0, MCQ_CTR_ZEROED, st));
     if (b.nq == 0) return MCQ_OK;
     const ShardDev sh = shp ? *shp : ShardDev{};
@@ -1897,36 +1919,38 @@ int mcq::launch_query(const mcq_db* db, mcq_ws* ws, const BatchDev& b, const Opt
     LaunchTimer tm(ws, st);
     int rc = tm.begin(); if (rc) return rc;
     const bool tap = dbg.mode != 0;     // mcq_debug_matches: the instantiations that also write the sorted match lists
-    LaunchPlan p; rc = plan_launch(db, od_in, tap, shp != nullptr, lean_req, p); if (rc) return rc;
+    const ExclDev ex = exp ? *exp : ExclDev{};
+    LaunchPlan p; rc = plan_launch(db, od_in, tap, shp != nullptr, exp != nullptr, lean_req, p); if (rc) return rc;
     const OptDev& od = p.rest;
     using Yes = std::true_type; using No = std::false_type;
-    // the launch role as <TAP, SH, BSH>: the sharded home side and the debug tap read the layout at run time, plain launches
-    // take the table's
+    // the launch role as <TAP, SH, BSH, EXCL>: the sharded home side, the debug tap and clade exclusion read the layout at run time,
+    // plain launches take the table's
     auto by_role = [&](auto f) {
-        if (shp) f(No{}, Yes{}, IntC<-1>{});
-        else if (tap) f(Yes{}, No{}, IntC<-1>{});
-        else with_layout(db, [&](auto BSH) { f(No{}, No{}, BSH); });
+        if (shp) f(No{}, Yes{}, IntC<-1>{}, No{});
+        else if (tap) f(Yes{}, No{}, IntC<-1>{}, No{});
+        else if (exp) f(No{}, No{}, IntC<-1>{}, Yes{});
+        else with_layout(db, [&](auto BSH) { f(No{}, No{}, BSH, No{}); });
     };
     rc = with_loc_form(db, [&](auto L) -> int {
         using Key = typename decltype(L)::Key;
         constexpr bool GW = decltype(L)::gw;
-        auto first = [&](auto TAP, auto SH, auto BSH, auto NL, auto LEAN, u32 g) {
-            hipLaunchKernelGGL((k_query_wave<Key, kLcapWave, TAP, SH, GW, BSH, NL, LEAN>), dim3(g), dim3(256), 0, st, D, b, p.first, o, ws->ctr, ws->ovf_list, dbg, sh, db->g);
+        auto first = [&](auto TAP, auto SH, auto BSH, auto NL, auto LEAN, auto EX, u32 g) {
+            hipLaunchKernelGGL((k_query_wave<Key, kLcapWave, TAP, SH, GW, BSH, NL, LEAN, EX>), dim3(g), dim3(256), 0, st, D, b, p.first, o, ws->ctr, ws->ovf_list, dbg, sh, db->g, ex);
         };
-        if (p.full) by_role([&](auto TAP, auto SH, auto BSH) { first(TAP, SH, BSH, IntC<1>{}, No{}, grid); });
+        if (p.full) by_role([&](auto TAP, auto SH, auto BSH, auto EX) { first(TAP, SH, BSH, IntC<1>{}, No{}, EX, grid); });
         if constexpr (sizeof(Key) == 4) {   // the NL and LEAN instantiations: 32-bit words, plain launches
-            if (p.many) with_layout(db, [&](auto BSH) { first(No{}, No{}, BSH, IntC<4>{}, No{}, grid_for(ws->cap_wave_many, want)); });
-            if (p.lean) with_layout(db, [&](auto BSH) { first(No{}, No{}, BSH, IntC<1>{}, Yes{}, grid); });
+            if (p.many) with_layout(db, [&](auto BSH) { first(No{}, No{}, BSH, IntC<4>{}, No{}, No{}, grid_for(ws->cap_wave_many, want)); });
+            if (p.lean) with_layout(db, [&](auto BSH) { first(No{}, No{}, BSH, IntC<1>{}, Yes{}, No{}, grid); });
         }
         rc = tm.mark(); if (rc) return rc;
         if constexpr (sizeof(Key) == 4) {   // second wave stage (back queue); no queue for 64-bit keys
-            by_role([&](auto TAP, auto SH, auto BSH) {
-                hipLaunchKernelGGL((k_query_wave16<TAP, SH, GW, BSH>), dim3(grid_for(ws->cap_wave16, want)), dim3(256), 0, st, D, b, od, o, ws->ctr,
-                                   ws->ovf_list, dbg, sh, db->g);
+            by_role([&](auto TAP, auto SH, auto BSH, auto EX) {
+                hipLaunchKernelGGL((k_query_wave16<TAP, SH, GW, BSH, EX>), dim3(grid_for(ws->cap_wave16, want)), dim3(256), 0, st, D, b, od, o, ws->ctr,
+                                   ws->ovf_list, dbg, sh, db->g, ex);
             });
             // third wave stage: front-queue entries of up to 2048 locations (see k_query_wave32); counts the narrow ones it leaves
-            if (p.with_tc) by_role([&](auto TAP, auto SH, auto BSH) {     // (no tap form: with_tc excludes the tap)
-                if constexpr (!TAP) hipLaunchKernelGGL((k_query_wave32<SH, GW, BSH>), dim3(grid_for(ws->cap_wave32, want)), dim3(256), 0, st, D, b, od, o,
+            if (p.with_tc) by_role([&](auto TAP, auto SH, auto BSH, auto EX) {     // (no tap or exclusion form: with_tc excludes both)
+                if constexpr (!TAP && !EX) hipLaunchKernelGGL((k_query_wave32<SH, GW, BSH>), dim3(grid_for(ws->cap_wave32, want)), dim3(256), 0, st, D, b, od, o,
                                                        ws->ctr, ws->ovf_list, sh, db->g);
             });
         }
@@ -1934,11 +1958,11 @@ int mcq::launch_query(const mcq_db* db, mcq_ws* ws, const BatchDev& b, const Opt
         // the workgroup kernel: list form BIG (2: od.lin, 1: od.big, else 0), plain or with the two-class tail (TC; 32-bit words)
         constexpr int lcap = sizeof(Key) == 4 ? MCQ_BLOCK_LCAP : kLcapBlock, nt = sizeof(Key) == 4 ? MCQ_BLOCK_NT : 1024;
         auto block = [&](auto TC, auto BIG) {
-            auto launch = [&](auto SH) {
-                hipLaunchKernelGGL((k_query_block<Key, lcap, nt, BIG, SH, GW, TC>), dim3(ws->n_block_wgs), dim3(nt), 0, st, D, b, od, o, ws->ctr,
-                                   (const u32*)ws->ovf_list, ws->sc, dbg, sh, db->g);
+            auto launch = [&](auto SH, auto EX) {
+                if constexpr (!(EX && TC)) hipLaunchKernelGGL((k_query_block<Key, lcap, nt, BIG, SH, GW, TC, EX>), dim3(ws->n_block_wgs), dim3(nt), 0, st, D, b, od, o, ws->ctr,
+                                   (const u32*)ws->ovf_list, ws->sc, dbg, sh, db->g, ex);
             };
-            if (shp) launch(Yes{}); else launch(No{});
+            if (shp) launch(Yes{}, No{}); else if (exp) launch(No{}, Yes{}); else launch(No{}, No{});
         };
         if (od.lin) block(No{}, IntC<2>{}); else if (od.big) block(No{}, IntC<1>{}); else block(No{}, IntC<0>{});
         if constexpr (sizeof(Key) == 4) if (p.with_tc) { if (od.lin) block(Yes{}, IntC<2>{}); else block(Yes{}, IntC<0>{}); }
@@ -1996,6 +2020,72 @@ extern "C" int mcq_ws_taxon_counts(mcq_ws* ws, uint64_t* host_out, int reset) {
     return MCQ_OK;
 }
 
+// ------------------------------------------------------------------ clade exclusion (-exclude RANK of the reference's query mode)
+extern "C" int mcq_ws_set_exclusion(mcq_ws* ws, const uint32_t* tgt_clade, uint32_t n_targets, uint32_t flags) {
+    if (!ws) return fail(MCQ_E_ARG, "null argument");
+    if (flags & ~(u32)MCQ_DEVICE_PTRS) return fail(MCQ_E_ARG, "unknown bits in flags");
+    HIPCHK(hipSetDevice(ws->device));
+    HIPCHK(hipDeviceSynchronize());              // (batches in flight read the table that goes)
+    if (ws->excl_tgt) { (void)hipFree(ws->excl_tgt); ws->excl_tgt = nullptr; ws->excl_n = 0; }
+    ws->qc_kind = 0;
+    if (!tgt_clade) return MCQ_OK;
+    if (!n_targets) return fail(MCQ_E_ARG, "a clade table of no targets");
+    if (!(flags & MCQ_DEVICE_PTRS))
+        for (u32 t = 0; t < n_targets; ++t)
+            if (tgt_clade[t] == MCQ_CLADE_KEEP_ALL) return fail(MCQ_E_ARG, "MCQ_CLADE_KEEP_ALL is a query's value, not a target's");
+    HIPCHK(hipMalloc(&ws->excl_tgt, (u64)n_targets * 4));
+    HIPCHK(hipMemcpy(ws->excl_tgt, tgt_clade, (u64)n_targets * 4, (flags & MCQ_DEVICE_PTRS) ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice));
+    ws->excl_n = n_targets;
+    return MCQ_OK;
+}
+
+extern "C" int mcq_ws_set_query_clades(mcq_ws* ws, const uint32_t* query_clade, uint64_t n_queries, uint32_t flags) {
+    if (!ws || !query_clade) return fail(MCQ_E_ARG, "null argument");
+    if (flags & ~(u32)MCQ_DEVICE_PTRS) return fail(MCQ_E_ARG, "unknown bits in flags");
+    if (!ws->excl_tgt) return fail(MCQ_E_ARG, "no clade table is attached to this workspace (mcq_ws_set_exclusion)");
+    if (n_queries > ws->max_queries) return fail(MCQ_E_ARG, "more clade keys than the workspace has queries");
+    if (flags & MCQ_DEVICE_PTRS) { ws->qc_dev = query_clade; ws->qc_kind = 1; }
+    else {
+        if (!ws->qc_host) ws->qc_host = new std::vector<u32>();
+        ws->qc_host->assign(query_clade, query_clade + n_queries);
+        ws->qc_kind = 2;
+    }
+    ws->qc_n = n_queries;
+    return MCQ_OK;
+}
+
+// The clade keys of the batch that is being enqueued, as the kernels take them: consumes what mcq_ws_set_query_clades handed over.
+// A host array goes through staging set `slot` (pinned + device) on stream `up`, which the batch's kernels are ordered behind.
+// on == false: the workspace has no exclusion attached, the batch runs as ever.
+static int take_query_clades(const mcq_db* db, mcq_ws* ws, u64 nq, int slot, hipStream_t up, ExclDev& ex, bool& on) {
+    on = ws->excl_tgt != nullptr;
+    if (!on) return MCQ_OK;
+    if (ws->excl_n != db->d.n_targets) return fail(MCQ_E_ARG, "the attached clade table has another number of targets than the database");
+    if (ws->qc_kind == 0) return fail(MCQ_E_ARG, "clade exclusion is attached but no clade keys were handed over for this batch (mcq_ws_set_query_clades)");
+    if (ws->qc_n != nq) return fail(MCQ_E_ARG, "the clade keys handed over are not one per query of this batch");
+    ex.tgt_clade = ws->excl_tgt;
+    if (ws->qc_kind == 1) ex.query_clade = ws->qc_dev;
+    else {
+        auto& sl = ws->qc_slot[slot];
+        if (!sl.pinned) {
+            const u64 bytes = std::max<u64>(1, ws->max_queries) * 4;
+            HIPCHK(hipHostMalloc(&sl.pinned, bytes));
+            HIPCHK(hipMalloc(&sl.dev, bytes));
+            HIPCHK(hipEventCreateWithFlags(&sl.ev, hipEventDisableTiming));
+        }
+        if (sl.used) HIPCHK(hipEventSynchronize(sl.ev));       // the upload before this one has read the pinned words
+        if (nq) {
+            memcpy(sl.pinned, ws->qc_host->data(), nq * 4);
+            HIPCHK(hipMemcpyAsync(sl.dev, sl.pinned, nq * 4, hipMemcpyHostToDevice, up));
+        }
+        HIPCHK(hipEventRecord(sl.ev, up));
+        sl.used = true;
+        ex.query_clade = sl.dev;
+    }
+    ws->qc_kind = 0;
+    return MCQ_OK;
+}
+
 extern "C" int mcq_query(const mcq_db* db, mcq_ws* ws, const mcq_batch* in, const mcq_query_opts* opt,
                          mcq_result* out, void* stream) {
     if (!db || !ws || !in || !opt || !out) return fail(MCQ_E_ARG, "null argument");
@@ -2030,7 +2120,10 @@ extern "C" int mcq_query(const mcq_db* db, mcq_ws* ws, const mcq_batch* in, cons
     if (!dev_out) { o.cands = ws->d_cands; o.ncand = ws->d_ncand; }
     else { o.cands = (u32*)out->cands; o.ncand = out->n_cand; }
     DebugDev dbg; memset(&dbg, 0, sizeof(dbg));
-    rc = launch_query(db, ws, b, od, o, st, lean_request(opt->flags), dbg);
+    ExclDev ex; bool excl;
+    rc = take_query_clades(db, ws, nq, 2, st, ex, excl);
+    if (rc) return rc;
+    rc = launch_query(db, ws, b, od, o, st, lean_request(opt->flags), dbg, nullptr, nullptr, excl ? &ex : nullptr);
     if (rc) return rc;
     rc = classify_batch(ws, o, nq, od.max_cand, st);
     if (rc) return rc;
@@ -2090,6 +2183,8 @@ extern "C" int mcq_query_pipelined(const mcq_db* db, mcq_ws* ws, const mcq_batch
     const u64 bytes = packed ? mcq_packed_bytes(nbases) : nbases;
     if (bytes) HIPCHK(hipMemcpyAsync(p.d_bases[k], in->bases, bytes, hipMemcpyHostToDevice, p.s_in));
     HIPCHK(hipMemcpyAsync(p.d_seq_off[k], in->seq_off, (in->n_seqs + 1) * 8, hipMemcpyHostToDevice, p.s_in));
+    ExclDev ex; bool excl;
+    rc = take_query_clades(db, ws, nq, k, p.s_in, ex, excl); if (rc) return rc;    // (this batch's own array: staging set k, as its bases)
     HIPCHK(hipEventRecord(p.ev_in[k], p.s_in));
     // compute: after its input arrived and its result set was copied out (call i - 2)
     HIPCHK(hipStreamWaitEvent(p.s_k, p.ev_in[k], 0));
@@ -2098,7 +2193,7 @@ extern "C" int mcq_query_pipelined(const mcq_db* db, mcq_ws* ws, const mcq_batch
     BatchDev b; rc = batch_dev(&hin, p.d_bases[k], p.d_seq_off[k], b); if (rc) return rc;
     OutDev o; o.cands = p.d_cands[k]; o.ncand = p.d_ncand[k];
     DebugDev dbg; memset(&dbg, 0, sizeof(dbg));
-    rc = launch_query(db, ws, b, od, o, p.s_k, lean_request(opt->flags), dbg); if (rc) return rc;
+    rc = launch_query(db, ws, b, od, o, p.s_k, lean_request(opt->flags), dbg, nullptr, nullptr, excl ? &ex : nullptr); if (rc) return rc;
     rc = classify_batch(ws, o, nq, od.max_cand, p.s_k); if (rc) return rc;
     HIPCHK(hipEventRecord(p.ev_k[k], p.s_k));
     // out

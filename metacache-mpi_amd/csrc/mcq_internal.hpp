@@ -97,6 +97,12 @@ struct mcq_ws {
     unsigned long long* cls_counts;
     u32 cls_n;
     hipEvent_t cls_ev;
+    // clade exclusion (mcq_ws_set_exclusion): the targets' clade keys on the device while attached; the query keys handed over for
+    // the NEXT batch (mcq_ws_set_query_clades: a device pointer as it came, or a copy of the host array), and where host arrays are
+    // staged -- one set per staging set of the pipelined call and one for mcq_query, each guarded by the event behind its last upload
+    u32* excl_tgt; u32 excl_n;
+    const u32* qc_dev; std::vector<u32>* qc_host; u64 qc_n; int qc_kind;      // qc_kind: 0 nothing handed over, 1 device pointer, 2 host copy
+    struct QcSlot { u32* pinned; u32* dev; hipEvent_t ev; bool used; } qc_slot[3];
 };
 
 // ------------------------------------------------------------------ a handle's form as template arguments
@@ -123,7 +129,8 @@ namespace mcq {
 // mcq_engine.hip
 __attribute__((visibility("hidden"))) int make_opt(const mcq_query_opts* o, OptDev& d, const mcq_db* db);
 __attribute__((visibility("hidden"))) int launch_query(const mcq_db* db, mcq_ws* ws, const BatchDev& b, const OptDev& od_in, const OutDev& o,
-                                                       hipStream_t st, LeanReq lean_req, const DebugDev& dbg, const ShardDev* shp = nullptr, const DbDev* dbd = nullptr);
+                                                       hipStream_t st, LeanReq lean_req, const DebugDev& dbg, const ShardDev* shp = nullptr, const DbDev* dbd = nullptr,
+                                                       const ExclDev* exp = nullptr /* clade exclusion: mcq_ws_set_exclusion */);
 // mcq_stages.hip (instantiated for InT = u32 and u64)
 __attribute__((visibility("hidden"))) int batch_dev(const mcq_batch* in, const char* d_bases, const u64* d_seq_off, BatchDev& b);
 template <class InT>

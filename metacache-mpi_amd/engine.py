@@ -27,6 +27,8 @@ MCQ_NO_WAVE16 = 0x800            # debug: 513..1024 locations take the workgroup
 MCQ_NO_TWO_CLASS = 0x4000        # debug: long match lists are sorted whole (no light / heavy split)
 MCQ_FORCE_LEAN_WAVE = 0x20000    # debug / A-B: the lean first wave stage (hands every list it does not want to the later stages)
 MCQ_FORCE_FULL_WAVE = 0x40000    # debug / A-B: the full first wave stage, whatever the batch before suggests
+MCQ_CLADE_NONE = 0xFFFFFFFF      # clade exclusion: no ancestor at the rank (a target's key, or a truth's)
+MCQ_CLADE_KEEP_ALL = 0xFFFFFFFE  # clade exclusion, query keys only: no ground truth, nothing is excluded
 
 MCQ_OK, MCQ_E_ARG, MCQ_E_HIP, MCQ_E_CAPACITY, MCQ_E_UNSUPPORTED = 0, -1, -2, -3, -4
 
@@ -174,6 +176,8 @@ def lib():
                                    C.c_void_p, C.c_void_p]
         L.mcq_ws_set_classify.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(ClassifyOpts)]
         L.mcq_ws_taxon_counts.argtypes = [C.c_void_p, C.c_void_p, C.c_int]
+        L.mcq_ws_set_exclusion.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32]
+        L.mcq_ws_set_query_clades.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint32]
         L.mcq_shard_create.argtypes = [C.c_void_p, C.POINTER(ShardCfg), C.POINTER(C.c_void_p)]
         L.mcq_shard_destroy.argtypes = [C.c_void_p]
         L.mcq_shard_unique_id.argtypes = [C.c_void_p]
@@ -380,6 +384,28 @@ class Workspace:
         out = np.zeros(getattr(self, "_cls_n", 0), np.uint64)
         _chk(lib().mcq_ws_taxon_counts(self.h, _np_ptr(out), 1 if reset else 0))
         return out
+
+    # ---- clade exclusion (mcq_ws_set_exclusion / mcq_ws_set_query_clades)
+    def set_exclusion(self, tgt_clade, device_ptr=None, n_targets=0):
+        """attaches the targets' clade keys (u32 [n_targets], MCQ_CLADE_NONE = no ancestor at the rank; None detaches): a host
+        array, or (device_ptr, n_targets); either is copied.  A device table is not searched for MCQ_CLADE_KEEP_ALL."""
+        if device_ptr is not None:
+            _chk(lib().mcq_ws_set_exclusion(self.h, device_ptr, n_targets, MCQ_DEVICE_PTRS))
+            return
+        if tgt_clade is None:
+            _chk(lib().mcq_ws_set_exclusion(self.h, None, 0, 0))
+            return
+        a = np.ascontiguousarray(tgt_clade, np.uint32)
+        _chk(lib().mcq_ws_set_exclusion(self.h, _np_ptr(a), len(a), 0))
+
+    def set_query_clades(self, query_clade, device_ptr=None, n_queries=0):
+        """the clade keys of the NEXT batch (u32 per query; MCQ_CLADE_KEEP_ALL = no ground truth): a host array, which is
+        copied, or (device_ptr, n_queries), which that batch's kernels read in place"""
+        if device_ptr is not None:
+            _chk(lib().mcq_ws_set_query_clades(self.h, device_ptr, n_queries, MCQ_DEVICE_PTRS))
+            return
+        a = np.ascontiguousarray(query_clade, np.uint32)
+        _chk(lib().mcq_ws_set_query_clades(self.h, _np_ptr(a) if len(a) else _np_ptr(np.zeros(1, np.uint32)), len(a), 0))
 
     def timing(self, enable):
         _chk(lib().mcq_ws_timing(self.h, 1 if enable else 0))

@@ -22,6 +22,10 @@ class TaxonRec(C.Structure):
                 ("index", C.c_uint64), ("windows", C.c_uint64)]
 
 
+class EvalStatsRec(C.Structure):
+    _fields_ = [(n, C.c_uint64 * 22) for n in ("assigned", "known", "correct", "wrong")]
+
+
 class ShardParams(C.Structure):
     _fields_ = [(n, C.c_uint64) for n in ("k", "sketch_size", "winlen", "winstride", "q_k", "q_sketch_size", "q_winlen",
                                          "q_winstride", "max_locs_per_feature")]
@@ -69,6 +73,24 @@ def lib():
         L.mcq_refdb_classify.restype = C.c_uint32
         L.mcq_refdb_classify.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_float, C.c_uint32]
         L.mcq_refdb_lineages.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
+        L.mcq_refdb_ground_truth.restype = C.c_uint32; L.mcq_refdb_ground_truth.argtypes = [C.c_void_p, C.c_char_p, C.c_uint64]
+        L.mcq_refdb_clade_keys.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p]
+        L.mcq_refdb_taxon_clade.restype = C.c_uint32; L.mcq_refdb_taxon_clade.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32]
+        L.mcq_refdb_ranked_lca.restype = C.c_uint32; L.mcq_refdb_ranked_lca.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32]
+        sp = C.POINTER(EvalStatsRec)
+        L.mcq_eval_stats_assign.restype = None; L.mcq_eval_stats_assign.argtypes = [sp, C.c_uint32]
+        L.mcq_eval_stats_assign_known_correct.restype = None
+        L.mcq_eval_stats_assign_known_correct.argtypes = [sp, C.c_uint32, C.c_uint32, C.c_uint32]
+        L.mcq_eval_stats_add.restype = None; L.mcq_eval_stats_add.argtypes = [sp, sp]
+        for f in ("total", "unknown"):
+            getattr(L, "mcq_eval_stats_" + f).restype = C.c_uint64; getattr(L, "mcq_eval_stats_" + f).argtypes = [sp]
+        for f in ("assigned", "known", "correct", "wrong"):
+            getattr(L, "mcq_eval_stats_" + f).restype = C.c_uint64; getattr(L, "mcq_eval_stats_" + f).argtypes = [sp, C.c_uint32]
+        for f in ("unknown_rate", "unclassified_rate"):
+            getattr(L, "mcq_eval_stats_" + f).restype = C.c_double; getattr(L, "mcq_eval_stats_" + f).argtypes = [sp]
+        for f in ("known_rate", "classification_rate", "precision", "sensitivity"):
+            getattr(L, "mcq_eval_stats_" + f).restype = C.c_double; getattr(L, "mcq_eval_stats_" + f).argtypes = [sp, C.c_uint32]
+        L.mcq_eval_stats_text.restype = C.c_int64; L.mcq_eval_stats_text.argtypes = [sp, C.c_char_p, C.c_char_p, C.c_size_t]
         L.mcq_refdb_abundance_text.restype = C.c_int64
         L.mcq_refdb_abundance_text.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint32, C.c_char_p, C.c_size_t]
         L.mcq_default_hits_min.restype = C.c_uint32; L.mcq_default_hits_min.argtypes = [C.c_uint32]
@@ -204,6 +226,26 @@ class RefDb:
     def ancestor(self, key, rank):
         return int(lib().mcq_refdb_ancestor(self.h, int(key), int(rank)))
 
+    def ground_truth(self, header):
+        """taxon index a read's header names (its next ranked ancestor), or NO_TAXON: mcq_refdb_ground_truth"""
+        h = header.encode("latin-1") if isinstance(header, str) else header
+        return int(lib().mcq_refdb_ground_truth(self.h, h, len(h)))
+
+    def clade_keys(self, rank):
+        """u32 [n_targets]: every target's ancestor at `rank`, 0xFFFFFFFF where it has none (Workspace.set_exclusion)"""
+        out = np.zeros(self.info.n_targets, np.uint32)
+        if lib().mcq_refdb_clade_keys(self.h, int(rank), out.ctypes.data_as(C.c_void_p)) != 0:
+            raise RuntimeError(lib().mcq_host_last_error().decode())
+        return out
+
+    def taxon_clade(self, truth, rank):
+        """clade key of a resolved truth at `rank` (0xFFFFFFFF: no ancestor there; 0xFFFFFFFE: no truth): one entry of Workspace.set_query_clades"""
+        return int(lib().mcq_refdb_taxon_clade(self.h, int(truth), int(rank)))
+
+    def ranked_lca(self, a, b):
+        """taxon index of the ranked LCA of two taxa, NO_TAXON if either is NO_TAXON or they share no rank: mcq_refdb_ranked_lca"""
+        return int(lib().mcq_refdb_ranked_lca(self.h, int(a), int(b)))
+
     def lineages(self):
         """(lineage u32 [n_taxa, 21], rank u8 [n_taxa]): the table mcq_taxonomy_create takes"""
         n = self.info.n_taxa
@@ -223,6 +265,46 @@ class RefDb:
             raise RuntimeError(lib().mcq_host_last_error().decode())
         buf = C.create_string_buffer(n + 1)
         lib().mcq_refdb_abundance_text(self.h, c.ctypes.data_as(C.c_void_p), int(total), int(est_rank), buf, n + 1)
+        return buf.raw[:n].decode("latin-1")
+
+
+class EvalStats:
+    """mcq_eval_stats: the reference's classification_statistics (assign, assign_known_correct, accessors, summary text)"""
+
+    def __init__(self):
+        self.rec = EvalStatsRec()
+
+    def assign(self, assigned):
+        lib().mcq_eval_stats_assign(C.byref(self.rec), int(assigned))
+
+    def assign_known_correct(self, assigned, known, correct):
+        lib().mcq_eval_stats_assign_known_correct(C.byref(self.rec), int(assigned), int(known), int(correct))
+
+    def add(self, other):
+        lib().mcq_eval_stats_add(C.byref(self.rec), C.byref(other.rec))
+
+    def _get(self, name, *rank):
+        return getattr(lib(), "mcq_eval_stats_" + name)(C.byref(self.rec), *[int(r) for r in rank])
+
+    def total(self): return int(self._get("total"))
+    def unknown(self): return int(self._get("unknown"))
+    def unassigned(self): return int(self._get("assigned", RANK_NONE))
+    def assigned(self, rank=20): return int(self._get("assigned", rank))
+    def known(self, rank=20): return int(self._get("known", rank))
+    def correct(self, rank=20): return int(self._get("correct", rank))
+    def wrong(self, rank=20): return int(self._get("wrong", rank))
+    def unknown_rate(self): return float(self._get("unknown_rate"))
+    def unclassified_rate(self): return float(self._get("unclassified_rate"))
+    def known_rate(self, rank=20): return float(self._get("known_rate", rank))
+    def classification_rate(self, rank=20): return float(self._get("classification_rate", rank))
+    def precision(self, rank): return float(self._get("precision", rank))
+    def sensitivity(self, rank): return float(self._get("sensitivity", rank))
+
+    def text(self, prefix="# "):
+        """the summary's statistics block (show_taxon_statistics): mcq_eval_stats_text"""
+        n = lib().mcq_eval_stats_text(C.byref(self.rec), prefix.encode(), None, 0)
+        buf = C.create_string_buffer(n + 1)
+        lib().mcq_eval_stats_text(C.byref(self.rec), prefix.encode(), buf, n + 1)
         return buf.raw[:n].decode("latin-1")
 
 
