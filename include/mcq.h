@@ -68,7 +68,8 @@ enum {
                                       MCQ_QUIRK_SEQ_DROP needs on a table with sequence-level taxa) instead of the one selection
                                       in the order (hits, rank, position) that gives the same list        */
     MCQ_FORCE_LEAN_WAVE = 0x20000u, /* test hook / A-B: the first wave stage in its lean form: it answers the
-                                      reads of at most 256 locations and queues every other one for the later stages.  Only where that form exists (32-bit location words, P x M within a wave's
+                                      reads of at most 256 locations and queues every other one for the later stages.  Only where that form exists (a table of the default sketch geometry -- k 16, sketch 16, windows
+                                      128 / 113, DESIGN.md section 17 --, 32-bit location words, P x M within a wave's
                                       lanes, not with another MCQ_FORCE_* / MCQ_NO_WAVE16 hook): MCQ_E_UNSUPPORTED otherwise   */
     MCQ_FORCE_FULL_WAVE = 0x40000u, /* test hook / A-B: the first wave stage in its full form, whatever the batch before it
                                       suggests.  Same results with either flag and with neither                      */

@@ -389,6 +389,70 @@ __device__ __forceinline__ u32 range_width(u64 qlen, u64 insert_size_max, u32 tg
     return (u32)(2 + m / tgt_stride);
 }
 
+// Sketch geometry as a policy (like the location forms above): what a kernel asks for k, s, the window sizes and the window arithmetic
+// of sequences shorter than 2^31 bases.  GeomRt reads the table's values (DbDev); GeomDefault is the reference's default build
+// (-kmerlen 16 -sketchlen 16 -winlen 128 -winstride 113, same stride on the target side): literals, and divisions the compiler
+// turns into a multiplication of its own.  geom_is_default: the tables GeomDefault may stand for.
+#define MCQ_GEOM_DEFAULT_K 16u
+#define MCQ_GEOM_DEFAULT_S 16u
+#define MCQ_GEOM_DEFAULT_WINLEN 128u
+#define MCQ_GEOM_DEFAULT_STRIDE 113u
+struct GeomRt {
+    const DbDev& db;
+    __device__ __forceinline__ explicit GeomRt(const DbDev& d) : db(d) {}
+    __device__ __forceinline__ u32 k() const { return db.k; }
+    __device__ __forceinline__ u32 s() const { return db.s; }
+    __device__ __forceinline__ u32 winlen() const { return db.winlen; }
+    __device__ __forceinline__ u32 winstride() const { return db.winstride; }
+    __device__ __forceinline__ u32 tgt_winstride() const { return db.tgt_winstride; }
+    __device__ __forceinline__ u32 num_windows(u32 n) const { return num_windows32(n, db.winlen, db.winstride, db.magic_stride); }
+    __device__ __forceinline__ void window_of(u32 n, u32 j, u32& beg, u32& len) const { window_of32(n, db.winlen, db.winstride, db.magic_stride, j, beg, len); }
+    __device__ __forceinline__ u32 range_width(u64 qlen, u64 insert_size_max) const { return mcq::range_width(qlen, insert_size_max, db.tgt_winstride, db.magic_tgt_stride); }
+};
+struct GeomDefault {
+    static constexpr u32 W = MCQ_GEOM_DEFAULT_WINLEN, S = MCQ_GEOM_DEFAULT_STRIDE;
+    __device__ __forceinline__ explicit GeomDefault(const DbDev&) {}
+    __device__ __forceinline__ static constexpr u32 k() { return MCQ_GEOM_DEFAULT_K; }
+    __device__ __forceinline__ static constexpr u32 s() { return MCQ_GEOM_DEFAULT_S; }
+    __device__ __forceinline__ static constexpr u32 winlen() { return W; }
+    __device__ __forceinline__ static constexpr u32 winstride() { return S; }
+    __device__ __forceinline__ static constexpr u32 tgt_winstride() { return S; }
+    __device__ __forceinline__ static u32 num_windows(u32 n) {
+        if (n <= W) return 1;
+        const u32 nfull = (n - W) / S + 1;
+        return nfull + ((nfull * S < n) ? 1u : 0u);
+    }
+    __device__ __forceinline__ static void window_of(u32 n, u32 j, u32& beg, u32& len) {
+        if (n <= W) { beg = 0; len = n; return; }
+        const u32 nfull = (n - W) / S + 1;
+        beg = j * S;
+        len = (j < nfull) ? W : (n - beg);
+    }
+    __device__ __forceinline__ static u32 range_width(u64 qlen, u64 insert_size_max) {
+        const u64 m = qlen > insert_size_max ? qlen : insert_size_max;
+        if (m < (1ull << 31)) return 2 + (u32)m / S;
+        return (u32)(2 + m / S);
+    }
+};
+inline bool geom_is_default(const DbDev& d) {
+    return d.k == MCQ_GEOM_DEFAULT_K && d.s == MCQ_GEOM_DEFAULT_S && d.winlen == MCQ_GEOM_DEFAULT_WINLEN &&
+           d.winstride == MCQ_GEOM_DEFAULT_STRIDE && d.tgt_winstride == MCQ_GEOM_DEFAULT_STRIDE;
+}
+// The form a batch is given in, the same way: BatchRt tests the batch's words; BatchForm<PAIRED, PACKED> knows two of them (a batch
+// given as ranges is told apart at run time in both).
+struct BatchRt {
+    const BatchDev& b;
+    __device__ __forceinline__ explicit BatchRt(const BatchDev& x) : b(x) {}
+    __device__ __forceinline__ bool paired() const { return b.paired != 0; }
+    __device__ __forceinline__ bool packed() const { return b.packed != 0; }
+};
+template <bool PAIRED, bool PACKED>
+struct BatchForm {
+    __device__ __forceinline__ explicit BatchForm(const BatchDev&) {}
+    __device__ __forceinline__ static constexpr bool paired() { return PAIRED; }
+    __device__ __forceinline__ static constexpr bool packed() { return PACKED; }
+};
+
 // ------------------------------------------------------------------ wave primitives
 // number of set bits of a wave-wide mask below this lane (v_mbcnt_lo/hi: the lane id itself is mbcnt(~0))
 __device__ __forceinline__ u32 lane_rank(u64 mask) {
@@ -789,11 +853,13 @@ __device__ __forceinline__ u32 wave_sketch(const char* __restrict__ seq, u32 n, 
     wave_words_of_chars(c0, c1, lane, w, am);
     return wave_sketch_words(w, am, n, k, s, lane, tmp, dst);
 }
-// window [at, at + n) of the batch, whichever form the batch is in
+// window [at, at + n) of the batch, whichever form the batch is in (F: BatchRt, or the form as a type).  k and s are values: with
+// GeomDefault's literals the shifts by 32 - 2k and the tests against k fold away in wave_sketch_words, which is inlined here
+template <class F = BatchRt>
 __device__ __forceinline__ u32 wave_sketch_b(const BatchDev& b, u64 at, u32 n, u32 k, u32 s, u32 lane, u32* tmp, u32* dst) {
     if (n < k) return 0;
     u32 w, am;
-    if (b.packed) wave_words_of_packed(b, at, lane, w, am);
+    if (F(b).packed()) wave_words_of_packed(b, at, lane, w, am);
     else { u32 c0, c1; window_chars(b.bases + at, n, lane, c0, c1); wave_words_of_chars(c0, c1, lane, w, am); }
     return wave_sketch_words(w, am, n, k, s, lane, tmp, dst);
 }

@@ -499,29 +499,33 @@ struct ReadGeom {
     bool ovf;            // not for the first wave stage
     bool wide;           // 65..128 features (5..8 windows, e.g. 2 x 250 bp): second wave stage, two features per lane
 };
+// (G, F: the sketch geometry and the batch's form as the kernel knows them -- GeomRt / BatchRt: the table's and the batch's words)
+template <class G = GeomRt, class F = BatchRt>
 __device__ __forceinline__ ReadGeom read_geom(const DbDev& db, const BatchDev& b, u64 q, bool block_only) {
     ReadGeom g;
-    const u64 a = b.paired ? 2 * q : q;
+    const G geo(db); const F form(b);
+    const u64 a = form.paired() ? 2 * q : q;
     u64 e0, e1;
     seq_bounds(b.seq_off, b.ranges, a, g.o0, e0);
-    if (b.paired) seq_bounds(b.seq_off, b.ranges, a + 1, g.o1, e1); else { g.o1 = e0; e1 = e0; }
+    if (form.paired()) seq_bounds(b.seq_off, b.ranges, a + 1, g.o1, e1); else { g.o1 = e0; e1 = e0; }
     const u64 l1 = e0 - g.o0, l2 = e1 - g.o1;
     g.qlen = l1 + l2;
     g.ovf = block_only || ((l1 | l2) >> 20) != 0;
     g.n1 = (u32)l1; g.n2 = (u32)l2; g.nw1 = 0; g.nw2 = 0; g.wide = false;
     if (!g.ovf) {
-        g.nw1 = num_windows32(g.n1, db.winlen, db.winstride, db.magic_stride);
-        g.nw2 = b.paired ? num_windows32(g.n2, db.winlen, db.winstride, db.magic_stride) : 0;
-        g.ovf = (g.nw1 + g.nw2) * db.s > 64;
-        g.wide = g.ovf && (g.nw1 + g.nw2) * db.s <= 128;
+        g.nw1 = geo.num_windows(g.n1);
+        g.nw2 = form.paired() ? geo.num_windows(g.n2) : 0;
+        g.ovf = (g.nw1 + g.nw2) * geo.s() > 64;
+        g.wide = g.ovf && (g.nw1 + g.nw2) * geo.s() <= 128;
     }
     return g;
 }
 // window w of the read (mate 1's windows, then mate 2's): offset into bases and length
+template <class G = GeomRt>
 __device__ __forceinline__ void window_span(const DbDev& db, const ReadGeom& g, u32 w, u64& at, u32& wl) {
     const bool m2 = w >= g.nw1;
     u32 beg;
-    window_of32(m2 ? g.n2 : g.n1, db.winlen, db.winstride, db.magic_stride, m2 ? w - g.nw1 : w, beg, wl);
+    G(db).window_of(m2 ? g.n2 : g.n1, m2 ? w - g.nw1 : w, beg, wl);
     at = (m2 ? g.o1 : g.o0) + beg;
 }
 // Top lists after a raw sort (32-bit keys).  The run heads are compacted to the front of the hit words; when they
@@ -607,15 +611,23 @@ __device__ __forceinline__ void tap_distinct(const DebugDev& dbg, const u32* SK,
 // as this stage's full form would: no lists in 6 or 8 registers per lane, no raw-sort fallback, no remembered failure, no direct
 // entry, no profiling hooks.  (Handing on more -- the reads of more than 64 distinct keys, so that the weighted sweep and the
 // wide top lists go too -- costs more in the second stage than it saves here: DESIGN.md section 15.)
+// The lean form is also compiled for one sketch geometry and one form of batch: GeomDefault (k, s, window length and both strides
+// of the reference's default build as literals) and BatchForm<PAIRED, PACKED>, where every other instantiation reads the table's and
+// the batch's words (GeomRt, BatchRt).  plan_launch gives a table of any other geometry the full form alone.
 // Which form runs is the batch before's word (CountersDev::direct_mode bit MCQ_MODE_LEAN; both are launched and the other one
 // returns at once) unless MCQ_HOOK_ONLY_LAUNCH says this launch is the only one.
-template <class KeyT, int LCAP, bool TAP = false, bool SH = false, bool GW = false, int BSH = -1, int NL = 1, bool LEAN = false, bool EXCL = false>
+template <class KeyT, int LCAP, bool TAP = false, bool SH = false, bool GW = false, int BSH = -1, int NL = 1, bool LEAN = false, bool EXCL = false,
+          bool PAIRED = false, bool PACKED = false>
 __global__ __launch_bounds__(256, sizeof(KeyT) == 4 ? (NL > 1 ? 5 : MCQ_WAVE_OCC) : 5) void k_query_wave(DbDev db, BatchDev b, OptDev opt, OutDev out,
                                                     CountersDev* ctr, u32* ovf_list, DebugDev dbg, ShardDev sh, GwDev gwd, ExclDev exd) {
     static_assert(LCAP == 512, "wave path: 8 keys per lane at most, entry index packed into 9 bits");
     static_assert(!GW || sizeof(KeyT) == 4, "the global-window form is a 32-bit word");
     static_assert(!LEAN || (sizeof(KeyT) == 4 && !TAP && !SH && NL == 1), "the lean form: 32-bit words, plain launches");
     static_assert(!EXCL || (!TAP && !SH && NL == 1 && !LEAN), "clade exclusion: plain launches of the full form, lists in a wave's lanes");
+    static_assert(LEAN || (!PAIRED && !PACKED), "only the lean form knows the batch's form at compile time");
+    using G = std::conditional_t<LEAN, GeomDefault, GeomRt>;                      // (plan_launch: a lean launch only on a table of the default geometry)
+    using F = std::conditional_t<LEAN, BatchForm<PAIRED, PACKED>, BatchRt>;
+    const G geo(db);
     constexpr u32 kKeepT = LEAN ? 256u : (u32)LCAP;   // the longest list this stage answers itself
     if (!(opt.hooks & MCQ_HOOK_ONLY_LAUNCH) && ((ctr->direct_mode & MCQ_MODE_LEAN) != 0) != LEAN) return;     // the other form's batch
     using LF = typename LocOf<KeyT, GW>::type;
@@ -684,7 +696,7 @@ __global__ __launch_bounds__(256, sizeof(KeyT) == 4 ? (NL > 1 ? 5 : MCQ_WAVE_OCC
         }
     }
     for (u64 q = (u64)blockIdx.x * 4 + wave; q < b.nq; q += nwaves) {
-        const ReadGeom g = read_geom(db, b, q, (hooks & MCQ_HOOK_BLOCK_ONLY) != 0);
+        const ReadGeom g = read_geom<G, F>(db, b, q, (hooks & MCQ_HOOK_BLOCK_ONLY) != 0);
         bool ovf = g.ovf;
         u32 myf = MCQ_EMPTY, nfeat = 0, T = 0, len = 0, pos = 0;
         u64 off = 0;
@@ -695,8 +707,8 @@ __global__ __launch_bounds__(256, sizeof(KeyT) == 4 ? (NL > 1 ? 5 : MCQ_WAVE_OCC
             } else {
             for (u32 w = 0; w < g.nw1 + g.nw2; ++w) {
                 u64 at; u32 wl;
-                window_span(db, g, w, at, wl);
-                nfeat += wave_sketch_b(b, at, wl, db.k, db.s, lane, sk_tmp, feat + nfeat);
+                window_span<G>(db, g, w, at, wl);
+                nfeat += wave_sketch_b<F>(b, at, wl, geo.k(), geo.s(), lane, sk_tmp, feat + nfeat);
             }
             if (lane < nfeat) myf = feat[lane];
             if (stop == 1) { if (myf == 12345u) out.ncand[q] = nfeat; continue; }
@@ -736,7 +748,7 @@ __global__ __launch_bounds__(256, sizeof(KeyT) == 4 ? (NL > 1 ? 5 : MCQ_WAVE_OCC
         if (T == 0) { if (lane == 0) out.ncand[q] = 0; continue; }
 
         wave_sync();                                   // feat[] (aliasing hits) has been consumed
-        const u32 numWindows = range_width(g.qlen, opt.insert_size_max, db.tgt_winstride, db.magic_tgt_stride);
+        const u32 numWindows = geo.range_width(g.qlen, opt.insert_size_max);
         const auto& hdb = heads_db<EXCL>(db, exd, q);  // what the top lists read the heads' taxa from (EXCL: without the query's own clade)
         if constexpr (sizeof(KeyT) == 4) {
             if (LEAN || (T <= MCQ_DEDUP_MAX_T && !(hooks & MCQ_HOOK_RAW_SORT))) {
@@ -1894,7 +1906,11 @@ static int plan_launch(const mcq_db* db, const OptDev& od_req, bool tap, bool sh
     if (p.many) { p.first.big = 0; p.first.seg = (u32)pow2ceil64(od_in.max_cand); p.first.hooks |= MCQ_HOOK_NO_WAVE16; }
     // The lean form of the first wave stage exists for plain launches on 32-bit words with the lists in a wave's lanes, no route hook and no stop
     // stage.  Without a request both forms are launched, each guarded by the batch before's word (the first batch of a workspace runs full).
-    const bool lean_can = compact && !tap && !sharded && !od_in.big && !route_hook && (od_in.hooks >> MCQ_HOOK_STOP_SHIFT) == 0;
+    // It is compiled for the reference's default sketch geometry (GeomDefault: k, s, window length and both strides as literals): a table
+    // built with any other has no lean form.
+    const bool lean_can = compact && !tap && !sharded && !od_in.big && !route_hook && (od_in.hooks >> MCQ_HOOK_STOP_SHIFT) == 0 && geom_is_default(db->d);
+    if (req == LeanReq::LeanOnly && !geom_is_default(db->d))
+        return fail(MCQ_E_UNSUPPORTED, "MCQ_FORCE_LEAN_WAVE: the lean first wave stage is compiled for the default sketch geometry (k 16, sketch 16, windows 128 / 113, target stride 113); this table was built with another");
     if (req == LeanReq::LeanOnly && !lean_can) return fail(MCQ_E_UNSUPPORTED, "MCQ_FORCE_LEAN_WAVE: this launch has no lean first wave stage (64-bit words, lists beyond a wave's lanes, tap or sharded)");
     const bool lean_auto = lean_can && req == LeanReq::Auto && MCQ_LEAN_AUTO && !getenv("MCQ_NO_LEAN_WAVE");
     p.lean = req == LeanReq::LeanOnly || lean_auto;          // (lean_can excludes `many`)
@@ -1934,13 +1950,18 @@ int mcq::launch_query(const mcq_db* db, mcq_ws* ws, const BatchDev& b, const Opt
     rc = with_loc_form(db, [&](auto L) -> int {
         using Key = typename decltype(L)::Key;
         constexpr bool GW = decltype(L)::gw;
-        auto first = [&](auto TAP, auto SH, auto BSH, auto NL, auto LEAN, auto EX, u32 g) {
-            hipLaunchKernelGGL((k_query_wave<Key, kLcapWave, TAP, SH, GW, BSH, NL, LEAN, EX>), dim3(g), dim3(256), 0, st, D, b, p.first, o, ws->ctr, ws->ovf_list, dbg, sh, db->g, ex);
+        auto first = [&](auto TAP, auto SH, auto BSH, auto NL, auto LEAN, auto EX, u32 g, auto PAIRED, auto PACKED) {
+            hipLaunchKernelGGL((k_query_wave<Key, kLcapWave, TAP, SH, GW, BSH, NL, LEAN, EX, PAIRED, PACKED>), dim3(g), dim3(256), 0, st, D, b, p.first, o, ws->ctr, ws->ovf_list, dbg, sh, db->g, ex);
         };
-        if (p.full) by_role([&](auto TAP, auto SH, auto BSH, auto EX) { first(TAP, SH, BSH, IntC<1>{}, No{}, EX, grid); });
+        if (p.full) by_role([&](auto TAP, auto SH, auto BSH, auto EX) { first(TAP, SH, BSH, IntC<1>{}, No{}, EX, grid, No{}, No{}); });
         if constexpr (sizeof(Key) == 4) {   // the NL and LEAN instantiations: 32-bit words, plain launches
-            if (p.many) with_layout(db, [&](auto BSH) { first(No{}, No{}, BSH, IntC<4>{}, No{}, No{}, grid_for(ws->cap_wave_many, want)); });
-            if (p.lean) with_layout(db, [&](auto BSH) { first(No{}, No{}, BSH, IntC<1>{}, Yes{}, No{}, grid); });
+            if (p.many) with_layout(db, [&](auto BSH) { first(No{}, No{}, BSH, IntC<4>{}, No{}, No{}, grid_for(ws->cap_wave_many, want), No{}, No{}); });
+            // the lean form knows the batch's form too: one instantiation per (layout, paired, packed)
+            if (p.lean) with_layout(db, [&](auto BSH) {
+                auto lean = [&](auto PAIRED, auto PACKED) { first(No{}, No{}, BSH, IntC<1>{}, Yes{}, No{}, grid, PAIRED, PACKED); };
+                if (b.paired) { if (b.packed) lean(Yes{}, Yes{}); else lean(Yes{}, No{}); }
+                else { if (b.packed) lean(No{}, Yes{}); else lean(No{}, No{}); }
+            });
         }
         rc = tm.mark(); if (rc) return rc;
         if constexpr (sizeof(Key) == 4) {   // second wave stage (back queue); no queue for 64-bit keys
