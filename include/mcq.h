@@ -246,9 +246,11 @@ int mcq_ws_wait(mcq_ws* ws, uint64_t ticket);
 int mcq_ws_sync(mcq_ws* ws, void* stream, mcq_stats* stats);
 
 /* ---- staged entry points (feature-sharded multi-GPU path) ---------
- * mcq_sketch  : rows 1-5.  features[w * sketch_size + i], n_feat[w] for window w of
- *               the batch; win_query[w] = query index of window w; returns the number
- *               of windows in *n_windows (device scalar when MCQ_DEVICE_PTRS).
+ * mcq_count_windows: row 1.  win_off[i] = first window of sequence i among the windows of the batch, win_off[n_seqs] =
+ *               their number (an empty sequence has one, empty, window).
+ * mcq_sketch  : rows 1-5.  win_off comes from mcq_count_windows.  One row of sketch_size features per window:
+ *               features[w * sketch_size + i] for i < n_feat[w], ascending; the unused slots of a row are 0xFFFFFFFF.
+ *               ASCII batches only (MCQ_BATCH_PACKED is rejected with MCQ_E_ARG).
  * mcq_lookup_*: rows 6-7 on the owning shard (counts, then gather).
  * mcq_assemble / mcq_reduce: rows 8-11 on the home GPU.                              */
 int mcq_count_windows(const mcq_db* db, const mcq_batch* in, uint64_t* win_off /* [n_seqs+1] */, void* stream);

@@ -352,11 +352,13 @@ __device__ __forceinline__ u32 canonical(u32 s, u32 k) {
 }
 
 // number of windows of a sequence of n bases (src/dna_encoding.h:259-276)
-__device__ __host__ __forceinline__ u32 num_windows(u64 n, u32 W, u32 S) {
+// (64 bits: mcq_count_windows takes any sequence, and 2^32 * S bases and more have more windows than a u32 holds)
+__device__ __host__ __forceinline__ u64 num_windows64(u64 n, u32 W, u32 S) {
     if (n <= W) return 1;
     u64 nfull = (n - W) / S + 1;
-    return (u32)(nfull + ((nfull * S < n) ? 1 : 0));
+    return nfull + ((nfull * S < n) ? 1 : 0);
 }
+__device__ __host__ __forceinline__ u32 num_windows(u64 n, u32 W, u32 S) { return (u32)num_windows64(n, W, S); }
 // window j of a sequence of n bases -> [beg, beg+len)
 __device__ __forceinline__ void window_of(u64 n, u32 W, u32 S, u32 j, u64& beg, u32& len) {
     if (n <= W) { beg = 0; len = (u32)n; return; }

@@ -89,7 +89,7 @@ template int mcq::device_exclusive_scan<u64>(const u64*, u64*, u64, hipStream_t,
 // ------------------------------------------------------------------ staged kernels (sharded path, DB build)
 __global__ void k_count_windows(const u64* seq_off, u32 ranges, u64 n_seqs, u32 W, u32 S, u64* cnt) {
     u64 i = (u64)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i < n_seqs) { u64 bg, en; seq_bounds(seq_off, ranges, i, bg, en); cnt[i] = num_windows(en - bg, W, S); }
+    if (i < n_seqs) { u64 bg, en; seq_bounds(seq_off, ranges, i, bg, en); cnt[i] = num_windows64(en - bg, W, S); }
 }
 
 // one wave per window: window w belongs to the last sequence i with win_off[i] <= w

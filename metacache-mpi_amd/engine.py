@@ -262,12 +262,13 @@ class Database:
         return int(lib().mcq_db_bytes(self.h))
 
     # ---- staged entry points (device pointers only) -------------------------------
-    def count_windows(self, bases_ptr, seq_off_ptr, n_seqs, win_off_ptr, stream=None):
-        b = Batch(n_seqs, bases_ptr, seq_off_ptr, 0, MCQ_DEVICE_PTRS)
+    def count_windows(self, bases_ptr, seq_off_ptr, n_seqs, win_off_ptr, stream=None, flags=0):
+        """flags: more batch flags (MCQ_BATCH_RANGES); the same for sketch and assemble"""
+        b = Batch(n_seqs, bases_ptr, seq_off_ptr, 0, MCQ_DEVICE_PTRS | flags)
         _chk(lib().mcq_count_windows(self.h, C.byref(b), win_off_ptr, stream))
 
-    def sketch(self, bases_ptr, seq_off_ptr, n_seqs, win_off_ptr, features_ptr, n_feat_ptr, stream=None):
-        b = Batch(n_seqs, bases_ptr, seq_off_ptr, 0, MCQ_DEVICE_PTRS)
+    def sketch(self, bases_ptr, seq_off_ptr, n_seqs, win_off_ptr, features_ptr, n_feat_ptr, stream=None, flags=0):
+        b = Batch(n_seqs, bases_ptr, seq_off_ptr, 0, MCQ_DEVICE_PTRS | flags)
         _chk(lib().mcq_sketch(self.h, C.byref(b), win_off_ptr, features_ptr, n_feat_ptr, stream))
 
     def lookup_count(self, features_ptr, n, list_len_ptr, list_src_ptr=None, stream=None):
@@ -290,8 +291,8 @@ class Database:
         return lo.as_dict()
 
     def assemble(self, n_lists, list_len_ptr, src_slot_ptr, n_slots, src_locs_ptr, bases_ptr, seq_off_ptr, n_seqs, paired,
-                 win_off_ptr, loc_off_ptr, query_len_ptr, dst_locs_ptr, stream=None):
-        b = Batch(n_seqs, bases_ptr, seq_off_ptr, 1 if paired else 0, MCQ_DEVICE_PTRS)
+                 win_off_ptr, loc_off_ptr, query_len_ptr, dst_locs_ptr, stream=None, flags=0):
+        b = Batch(n_seqs, bases_ptr, seq_off_ptr, 1 if paired else 0, MCQ_DEVICE_PTRS | flags)
         _chk(lib().mcq_assemble(self.h, n_lists, list_len_ptr, src_slot_ptr, n_slots, src_locs_ptr, C.byref(b), win_off_ptr,
                                 loc_off_ptr, query_len_ptr, dst_locs_ptr, stream))
 
