@@ -584,6 +584,59 @@ static const uint32_t MCQ_CLADE_KEEP_ALL = 0xFFFFFFFEu;   /* query_clade only: n
 int mcq_ws_set_exclusion(mcq_ws* ws, const uint32_t* tgt_clade, uint32_t n_targets, uint32_t flags);
 int mcq_ws_set_query_clades(mcq_ws* ws, const uint32_t* query_clade, uint64_t n_queries, uint32_t flags);
 
+/* ---- per-target window hit lists: what `-hits-per-seq` prints (csrc/mcq_target_hits.hip) ---------------------------------------
+ * matches_per_target::insert (src/matches_per_target.h:111-155) keeps, for a candidate of a read, the windows of the candidate's
+ * range with the number of the read's matches on each.  mcq_query gives out no window of a target (after a fold not even the
+ * range), so mcq_target_hits works a batch through rows 1-7 once more and keeps only the locations of the targets the caller names:
+ *   targets     device, [n_queries * n_slots], n_slots 1..MCQ_TARGET_HITS_MAX_SLOTS; MCQ_TARGET_UNUSED = the slot is unused.  The
+ *               targets of a query should differ; a target named twice is answered twice.
+ *   out_ranges  device, [n_queries * n_slots]: the read's per-target candidate on that target (for_all_contiguous_window_ranges,
+ *               src/candidates.h:118-180: the first strictly best contiguous range of at most numWindows = 2 + max(len1 + len2,
+ *               insert_size_max) / target stride windows among all windows of the target the read hits).  n_win = hits = 0 when the
+ *               read has no location on the target, when the target does not exist, and for an unused slot (tgt is copied).
+ *   out_counts  device, [n_queries * n_slots * range_cap]: counts[i] = the read's matches on (tgt, win_beg + i) for i < n_win, 0 for a
+ *               window of the range without a match.  The words from n_win on are left as the caller set them.
+ *   status      device, [n_queries]: 0, or MCQ_TARGET_HITS_* bits of a query that exceeded a capacity.  Such a query gets n_win = 0
+ *               in ALL its slots and is counted like a query that overflowed the workspace: the next mcq_ws_sync(ws) returns
+ *               MCQ_E_CAPACITY.  Nothing is answered wrongly in silence.
+ * The capacities: the range width numWindows of the query exceeds range_cap (mcq_target_hits_range_cap gives the width of the
+ * longest query of a batch: pass that); the query has more than MCQ_TARGET_HITS_MAX_KEYS distinct (target, window) pairs on its slot
+ * targets; a window id inside a target of 2^28 or more, or a sequence of 2^31 bases or more.
+ * Batches as mcq_query takes them (ASCII or MCQ_BATCH_PACKED, offsets or MCQ_BATCH_RANGES, paired or not) but device pointers only
+ * (MCQ_DEVICE_PTRS); every location form and bucket layout; any sketch geometry the handle accepts.  The call only enqueues work on
+ * `stream`.  It does not touch the counters mcq_ws_sync reports except the capacity count.
+ * THE CAPACITY COUNT IS THE WORKSPACE'S AND IT STAYS: this call adds to it and never zeroes it (a query enqueued in front of it on
+ * the same stream may have counted too, and that must not be lost); only the next mcq_query / mcq_reduce on the workspace zeroes
+ * it.  So after one reported query EVERY later mcq_ws_sync on the workspace returns MCQ_E_CAPACITY -- also behind later
+ * mcq_target_hits calls whose queries were all answered -- until a query call has run; and a sync that comes after that query call
+ * no longer reports it.  A caller that uses this entry point without mcq_query reads status[] (which is exact per call and per
+ * query) and treats the sync's code as "some call since the last query reported one".  The text of that error speaks of the
+ * workspace's per-query capacity; here it means the capacities above.  A workspace under clade exclusion (mcq_ws_set_exclusion) is not looked at: excluded
+ * targets never become candidates, so a caller that names candidates' targets never names one.                                     */
+#define MCQ_TARGET_HITS_MAX_SLOTS 16u
+#define MCQ_TARGET_HITS_MAX_KEYS 1024u   /* distinct (target, window) pairs of one query over all its slot targets */
+#define MCQ_TARGET_UNUSED 0xFFFFFFFFu
+enum { MCQ_TARGET_HITS_RANGE = 1u,      /* status: the query's range width exceeds range_cap                          */
+       MCQ_TARGET_HITS_KEYS = 2u,       /* ... more than MCQ_TARGET_HITS_MAX_KEYS distinct (target, window) pairs      */
+       MCQ_TARGET_HITS_WINDOW = 4u };   /* ... a window id >= 2^28 inside a slot target, or a sequence of >= 2^31 bases */
+typedef struct {
+    uint32_t tgt;
+    uint32_t hits;              /* matches inside the range (match_candidate::hits)  */
+    uint32_t win_beg;           /* first window of the range                          */
+    uint32_t n_win;             /* its width: win_end = win_beg + n_win - 1; 0 = none */
+} mcq_target_range;
+/* range width of a query of `longest_query` bases (both mates) = the range_cap a batch whose longest query that is needs */
+uint32_t mcq_target_hits_range_cap(const mcq_db* db, uint64_t longest_query, uint64_t insert_size_max);
+int mcq_target_hits(const mcq_db* db, mcq_ws* ws, const mcq_batch* in, const uint32_t* targets, uint32_t n_slots,
+                    uint64_t insert_size_max, uint32_t range_cap, mcq_target_range* out_ranges, uint32_t* out_counts,
+                    uint32_t* status, void* stream);
+/* The slot targets of a batch from its device results (mcq_query's `out` with MCQ_DEVICE_PTRS): per query the targets of its
+ * sequence-level candidates (key bit 31) with hits >= hits_min, in list order, the other slots MCQ_TARGET_UNUSED -- the candidates
+ * matches_per_target::insert takes.  tax2tgt (device, [n_taxa]): target id of taxon index (key & 0x7FFFFFFF), MCQ_TARGET_UNUSED for
+ * a taxon that is no target (mcq_refdb_tax2tgt of include/mcq_host.h makes it).  Only enqueues work on `stream`.                  */
+int mcq_target_slots(const mcq_result* cands, uint64_t n_queries, uint32_t max_cand, uint32_t hits_min,
+                     const uint32_t* tax2tgt, uint32_t n_taxa, uint32_t* targets, uint32_t n_slots, void* stream);
+
 /* ---- debug / parity taps ------------------------------------------------------------
  * Row 5 in isolation is mcq_count_windows + mcq_sketch above (the sketches of every window).
  * Rows 7-8 in isolation: the sorted match list of every query (what merge_sort returns,

@@ -190,6 +190,44 @@ int mcq_refdb_lineages(const mcq_refdb* db, uint32_t* lineage, uint8_t* rank);
 int64_t mcq_refdb_abundance_text(const mcq_refdb* db, const uint64_t* counts, uint64_t total, uint32_t est_rank,
                                  char* buf, size_t cap);
 
+/* ---- the table of `-hits-per-seq`: matches_per_target (src/matches_per_target.h:43-188) and show_matches_per_targets
+ * (src/printing.cpp:437-469).  For every reference sequence that is a candidate of some read the reads that hit it, and for each
+ * read the windows of the read's candidate range on it with a hit count per window.  The ranges and counts come from
+ * mcq_target_hits of include/mcq.h; this is the accumulator and the writer.
+ * mcq_hits_table_add: one read on one target -- query id, target, the range [win_beg, win_beg + n_win) and counts[n_win].  Windows
+ * with a count of 0 are dropped (the reference's vector holds only windows with a match); a range without any is not an entry.
+ * mcq_hits_table_merge: matches_per_target::merge -- moves every entry of `from` into `into` (per-thread accumulators).
+ * mcq_hits_table_text: sort_match_lists (:172-184: a target's entries by first window, then last window, then query id), then the
+ * block of show_matches_per_targets: the three lines behind `comment` and one row per target -- show_taxon of the target (the
+ * reference's src/printing.cpp:305-330 with the taxon print mode below), `column`, windows_in_sequence (the `windows` field of the
+ * target's taxon on the rank that owns it), `column`, qid/win:hits/win:hits...,qid/...  Text to buf as mcq_refdb_abundance_text
+ * does; returns its length (cap = 0: only that), negative on error.
+ * ROW ORDER: ascending target id.  The reference iterates an unordered_map keyed by taxon pointers, so its row order is not
+ * defined by its inputs; a comparison sorts the rows.
+ * mcq_taxon_print: how a taxon is written (taxon_print_mode, src/query_options.h:68-71): show_ranks = the "<rank>:" prefix, body
+ * 0 name / 1 id / 2 name(id); lineage != 0: every rank from max(lowest_rank, the taxon's) to highest_rank, else that one rank. */
+typedef struct mcq_hits_table mcq_hits_table;
+typedef struct { uint32_t show_ranks, body, lineage, lowest_rank, highest_rank; } mcq_taxon_print;
+int mcq_hits_table_create(mcq_hits_table** out);
+int mcq_hits_table_add(mcq_hits_table* t, uint64_t query_id, uint32_t target, uint32_t win_beg, uint32_t n_win, const uint32_t* counts);
+int mcq_hits_table_merge(mcq_hits_table* into, mcq_hits_table* from);
+uint64_t mcq_hits_table_targets(const mcq_hits_table* t);
+uint64_t mcq_hits_table_entries(const mcq_hits_table* t);
+int64_t mcq_hits_table_text(mcq_hits_table* t, const mcq_refdb* db, const char* comment, const char* column,
+                            const mcq_taxon_print* mode, char* buf, size_t cap);
+/* The same block handed to `sink` piece by piece -- the three head lines, then one piece per row -- so that a table that has grown
+ * with the input is formatted once and never held as one text (mcq_query_cli writes it this way; mcq_hits_table_text with its
+ * length-first convention formats twice).  sink returns 0 to go on; anything else ends the call with an error.  The lists are
+ * sorted once: a later call without an add or merge in between does not sort again.                                        */
+typedef int (*mcq_text_sink)(void* user, const char* data, size_t n);
+int mcq_hits_table_write(mcq_hits_table* t, const mcq_refdb* db, const char* comment, const char* column,
+                         const mcq_taxon_print* mode, mcq_text_sink sink, void* user);
+int mcq_hits_table_free(mcq_hits_table* t);
+/* the sequence-level taxon key (bit 31 set) of a target, MCQ_NO_TAXON if it has none; and the way back for the device: out[n_taxa],
+ * target id of every taxon index that is a target's sequence-level taxon, MCQ_NO_TAXON for the others (mcq_target_slots) */
+uint32_t mcq_refdb_target_key(const mcq_refdb* db, uint32_t target);
+int mcq_refdb_tax2tgt(const mcq_refdb* db, uint32_t* out /* [n_taxa] */);
+
 /* ---- read files in chunks (mcq_query_cli's input stage) -------------------------------------------------------------
  * mcq_read_stream_fill puts into buf (cap bytes) first the bytes that the last fill left unconsumed, then read()s of the
  * file until buf holds `want` bytes (want <= cap) or the file ends: *len bytes, *eof = 1 when buf[0 .. *len) runs to the end

@@ -13,6 +13,7 @@ _UNITS = {
     os.path.join(_CSRC, "mcq_table.hip"): _INTERNAL,       # mcq_db_*
     os.path.join(_CSRC, "mcq_stages.hip"): _INTERNAL,      # staged and routing entry points, batch preparation
     os.path.join(_CSRC, "mcq_shard.hip"): _INTERNAL,       # mcq_shard_*
+    os.path.join(_CSRC, "mcq_target_hits.hip"): _INTERNAL, # per-target window hit lists (-hits-per-seq)
     os.path.join(_CSRC, "mcq_build.hip"): [_HDR],          # table construction (rocPRIM sorts)
     os.path.join(_CSRC, "mcq_classify.hip"): [os.path.join(_CSRC, "mcq_classify.hpp"), _HDR],   # classification + taxon counts
 }

@@ -15,6 +15,9 @@
 //                                              estimate_abundance src/classification.cpp:362-428 (mcq_refdb_abundance_text)
 //         after the mapping lines, into the -out file or the -abundances FILE (src/mode_query.cpp:59-117); the counts come
 //         from the device (mcq_classify), checked against the host classification's total
+//   * -hits-per-seq [FILE] (mcq_query_cli only)  show_matches_per_targets src/printing.cpp:437-469 (mcq_hits_table_text) after the
+//         mapping lines and in front of the abundance tables (src/classification.cpp:847-862), into the -out file or FILE; the
+//         query_id column of the TABLE_LAYOUT and of every mapping line, two parameter lines
 //   * the summary                              show_summary             src/printing.cpp:622-641,
 //                                              show_taxon_statistics    src/printing.cpp:522-600 (mcq_eval_stats_text)
 //   * -exclude RANK / -ground-truth / -precision (mcq_query_cli only; get_evaluation_options, src/query_options.cpp:190-213):
@@ -30,7 +33,8 @@
 // usage: mcq_query_cli <dbprefix> <n_ranks> <file|directory>... [-pairfiles | -pairseq] [-splitout PREFIX] [-lowest R] [-highest R]
 //            [-maxcand N] [-hitmin N] [-hitdiff X] [-insertsize N] [-threads N] [-tophits] [-taxids] [-taxids-only] [-omit-ranks]
 //            [-lineage] [-mapped-only] [-nomap] [-noquirks] [-abundances [FILE]] [-abundance-per R] [-out FILE] [-batch N]
-//            [-batch-bases N] [-read-chunk BYTES] [-reader gpu|host] [-exclude RANK] [-ground-truth] [-precision] [-help]
+//            [-batch-bases N] [-read-chunk BYTES] [-reader gpu|host] [-exclude RANK] [-ground-truth] [-precision] [-hits-per-seq [FILE]]
+//            [-help]
 // (inputs: every argument up to the first option; a directory stands for the files in it (files_in_directory below).  -pairseq
 //  without -pairfiles comes first: every file is interleaved pairs, also the two of `r1 r2` and the one of `r1 -`.  Without it,
 //  `r1 r2` alone is one pair of files in the given order and `r1 -` one single-end file.  Otherwise -pairfiles sorts the names and pairs
@@ -85,6 +89,8 @@ struct Options {
     std::string abundance_file;          // ... its FILE (cleared when it names the -out file: src/query_options.cpp:355)
     uint32_t abundance_rank = MCQ_RANK_NONE;   // -abundance-per R: the estimate to rank R (< root)
     bool tax_counts() const { return abundances || abundance_rank != MCQ_RANK_NONE; }
+    bool hits_per_seq = false;           // -hits-per-seq [FILE]: the per-reference window hit lists, and the query_id column
+    std::string hits_file;               // ... its FILE (cleared when it names the -out file: src/query_options.cpp:353)
     uint32_t exclude_rank = MCQ_RANK_NONE;     // -exclude R (< root): drop the hits on the read's own clade at R
     bool ground_truth = false, precision = false;   // -ground-truth: the truth_ column; -precision: the evaluation statistics
     bool wants_truth() const { return ground_truth || precision || exclude_rank != MCQ_RANK_NONE; }   // prepare_evaluation, src/classification.cpp:172-177
@@ -168,10 +174,17 @@ static const char* const kQueryUsage =
     "  -precision       known / correct / precision / sensitivity per rank in the summary\n"
     "                   The truth is resolved against the whole database and kept up to the evaluation (the reference's\n"
     "                   MPI program resolves it per shard and evaluates without it).\n"
+    "where the reads land:\n"
+    "  -hits-per-seq [FILE]  (mcq_query_cli only; mcq_query_mpi rejects it and names mcq_query_cli; aliases -hitsperseq, -hits_per_seq,\n"
+    "                   -hits-per-sequence, ...) after the mapping lines, or into FILE: for every reference sequence that is a\n"
+    "                   candidate of some read the reads that hit it, as queryid/window:hits/window:hits...; a query_id column in\n"
+    "                   front of every mapping line.  Rows in ascending target order.  Host memory grows with the input (one\n"
+    "                   entry per read and candidate is kept until the end, as in the reference).  A read with more than %u\n"
+    "                   distinct (sequence, window) pairs on its candidates ends the run with an ABORT line that names it.\n"
     "rejected:        -taxon-coverage (both programs): the coverage statistics are not reproduced\n";
 
 static bool parse_options(int argc, char** argv, Options& o) {
-    for (int a = 1; a < argc; ++a) if (std::string(argv[a]) == "-help" || std::string(argv[a]) == "--help" || std::string(argv[a]) == "-h") { std::fputs(kQueryUsage, stdout); return false; }
+    for (int a = 1; a < argc; ++a) if (std::string(argv[a]) == "-help" || std::string(argv[a]) == "--help" || std::string(argv[a]) == "-h") { std::printf(kQueryUsage, (unsigned)MCQ_TARGET_HITS_MAX_KEYS); return false; }   // (the text's one %u: the kernel's key capacity)
     std::vector<std::string> named;                      // argv[3 ..] up to the first option
     int i = 3;
     for (; i < argc && !(argv[i][0] == '-' && argv[i][1] != '\0'); ++i) named.push_back(argv[i]);
@@ -218,6 +231,10 @@ static bool parse_options(int argc, char** argv, Options& o) {
         else if (a == "-abundance-per" || a == "-abundances-per" || a == "-abundance_per" || a == "-abundances_per") {
             const uint32_t r = mcq_rank_from_name(next()); if (r < MCQ_RANK_ROOT) o.abundance_rank = r;
         }
+        else if (opt_named(a, {"-hits-per-seq", "-hitsperseq", "-hits_per_seq", "-hits-per-sequence", "-hitspersequence", "-hits_per_sequence"})) {   // src/query_options.cpp:299-306
+            o.hits_per_seq = true;
+            if (i + 1 < argc && argv[i + 1][0] != '-') o.hits_file = argv[++i];
+        }
         else if (a == "-exclude") { const uint32_t r = mcq_rank_from_name(next()); if (r < MCQ_RANK_ROOT) o.exclude_rank = r; }   // src/query_options.cpp:205-210
         else if (opt_named(a, {"-ground-truth", "-ground_truth", "-groundtruth"})) o.ground_truth = true;                       // :196-198
         else if (a == "-precision") o.precision = true;                                                                         // :203
@@ -229,6 +246,7 @@ static bool parse_options(int argc, char** argv, Options& o) {
     }
     if (o.split && o.outfile.empty()) o.outfile = split_prefix;              // src/query_options.cpp:346-351
     if (o.abundance_file == o.outfile) o.abundance_file.clear();
+    if (o.hits_file == o.outfile) o.hits_file.clear();                       // src/query_options.cpp:353
     if (!make_units(named, pairfiles, pairseq, o)) return false;
     if (o.lowest > o.highest) o.lowest = o.highest;
     if (o.nomap && o.tophits) { o.nomap = false; o.mapped_only = true; }   // "showing hits changes the mapping mode", src/query_options.cpp:289-292
@@ -296,12 +314,17 @@ static void write_head(std::ostream& os, const Out& o, uint32_t hitmin) {
                                         << cm << "  Max insert size considered " << p.insertsize << ".\n";
     else if (p.pairing == Options::SEQUENCES) os << cm << "Per file paired-end mode:\n" << cm << "  Reads from two consecutive sequences in each file will be paired up.\n"
                                                  << cm << "  Max insert size considered " << p.insertsize << ".\n";
-    if (p.abundance_rank != MCQ_RANK_NONE)                                  // (the reference keys the -abundances line on -hits-per-seq, :100-103)
+    if (p.hits_per_seq)                                                     // (both lines hang on -hits-per-seq in the reference: the second one is its quirk, :95-103)
+        os << cm << "A list of hits per reference sequence will be generated after the read mapping.\n"
+           << cm << "A list of absolute and relative abundances per taxon will be generated after the read mapping.\n";
+    if (p.abundance_rank != MCQ_RANK_NONE)
         os << cm << "A list of absolute and relative abundances for each '" << mcq_rank_name(p.abundance_rank)
            << "' will be generated after the read mapping.\n";
     os << cm << "Using " << p.threads << " threads\n";
     if (!p.nomap) {
-        os << cm << "TABLE_LAYOUT: query_header" << o.col;
+        os << cm << "TABLE_LAYOUT: ";
+        if (p.hits_per_seq) os << "query_id" << o.col;                       // showQueryIds, src/query_options.cpp:308, src/classification.cpp:495
+        os << "query_header" << o.col;
         if (p.ground_truth) { o.header_taxon(os, "truth_"); os << o.col; }
         if (p.tophits) os << "top_hits" << o.col;
         o.header_taxon(os);
@@ -319,6 +342,7 @@ static Options split_options(const Options& p, const ReadUnit& u) {
     const std::string tail = "_" + extract_filename(u.f1) + (u.f2.empty() ? std::string() : "_" + extract_filename(u.f2)) + ".txt";
     if (!p.outfile.empty()) s.outfile = p.outfile + tail;
     if (!p.abundance_file.empty()) s.abundance_file = p.abundance_file + tail;
+    if (!p.hits_file.empty()) s.hits_file = p.hits_file + tail;             // src/mode_query.cpp:186-190, :213-218
     return s;
 }
 // -list-inputs
@@ -352,7 +376,7 @@ static std::vector<Options> output_runs(const Options& p) {
 //  column and, with `ev`, evaluate_classification's assign_known_correct, src/classification.cpp:329-353)
 static void write_query(std::ostream& os, const Out& o, uint32_t hitmin, const char* token, size_t token_len,
                         const mcq_cand* cands, uint32_t ncand, uint64_t* assigned /* [MCQ_RANK_NONE + 1] */,
-                        uint32_t truth = MCQ_NO_TAXON, mcq_eval_stats* ev = nullptr) {
+                        uint32_t truth = MCQ_NO_TAXON, mcq_eval_stats* ev = nullptr, uint64_t query_id = 0) {
     mcq_refdb* rdb = o.db; const Options& p = o.p;
     const uint32_t best = mcq_refdb_classify(rdb, reinterpret_cast<const uint32_t*>(cands), ncand, hitmin, p.hitdiff, p.highest);
     if (best == MCQ_NO_TAXON) ++assigned[MCQ_RANK_NONE];
@@ -360,6 +384,7 @@ static void write_query(std::ostream& os, const Out& o, uint32_t hitmin, const c
     if (ev) mcq_eval_stats_assign_known_correct(ev, mcq_refdb_taxon_rank(rdb, best), mcq_refdb_taxon_rank(rdb, truth),
                                                 mcq_refdb_taxon_rank(rdb, mcq_refdb_ranked_lca(rdb, best, truth)));
     if (p.nomap || (p.mapped_only && best == MCQ_NO_TAXON)) return;
+    if (p.hits_per_seq) os << query_id << o.col;                             // showQueryIds, src/classification.cpp:537
     os.write(token, (std::streamsize)token_len) << o.col;
     if (p.ground_truth) { o.best(os, truth); os << o.col; }                  // show_taxon(os, db, opt, query.groundTruth), :611-614
     if (p.tophits) {                                                         // show_matches, src/printing.cpp:333-360

@@ -51,6 +51,7 @@ struct mcq_refdb {
     std::string prefix;
     std::vector<uint64_t> table_pos, table_keys, table_locs, file_bytes;
     std::vector<uint32_t> tgt_windows;      // windows of every target, from the rank that owns it
+    std::vector<uint64_t> seq_windows;      // the same, kept by both openers: windows_in_sequence of the -hits-per-seq table
 };
 
 namespace {
@@ -147,6 +148,9 @@ extern "C" int mcq_refdb_open(const char* prefix, uint32_t n_ranks, mcq_refdb** 
             taxa.push_back(std::move(t));
         }
         const uint32_t ntargets = rd.get<uint32_t>();
+        if (r == 0) db->seq_windows.assign(ntargets, 0);
+        for (const Taxon& t : taxa)          // (`windows` is non-zero only on the rank that owns the target, src/taxonomy.h:326-335)
+            if (t.id < 0 && (uint64_t)(-t.id - 1) < db->seq_windows.size() && t.windows) db->seq_windows[(size_t)(-t.id - 1)] = t.windows;
         if (r == 0) {
             db->info.k = (uint32_t)p[0]; db->info.sketch_size = (uint32_t)p[1]; db->info.winlen = (uint32_t)p[2];
             db->info.winstride = (uint32_t)p[3]; db->info.q_sketch_size = (uint32_t)p[5]; db->info.q_winlen = (uint32_t)p[6];
@@ -221,7 +225,7 @@ extern "C" int mcq_refdb_open_meta(const char* prefix, uint32_t n_ranks, mcq_ref
             db->info.winstride = (uint32_t)p[3]; db->info.q_sketch_size = (uint32_t)p[5]; db->info.q_winlen = (uint32_t)p[6];
             db->info.q_winstride = (uint32_t)p[7]; db->info.max_locs_per_feature = (uint32_t)p[8];
             db->info.n_targets = ntargets; db->info.n_taxa = (uint32_t)ntaxa; db->info.n_ranks = n_ranks;
-            db->tgt_windows.assign(ntargets, 0);
+            db->tgt_windows.assign(ntargets, 0); db->seq_windows.assign(ntargets, 0);
         } else if (ntargets != db->info.n_targets || ntaxa != db->info.n_taxa) {
             delete db; return fail("shard " + path + " does not belong to the same database");
         }
@@ -230,6 +234,7 @@ extern "C" int mcq_refdb_open_meta(const char* prefix, uint32_t n_ranks, mcq_ref
             if (t.id < 0 && (uint64_t)(-t.id - 1) < ntargets && t.windows) {
                 if (t.windows >= (1ull << 32)) { delete db; return fail("a target with 2^32 windows or more"); }
                 db->tgt_windows[(size_t)(-t.id - 1)] = (uint32_t)t.windows;
+                db->seq_windows[(size_t)(-t.id - 1)] = t.windows;
             }
         if (r == 0) db->taxa = std::move(taxa);
         uint64_t nkeys = 0, nlocs = 0;
@@ -644,6 +649,141 @@ extern "C" int64_t mcq_refdb_abundance_text(const mcq_refdb* db, const uint64_t*
     }
     if (cap) { const size_t n = std::min(cap - 1, s.size()); std::memcpy(buf, s.data(), n); buf[n] = 0; }
     return (int64_t)s.size();
+}
+
+// ---- the table of -hits-per-seq: matches_per_target (src/matches_per_target.h:43-188) and show_matches_per_targets
+// (src/printing.cpp:437-469)
+struct mcq_hits_table {
+    struct Entry { uint64_t qid; std::vector<std::pair<uint32_t, uint32_t>> wins; };       // (window, hits), ascending windows
+    std::map<uint32_t, std::vector<Entry>> per_target;                                    // ascending target id: the row order
+    bool sorted = false;                                                                  // sort_match_lists has run since the last add / merge
+};
+extern "C" int mcq_hits_table_create(mcq_hits_table** out) {
+    if (!out) return fail("bad argument");
+    *out = new mcq_hits_table();
+    return 0;
+}
+extern "C" int mcq_hits_table_free(mcq_hits_table* t) { delete t; return 0; }
+extern "C" int mcq_hits_table_add(mcq_hits_table* t, uint64_t query_id, uint32_t target, uint32_t win_beg, uint32_t n_win, const uint32_t* counts) {
+    if (!t || (n_win && !counts)) return fail("bad argument");
+    mcq_hits_table::Entry e; e.qid = query_id;
+    for (uint32_t i = 0; i < n_win; ++i) if (counts[i]) e.wins.emplace_back(win_beg + i, counts[i]);    // (the reference's vector holds only windows with a match)
+    if (e.wins.empty()) return 0;                     // no match in the range: no candidate the reference could have had
+    t->per_target[target].push_back(std::move(e));
+    t->sorted = false;
+    return 0;
+}
+extern "C" int mcq_hits_table_merge(mcq_hits_table* into, mcq_hits_table* from) {          // matches_per_target::merge: `from` is left empty
+    if (!into || !from) return fail("bad argument");
+    for (auto& m : from->per_target) {
+        auto& dst = into->per_target[m.first];
+        dst.insert(dst.end(), std::make_move_iterator(m.second.begin()), std::make_move_iterator(m.second.end()));
+    }
+    from->per_target.clear();
+    into->sorted = false;
+    return 0;
+}
+extern "C" uint64_t mcq_hits_table_targets(const mcq_hits_table* t) { return t ? t->per_target.size() : 0; }
+extern "C" uint64_t mcq_hits_table_entries(const mcq_hits_table* t) {
+    uint64_t n = 0;
+    if (t) for (const auto& m : t->per_target) n += m.second.size();
+    return n;
+}
+extern "C" uint32_t mcq_refdb_target_key(const mcq_refdb* db, uint32_t target) {
+    if (!db) return MCQ_NO_TAXON;
+    auto it = db->by_id.find(-(int64_t)target - 1);
+    return it == db->by_id.end() ? MCQ_NO_TAXON : (0x80000000u | it->second);
+}
+extern "C" int mcq_refdb_tax2tgt(const mcq_refdb* db, uint32_t* out) {
+    if (!db || !out) return fail("bad argument");
+    for (size_t i = 0; i < db->taxa.size(); ++i) {
+        const Taxon& t = db->taxa[i];
+        out[i] = (t.rank == MCQ_RANK_SEQUENCE && t.id < 0 && (uint64_t)(-t.id - 1) < db->info.n_targets) ? (uint32_t)(-t.id - 1) : MCQ_NO_TAXON;
+    }
+    return 0;
+}
+namespace {
+// show_taxon / show_no_taxon (src/printing.cpp:117-176) for one taxon index or, with MCQ_NO_TAXON, the blank of `rank`
+void put_taxon(std::string& s, const mcq_refdb* db, uint32_t idx, uint32_t rank, const mcq_taxon_print& m) {
+    const bool have = idx != MCQ_NO_TAXON;
+    if (m.show_ranks) { s += mcq_rank_name(have ? db->taxa[idx].rank : rank); s += ':'; }
+    const std::string id = std::to_string(have ? (long long)db->taxa[idx].id : 0ll);
+    if (m.body != 1) s += have ? db->taxa[idx].name : std::string("--");
+    if (m.body == 2) s += '(';
+    if (m.body != 0) s += id;
+    if (m.body == 2) s += ')';
+}
+}  // namespace
+// the block of show_matches_per_targets, handed to `sink` piece by piece (the head, then one piece per row): nothing of the table's
+// text is held beyond one row
+extern "C" int mcq_hits_table_write(mcq_hits_table* t, const mcq_refdb* db, const char* comment, const char* column,
+                                    const mcq_taxon_print* mode, mcq_text_sink sink, void* user) {
+    if (!t || !db || !comment || !column || !mode || !sink || mode->body > 2) return fail("bad argument");
+    // sort_match_lists (src/matches_per_target.h:172-184): first window, then last window, then query id
+    if (!t->sorted) {
+        for (auto& m : t->per_target)
+            std::sort(m.second.begin(), m.second.end(), [](const mcq_hits_table::Entry& a, const mcq_hits_table::Entry& b) {
+                if (a.wins.front().first != b.wins.front().first) return a.wins.front().first < b.wins.front().first;
+                if (a.wins.back().first != b.wins.back().first) return a.wins.back().first < b.wins.back().first;
+                return a.qid < b.qid;
+            });
+        t->sorted = true;
+    }
+    std::string s;
+    s += comment; s += "--- list of hits for each reference sequence ---\n";
+    s += comment; s += "window start position within sequence = window_index * window_stride(=" + std::to_string(db->info.q_winstride) + ")\n";
+    s += comment; s += "TABLE_LAYOUT:  sequence "; s += column; s += " windows_in_sequence "; s += column;
+    s += "queryid/window_index:hits/window_index:hits/...,queryid/...\n";
+    if (sink(user, s.data(), s.size())) return fail("the sink refused the table's head");
+    // (rows in ascending target id: the reference walks an unordered_map of taxon pointers, an order no two runs need share)
+    for (const auto& m : t->per_target) {
+        s.clear();
+        const uint32_t key = mcq_refdb_target_key(db, m.first);
+        if (key == MCQ_NO_TAXON) return fail("target " + std::to_string(m.first) + " has no sequence-level taxon");
+        const uint32_t idx = key & 0x7FFFFFFFu;
+        // show_taxon(os, db, opt, tax) (src/printing.cpp:305-330) of a sequence-level taxon, as Out::best of mcq_cli_common.hpp writes it
+        // (highest_rank beyond root is read as root: the lineage has no entry above it)
+        const uint32_t highest = std::min<uint32_t>(mode->highest_rank, MCQ_RANK_ROOT);
+        if (db->taxa[idx].rank > highest) s += (mode->body == 1 && !mode->show_ranks) ? "0" : "--";
+        else {
+            const uint32_t rmin = std::max<uint32_t>(mode->lowest_rank, db->taxa[idx].rank);
+            const uint32_t rmax = mode->lineage ? highest : rmin;
+            for (uint32_t r = rmin; r <= rmax; ++r) {
+                put_taxon(s, db, db->lineage[(size_t)idx * kNumRanks + r], r, *mode);
+                if (r < rmax) s += ',';
+            }
+        }
+        const uint64_t windows = m.first < db->seq_windows.size() ? db->seq_windows[m.first] : db->taxa[idx].windows;
+        s += column; s += std::to_string(windows); s += column;
+        bool first = true;
+        for (const auto& e : m.second) {
+            if (first) first = false; else s += ',';
+            s += std::to_string(e.qid);
+            for (const auto& w : e.wins) { s += '/'; s += std::to_string(w.first); s += ':'; s += std::to_string(w.second); }
+        }
+        s += '\n';
+        if (sink(user, s.data(), s.size())) return fail("the sink refused a row of the table");
+    }
+    return 0;
+}
+namespace {
+struct TextBuf { char* buf; size_t cap, len; };
+int text_buf_sink(void* user, const char* data, size_t n) {
+    TextBuf* b = static_cast<TextBuf*>(user);
+    if (b->cap && b->len < b->cap - 1) std::memcpy(b->buf + b->len, data, std::min(n, b->cap - 1 - b->len));
+    b->len += n;
+    return 0;
+}
+}  // namespace
+// the same into a caller's buffer (cut to cap - 1 bytes, NUL-terminated); returns the whole length.  For tests and small tables: a
+// caller that asks for the length first formats the table twice -- mcq_hits_table_write formats it once
+extern "C" int64_t mcq_hits_table_text(mcq_hits_table* t, const mcq_refdb* db, const char* comment, const char* column,
+                                       const mcq_taxon_print* mode, char* buf, size_t cap) {
+    if (cap && !buf) return fail("bad argument");
+    TextBuf b{buf, cap, 0};
+    if (mcq_hits_table_write(t, db, comment, column, mode, text_buf_sink, &b)) return -1;
+    if (cap) buf[std::min(b.len, cap - 1)] = 0;
+    return (int64_t)b.len;
 }
 
 extern "C" uint32_t mcq_default_hits_min(uint32_t s) { return s >= 6 ? (uint32_t)(s / 3.0) : (s >= 4 ? 2u : 1u); }

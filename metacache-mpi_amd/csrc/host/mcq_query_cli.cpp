@@ -10,6 +10,13 @@
 // slot's chunk, from the printed token on to the end of the line) next to its classification.  -exclude RANK needs the truths BEFORE
 // the query: the batch's header ranges come to the host and its clade keys go to the device before mcq_query is enqueued
 // (Run::stage_clades), which costs overlap between the input and the query stage.  Only that option pays it.
+//
+// -hits-per-seq (with -lowest sequence; above it the table has no rows and nothing of this runs): behind a batch's query, on the
+// same stream, mcq_target_slots turns the batch's device results into slot targets (the sequence-level candidates with hits >=
+// hitmin) and mcq_target_hits answers each with its window range and per-window counts, which come back with the results.  The
+// width of the count rows is the range width of the batch's longest query, so the batch's offsets are looked at on the host first
+// (Run::stage_hits).  The writer threads feed one accumulator each (mcq_hits_table_*), merged and written after the last
+// mapping line; host memory grows with the input, as the reference's does.  A read beyond the kernel's capacity ends the run.
 #include "mcq_cli_common.hpp"
 #include "mcq_read_batches.hpp"
 
@@ -23,6 +30,11 @@ namespace {
 struct Slot : ReadSlot {
     DeviceBuf<mcq_cand> d_cands; DeviceBuf<uint32_t> d_ncand; PinnedBuf<mcq_cand> cands; PinnedBuf<uint32_t> ncand; Event done;
     std::vector<uint32_t> truth; PinnedBuf<uint32_t> clade; DeviceBuf<uint32_t> d_clade;   // -exclude: the truths and clade keys of the batch
+    // -hits-per-seq: the batch's slot targets, and per slot the range and the counts of its windows (mcq_target_hits)
+    DeviceBuf<uint32_t> d_tgt, d_cnt, d_hst; DeviceBuf<mcq_target_range> d_rng;
+    PinnedBuf<uint32_t> cnt, hst; PinnedBuf<mcq_target_range> rng; PinnedBuf<uint64_t> seq_off;
+    uint32_t range_cap = 0; bool hits = false;
+    uint64_t first_id = 0;                                                               // query id of the batch's first query
 };
 constexpr int NS = 3;
 
@@ -40,9 +52,12 @@ struct Run {
     size_t issued = 0, retired = 0;                              // batches enqueued; batches whose lines are written or being written
     size_t announced = 0;                                        // units whose "# f1 + f2" line is written (by finish, in batch order)
     std::future<bool> pending;                                   // the formatting of batch `retired - 1`, beside the reading of the next
+    uint64_t next_id = 1;                                        // query ids: the 1-based running number of the read (pair) over all units of this output
+    std::vector<mcq_hits_table*> hit_acc;                        // -hits-per-seq: one accumulator per writer thread
+    DeviceBuf<uint32_t> d_tax2tgt; uint32_t n_taxa = 0, n_slots = 0;
 
     Run(const Options& p_, const Database& db_) : p(p_), db(db_), o(make_out(db_.rdb, p_)), co(classify_opts(p_, db_.hitmin)) { std::memset(&eval, 0, sizeof(eval)); }
-    ~Run() { if (pending.valid()) pending.wait(); mcq_ws_destroy(ws); mcq_taxonomy_destroy(tx); }
+    ~Run() { if (pending.valid()) pending.wait(); mcq_ws_destroy(ws); mcq_taxonomy_destroy(tx); for (mcq_hits_table* t : hit_acc) mcq_hits_table_free(t); }
 
     bool init() {
         if (p.tax_counts()) {
@@ -54,6 +69,18 @@ struct Run {
             tgt_clade.resize(db.t2t.size());
             if (mcq_refdb_clade_keys(db.rdb, p.exclude_rank, tgt_clade.data())) { std::fprintf(stderr, "ABORT: %s\n", mcq_host_last_error()); return false; }
         }
+        if (p.hits_per_seq) {
+            hit_acc.assign(std::max(1u, p.threads), nullptr);
+            for (mcq_hits_table*& t : hit_acc) if (mcq_hits_table_create(&t)) return false;
+        }
+        if (hits_on()) {                                         // candidates above sequence level are skipped: no kernel, no rows
+            mcq_refdb_info rinfo; mcq_refdb_get_info(db.rdb, &rinfo);
+            std::vector<uint32_t> t2g(rinfo.n_taxa);
+            if (mcq_refdb_tax2tgt(db.rdb, t2g.data())) { std::fprintf(stderr, "ABORT: %s\n", mcq_host_last_error()); return false; }
+            n_taxa = rinfo.n_taxa; n_slots = std::min<uint32_t>(std::max(1u, p.maxcand), MCQ_TARGET_HITS_MAX_SLOTS);
+            if (!d_tax2tgt.grow(n_taxa)) return false;
+            MCQ_HIP(hipMemcpy(d_tax2tgt.p, t2g.data(), (size_t)n_taxa * 4, hipMemcpyHostToDevice), return false);
+        }
         if (!s_k.create() || !ev_in.create()) return false;
         for (Slot& S : slot) if (!S.done.create()) return false;
         os = &open_out(p, fout);
@@ -62,6 +89,39 @@ struct Run {
     }
 
     bool excluding() const { return p.exclude_rank != MCQ_RANK_NONE; }
+    bool hits_on() const { return p.hits_per_seq && p.lowest == MCQ_RANK_SEQUENCE; }
+    // -hits-per-seq: behind the batch's query on s_k, its slot targets, their ranges and window counts, and the copies out.  The count
+    // rows are as wide as the range of the batch's longest query: its offsets come to the host first (`st` has prepared the batch).
+    bool stage_hits(Slot& S, const mcq_batch& in, const mcq_result& res, hipStream_t st) {
+        const uint64_t n = S.n, ns = in.n_seqs;
+        const uint64_t* off = S.h_seq_off.data();
+        if (!S.host_parsed) {
+            if (!S.seq_off.grow(ns + 1)) return false;
+            MCQ_HIP(hipMemcpyAsync(S.seq_off.p, S.d_seq_off.p, (ns + 1) * 8, hipMemcpyDeviceToHost, st), return false);
+            MCQ_HIP(hipStreamSynchronize(st), return false);
+            off = S.seq_off.p;
+        }
+        const uint64_t m = in.paired ? 2 : 1;
+        uint64_t longest = 0;
+        for (uint64_t q = 0; q < n; ++q) longest = std::max(longest, off[m * q + m] - off[m * q]);
+        S.range_cap = mcq_target_hits_range_cap(db.edb, longest, p.insertsize);
+        const uint64_t words = n * n_slots * S.range_cap;
+        if (words > (1ull << 29)) {                              // 2 GiB of counts: one very long read among many
+            std::fprintf(stderr, "ABORT: -hits-per-seq needs %llu MB for the window counts of a batch of %llu reads whose longest has %llu bases: "
+                                 "use a smaller -batch\n", (unsigned long long)(words >> 18), (unsigned long long)n, (unsigned long long)longest);
+            return false;
+        }
+        if (!S.d_tgt.grow(n * n_slots) || !S.d_rng.grow(n * n_slots) || !S.rng.grow(n * n_slots) || !S.d_cnt.grow(words) || !S.cnt.grow(words) ||
+            !S.d_hst.grow(n) || !S.hst.grow(n)) return false;
+        if (mcq_target_slots(&res, n, p.maxcand, db.hitmin, d_tax2tgt.p, n_taxa, S.d_tgt.p, n_slots, s_k) ||
+            mcq_target_hits(db.edb, ws, &in, S.d_tgt.p, n_slots, p.insertsize, S.range_cap, S.d_rng.p, S.d_cnt.p, S.d_hst.p, s_k)) {
+            std::fprintf(stderr, "FAIL: %s\n", mcq_last_error()); return false;
+        }
+        MCQ_HIP(hipMemcpyAsync(S.rng.p, S.d_rng.p, n * n_slots * sizeof(mcq_target_range), hipMemcpyDeviceToHost, s_k), return false);
+        MCQ_HIP(hipMemcpyAsync(S.cnt.p, S.d_cnt.p, words * 4, hipMemcpyDeviceToHost, s_k), return false);
+        MCQ_HIP(hipMemcpyAsync(S.hst.p, S.d_hst.p, n * 4, hipMemcpyDeviceToHost, s_k), return false);
+        return true;
+    }
     // the ground truth of query q of the batch in S: from its whole header, which goes on behind the printed token to the end of its line
     uint32_t truth_of(const Slot& S, uint64_t q) const {
         const char* h = S.text[0].p + S.hdr.p[2 * q];
@@ -101,10 +161,18 @@ struct Run {
         if (hipEventSynchronize(S.done) != hipSuccess) { std::fprintf(stderr, "FAIL: batch %zu did not complete\n", j); return false; }
         announce(S.unit + 1);
         const uint64_t n = S.n;
+        if (S.hits) for (uint64_t q = 0; q < n; ++q) if (S.hst.p[q]) {        // beyond mcq_target_hits' capacity: reported, never dropped in silence
+            std::fprintf(stderr, "ABORT: -hits-per-seq: read %llu (%.*s) %s\n", (unsigned long long)(S.first_id + q),
+                         (int)(S.hdr.p[2 * q + 1] - S.hdr.p[2 * q]), S.text[0].p + S.hdr.p[2 * q],
+                         (S.hst.p[q] & MCQ_TARGET_HITS_KEYS) ? ("hits more than " + std::to_string(MCQ_TARGET_HITS_MAX_KEYS) + " (MCQ_TARGET_HITS_MAX_KEYS) distinct windows of its candidate sequences").c_str()
+                                                             : "is beyond what mcq_target_hits takes (range width, window ids of 2^28 and more, 2^31 bases)");
+            return false;
+        }
         const unsigned T = (unsigned)std::min<uint64_t>(std::max(1u, p.threads), std::max<uint64_t>(1, n / 64));
         std::vector<std::string> out(T);
         std::vector<std::array<uint64_t, MCQ_RANK_NONE + 1>> asg(T);
         std::vector<mcq_eval_stats> evs(T);
+        std::vector<char> add_failed(T, 0);                                       // -hits-per-seq: a thread's accumulator refused an entry
         auto slice = [&](unsigned t) {
             std::ostringstream ss;
             asg[t].fill(0);
@@ -112,7 +180,13 @@ struct Run {
             for (uint64_t q = n * t / T; q < n * (t + 1) / T; ++q) {
                 const uint32_t truth = !p.wants_truth() ? MCQ_NO_TAXON : (excluding() ? S.truth[q] : truth_of(S, q));
                 write_query(ss, o, db.hitmin, S.text[0].p + S.hdr.p[2 * q], (size_t)(S.hdr.p[2 * q + 1] - S.hdr.p[2 * q]),
-                            &S.cands.p[q * p.maxcand], S.ncand.p[q], asg[t].data(), truth, p.precision ? &evs[t] : nullptr);
+                            &S.cands.p[q * p.maxcand], S.ncand.p[q], asg[t].data(), truth, p.precision ? &evs[t] : nullptr, S.first_id + q);
+                if (S.hits) for (uint32_t s = 0; s < n_slots; ++s) {        // matches_per_target::insert of this read's candidates
+                    const mcq_target_range& r = S.rng.p[q * n_slots + s];
+                    if (r.tgt != MCQ_TARGET_UNUSED && r.n_win &&
+                        mcq_hits_table_add(hit_acc[t], S.first_id + q, r.tgt, r.win_beg, r.n_win, &S.cnt.p[(q * n_slots + s) * (uint64_t)S.range_cap]))
+                        add_failed[t] = 1;
+                }
             }
             out[t] = ss.str();
         };
@@ -126,8 +200,29 @@ struct Run {
             os->write(out[t].data(), (std::streamsize)out[t].size());
             for (int r = 0; r <= MCQ_RANK_NONE; ++r) assigned[r] += asg[t][r];
             mcq_eval_stats_add(&eval, &evs[t]);
+            if (add_failed[t]) { std::fprintf(stderr, "ABORT: -hits-per-seq: an entry of batch %zu could not be kept\n", j); return false; }
         }
         return true;
+    }
+    // -hits-per-seq: the writer threads' accumulators merged, sorted and written (show_matches_per_targets) into the -hits-per-seq FILE
+    // if one was named, else behind the mapping lines
+    bool write_hits_table() {
+        for (size_t t = 1; t < hit_acc.size(); ++t) mcq_hits_table_merge(hit_acc[0], hit_acc[t]);
+        const mcq_taxon_print mode = {o.mode.rank_prefix ? 1u : 0u, (uint32_t)o.mode.body, p.lineage ? 1u : 0u, p.lowest, p.highest};
+        std::ofstream fh;
+        if (!p.hits_file.empty()) {
+            fh.open(p.hits_file);
+            if (!fh.good()) { std::fprintf(stderr, "ABORT: Could not write to file %s\n", p.hits_file.c_str()); return false; }
+            std::cout << "Per-Target mappings will be written to file: " << p.hits_file << std::endl;
+        }
+        std::ostream& ho = p.hits_file.empty() ? *os : fh;
+        auto sink = [](void* user, const char* data, size_t n) -> int {          // row by row: the table is formatted once and never held whole
+            std::ostream& out = *static_cast<std::ostream*>(user);
+            out.write(data, (std::streamsize)n);
+            return out.good() ? 0 : 1;
+        };
+        if (mcq_hits_table_write(hit_acc[0], db.rdb, o.comment, o.col, &mode, sink, &ho)) { std::fprintf(stderr, "ABORT: %s\n", mcq_host_last_error()); return false; }
+        return ho.good();
     }
     // the lines of the units before `end` that have none yet: a batch's own unit, and units without records before it
     void announce(size_t end) { for (; announced < end; ++announced) write_unit_line(*os, o, p.units[announced]); }
@@ -173,6 +268,7 @@ static int run_queries(const Options& p, const Database& db) {
         if (got == ReadBatcher::ERROR) return 1;
         if (got == ReadBatcher::END) break;
         const uint64_t n = S.n;
+        S.first_id = run.next_id; run.next_id += n; S.hits = run.hits_on();
         if (!run.ensure_ws(n) || !S.d_cands.grow(n * p.maxcand) || !S.d_ncand.grow(n) || !S.cands.grow(n * p.maxcand) || !S.ncand.grow(n)) return 1;
         mcq_batch in; std::memset(&in, 0, sizeof(in));
         in.n_seqs = n * mates; in.bases = S.d_bases.p; in.seq_off = S.d_seq_off.p; in.paired = mates == 2; in.flags = MCQ_DEVICE_PTRS;
@@ -184,11 +280,13 @@ static int run_queries(const Options& p, const Database& db) {
         MCQ_HIP(hipMemcpyAsync(S.cands.p, S.d_cands.p, n * p.maxcand * sizeof(mcq_cand), hipMemcpyDeviceToHost, run.s_k), return 1);
         MCQ_HIP(hipMemcpyAsync(S.ncand.p, S.d_ncand.p, n * 4, hipMemcpyDeviceToHost, run.s_k), return 1);
         if (!S.host_parsed && !run.excluding()) MCQ_HIP(hipMemcpyAsync(S.hdr.p, S.d_hdr.p, 2 * n * 8, hipMemcpyDeviceToHost, run.s_k), return 1);
+        if (S.hits && !run.stage_hits(S, in, res, reads.stream())) return 1;
         MCQ_HIP(hipEventRecord(S.done, run.s_k), return 1);
         ++run.issued;
     }
     if (!run.drain()) return 1;
     run.announce(p.units.size());
+    if (p.hits_per_seq && !run.write_hits_table()) return 1;     // before the abundance tables: src/classification.cpp:847-862
     if (run.tx) {
         if (run.ws && !add_taxon_counts(run.ws, run.tax_counts)) return 1;
         if (!write_abundances(*run.os, db.rdb, p, run.tax_counts, run.assigned)) return 1;

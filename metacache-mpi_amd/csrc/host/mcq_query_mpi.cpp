@@ -24,6 +24,7 @@
 // usage: mpiexec -n N mcq_query_mpi <dbprefix> <P> <file|directory>... [options of mcq_query_cli] [-transport rccl|mpi]
 //                                   [-batch N] [-batch-bases N]
 // -exclude, -ground-truth and -precision are rejected with a line that names mcq_query_cli: the sharded kernels have no exclusion.
+// -hits-per-seq is rejected the same way: mcq_target_hits is a kernel of the one-GPU path.
 #include <mpi.h>
 #include <hip/hip_runtime_api.h>
 
@@ -114,6 +115,10 @@ int main(int argc, char** argv) {
     if (p.list_inputs) { if (rank == 0) list_inputs(std::cout, p); MPI_Finalize(); return 0; }
     if (p.wants_truth()) {                                                  // (before any GPU work)
         if (rank == 0) std::fprintf(stderr, "ABORT: -exclude, -ground-truth and -precision are options of mcq_query_cli; mcq_query_mpi does not evaluate against a ground truth\n");
+        MPI_Finalize(); return 2;
+    }
+    if (p.hits_per_seq) {                                                   // (before any GPU work)
+        if (rank == 0) std::fprintf(stderr, "ABORT: -hits-per-seq is an option of mcq_query_cli; mcq_query_mpi keeps no window hit lists (the sharded path has none)\n");
         MPI_Finalize(); return 2;
     }
     int n_dev = 0;

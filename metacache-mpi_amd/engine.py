@@ -29,6 +29,10 @@ MCQ_FORCE_LEAN_WAVE = 0x20000    # debug / A-B: the lean first wave stage (hands
 MCQ_FORCE_FULL_WAVE = 0x40000    # debug / A-B: the full first wave stage, whatever the batch before suggests
 MCQ_CLADE_NONE = 0xFFFFFFFF      # clade exclusion: no ancestor at the rank (a target's key, or a truth's)
 MCQ_CLADE_KEEP_ALL = 0xFFFFFFFE  # clade exclusion, query keys only: no ground truth, nothing is excluded
+MCQ_TARGET_HITS_MAX_SLOTS = 16   # mcq_target_hits: slot targets per query
+MCQ_TARGET_HITS_MAX_KEYS = 1024  # ... distinct (target, window) pairs of one query over all its slot targets
+MCQ_TARGET_UNUSED = 0xFFFFFFFF   # ... an unused slot
+MCQ_TARGET_HITS_RANGE, MCQ_TARGET_HITS_KEYS, MCQ_TARGET_HITS_WINDOW = 1, 2, 4    # ... status bits of a query beyond a capacity
 
 MCQ_OK, MCQ_E_ARG, MCQ_E_HIP, MCQ_E_CAPACITY, MCQ_E_UNSUPPORTED = 0, -1, -2, -3, -4
 
@@ -178,6 +182,12 @@ def lib():
         L.mcq_ws_taxon_counts.argtypes = [C.c_void_p, C.c_void_p, C.c_int]
         L.mcq_ws_set_exclusion.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32]
         L.mcq_ws_set_query_clades.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint32]
+        if hasattr(L, "mcq_target_hits"):           # (an MCQ_HIP_LIB variant built from an older state has none: same-box A/B against a parent)
+            L.mcq_target_hits_range_cap.restype = C.c_uint32; L.mcq_target_hits_range_cap.argtypes = [C.c_void_p, C.c_uint64, C.c_uint64]
+            L.mcq_target_hits.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(Batch), C.c_void_p, C.c_uint32, C.c_uint64, C.c_uint32,
+                                          C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+            L.mcq_target_slots.argtypes = [C.POINTER(Result), C.c_uint64, C.c_uint32, C.c_uint32, C.c_void_p, C.c_uint32, C.c_void_p,
+                                           C.c_uint32, C.c_void_p]
         L.mcq_shard_create.argtypes = [C.c_void_p, C.POINTER(ShardCfg), C.POINTER(C.c_void_p)]
         L.mcq_shard_destroy.argtypes = [C.c_void_p]
         L.mcq_shard_unique_id.argtypes = [C.c_void_p]
@@ -407,6 +417,62 @@ class Workspace:
             return
         a = np.ascontiguousarray(query_clade, np.uint32)
         _chk(lib().mcq_ws_set_query_clades(self.h, _np_ptr(a) if len(a) else _np_ptr(np.zeros(1, np.uint32)), len(a), 0))
+
+    # ---- per-target window hit lists (mcq_target_hits): what -hits-per-seq prints
+    def target_hits_range_cap(self, longest_query, insert_size_max=0):
+        """range width of a query of that many bases (both mates): the range_cap a batch with that longest query needs"""
+        return int(lib().mcq_target_hits_range_cap(self.db.h, longest_query, insert_size_max))
+
+    def target_hits(self, bases_ptr, seq_off_ptr, n_seqs, paired, targets_ptr, n_slots, range_cap, ranges_ptr, counts_ptr,
+                    status_ptr, insert_size_max=0, stream=None, ranges=False, packed_bases=0):
+        """device pointers, enqueue only: targets u32 [nq, n_slots] (MCQ_TARGET_UNUSED = unused slot) -> ranges u32 [nq, n_slots, 4]
+        (tgt, hits, win_beg, n_win), counts u32 [nq, n_slots, range_cap] (written for i < n_win only), status u32 [nq].  A query
+        beyond a capacity gets n_win = 0 everywhere, a status bit, and makes the next sync() raise MCQ_E_CAPACITY."""
+        b = Batch(n_seqs, bases_ptr, seq_off_ptr, 1 if paired else 0,
+                  MCQ_DEVICE_PTRS | (MCQ_BATCH_RANGES if ranges else 0) | (MCQ_BATCH_PACKED if packed_bases else 0), packed_bases)
+        _chk(lib().mcq_target_hits(self.db.h, self.h, C.byref(b), targets_ptr, n_slots, insert_size_max, range_cap, ranges_ptr,
+                                   counts_ptr, status_ptr, stream))
+
+    def target_hits_host(self, bases, seq_off, paired, targets, range_cap=None, insert_size_max=0, packed=False, fill=0, sync=True,
+                         ranges=False):
+        """convenience form for tests: numpy in, numpy out (the copies go through torch; waits for the device).  targets: u32
+        [nq, n_slots].  range_cap None: what the longest query needs.  The words of counts the kernel leaves alone hold `fill`.
+        Every output has 64 guard words behind it; a changed one raises.  sync False: the caller calls sync() (and gets the
+        capacity error there).  ranges: seq_off holds 2 * n_seqs (begin, end) byte ranges into `bases` (MCQ_BATCH_RANGES)."""
+        import torch
+        dev = torch.device("cuda", self.db.device)
+        seq_off = np.ascontiguousarray(seq_off, np.uint64)
+        n_seqs = len(seq_off) // 2 if ranges else len(seq_off) - 1
+        nq = n_seqs // 2 if paired else n_seqs
+        targets = np.ascontiguousarray(targets, np.uint32).reshape(nq, -1)
+        n_slots = targets.shape[1]
+        lens = (seq_off[1::2].astype(np.int64) - seq_off[0::2].astype(np.int64)) if ranges else np.diff(seq_off.astype(np.int64))
+        qlens = lens[0:2 * nq:2] + lens[1:2 * nq:2] if paired else lens
+        if range_cap is None:
+            range_cap = self.target_hits_range_cap(int(qlens.max()) if nq else 0, insert_size_max)
+        raw = np.frombuffer(bases, dtype=np.uint8) if not isinstance(bases, np.ndarray) else bases.view(np.uint8)
+        d_bases = torch.from_numpy(np.concatenate([raw, np.zeros(8, np.uint8)])).to(dev)
+        d_off = torch.from_numpy(seq_off.view(np.int64)).to(dev)
+        d_tgt = torch.from_numpy(targets.view(np.int32)).to(dev)
+        guard, G = 0x5EEDFACE, 64
+        sizes = (nq * n_slots * 4, nq * n_slots * range_cap, nq)
+        host = [np.full(n + G, g, np.uint32) for n, g in zip(sizes, (guard, fill, guard))]
+        for h, n in zip(host, sizes):
+            h[n:] = guard
+        d_rng, d_cnt, d_st = (torch.from_numpy(h.view(np.int32)).to(dev) for h in host)
+        st = torch.cuda.current_stream(dev).cuda_stream
+        self.target_hits(d_bases.data_ptr(), d_off.data_ptr(), n_seqs, paired, d_tgt.data_ptr(), n_slots, range_cap, d_rng.data_ptr(),
+                         d_cnt.data_ptr(), d_st.data_ptr(), insert_size_max=insert_size_max, stream=st, ranges=ranges,
+                         packed_bases=int(seq_off[-1]) if packed else 0)
+        torch.cuda.synchronize(dev)
+        got = [d.cpu().numpy().view(np.uint32) for d in (d_rng, d_cnt, d_st)]
+        for g, n in zip(got, sizes):
+            if not (g[n:] == guard).all():
+                raise AssertionError("mcq_target_hits wrote behind an output")
+        out = (got[0][:sizes[0]].reshape(nq, n_slots, 4), got[1][:sizes[1]].reshape(nq, n_slots, range_cap), got[2][:nq])
+        if sync:
+            self.sync(st)
+        return out
 
     def timing(self, enable):
         _chk(lib().mcq_ws_timing(self.h, 1 if enable else 0))
@@ -776,3 +842,9 @@ def reads_prepare(text1_ptr, len1, text2_ptr, len2, flags, max_queries, max_base
 
 def owner(feature, n_shards):
     return int(lib().mcq_owner(feature, n_shards))
+
+
+def target_slots(cands_ptr, ncand_ptr, n_queries, max_cand, hits_min, tax2tgt_ptr, n_taxa, targets_ptr, n_slots, stream=None):
+    """mcq_target_slots: the slot targets of a batch from its device results (sequence-level candidates with hits >= hits_min)"""
+    r = Result(cands_ptr, ncand_ptr, MCQ_DEVICE_PTRS)
+    _chk(lib().mcq_target_slots(C.byref(r), n_queries, max_cand, hits_min, tax2tgt_ptr, n_taxa, targets_ptr, n_slots, stream))

@@ -26,6 +26,11 @@ class EvalStatsRec(C.Structure):
     _fields_ = [(n, C.c_uint64 * 22) for n in ("assigned", "known", "correct", "wrong")]
 
 
+class TaxonPrint(C.Structure):
+    _fields_ = [("show_ranks", C.c_uint32), ("body", C.c_uint32), ("lineage", C.c_uint32), ("lowest_rank", C.c_uint32),
+                ("highest_rank", C.c_uint32)]
+
+
 class ShardParams(C.Structure):
     _fields_ = [(n, C.c_uint64) for n in ("k", "sketch_size", "winlen", "winstride", "q_k", "q_sketch_size", "q_winlen",
                                          "q_winstride", "max_locs_per_feature")]
@@ -93,6 +98,16 @@ def lib():
         L.mcq_eval_stats_text.restype = C.c_int64; L.mcq_eval_stats_text.argtypes = [sp, C.c_char_p, C.c_char_p, C.c_size_t]
         L.mcq_refdb_abundance_text.restype = C.c_int64
         L.mcq_refdb_abundance_text.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint32, C.c_char_p, C.c_size_t]
+        L.mcq_hits_table_create.argtypes = [C.POINTER(C.c_void_p)]
+        L.mcq_hits_table_add.argtypes = [C.c_void_p, C.c_uint64, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p]
+        L.mcq_hits_table_merge.argtypes = [C.c_void_p, C.c_void_p]
+        L.mcq_hits_table_targets.restype = C.c_uint64; L.mcq_hits_table_targets.argtypes = [C.c_void_p]
+        L.mcq_hits_table_entries.restype = C.c_uint64; L.mcq_hits_table_entries.argtypes = [C.c_void_p]
+        L.mcq_hits_table_text.restype = C.c_int64
+        L.mcq_hits_table_text.argtypes = [C.c_void_p, C.c_void_p, C.c_char_p, C.c_char_p, C.POINTER(TaxonPrint), C.c_char_p, C.c_size_t]
+        L.mcq_hits_table_free.argtypes = [C.c_void_p]
+        L.mcq_refdb_target_key.restype = C.c_uint32; L.mcq_refdb_target_key.argtypes = [C.c_void_p, C.c_uint32]
+        L.mcq_refdb_tax2tgt.argtypes = [C.c_void_p, C.c_void_p]
         L.mcq_default_hits_min.restype = C.c_uint32; L.mcq_default_hits_min.argtypes = [C.c_uint32]
         L.mcq_rank_from_name.restype = C.c_uint32; L.mcq_rank_from_name.argtypes = [C.c_char_p]
         L.mcq_rank_name.restype = C.c_char_p; L.mcq_rank_name.argtypes = [C.c_uint32]
@@ -254,6 +269,14 @@ class RefDb:
             raise RuntimeError(lib().mcq_host_last_error().decode())
         return lin, rank
 
+    def target_key(self, target):
+        return int(lib().mcq_refdb_target_key(self.h, int(target)))
+
+    def tax2tgt(self):
+        out = np.zeros(self.info.n_taxa, np.uint32)
+        lib().mcq_refdb_tax2tgt(self.h, out.ctypes.data_as(C.c_void_p))
+        return out
+
     def abundance_text(self, counts, total, est_rank=RANK_NONE):
         """counts: u64 [n_taxa] classified queries per taxon index; est_rank RANK_NONE = the plain table, else the
         estimate to that rank (mcq_refdb_abundance_text)"""
@@ -266,6 +289,48 @@ class RefDb:
         buf = C.create_string_buffer(n + 1)
         lib().mcq_refdb_abundance_text(self.h, c.ctypes.data_as(C.c_void_p), int(total), int(est_rank), buf, n + 1)
         return buf.raw[:n].decode("latin-1")
+
+
+class HitsTable:
+    """mcq_hits_table: the accumulator and writer of the -hits-per-seq table (matches_per_target, show_matches_per_targets)"""
+
+    def __init__(self):
+        self.h = C.c_void_p()
+        lib().mcq_hits_table_create(C.byref(self.h))
+
+    def add(self, query_id, target, win_beg, counts):
+        c = np.ascontiguousarray(counts, np.uint32)
+        if lib().mcq_hits_table_add(self.h, int(query_id), int(target), int(win_beg), len(c), c.ctypes.data_as(C.c_void_p)) != 0:
+            raise RuntimeError(lib().mcq_host_last_error().decode())
+
+    def merge(self, other):
+        lib().mcq_hits_table_merge(self.h, other.h)
+
+    def entries(self):
+        return int(lib().mcq_hits_table_entries(self.h))
+
+    def targets(self):
+        return int(lib().mcq_hits_table_targets(self.h))
+
+    def text(self, db, comment="# ", column="\t|\t", show_ranks=True, body=0, lineage=False, lowest_rank=0, highest_rank=19):
+        """body: 0 name, 1 id, 2 name(id)"""
+        m = TaxonPrint(1 if show_ranks else 0, body, 1 if lineage else 0, lowest_rank, highest_rank)
+        n = lib().mcq_hits_table_text(self.h, db.h, comment.encode(), column.encode(), C.byref(m), None, 0)
+        if n < 0:
+            raise RuntimeError(lib().mcq_host_last_error().decode())
+        buf = C.create_string_buffer(n + 1)
+        lib().mcq_hits_table_text(self.h, db.h, comment.encode(), column.encode(), C.byref(m), buf, n + 1)
+        return buf.raw[:n].decode("latin-1")
+
+    def close(self):
+        if getattr(self, "h", None):
+            lib().mcq_hits_table_free(self.h); self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
 
 
 class EvalStats:
