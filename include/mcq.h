@@ -480,6 +480,19 @@ int mcq_table_free(mcq_table* t);
  * mcq_table_info gives its device arrays (win_off: the union's), mcq_table_free releases it.  A rank without targets gives an
  * empty table (n_keys = 0), not an error.  What mcq_refdb_write_shard (include/mcq_host.h) takes, one rank at a time.        */
 int mcq_table_rank_split(const mcq_table* t, uint32_t n_ranks, uint32_t rank, mcq_table** out);
+/* -remove-ambig-features on a table (remove_ambiguous_features, src/sketch_database.h:428-470): *out holds every key of t whose
+ * list names at most max_keys (1..255) distinct values of tgt_key[target], with its list unchanged; keys and lists keep their order.
+ * tgt_key[n_targets] (host, or device with MCQ_DEVICE_PTRS in flags; n_targets must be the table's) are opaque 32-bit words, as in
+ * mcq_ws_set_exclusion: the target's ancestor at the rank (mcq_taxa_clade_keys / mcq_refdb_clade_keys of include/mcq_host.h;
+ * 0xFFFFFFFF, "none", is a key like any other: two targets without an ancestor count once), or the target id itself for rank sequence.
+ * *n_removed = keys dropped.  Done on the device (count per key -- the distinct keys of a list are kept in LDS, max_keys = 1 needs
+ * none --, scans, scatter); *out is a table of its own, as after mcq_table_rank_split (win_off: the input's); it may be empty
+ * (n_keys = 0), and an empty input gives an empty output.  Device memory at the peak: the input table and the output table (8 B
+ * per location and 12 B per key each) plus 24 B per input key of temporaries (and 4 B per target for host keys).
+ * MCQ_E_ARG: a null argument, n_targets other than the table's, max_keys outside 1..255 (text: mcq_build_last_error).            */
+int mcq_table_remove_ambiguous(const mcq_table* t, const uint32_t* tgt_key /* [n_targets] */, uint32_t n_targets,
+                               uint32_t max_keys /* 1..255 */, uint32_t flags /* MCQ_DEVICE_PTRS: tgt_key is on the device */,
+                               mcq_table** out, uint64_t* n_removed);
 /* windows of every target (the `windows` field of its sequence-level taxon, src/taxonomy.h:326-335) to host memory [n_targets] */
 int mcq_table_tgt_windows(const mcq_table* t, uint32_t* out);
 /* mcq_build_table + mcq_db_create in one call; the queryable handle is the only thing left in HBM */

@@ -133,6 +133,11 @@ uint32_t mcq_refdb_ancestor(const mcq_refdb* db, uint32_t key, uint32_t rank);
 uint32_t mcq_refdb_ground_truth(const mcq_refdb* db, const char* header, uint64_t len);
 int mcq_refdb_clade_keys(const mcq_refdb* db, uint32_t rank, uint32_t* out /* [n_targets] */);
 uint32_t mcq_refdb_taxon_clade(const mcq_refdb* db, uint32_t truth, uint32_t rank);
+/* mcq_refdb_clade_keys without a database: the keys of targets 0 .. n_targets-1 from the taxon list a build is about to write
+ * (mcq_refdb_write_shard: sequence-level taxa, id -(target + 1), then the dump's) -- the values mcq_refdb_clade_keys returns on the
+ * written files: index into `taxa` of the ancestor at exactly `rank`, or MCQ_CLADE_NONE.  What mcq_table_remove_ambiguous
+ * (include/mcq.h) takes for -remove-ambig-features RANK; for rank sequence the caller passes the target ids themselves.       */
+int mcq_taxa_clade_keys(const mcq_taxon_rec* taxa, uint64_t n_taxa, uint32_t n_targets, uint32_t rank, uint32_t* out /* [n_targets] */);
 
 /* ---- evaluation statistics (`-precision`): classification_statistics (src/classification_statistics.h:40-235) restated
  * type for type.  The four arrays are indexed by rank, [MCQ_RANK_NONE] counting the queries without: assigned[r] = queries

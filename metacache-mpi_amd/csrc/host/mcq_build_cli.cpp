@@ -5,13 +5,22 @@
 //      (mcq_genome_files), their sequences streamed through two pinned buffers into device memory (mcq_genome_reader_*): target
 //      ids, names and parents as the reference gives them
 //   2. the union of the P rank tables on the GPU (mcq_build_table: sketch, per-(feature, rank) limit, rank merge,
-//      -remove-overpopulated-features)
+//      -remove-overpopulated-features), then -remove-ambig-features on that union (mcq_table_remove_ambiguous with the targets'
+//      clade keys from mcq_taxa_clade_keys); the unfiltered table is released before the rank split
 //   3. per rank: its table cut out of the union on the GPU (mcq_table_rank_split), copied to the host and written by
 //      mcq_refdb_write_shard with the whole taxon list (`windows` set for the targets the rank owns, src/sketch_database.h:540-542)
 // Host memory: two read buffers (-read-buffer) and the tables of -ranks-per-pass ranks; never the union table.
 //
 // usage: mcq_build_cli DB P GENOMES... -taxonomy DIR [-kmerlen K] [-sketchlen S] [-winlen W] [-winstride X]
-//            [-max-locations-per-feature N] [-remove-overpopulated-features] [-device D] [-ranks-per-pass R] [-read-buffer BYTES]
+//            [-max-locations-per-feature N] [-remove-overpopulated-features] [-remove-ambig-features RANK] [-max-ambig-per-feature N]
+//            [-device D] [-ranks-per-pass R] [-read-buffer BYTES]
+// -remove-ambig-features RANK [-max-ambig-per-feature N, default 1]: a feature whose locations, over all P ranks and after the limit
+// and -remove-overpopulated-features, name more than N distinct taxa at RANK (targets without one count as one taxon; the targets
+// themselves for `sequence`) is left out of every file: remove_ambiguous_features (src/sketch_database.h:428-470) as the
+// non-distributed post_process_features calls it (src/mode_build.cpp:729-747), on the whole database.  N is narrowed to 8 bits, then
+// 0 becomes 1; RANK `none` or unknown leaves the option off (a warning); nothing happens when the dump holds at most one taxon.
+// DIVERGENCE: the reference's `mpiexec -n P metacache_mpi build` accepts the options and ignores them (the call is commented out in
+// post_process_features_distributed, src/mode_build.cpp:770-789, at every P): there is no reference file to compare with.
 // Not reproduced: the order of the keys inside a file (the reference's hash table order; its reader inserts key by key, any order
 // reads back the same), and the mapping of sequences to taxa through assembly_summary.txt / *.accession2taxid files: a target's
 // parent is the N of "taxid|N" in its header, or 0.  The sequences and the temporaries of the one-piece build must fit the
@@ -28,17 +37,23 @@ struct BuildOptions {
     std::string db, taxonomy; uint32_t P = 1; std::vector<std::string> inputs;
     int kmerlen = 16, sketchlen = 16, winlen = 128, winstride = -1, max_locs = 254;      // src/mode_build.cpp:63-72, :108-119
     bool remove_overpopulated = false;
+    uint32_t ambig_rank = MCQ_RANK_NONE; int max_ambig = 1;                             // src/mode_build.cpp:74-75, :124-131
     int device = 0; uint32_t ranks_per_pass = 1; uint64_t read_buffer = 64u << 20;
 };
 
 const char* kUsage =
     "usage: mcq_build_cli DB P GENOMES... -taxonomy DIR [-kmerlen K] [-sketchlen S] [-winlen W] [-winstride X]\n"
-    "           [-max-locations-per-feature N] [-remove-overpopulated-features] [-device D] [-ranks-per-pass R] [-read-buffer BYTES]\n"
+    "           [-max-locations-per-feature N] [-remove-overpopulated-features] [-remove-ambig-features RANK] [-max-ambig-per-feature N]\n"
+    "           [-device D] [-ranks-per-pass R] [-read-buffer BYTES]\n"
     "writes DB.db_0 .. DB.db_<P-1>: the files `mpiexec -n P metacache_mpi build DB GENOMES... -taxonomy DIR` writes\n"
     "  GENOMES        FASTA files or directories of them (before the first option); directories are read recursively\n"
     "  -taxonomy DIR  nodes.dmp, names.dmp and, if present, merged.dmp\n"
     "  defaults       -kmerlen 16 -sketchlen 16 -winlen 128 -winstride winlen-kmerlen+1 -max-locations-per-feature 254\n"
     "  limits         kmerlen <= 16, sketchlen <= 32, winlen <= 128 (the kernels' limits)\n"
+    "  -remove-ambig-features RANK [-max-ambig-per-feature N]   leaves out every feature whose locations, over all P ranks, name more\n"
+    "                 than N (default 1; narrowed to 8 bits, 0 -> 1) distinct taxa at RANK (sequence .. root; targets without a taxon there\n"
+    "                 count as one); `none` or an unknown RANK leaves it off.  Divergence: the reference's `mpiexec -n P metacache_mpi\n"
+    "                 build` accepts the options and ignores them; here they do what the reference documents\n"
     "  -ranks-per-pass R   ranks whose tables are in host memory at a time (default 1); -read-buffer: bytes of each of the two read buffers\n"
     "not supported: assembly_summary.txt / *.accession2taxid mapping files (a target's parent is the N of 'taxid|N' in its\n"
     "header, else none), FASTQ genome files, adding to an existing database; the key order inside a file is not the reference's\n";
@@ -61,6 +76,12 @@ bool parse(int argc, char** argv, BuildOptions& o) {
         else if (opt_named(a, {"-winstride"})) o.winstride = std::atoi(next());
         else if (opt_named(a, {"-max-locations-per-feature", "-max_locations_per_feature"})) o.max_locs = std::atoi(next());
         else if (opt_named(a, {"-remove-overpopulated-features", "-remove_overpopulated_features"})) o.remove_overpopulated = true;
+        else if (opt_named(a, {"-remove-ambig-features", "-remove_ambig_features"})) {
+            const std::string name = next();
+            o.ambig_rank = mcq_rank_from_name(name.c_str());                // (`none` and unknown names: off, src/taxonomy.h:173-213)
+            if (o.ambig_rank >= MCQ_RANK_NONE) std::fprintf(stderr, "warning: -remove-ambig-features %s names no rank: no feature is removed\n", name.c_str());
+        }
+        else if (opt_named(a, {"-max-ambig-per-feature", "-max_ambig_per_feature"})) o.max_ambig = std::atoi(next());
         else if (opt_named(a, {"-device"})) o.device = std::atoi(next());
         else if (opt_named(a, {"-ranks-per-pass"})) o.ranks_per_pass = (uint32_t)std::max(1, std::atoi(next()));
         else if (opt_named(a, {"-read-buffer"})) o.read_buffer = std::max<uint64_t>(1, std::strtoull(next(), nullptr, 10));
@@ -75,6 +96,9 @@ bool parse(int argc, char** argv, BuildOptions& o) {
     // the bucket size type, 8 bits (src/config.h:77: 256 -> 0, 300 -> 44), then brought into 1..254 (src/sketch_database.h:356-368)
     if (o.max_locs <= 0) o.max_locs = 254;
     else { o.max_locs &= 0xFF; o.max_locs = std::min(std::max(o.max_locs, 1), 254); }
+    // -max-ambig-per-feature N: the parameter is a bucket_size_type, 8 bits (256 -> 0, 300 -> 44); then 0 -> 1 (src/sketch_database.h:437)
+    o.max_ambig &= 0xFF;
+    if (o.max_ambig == 0) o.max_ambig = 1;
     return true;
 }
 
@@ -182,11 +206,32 @@ int main(int argc, char** argv) {
     if (mcq_table_tgt_windows(table.h, windows.data())) { std::fprintf(stderr, "ABORT: %s\n", mcq_build_last_error()); return 1; }
     phase("sketch + sort");
 
-    // ---- 3. rank by rank: split on the device, copy, write.  The taxon list: sequence-level taxa (id -(target + 1): the last
-    // target first) before the taxonomy's, both in ascending id (src/taxonomy.h:290-294, :348)
+    // The taxon list: sequence-level taxa (id -(target + 1): the last target first) before the taxonomy's, both in ascending id
+    // (src/taxonomy.h:290-294, :348)
     std::vector<mcq_taxon_rec> taxa;
     for (uint32_t t = nt; t-- > 0;) taxa.push_back(targets[t]);
     for (uint64_t i = 0; i < mcq_taxdump_count(tax.h); ++i) taxa.push_back(mcq_taxdump_taxa(tax.h)[i]);
+
+    // ---- 2b. -remove-ambig-features: once, on the union table (non_target_taxon_count() > 1, src/mode_build.cpp:729-730)
+    std::string ambig_line;
+    if (o.ambig_rank < MCQ_RANK_NONE && mcq_taxdump_count(tax.h) > 1) {
+        std::vector<uint32_t> tgt_key(nt);
+        if (o.ambig_rank == MCQ_RANK_SEQUENCE) for (uint32_t t = 0; t < nt; ++t) tgt_key[t] = t;
+        else if (mcq_taxa_clade_keys(taxa.data(), taxa.size(), nt, o.ambig_rank, tgt_key.data())) return host_fail();
+        uint64_t keys_before = 0, removed = 0;
+        Table kept;
+        if (mcq_table_info(table.h, &keys_before, nullptr, nullptr, nullptr, nullptr, nullptr) ||
+            mcq_table_remove_ambiguous(table.h, tgt_key.data(), nt, (uint32_t)o.max_ambig, 0, &kept.h, &removed)) {
+            std::fprintf(stderr, "ABORT: %s\n", mcq_build_last_error()); return 1;
+        }
+        table.reset();                                                       // (the unfiltered table goes before the rank split)
+        std::swap(table.h, kept.h);
+        ambig_line = "ambiguous features on rank " + std::string(mcq_rank_name(o.ambig_rank)) + " (more than " + std::to_string(o.max_ambig) +
+                     " taxa): " + std::to_string(removed) + " of " + std::to_string(keys_before) + " removed\n";
+        phase("remove ambiguous features");
+    }
+
+    // ---- 3. rank by rank: split on the device, copy, write
     mcq_shard_params sp;
     sp.k = sp.q_k = (uint64_t)o.kmerlen; sp.sketch_size = sp.q_sketch_size = (uint64_t)o.sketchlen;     // the query sketcher starts as the target
     sp.winlen = sp.q_winlen = (uint64_t)o.winlen; sp.winstride = sp.q_winstride = (uint64_t)o.winstride;   // sketcher (src/sketch_database.h:247-260)
@@ -227,6 +272,7 @@ int main(int argc, char** argv) {
         t_split += std::chrono::duration<double>(tb - ta).count(); t_write += std::chrono::duration<double>(tc - tb).count();
     }
     if (phase.on) std::fprintf(stderr, "[mcq_build_cli] %-28s %8.3f s\n[mcq_build_cli] %-28s %8.3f s\n", "rank split", t_split, "write", t_write);
+    std::fputs(ambig_line.c_str(), stdout);
     std::printf("%u targets, %llu bases -> %u files %s_0 .. _%u: %llu keys, %llu locations\n", nt, (unsigned long long)n_bases, o.P, o.db.c_str(),
                 o.P - 1, (unsigned long long)keys_total, (unsigned long long)locs_total);
     return 0;

@@ -454,6 +454,22 @@ extern "C" int mcq_refdb_clade_keys(const mcq_refdb* db, uint32_t rank, uint32_t
     return 0;
 }
 
+// the same keys from a taxon list that has not been written yet (what mcq_build_cli is about to hand to mcq_refdb_write_shard):
+// a handle without files around the list, the lineages of build_lineages, mcq_refdb_clade_keys
+extern "C" int mcq_taxa_clade_keys(const mcq_taxon_rec* taxa, uint64_t n_taxa, uint32_t n_targets, uint32_t rank, uint32_t* out) {
+    if ((n_taxa && !taxa) || (n_targets && !out)) return fail("bad argument");
+    mcq_refdb db;
+    db.taxa.reserve(n_taxa);
+    for (uint64_t i = 0; i < n_taxa; ++i) {
+        Taxon t; t.id = taxa[i].id; t.parent = taxa[i].parent; t.rank = taxa[i].rank; t.name = taxa[i].name ? taxa[i].name : "";
+        t.index = taxa[i].index; t.windows = taxa[i].windows;
+        db.taxa.push_back(std::move(t));
+    }
+    db.info.n_targets = n_targets; db.info.n_taxa = (uint32_t)n_taxa;
+    build_lineages(&db);
+    return mcq_refdb_clade_keys(&db, rank, out);
+}
+
 extern "C" uint32_t mcq_refdb_ranked_lca(const mcq_refdb* db, uint32_t a, uint32_t b) {
     if (!valid_key(db, a) || !valid_key(db, b)) return MCQ_NO_TAXON;
     const uint32_t* la = &db->lineage[(size_t)(a & 0x7FFFFFFFu) * kNumRanks];

@@ -952,6 +952,148 @@ extern "C" int mcq_table_rank_split(const mcq_table* t, uint32_t n_ranks, uint32
     return MCQ_OK;
 }
 
+// ---- -remove-ambig-features: keys whose list names more than max_keys distinct clades (mcq_table_remove_ambiguous of include/mcq.h) ----
+// remove_ambiguous_features (src/sketch_database.h:428-470) over the union table: a feature goes when the targets of its list have more
+// than max_keys distinct values of tgt_key[target] (the target's ancestor at the rank, "none" being one value; the target itself for
+// rank sequence).  Same traversal as the rank split above: a group of 16 lanes per key, four keys per wave, 16 consecutive locations
+// per step, trip counts uniform over the wave; a count pass (alive, surviving length = the whole list or nothing), the two scans, a
+// scatter pass that copies the lists of the keys that stay.  No atomics, nothing comes back to the host per key.
+//   max_keys = 1 (the default): a list is ambiguous as soon as one key differs from that of its first location -- one ballot per step.
+//   max_keys > 1: the group keeps the distinct keys it has seen in LDS, max_keys + 1 words per group (at most 256: 16 KB per block of
+//   16 groups).  A list is sorted by (target, window), so the locations of one target are a run: only the first location of a run is
+//   a candidate (equal keys of DIFFERENT targets are not adjacent and are found by the set).  A candidate scans the set; candidates
+//   that are not in it are made unique among the 16 lanes by shuffles (only in steps where some group of the wave has two of them),
+//   then appended at ballot-prefix positions.  The count saturates at max_keys + 1, where the group stops looking.
+namespace {
+__device__ __forceinline__ u32 ambig_key(const u32* tgt_key, u32 n_targets, u64 loc) {
+    const u32 t = (u32)(loc >> 32);
+    return t < n_targets ? tgt_key[t] : 0u;
+}
+template <bool ONE>
+__global__ void __launch_bounds__(256) k_ambig_count(const u64* list_off, const u64* locs, u64 n_keys, const u32* tgt_key, u32 n_targets,
+                                                    u32 max_keys, u32* cnt, u32* alive) {
+    extern __shared__ u32 s_seen[];                              // [blockDim.x / 16][max_keys + 1]; not used by ONE
+    const u32 lane = threadIdx.x & 63, sub = lane % SPLIT_GROUP, shift = lane - sub;
+    const u64 wave = ((u64)blockIdx.x * blockDim.x + threadIdx.x) >> 6, n_waves = ((u64)gridDim.x * blockDim.x) >> 6;
+    const u32 cap = max_keys + 1;
+    u32* seen = s_seen + (threadIdx.x / SPLIT_GROUP) * cap;
+    for (u64 base = wave * 4; base < n_keys; base += n_waves * 4) {
+        const SplitKey s = split_key(list_off, n_keys, base, lane);
+        bool ambiguous = false;
+        if (ONE) {
+            u32 first = 0;
+            for (u32 i = 0; i < s.steps; ++i) {
+                const u32 j = i * SPLIT_GROUP + sub;
+                const bool valid = j < s.len;
+                const u32 k = valid ? ambig_key(tgt_key, n_targets, locs[s.beg + j]) : 0u;
+                if (i == 0) first = (u32)__shfl((int)k, (int)shift, 64);
+                ambiguous |= ((__ballot(valid && k != first) >> shift) & 0xFFFFull) != 0;
+                if (!__ballot(!ambiguous && (i + 1) * SPLIT_GROUP < s.len)) break;       // (uniform) no group of the wave has anything left to learn
+            }
+        } else {
+            u32 n = 0, last_t = 0xFFFFFFFFu;                     // distinct keys so far; target of the location before this step's first
+            for (u32 i = 0; i < s.steps; ++i) {
+                const u32 j = i * SPLIT_GROUP + sub;
+                const bool valid = j < s.len;
+                const u64 w = valid ? locs[s.beg + j] : 0;
+                const u32 t = (u32)(w >> 32);
+                const u32 k = valid ? ambig_key(tgt_key, n_targets, w) : 0u;
+                const u32 before = (u32)__shfl((int)t, (int)((lane + 63) & 63), 64);
+                bool cand = valid && n < cap && t != (sub ? before : last_t);
+                last_t = (u32)__shfl((int)t, (int)(shift + SPLIT_GROUP - 1), 64);
+                if (cand) for (u32 q = 0; q < n; ++q) if (seen[q] == k) { cand = false; break; }
+                bool fresh = cand;
+                const u32 bits = (u32)((__ballot(cand) >> shift) & 0xFFFFull);
+                if (__ballot((bits & (bits - 1)) != 0)) {        // some group has two candidates: the lowest lane of every key stays
+                    for (u32 d = 1; d < SPLIT_GROUP; ++d) {
+                        const u32 ko = (u32)__shfl((int)k, (int)((lane + 64 - d) & 63), 64);
+                        const int co = __shfl((int)cand, (int)((lane + 64 - d) & 63), 64);
+                        if (sub >= d && co && ko == k) fresh = false;
+                    }
+                }
+                const u32 add = (u32)((__ballot(fresh) >> shift) & 0xFFFFull);
+                const u32 at = n + (u32)__builtin_popcount(add & ((1u << sub) - 1u));
+                if (fresh && at < cap) seen[at] = k;
+                n = min(n + (u32)__builtin_popcount(add), cap);
+                __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");       // the group's next step reads what this one wrote
+                __builtin_amdgcn_wave_barrier();
+                __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+                if (!__ballot(n < cap && (i + 1) * SPLIT_GROUP < s.len)) break;
+            }
+            ambiguous = n > max_keys;
+        }
+        if (sub == 0 && s.kx < n_keys) { const bool stays = s.len && !ambiguous; cnt[s.kx] = stays ? s.len : 0u; alive[s.kx] = stays ? 1u : 0u; }
+    }
+}
+__global__ void __launch_bounds__(256) k_ambig_scatter(const u32* keys, const u64* list_off, const u64* locs, u64 n_keys, const u32* alive,
+                                                      const u64* key_pos, const u64* loc_pos, u64 n_keys_out, u64 n_locs_out,
+                                                      u32* okeys, u64* ooff, u64* olocs) {
+    const u32 lane = threadIdx.x & 63, sub = lane % SPLIT_GROUP;
+    const u64 wave = ((u64)blockIdx.x * blockDim.x + threadIdx.x) >> 6, n_waves = ((u64)gridDim.x * blockDim.x) >> 6;
+    if (blockIdx.x == 0 && threadIdx.x == 0) ooff[n_keys_out] = n_locs_out;
+    for (u64 base = wave * 4; base < n_keys; base += n_waves * 4) {
+        const u64 kx = base + lane / SPLIT_GROUP;
+        if (kx >= n_keys || !alive[kx]) continue;
+        const u64 beg = list_off[kx], out = loc_pos[kx];
+        const u32 len = (u32)(list_off[kx + 1] - beg);
+        if (sub == 0) { const u64 ko = key_pos[kx]; if (ko < n_keys_out) { okeys[ko] = keys[kx]; ooff[ko] = out; } }
+        for (u32 j = sub; j < len; j += SPLIT_GROUP) if (out + j < n_locs_out) olocs[out + j] = locs[beg + j];
+    }
+}
+}  // namespace
+
+extern "C" int mcq_table_remove_ambiguous(const mcq_table* t, const uint32_t* tgt_key, uint32_t n_targets, uint32_t max_keys, uint32_t flags,
+                                          mcq_table** out, uint64_t* n_removed) {
+    if (!t || !tgt_key || !out || !n_removed) return bfail(MCQ_E_ARG, "null argument");
+    if (n_targets != t->n_targets) return bfail(MCQ_E_ARG, "n_targets is not the table's (" + std::to_string(t->n_targets) + ")");
+    if (max_keys < 1 || max_keys > 255) return bfail(MCQ_E_ARG, "max_keys must be 1..255");
+    BCHK(hipSetDevice(t->device));
+    const u64 nk = t->n_keys;
+    mcq_table* R = new mcq_table();
+    std::memset(R, 0, sizeof(*R));
+    R->device = t->device; R->n_targets = t->n_targets;
+    struct TableGuard { mcq_table*& t; ~TableGuard() { if (t) mcq_table_free(t); } } guard{R};
+    BCHK(hipMalloc(&R->win_off, ((u64)t->n_targets + 1) * 8));
+    BCHK(hipMemcpy(R->win_off, t->win_off, ((u64)t->n_targets + 1) * 8, hipMemcpyDeviceToDevice));
+    u32 *cnt = nullptr, *alive = nullptr, *d_key = nullptr; u64 *key_pos = nullptr, *loc_pos = nullptr;
+    struct Tmp { void** p; ~Tmp() { (void)hipFree(*p); } };
+    Tmp f0{(void**)&d_key};
+    const u32* keyp = tgt_key;
+    if (!(flags & MCQ_DEVICE_PTRS)) {
+        BCHK(hipMalloc(&d_key, (u64)n_targets * 4));
+        BCHK(hipMemcpy(d_key, tgt_key, (u64)n_targets * 4, hipMemcpyHostToDevice));
+        keyp = d_key;
+    }
+    BCHK(hipMalloc(&cnt, (nk ? nk : 1) * 4)); Tmp f1{(void**)&cnt};
+    BCHK(hipMalloc(&alive, (nk ? nk : 1) * 4)); Tmp f2{(void**)&alive};
+    BCHK(hipMalloc(&key_pos, (nk ? nk : 1) * 8)); Tmp f3{(void**)&key_pos};
+    BCHK(hipMalloc(&loc_pos, (nk ? nk : 1) * 8)); Tmp f4{(void**)&loc_pos};
+    const dim3 grid = grid_for((nk + 3) / 4 * 64);               // four keys per wave of 64 lanes
+    u64 n_keys_out = 0, n_locs_out = 0;
+    if (nk) {
+        if (max_keys == 1)
+            hipLaunchKernelGGL(k_ambig_count<true>, grid, dim3(TB), 0, 0, (const u64*)t->list_off, (const u64*)t->locs, nk, keyp, n_targets, max_keys, cnt, alive);
+        else
+            hipLaunchKernelGGL(k_ambig_count<false>, grid, dim3(TB), (TB / SPLIT_GROUP) * (max_keys + 1) * 4, 0, (const u64*)t->list_off, (const u64*)t->locs, nk,
+                               keyp, n_targets, max_keys, cnt, alive);
+    }
+    MCHK(excl_scan(cnt, loc_pos, nk, &n_locs_out));
+    MCHK(excl_scan(alive, key_pos, nk, &n_keys_out));
+    R->n_keys = n_keys_out; R->n_locs = n_locs_out;
+    BCHK(hipMalloc(&R->keys, (n_keys_out ? n_keys_out : 1) * 4));
+    BCHK(hipMalloc(&R->list_off, (n_keys_out + 1) * 8));
+    BCHK(hipMalloc(&R->locs, (n_locs_out ? n_locs_out : 1) * 8));
+    if (nk) hipLaunchKernelGGL(k_ambig_scatter, grid, dim3(TB), 0, 0, (const u32*)t->keys, (const u64*)t->list_off, (const u64*)t->locs, nk,
+                               (const u32*)alive, (const u64*)key_pos, (const u64*)loc_pos, n_keys_out, n_locs_out, R->keys, R->list_off, R->locs);
+    else BCHK(hipMemset(R->list_off, 0, 8));
+    BCHK(hipDeviceSynchronize());
+    BCHK(hipGetLastError());
+    *n_removed = nk - n_keys_out;
+    *out = R;
+    R = nullptr;
+    return MCQ_OK;
+}
+
 extern "C" int mcq_table_tgt_windows(const mcq_table* t, uint32_t* out) {
     if (!t || !out) return bfail(MCQ_E_ARG, "null argument");
     BCHK(hipSetDevice(t->device));

@@ -160,6 +160,8 @@ def lib():
         L.mcq_table_free.argtypes = [C.c_void_p]
         L.mcq_table_rank_split.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.POINTER(C.c_void_p)]
         L.mcq_table_tgt_windows.argtypes = [C.c_void_p, C.c_void_p]
+        L.mcq_table_remove_ambiguous.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(C.c_void_p),
+                                                 C.POINTER(C.c_uint64)]
         L.mcq_build_last_error.restype = C.c_char_p
         L.mcq_build_parts.argtypes = [C.POINTER(BuildDesc), C.POINTER(C.c_void_p)]
         L.mcq_parts_info.argtypes = [C.c_void_p, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_uint32), C.POINTER(C.c_uint64)]
@@ -706,6 +708,28 @@ class Table:
         t = Table.__new__(Table)
         t._adopt(h, self.n_targets, self.device)
         return t
+
+    def remove_ambiguous(self, tgt_key, max_keys=1, n_targets=None):
+        """mcq_table_remove_ambiguous (-remove-ambig-features): (the table without the keys whose list names more than `max_keys`
+        distinct tgt_key[target], number of keys dropped).  tgt_key: a numpy array (u32 [n_targets], host), or a raw device
+        pointer (int) to that many words; n_targets defaults to the table's."""
+        n = self.n_targets if n_targets is None else n_targets
+        if isinstance(tgt_key, int):
+            ptr, flags = C.c_void_p(tgt_key), MCQ_DEVICE_PTRS
+        elif tgt_key is None:
+            ptr, flags = None, 0
+        else:
+            keep = np.ascontiguousarray(tgt_key, np.uint32)
+            if n_targets is None:
+                n = len(keep)
+            ptr, flags = _np_ptr(keep), 0
+        h, removed = C.c_void_p(), C.c_uint64()
+        rc = lib().mcq_table_remove_ambiguous(self.h, ptr, n, max_keys, flags, C.byref(h), C.byref(removed))
+        if rc != 0:
+            raise McqError(rc, (lib().mcq_build_last_error() or b"").decode())
+        t = Table.__new__(Table)
+        t._adopt(h, self.n_targets, self.device)
+        return t, int(removed.value)
 
     def tgt_windows(self):
         """windows of every target (u32 [n_targets])"""

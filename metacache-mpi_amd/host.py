@@ -80,6 +80,7 @@ def lib():
         L.mcq_refdb_lineages.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
         L.mcq_refdb_ground_truth.restype = C.c_uint32; L.mcq_refdb_ground_truth.argtypes = [C.c_void_p, C.c_char_p, C.c_uint64]
         L.mcq_refdb_clade_keys.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p]
+        L.mcq_taxa_clade_keys.argtypes = [C.POINTER(TaxonRec), C.c_uint64, C.c_uint32, C.c_uint32, C.c_void_p]
         L.mcq_refdb_taxon_clade.restype = C.c_uint32; L.mcq_refdb_taxon_clade.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32]
         L.mcq_refdb_ranked_lca.restype = C.c_uint32; L.mcq_refdb_ranked_lca.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32]
         sp = C.POINTER(EvalStatsRec)
@@ -503,6 +504,23 @@ def read_taxdump(directory):
         return [_rec(arr[i]) for i in range(lib().mcq_taxdump_count(h))]
     finally:
         lib().mcq_taxdump_free(h)
+
+
+def taxa_clade_keys(targets, dump, rank):
+    """mcq_taxa_clade_keys: per target the key of its ancestor at `rank` (index into the taxon list a build writes: the targets'
+    sequence-level taxa, last target first, then the dump's), NO_TAXON where it has none -- RefDb.clade_keys of the database
+    built from these inputs, without the database.  targets: the records read_genomes gives; dump: those of read_taxdump."""
+    taxa = list(reversed(targets)) + list(dump)
+    arr = (TaxonRec * max(1, len(taxa)))()
+    keep = []
+    for i, t in enumerate(taxa):
+        nm, fl = t["name"].encode("latin-1"), t["file"].encode("latin-1")
+        keep += [nm, fl]
+        arr[i] = TaxonRec(t["id"], t["parent"], t["rank"], nm, fl, t["index"], t["windows"])
+    out = np.zeros(len(targets), np.uint32)
+    if lib().mcq_taxa_clade_keys(arr, len(taxa), len(targets), rank, out.ctypes.data_as(C.c_void_p)) != 0:
+        raise _err()
+    return out
 
 
 def target_name(header):
