@@ -14,9 +14,11 @@
 #include <chrono>
 #include <cstdio>
 #include <hip/hip_runtime.h>
+#include <memory>
 #include <rocprim/rocprim.hpp>
 #include <stdint.h>
 #include <string>
+#include <utility>
 #include <vector>
 
 #include "../../include/mcq.h"
@@ -30,6 +32,26 @@ int bfail(int code, const std::string& m) { g_berr = m; return code; }
 #define BCHK(expr) do { hipError_t e_ = (expr); if (e_ != hipSuccess) \
     return bfail(MCQ_E_HIP, std::string(#expr) + ": " + hipGetErrorString(e_)); } while (0)
 #define MCHK(expr) do { int r_ = (expr); if (r_ != MCQ_OK) return r_; } while (0)
+
+// n elements of T from hipMalloc (never fewer than one), behind a move-only owner whose destructor gives them back: every way
+// out of a function frees.  What the handles of this unit keep lives in these; the temporaries of a build come from Scratch.
+template <class T> struct Dev {
+    T* p = nullptr;
+    Dev() = default;
+    Dev(Dev&& o) noexcept : p(o.release()) {}
+    Dev& operator=(Dev&& o) noexcept { if (this != &o) { reset(); p = o.release(); } return *this; }
+    ~Dev() { reset(); }
+    hipError_t alloc(u64 n) { reset(); return hipMalloc(&p, (n ? n : 1) * sizeof(T)); }
+    T* get() const { return p; }
+    void reset() { if (p) (void)hipFree(p); p = nullptr; }
+    T* release() { T* q = p; p = nullptr; return q; }
+};
+// a half-built handle: freed by its own *_free / mcq_db_destroy unless released into *out
+template <class H, int (*Free)(H*)> struct HandleFree { void operator()(H* h) const { (void)Free(h); } };
+typedef std::unique_ptr<mcq_table, HandleFree<mcq_table, mcq_table_free>> TablePtr;
+typedef std::unique_ptr<mcq_parts, HandleFree<mcq_parts, mcq_parts_free>> PartsPtr;
+typedef std::unique_ptr<mcq_parts_builder, HandleFree<mcq_parts_builder, mcq_parts_builder_free>> BuilderPtr;
+typedef std::unique_ptr<mcq_db, HandleFree<mcq_db, mcq_db_destroy>> DbPtr;
 
 // Temporaries of one build come from the device's default memory pool with its release threshold lifted, so a buffer
 // freed by one phase is handed to the next without unmapping and remapping HBM (hipMalloc / hipFree of tens of GB were
@@ -152,23 +174,22 @@ int excl_scan(const u32* in, u64* out, u64 n, u64* total) {
     size_t tmp = 0;
     auto first = rocprim::make_transform_iterator(in, [] __device__(u32 x) { return (u64)x; });
     BCHK(rocprim::exclusive_scan(nullptr, tmp, first, out, (u64)0, n, rocprim::plus<u64>()));
-    void* t = nullptr;
-    BCHK(hipMalloc(&t, tmp ? tmp : 1));
-    BCHK(rocprim::exclusive_scan(t, tmp, first, out, (u64)0, n, rocprim::plus<u64>()));
+    Dev<char> t;
+    BCHK(t.alloc(tmp));
+    BCHK(rocprim::exclusive_scan(t.get(), tmp, first, out, (u64)0, n, rocprim::plus<u64>()));
     u64 last_out = 0; u32 last_in = 0;
     BCHK(hipMemcpy(&last_out, out + n - 1, 8, hipMemcpyDeviceToHost));
     BCHK(hipMemcpy(&last_in, in + n - 1, 4, hipMemcpyDeviceToHost));
-    BCHK(hipFree(t));
     *total = last_out + last_in;
     return MCQ_OK;
 }
 }  // namespace
 
-struct mcq_table {            // device arrays, freed by mcq_table_free
-    u64 n_keys, n_locs;
-    u32* keys; u64* list_off; u64* locs;
-    u64* win_off; u32 n_targets;
-    int device;
+struct mcq_table {            // device arrays, freed with the handle (mcq_table_free)
+    u64 n_keys = 0, n_locs = 0;
+    Dev<u32> keys; Dev<u64> list_off, locs;
+    Dev<u64> win_off; u32 n_targets = 0;
+    int device = 0;
 };
 
 extern "C" const char* mcq_build_last_error(void) { return g_berr.c_str(); }
@@ -176,7 +197,6 @@ extern "C" const char* mcq_build_last_error(void) { return g_berr.c_str(); }
 extern "C" int mcq_table_free(mcq_table* t) {
     if (!t) return MCQ_OK;
     (void)hipSetDevice(t->device);
-    (void)hipFree(t->keys); (void)hipFree(t->list_off); (void)hipFree(t->locs); (void)hipFree(t->win_off);
     delete t;
     return MCQ_OK;
 }
@@ -185,10 +205,10 @@ extern "C" int mcq_table_info(const mcq_table* t, uint64_t* n_keys, uint64_t* n_
     if (!t) return bfail(MCQ_E_ARG, "null argument");
     if (n_keys) *n_keys = t->n_keys;
     if (n_locs) *n_locs = t->n_locs;
-    if (keys) *keys = t->keys;
-    if (list_off) *list_off = t->list_off;
-    if (locs) *locs = t->locs;
-    if (win_off) *win_off = t->win_off;
+    if (keys) *keys = t->keys.get();
+    if (list_off) *list_off = t->list_off.get();
+    if (locs) *locs = t->locs.get();
+    if (win_off) *win_off = t->win_off.get();
     return MCQ_OK;
 }
 
@@ -282,6 +302,16 @@ struct PhaseTrace {
     }
 };
 
+// a key-less handle carries the sketching parameters of a build; null (and the error text set) when they are refused
+static DbPtr make_sketch_handle(const mcq_build_desc* d) {
+    mcq_db_desc sd; std::memset(&sd, 0, sizeof(sd));
+    sd.k = d->k; sd.sketch_size = d->sketch_size; sd.winlen = d->winlen; sd.winstride = d->winstride;
+    const u64 zero = 0; sd.list_off = &zero; sd.n_shards = 1; sd.device = d->device;
+    mcq_db* sk = nullptr;
+    if (mcq_db_create(&sd, &sk) != MCQ_OK) { bfail(MCQ_E_ARG, std::string("sketch parameters: ") + mcq_last_error()); return DbPtr(); }
+    return DbPtr(sk);
+}
+
 extern "C" int mcq_build_table(const mcq_build_desc* d, mcq_table** out) {
     if (!d || !out || !d->seq_off || (d->n_targets && !d->bases)) return bfail(MCQ_E_ARG, "null argument");
     if (d->n_targets < 1) return bfail(MCQ_E_ARG, "no targets");
@@ -304,55 +334,49 @@ extern "C" int mcq_build_table(const mcq_build_desc* d, mcq_table** out) {
         BCHK(hipMemcpy(t_off, d->seq_off, (u64)(nt + 1) * 8, hipMemcpyHostToDevice));
         bases = t_bases; seq_off = t_off;
     }
-    // a key-less handle carries the sketching parameters
-    mcq_db_desc sd; std::memset(&sd, 0, sizeof(sd));
-    sd.k = d->k; sd.sketch_size = d->sketch_size; sd.winlen = d->winlen; sd.winstride = d->winstride;
-    const u64 zero = 0; sd.list_off = &zero; sd.n_shards = 1; sd.device = d->device;
-    mcq_db* sk = nullptr;
-    if (mcq_db_create(&sd, &sk) != MCQ_OK) return bfail(MCQ_E_ARG, std::string("sketch parameters: ") + mcq_last_error());
+    DbPtr sk = make_sketch_handle(d);
+    if (!sk) return MCQ_E_ARG;
 
-    mcq_table* T = new mcq_table();
-    std::memset(T, 0, sizeof(*T));
+    TablePtr T(new mcq_table());
     T->device = d->device; T->n_targets = nt;
-    struct TableGuard { mcq_table*& t; ~TableGuard() { if (t) mcq_table_free(t); } } guard{T};     // error paths
-    BCHK(hipMalloc(&T->win_off, (u64)(nt + 1) * 8));
+    BCHK(T->win_off.alloc((u64)nt + 1));
+    u64* const win_off = T->win_off.get();
     mcq_batch b; b.n_seqs = nt; b.bases = bases; b.seq_off = seq_off; b.paired = 0; b.flags = MCQ_DEVICE_PTRS;
-    MCHK(mcq_count_windows(sk, &b, T->win_off, nullptr));
+    MCHK(mcq_count_windows(sk.get(), &b, win_off, nullptr));
     u64 n_win = 0;
-    BCHK(hipMemcpy(&n_win, T->win_off + nt, 8, hipMemcpyDeviceToHost));
+    BCHK(hipMemcpy(&n_win, win_off + nt, 8, hipMemcpyDeviceToHost));
     if (n_win >= (1ull << 32)) return bfail(MCQ_E_UNSUPPORTED, "more than 2^32 windows");
     const u32 s = d->sketch_size;
     const u64 n = n_win * s;
     u32 *feat = nullptr, *nfeat = nullptr;
     BCHK(tmpbuf.get(&feat, (n ? n : 1) * 4)); BCHK(tmpbuf.get(&nfeat, (n_win ? n_win : 1) * 4));
-    MCHK(mcq_sketch(sk, &b, T->win_off, feat, nfeat, nullptr));
+    MCHK(mcq_sketch(sk.get(), &b, win_off, feat, nfeat, nullptr));
     BCHK(hipDeviceSynchronize());
-    mcq_db_destroy(sk);
+    sk.reset();
     tmpbuf.put(nfeat);
     phase("windows + sketches");
 
     // (feature * P + rank, global window) in window order
     u64* key = nullptr; u32* val = nullptr;
     BCHK(tmpbuf.get(&key, (n ? n : 1) * 8)); BCHK(tmpbuf.get(&val, (n ? n : 1) * 4));
-    if (n) hipLaunchKernelGGL(k_make_pairs, grid_for(n), dim3(TB), 0, 0, feat, n, s, T->win_off, nt, P, key, val);
+    if (n) hipLaunchKernelGGL(k_make_pairs, grid_for(n), dim3(TB), 0, 0, feat, n, s, win_off, nt, P, key, val);
     tmpbuf.put(feat);
     phase("pairs");
     Lists L;
     MCHK(sort_truncate(tmpbuf, key, val, n, P, max_locs, (d->flags & MCQ_BUILD_REMOVE_OVERPOPULATED) != 0, L, phase));
     // keys, offsets, (target, window) locations
     T->n_keys = L.n_keys; T->n_locs = L.n_kept;
-    BCHK(hipMalloc(&T->keys, (L.n_keys ? L.n_keys : 1) * 4)); BCHK(hipMalloc(&T->list_off, (L.n_keys + 1) * 8));
-    BCHK(hipMalloc(&T->locs, (L.n_kept ? L.n_kept : 1) * 8));
-    if (L.n_kept) hipLaunchKernelGGL(k_emit, grid_for(L.n_kept), dim3(TB), 0, 0, L.fw, L.head, L.kid, L.n_kept, L.n_keys, T->win_off, nt, T->keys, T->list_off, T->locs);
-    else BCHK(hipMemset(T->list_off, 0, 8));
+    BCHK(T->keys.alloc(L.n_keys)); BCHK(T->list_off.alloc(L.n_keys + 1));
+    BCHK(T->locs.alloc(L.n_kept));
+    if (L.n_kept) hipLaunchKernelGGL(k_emit, grid_for(L.n_kept), dim3(TB), 0, 0, L.fw, L.head, L.kid, L.n_kept, L.n_keys, win_off, nt, T->keys.get(), T->list_off.get(), T->locs.get());
+    else BCHK(hipMemset(T->list_off.get(), 0, 8));
     BCHK(hipDeviceSynchronize());
     BCHK(hipGetLastError());
     tmpbuf.put(L.fw); tmpbuf.put(L.head); tmpbuf.put(L.kid);
     phase("emit keys / offsets / locations");
     if (t_bases) tmpbuf.put(t_bases);
     if (t_off) tmpbuf.put(t_off);
-    *out = T;
-    T = nullptr;
+    *out = T.release();
     return MCQ_OK;
 }
 
@@ -363,13 +387,15 @@ extern "C" int mcq_build_table(const mcq_build_desc* d, mcq_table** out) {
 // kept, which the stable sort relies on -- and runs the pipeline above on them; what is left of a pass is its part of the
 // table in the form the query side stores: keys, list lengths, 32-bit global-window words.
 struct mcq_parts {
-    int device; u32 n_targets;
-    u32 k, s, winlen, winstride;      // what the handle sketches QUERIES with
-    u32 tgt_winstride;                // window stride of the targets (range width of the candidates); 0 = winstride
-    u64 n_windows;
-    u32* tgt_windows;         // device [n_targets]
-    std::vector<mcq_db_part> parts;
-    u64 n_keys, n_locs, bytes;
+    int device = 0; u32 n_targets = 0;
+    u32 k = 0, s = 0, winlen = 0, winstride = 0;      // what the handle sketches QUERIES with
+    u32 tgt_winstride = 0;            // window stride of the targets (range width of the candidates); 0 = winstride
+    u64 n_windows = 0;
+    Dev<u32> tgt_windows;     // device [n_targets]
+    struct Part { Dev<u32> keys, list_len, locs; };
+    std::vector<Part> own;            // the arrays of every part ...
+    std::vector<mcq_db_part> parts;   // ... and what mcq_db_create_parts reads of them (filled by emit_part)
+    u64 n_keys = 0, n_locs = 0, bytes = 0;
 };
 namespace {
 __device__ __forceinline__ u32 tmh_dev(u32 x) {        // thomas_mueller_hash (src/hash_int.h:39-45), as mcq_owner
@@ -425,8 +451,6 @@ __global__ void k_part_len(const u64* first, u64 n_keys, u64 n, u32* list_len) {
 extern "C" int mcq_parts_free(mcq_parts* p) {
     if (!p) return MCQ_OK;
     (void)hipSetDevice(p->device);
-    for (auto& q : p->parts) { (void)hipFree((void*)q.keys); (void)hipFree((void*)q.list_len); (void)hipFree((void*)q.locs); }
-    (void)hipFree(p->tgt_windows);
     delete p;
     return MCQ_OK;
 }
@@ -437,6 +461,29 @@ extern "C" int mcq_parts_info(const mcq_parts* p, uint64_t* n_keys, uint64_t* n_
     if (n_windows) *n_windows = p->n_windows;
     if (n_parts) *n_parts = (u32)p->parts.size();
     if (bytes) *bytes = p->bytes;
+    return MCQ_OK;
+}
+
+// One part of R from sorted lists (fw / head / kid as sort_truncate leaves them, all null for an empty range): keys, list lengths
+// and words, owned by R from the first allocation on.  Gives fw / head / kid back to tmpbuf.
+static int emit_part(Scratch& tmpbuf, mcq_parts& R, u64* fw, u32* head, u64* kid, u64 n_locs, u64 n_keys) {
+    R.own.emplace_back();
+    mcq_parts::Part& o = R.own.back();
+    BCHK(o.keys.alloc(n_keys)); BCHK(o.list_len.alloc(n_keys)); BCHK(o.locs.alloc(n_locs));
+    mcq_db_part q; q.n_keys = n_keys; q.n_locs = n_locs; q.keys = o.keys.get(); q.list_len = o.list_len.get(); q.locs = o.locs.get();
+    R.parts.push_back(q);
+    if (n_locs) {
+        u64* first = nullptr;
+        BCHK(tmpbuf.get(&first, (n_keys ? n_keys : 1) * 8));
+        hipLaunchKernelGGL(k_part_first, grid_for(n_locs), dim3(TB), 0, 0, (const u32*)head, (const u64*)kid, n_locs, first);
+        hipLaunchKernelGGL(k_part_len, grid_for(n_keys), dim3(TB), 0, 0, (const u64*)first, n_keys, n_locs, o.list_len.get());
+        hipLaunchKernelGGL(k_emit_part, grid_for(n_locs), dim3(TB), 0, 0, (const u64*)fw, (const u32*)head, (const u64*)kid, n_locs, o.keys.get(), o.locs.get());
+        BCHK(hipDeviceSynchronize());
+        BCHK(hipGetLastError());
+        tmpbuf.put(first);
+    }
+    tmpbuf.put(fw); tmpbuf.put(head); tmpbuf.put(kid);
+    R.n_keys += n_keys; R.n_locs += n_locs; R.bytes += n_keys * 8 + n_locs * 4;
     return MCQ_OK;
 }
 
@@ -453,30 +500,24 @@ extern "C" int mcq_build_parts(const mcq_build_desc* d, mcq_parts** out) {
     BCHK(tmpbuf.init(d->device));
     const u32 nt = d->n_targets, s = d->sketch_size;
     PhaseTrace phase;
-    mcq_db_desc sd; std::memset(&sd, 0, sizeof(sd));
-    sd.k = d->k; sd.sketch_size = d->sketch_size; sd.winlen = d->winlen; sd.winstride = d->winstride;
-    const u64 zero = 0; sd.list_off = &zero; sd.n_shards = 1; sd.device = d->device;
-    mcq_db* sk = nullptr;
-    if (mcq_db_create(&sd, &sk) != MCQ_OK) return bfail(MCQ_E_ARG, std::string("sketch parameters: ") + mcq_last_error());
-    struct SkGuard { mcq_db* h; ~SkGuard() { mcq_db_destroy(h); } } skg{sk};
+    DbPtr sk = make_sketch_handle(d);
+    if (!sk) return MCQ_E_ARG;
 
-    mcq_parts* R = new mcq_parts();
-    R->device = d->device; R->n_targets = nt; R->k = d->k; R->s = s; R->winlen = d->winlen; R->winstride = d->winstride; R->tgt_winstride = 0;
-    R->n_windows = 0; R->tgt_windows = nullptr; R->n_keys = R->n_locs = R->bytes = 0;
-    struct PartsGuard { mcq_parts*& p; ~PartsGuard() { if (p) mcq_parts_free(p); } } guard{R};
+    PartsPtr R(new mcq_parts());
+    R->device = d->device; R->n_targets = nt; R->k = d->k; R->s = s; R->winlen = d->winlen; R->winstride = d->winstride;
 
     // windows of every target (device + host copy: the chunks are cut at target boundaries)
     u64* win_off = nullptr;
     BCHK(tmpbuf.get(&win_off, (u64)(nt + 1) * 8));
     mcq_batch b; b.n_seqs = nt; b.bases = d->bases; b.seq_off = d->seq_off; b.paired = 0; b.flags = MCQ_DEVICE_PTRS; b.n_bases = 0;
-    MCHK(mcq_count_windows(sk, &b, win_off, nullptr));
+    MCHK(mcq_count_windows(sk.get(), &b, win_off, nullptr));
     std::vector<u64> h_win(nt + 1);
     BCHK(hipMemcpy(h_win.data(), win_off, (u64)(nt + 1) * 8, hipMemcpyDeviceToHost));
     const u64 n_win = h_win[nt];
     if (n_win >= 0xFFFFFFFFull) return bfail(MCQ_E_UNSUPPORTED, "2^32 - 1 windows or more");
     R->n_windows = n_win;
-    BCHK(hipMalloc(&R->tgt_windows, (u64)nt * 4));
-    hipLaunchKernelGGL(k_windows_of, dim3((nt + TB - 1) / TB), dim3(TB), 0, 0, (const u64*)win_off, nt, R->tgt_windows);
+    BCHK(R->tgt_windows.alloc(nt));
+    hipLaunchKernelGGL(k_windows_of, dim3((nt + TB - 1) / TB), dim3(TB), 0, 0, (const u64*)win_off, nt, R->tgt_windows.get());
     phase("windows");
 
     // chunks of whole targets for the sketch (MCQ_BUILD_CHUNK_WINDOWS: tuning knob / test hook)
@@ -522,7 +563,7 @@ extern "C" int mcq_build_parts(const mcq_build_desc* d, mcq_parts** out) {
             if (!nw) continue;
             hipLaunchKernelGGL(k_shift_off, dim3((t1 - t0 + 1 + TB - 1) / TB), dim3(TB), 0, 0, (const u64*)(win_off + t0), (u64)(t1 - t0) + 1, w0, woff);
             mcq_batch cb; cb.n_seqs = t1 - t0; cb.bases = d->bases; cb.seq_off = d->seq_off + t0; cb.paired = 0; cb.flags = MCQ_DEVICE_PTRS; cb.n_bases = 0;
-            MCHK(mcq_sketch(sk, &cb, woff, feat, nfeat, nullptr));
+            MCHK(mcq_sketch(sk.get(), &cb, woff, feat, nfeat, nullptr));
             hipLaunchKernelGGL(k_part_flags, grid_for(ns), dim3(TB), 0, 0, (const u32*)feat, ns, n_ranges, range, flag);
             u64 kept = 0;
             MCHK(excl_scan(flag, pos, ns, &kept));
@@ -547,27 +588,11 @@ extern "C" int mcq_build_parts(const mcq_build_desc* d, mcq_parts** out) {
         phase("  sketch + keep the part's features");
         Lists L;
         MCHK(sort_truncate(tmpbuf, key, val, cursor, P, max_locs, (d->flags & MCQ_BUILD_REMOVE_OVERPOPULATED) != 0, L, phase));
-        mcq_db_part q; q.n_keys = L.n_keys; q.n_locs = L.n_kept; q.keys = nullptr; q.list_len = nullptr; q.locs = nullptr;
-        u32 *pk = nullptr, *pl = nullptr, *pw = nullptr; u64* first = nullptr;
-        BCHK(hipMalloc(&pk, (L.n_keys ? L.n_keys : 1) * 4)); q.keys = pk;
-        R->parts.push_back(q);                                   // (owned by R from here: freed by the guard on an error)
-        BCHK(hipMalloc(&pl, (L.n_keys ? L.n_keys : 1) * 4)); R->parts.back().list_len = pl;
-        BCHK(hipMalloc(&pw, (L.n_kept ? L.n_kept : 1) * 4)); R->parts.back().locs = pw;
-        BCHK(tmpbuf.get(&first, (L.n_keys ? L.n_keys : 1) * 8));
-        if (L.n_kept) {
-            hipLaunchKernelGGL(k_part_first, grid_for(L.n_kept), dim3(TB), 0, 0, (const u32*)L.head, (const u64*)L.kid, L.n_kept, first);
-            hipLaunchKernelGGL(k_part_len, grid_for(L.n_keys), dim3(TB), 0, 0, (const u64*)first, L.n_keys, L.n_kept, pl);
-            hipLaunchKernelGGL(k_emit_part, grid_for(L.n_kept), dim3(TB), 0, 0, (const u64*)L.fw, (const u32*)L.head, (const u64*)L.kid, L.n_kept, pk, pw);
-        }
-        BCHK(hipDeviceSynchronize());
-        BCHK(hipGetLastError());
-        tmpbuf.put(first); tmpbuf.put(L.fw); tmpbuf.put(L.head); tmpbuf.put(L.kid);
-        R->n_keys += L.n_keys; R->n_locs += L.n_kept; R->bytes += L.n_keys * 8 + L.n_kept * 4;
+        MCHK(emit_part(tmpbuf, *R, L.fw, L.head, L.kid, L.n_kept, L.n_keys));
         phase("  part emitted");
     }
     tmpbuf.put(feat); tmpbuf.put(nfeat); tmpbuf.put(flag); tmpbuf.put(pos); tmpbuf.put(woff); tmpbuf.put(win_off);
-    *out = R;
-    R = nullptr;
+    *out = R.release();
     return MCQ_OK;
 }
 
@@ -581,14 +606,14 @@ extern "C" int mcq_build_parts(const mcq_build_desc* d, mcq_parts** out) {
 struct mcq_parts_builder {
     int device = 0; u32 nt = 0, n_ranges = 1, n_shards = 1, shard_id = 0;
     u32 k = 0, s = 0, winlen = 0, winstride = 0, tgt_winstride = 0;
-    u32* tgt_windows = nullptr;       // device [nt] (moves into the parts)
-    u32* gw_off = nullptr;            // device [nt + 1]
+    Dev<u32> tgt_windows;             // device [nt] (moves into the parts)
+    Dev<u32> gw_off;                  // device [nt + 1]
     u64 n_windows = 0;
-    std::vector<u64*> buf; std::vector<u64> cnt, cap;
-    u64** d_buf = nullptr;            // device copy of the buffer pointers
-    unsigned long long* d_cur = nullptr;   // device write cursors [n_ranges]
-    u32* d_hist = nullptr;            // device [n_ranges + 1]: chunk histogram, [n_ranges] = bad triples
-    u32 *d_feat = nullptr, *d_tgt = nullptr, *d_win = nullptr; u64 stage_cap = 0;
+    std::vector<Dev<u64>> buf; std::vector<u64> cnt, cap;
+    Dev<u64*> d_buf;                  // device copy of the buffer pointers
+    Dev<unsigned long long> d_cur;    // device write cursors [n_ranges]
+    Dev<u32> d_hist;                  // device [n_ranges + 1]: chunk histogram, [n_ranges] = bad triples
+    Dev<u32> d_feat, d_tgt, d_win; u64 stage_cap = 0;
     u64 n_added = 0, n_kept = 0;
 };
 namespace {
@@ -635,9 +660,6 @@ __global__ void k_triple_scatter(const u32* feat, const u32* tgt, const u32* win
 extern "C" int mcq_parts_builder_free(mcq_parts_builder* b) {
     if (!b) return MCQ_OK;
     (void)hipSetDevice(b->device);
-    for (u64* p : b->buf) (void)hipFree(p);
-    (void)hipFree(b->tgt_windows); (void)hipFree(b->gw_off); (void)hipFree(b->d_buf); (void)hipFree(b->d_cur); (void)hipFree(b->d_hist);
-    (void)hipFree(b->d_feat); (void)hipFree(b->d_tgt); (void)hipFree(b->d_win);
     delete b;
     return MCQ_OK;
 }
@@ -647,18 +669,17 @@ extern "C" int mcq_parts_builder_create(const mcq_parts_builder_desc* d, mcq_par
     const u32 n_shards = d->n_shards ? d->n_shards : 1;
     if (d->shard_id >= n_shards) return bfail(MCQ_E_ARG, "shard_id >= n_shards");
     BCHK(hipSetDevice(d->device));
-    mcq_parts_builder* b = new mcq_parts_builder();
-    struct Guard { mcq_parts_builder*& p; ~Guard() { if (p) mcq_parts_builder_free(p); } } guard{b};
+    BuilderPtr b(new mcq_parts_builder());
     b->device = d->device; b->nt = d->n_targets; b->n_shards = n_shards; b->shard_id = d->shard_id;
     b->k = d->k; b->s = d->sketch_size; b->winlen = d->winlen; b->winstride = d->winstride; b->tgt_winstride = d->tgt_winstride;
     u64 total = 0;
     for (u32 t = 0; t < d->n_targets; ++t) total += d->tgt_windows[t];
     if (total >= 0xFFFFFFFFull) return bfail(MCQ_E_UNSUPPORTED, "2^32 - 1 windows or more");
     b->n_windows = total;
-    BCHK(hipMalloc(&b->tgt_windows, (u64)d->n_targets * 4));
-    BCHK(hipMemcpy(b->tgt_windows, d->tgt_windows, (u64)d->n_targets * 4, hipMemcpyHostToDevice));
-    BCHK(hipMalloc(&b->gw_off, ((u64)d->n_targets + 1) * 4));
-    hipLaunchKernelGGL(k_gwoff, dim3(1), dim3(1), 0, 0, (const u32*)b->tgt_windows, d->n_targets, b->gw_off);
+    BCHK(b->tgt_windows.alloc(d->n_targets));
+    BCHK(hipMemcpy(b->tgt_windows.get(), d->tgt_windows, (u64)d->n_targets * 4, hipMemcpyHostToDevice));
+    BCHK(b->gw_off.alloc((u64)d->n_targets + 1));
+    hipLaunchKernelGGL(k_gwoff, dim3(1), dim3(1), 0, 0, (const u32*)b->tgt_windows.get(), d->n_targets, b->gw_off.get());
     // ranges: what the sort of one range needs at its peak (~30 B per location: the words twice, heads, key ids) against a
     // quarter of the free memory, from the caller's estimate of the locations this shard will receive
     size_t mem_free = 0, mem_total = 0;
@@ -669,13 +690,12 @@ extern "C" int mcq_parts_builder_create(const mcq_parts_builder_desc* d, mcq_par
     if (const char* e = getenv("MCQ_BUILD_PARTS")) n_ranges = (u32)std::max<u64>(1, strtoull(e, nullptr, 10));      // (test hook, as mcq_build_parts)
     if ((u64)n_ranges * n_shards > (1u << 20)) return bfail(MCQ_E_UNSUPPORTED, "too many ranges");
     b->n_ranges = n_ranges;
-    b->buf.assign(n_ranges, nullptr); b->cnt.assign(n_ranges, 0); b->cap.assign(n_ranges, 0);
-    BCHK(hipMalloc(&b->d_buf, (u64)n_ranges * 8));
-    BCHK(hipMalloc(&b->d_cur, (u64)n_ranges * 8));
-    BCHK(hipMalloc(&b->d_hist, ((u64)n_ranges + 1) * 4));
+    b->buf.resize(n_ranges); b->cnt.assign(n_ranges, 0); b->cap.assign(n_ranges, 0);
+    BCHK(b->d_buf.alloc(n_ranges));
+    BCHK(b->d_cur.alloc(n_ranges));
+    BCHK(b->d_hist.alloc((u64)n_ranges + 1));
     BCHK(hipDeviceSynchronize());
-    *out = b;
-    b = nullptr;
+    *out = b.release();
     return MCQ_OK;
 }
 
@@ -687,23 +707,23 @@ extern "C" int mcq_parts_builder_add(mcq_parts_builder* b, const uint32_t* feat,
     const u32 *df = feat, *dt = tgt, *dw = win;
     if (!(flags & MCQ_DEVICE_PTRS)) {
         if (n > b->stage_cap) {
-            (void)hipFree(b->d_feat); (void)hipFree(b->d_tgt); (void)hipFree(b->d_win); b->d_feat = b->d_tgt = b->d_win = nullptr; b->stage_cap = 0;
-            BCHK(hipMalloc(&b->d_feat, n * 4)); BCHK(hipMalloc(&b->d_tgt, n * 4)); BCHK(hipMalloc(&b->d_win, n * 4));
+            b->d_feat.reset(); b->d_tgt.reset(); b->d_win.reset(); b->stage_cap = 0;      // (all three go before the larger ones come)
+            BCHK(b->d_feat.alloc(n)); BCHK(b->d_tgt.alloc(n)); BCHK(b->d_win.alloc(n));
             b->stage_cap = n;
         }
-        BCHK(hipMemcpyAsync(b->d_feat, feat, n * 4, hipMemcpyHostToDevice, 0));
-        BCHK(hipMemcpyAsync(b->d_tgt, tgt, n * 4, hipMemcpyHostToDevice, 0));
-        BCHK(hipMemcpyAsync(b->d_win, win, n * 4, hipMemcpyHostToDevice, 0));
-        df = b->d_feat; dt = b->d_tgt; dw = b->d_win;
+        df = b->d_feat.get(); dt = b->d_tgt.get(); dw = b->d_win.get();
+        BCHK(hipMemcpyAsync(b->d_feat.get(), feat, n * 4, hipMemcpyHostToDevice, 0));
+        BCHK(hipMemcpyAsync(b->d_tgt.get(), tgt, n * 4, hipMemcpyHostToDevice, 0));
+        BCHK(hipMemcpyAsync(b->d_win.get(), win, n * 4, hipMemcpyHostToDevice, 0));
     }
-    u32* rng = nullptr;
-    BCHK(hipMalloc(&rng, n * 4));
-    struct Free { void* p; ~Free() { (void)hipFree(p); } } fr{rng};
-    BCHK(hipMemsetAsync(b->d_hist, 0, ((u64)b->n_ranges + 1) * 4, 0));
+    Dev<u32> rng_buf;
+    BCHK(rng_buf.alloc(n));
+    u32* const rng = rng_buf.get();
+    BCHK(hipMemsetAsync(b->d_hist.get(), 0, ((u64)b->n_ranges + 1) * 4, 0));
     hipLaunchKernelGGL(k_triple_range, grid_for(n), dim3(TB), 0, 0, df, dt, dw, n, b->n_ranges, b->n_shards, b->shard_id,
-                       (const u32*)b->tgt_windows, b->nt, rng, b->d_hist);
+                       (const u32*)b->tgt_windows.get(), b->nt, rng, b->d_hist.get());
     std::vector<u32> hist(b->n_ranges + 1);
-    BCHK(hipMemcpy(hist.data(), b->d_hist, hist.size() * 4, hipMemcpyDeviceToHost));
+    BCHK(hipMemcpy(hist.data(), b->d_hist.get(), hist.size() * 4, hipMemcpyDeviceToHost));
     if (hist[b->n_ranges]) return bfail(MCQ_E_ARG, std::to_string(hist[b->n_ranges]) + " triples name a target or a window the database does not have");
     // room in every range's buffer (grown by half when it runs out: a copy of what is there)
     bool moved = false;
@@ -711,15 +731,19 @@ extern "C" int mcq_parts_builder_add(mcq_parts_builder* b, const uint32_t* feat,
         const u64 need = b->cnt[r] + hist[r];
         if (need <= b->cap[r]) continue;
         const u64 ncap = std::max<u64>(need + need / 2, 1u << 20);
-        u64* nb = nullptr;
-        BCHK(hipMalloc(&nb, ncap * 8));
-        if (b->cnt[r]) BCHK(hipMemcpy(nb, b->buf[r], b->cnt[r] * 8, hipMemcpyDeviceToDevice));
-        (void)hipFree(b->buf[r]);
-        b->buf[r] = nb; b->cap[r] = ncap; moved = true;
+        Dev<u64> nb;
+        BCHK(nb.alloc(ncap));
+        if (b->cnt[r]) BCHK(hipMemcpy(nb.get(), b->buf[r].get(), b->cnt[r] * 8, hipMemcpyDeviceToDevice));
+        b->buf[r] = std::move(nb);                               // (frees the old one)
+        b->cap[r] = ncap; moved = true;
     }
-    if (moved) BCHK(hipMemcpy(b->d_buf, b->buf.data(), (u64)b->n_ranges * 8, hipMemcpyHostToDevice));
-    BCHK(hipMemcpy(b->d_cur, b->cnt.data(), (u64)b->n_ranges * 8, hipMemcpyHostToDevice));
-    hipLaunchKernelGGL(k_triple_scatter, grid_for(n), dim3(TB), 0, 0, df, dt, dw, (const u32*)rng, n, (const u32*)b->gw_off, (u64* const*)b->d_buf, b->d_cur);
+    if (moved) {
+        std::vector<u64*> ptrs(b->n_ranges);
+        for (u32 r = 0; r < b->n_ranges; ++r) ptrs[r] = b->buf[r].get();
+        BCHK(hipMemcpy(b->d_buf.get(), ptrs.data(), (u64)b->n_ranges * 8, hipMemcpyHostToDevice));
+    }
+    BCHK(hipMemcpy(b->d_cur.get(), b->cnt.data(), (u64)b->n_ranges * 8, hipMemcpyHostToDevice));
+    hipLaunchKernelGGL(k_triple_scatter, grid_for(n), dim3(TB), 0, 0, df, dt, dw, (const u32*)rng, n, (const u32*)b->gw_off.get(), (u64* const*)b->d_buf.get(), b->d_cur.get());
     BCHK(hipDeviceSynchronize());
     BCHK(hipGetLastError());
     for (u32 r = 0; r < b->n_ranges; ++r) { b->cnt[r] += hist[r]; b->n_kept += hist[r]; }
@@ -733,50 +757,31 @@ extern "C" int mcq_parts_builder_finish(mcq_parts_builder* b, mcq_parts** out) {
     Scratch tmpbuf;
     BCHK(tmpbuf.init(b->device));
     PhaseTrace phase;
-    mcq_parts* R = new mcq_parts();
+    PartsPtr R(new mcq_parts());
     R->device = b->device; R->n_targets = b->nt; R->k = b->k; R->s = b->s; R->winlen = b->winlen; R->winstride = b->winstride;
     R->tgt_winstride = b->tgt_winstride;
-    R->n_windows = b->n_windows; R->tgt_windows = b->tgt_windows; b->tgt_windows = nullptr;
-    R->n_keys = R->n_locs = R->bytes = 0;
-    struct PartsGuard { mcq_parts*& p; ~PartsGuard() { if (p) mcq_parts_free(p); } } guard{R};
-    (void)hipFree(b->d_feat); (void)hipFree(b->d_tgt); (void)hipFree(b->d_win); b->d_feat = b->d_tgt = b->d_win = nullptr;
+    R->n_windows = b->n_windows; R->tgt_windows = std::move(b->tgt_windows);
+    b->d_feat.reset(); b->d_tgt.reset(); b->d_win.reset(); b->stage_cap = 0;
     for (u32 r = 0; r < b->n_ranges; ++r) {
         const u64 n = b->cnt[r];
-        mcq_db_part q; q.n_keys = 0; q.n_locs = n; q.keys = nullptr; q.list_len = nullptr; q.locs = nullptr;
-        u64* fw = nullptr; u32* head = nullptr; u64 *kid = nullptr, *first = nullptr; u64 n_keys = 0;
+        u64* fw = nullptr; u32* head = nullptr; u64* kid = nullptr; u64 n_keys = 0;
         if (n) {
             BCHK(tmpbuf.get(&fw, n * 8));
             size_t tmp = 0;
-            BCHK(rocprim::radix_sort_keys(nullptr, tmp, b->buf[r], fw, n, 0, 64));
+            BCHK(rocprim::radix_sort_keys(nullptr, tmp, b->buf[r].get(), fw, n, 0, 64));
             void* t = nullptr; BCHK(tmpbuf.get(&t, tmp ? tmp : 1));
-            BCHK(rocprim::radix_sort_keys(t, tmp, b->buf[r], fw, n, 0, 64));
+            BCHK(rocprim::radix_sort_keys(t, tmp, b->buf[r].get(), fw, n, 0, 64));
             BCHK(hipDeviceSynchronize());
             tmpbuf.put(t);
-            (void)hipFree(b->buf[r]); b->buf[r] = nullptr; b->cap[r] = 0;
+            b->buf[r].reset(); b->cap[r] = 0;                    // (sorted into fw: the range's buffer goes before its part comes)
             BCHK(tmpbuf.get(&head, n * 4)); BCHK(tmpbuf.get(&kid, n * 8));
             hipLaunchKernelGGL(k_feat_heads, grid_for(n), dim3(TB), 0, 0, (const u64*)fw, n, head);
             MCHK(excl_scan(head, kid, n, &n_keys));
         }
-        q.n_keys = n_keys;
-        u32 *pk = nullptr, *pl = nullptr, *pw = nullptr;
-        BCHK(hipMalloc(&pk, (n_keys ? n_keys : 1) * 4)); q.keys = pk;
-        R->parts.push_back(q);                                   // (owned by R from here)
-        BCHK(hipMalloc(&pl, (n_keys ? n_keys : 1) * 4)); R->parts.back().list_len = pl;
-        BCHK(hipMalloc(&pw, (n ? n : 1) * 4)); R->parts.back().locs = pw;
-        if (n) {
-            BCHK(tmpbuf.get(&first, (n_keys ? n_keys : 1) * 8));
-            hipLaunchKernelGGL(k_part_first, grid_for(n), dim3(TB), 0, 0, (const u32*)head, (const u64*)kid, n, first);
-            hipLaunchKernelGGL(k_part_len, grid_for(n_keys), dim3(TB), 0, 0, (const u64*)first, n_keys, n, pl);
-            hipLaunchKernelGGL(k_emit_part, grid_for(n), dim3(TB), 0, 0, (const u64*)fw, (const u32*)head, (const u64*)kid, n, pk, pw);
-            BCHK(hipDeviceSynchronize());
-            BCHK(hipGetLastError());
-            tmpbuf.put(first); tmpbuf.put(fw); tmpbuf.put(head); tmpbuf.put(kid);
-        }
-        R->n_keys += n_keys; R->n_locs += n; R->bytes += n_keys * 8 + n * 4;
+        MCHK(emit_part(tmpbuf, *R, fw, head, kid, n, n_keys));   // (an empty range is a part of its own: no keys, one-element arrays)
         phase("  range sorted + emitted");
     }
-    *out = R;
-    R = nullptr;
+    *out = R.release();
     mcq_parts_builder_free(b);
     return MCQ_OK;
 }
@@ -784,19 +789,18 @@ extern "C" int mcq_parts_builder_finish(mcq_parts_builder* b, mcq_parts** out) {
 extern "C" int mcq_db_from_parts(const mcq_parts* p, const uint32_t* tgt2tax, uint32_t n_shards, uint32_t shard_id, uint32_t flags, mcq_db** out) {
     if (!p || !tgt2tax || !out) return bfail(MCQ_E_ARG, "null argument");
     BCHK(hipSetDevice(p->device));
-    u32* t2t = nullptr;
+    Dev<u32> t2t;
     if (!(flags & MCQ_DEVICE_PTRS)) {
-        BCHK(hipMalloc(&t2t, (u64)p->n_targets * 4));
-        BCHK(hipMemcpy(t2t, tgt2tax, (u64)p->n_targets * 4, hipMemcpyHostToDevice));
+        BCHK(t2t.alloc(p->n_targets));
+        BCHK(hipMemcpy(t2t.get(), tgt2tax, (u64)p->n_targets * 4, hipMemcpyHostToDevice));
     }
     mcq_db_desc c; std::memset(&c, 0, sizeof(c));
     c.k = p->k; c.sketch_size = p->s; c.winlen = p->winlen; c.winstride = p->winstride; c.tgt_winstride = p->tgt_winstride ? p->tgt_winstride : p->winstride;
-    c.n_targets = p->n_targets; c.tgt2tax = t2t ? t2t : tgt2tax; c.tgt_windows = p->tgt_windows;
+    c.n_targets = p->n_targets; c.tgt2tax = t2t.get() ? t2t.get() : tgt2tax; c.tgt_windows = p->tgt_windows.get();
     c.n_shards = n_shards ? n_shards : 1; c.shard_id = shard_id; c.device = p->device;
     c.flags = MCQ_DEVICE_PTRS | (flags & (MCQ_DB_SLOTS_16 | MCQ_DB_BUCKETS_64));
     const int rc = mcq_db_create_parts(&c, p->parts.data(), (u32)p->parts.size(), out);
     if (rc != MCQ_OK) g_berr = mcq_last_error();
-    (void)hipFree(t2t);
     return rc;
 }
 
@@ -824,35 +828,31 @@ extern "C" int mcq_db_build(const mcq_build_desc* d, mcq_db** out) {
             }
         }
         if (in_parts) {
-            mcq_parts* parts = nullptr;
-            MCHK(mcq_build_parts(d, &parts));
-            const int rc = mcq_db_from_parts(parts, d->tgt2tax, d->n_shards, d->shard_id, d->flags & (MCQ_DEVICE_PTRS | MCQ_DB_SLOTS_16 | MCQ_DB_BUCKETS_64), out);
-            mcq_parts_free(parts);
-            return rc;
+            mcq_parts* built = nullptr;
+            MCHK(mcq_build_parts(d, &built));
+            PartsPtr parts(built);
+            return mcq_db_from_parts(parts.get(), d->tgt2tax, d->n_shards, d->shard_id, d->flags & (MCQ_DEVICE_PTRS | MCQ_DB_SLOTS_16 | MCQ_DB_BUCKETS_64), out);
         }
     }
-    mcq_table* T = nullptr;
-    MCHK(mcq_build_table(d, &T));
-    u32* t2t = nullptr;
-    BCHK(hipMalloc(&t2t, (u64)d->n_targets * 4));
-    BCHK(hipMemcpy(t2t, d->tgt2tax, (u64)d->n_targets * 4, (d->flags & MCQ_DEVICE_PTRS) ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice));
+    mcq_table* built = nullptr;
+    MCHK(mcq_build_table(d, &built));
+    TablePtr T(built);
+    Dev<u32> t2t, tw;
+    BCHK(t2t.alloc(d->n_targets));
+    BCHK(hipMemcpy(t2t.get(), d->tgt2tax, (u64)d->n_targets * 4, (d->flags & MCQ_DEVICE_PTRS) ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice));
     mcq_db_desc c; std::memset(&c, 0, sizeof(c));
     c.k = d->k; c.sketch_size = d->sketch_size; c.winlen = d->winlen; c.winstride = d->winstride; c.tgt_winstride = d->winstride;
     c.n_targets = d->n_targets; c.n_keys = T->n_keys; c.n_locs = T->n_locs;
-    c.keys = T->keys; c.list_off = T->list_off; c.locs = T->locs; c.tgt2tax = t2t;
+    c.keys = T->keys.get(); c.list_off = T->list_off.get(); c.locs = T->locs.get(); c.tgt2tax = t2t.get();
     c.n_shards = d->n_shards ? d->n_shards : 1; c.shard_id = d->shard_id; c.flags = MCQ_DEVICE_PTRS | (d->flags & (MCQ_DB_LOCS_64 | MCQ_DB_LOCS_GW | MCQ_DB_SLOTS_16 | MCQ_DB_BUCKETS_64)); c.device = d->device;
     // the true window counts of the targets (what the parts route defines its words by), and for a sharded table that form
-    u32* tw = nullptr;
-    BCHK(hipMalloc(&tw, (u64)d->n_targets * 4));
-    hipLaunchKernelGGL(k_windows_of, dim3((d->n_targets + TB - 1) / TB), dim3(TB), 0, 0, (const u64*)T->win_off, d->n_targets, tw);
-    c.tgt_windows = tw;
+    BCHK(tw.alloc(d->n_targets));
+    hipLaunchKernelGGL(k_windows_of, dim3((d->n_targets + TB - 1) / TB), dim3(TB), 0, 0, (const u64*)T->win_off.get(), d->n_targets, tw.get());
+    c.tgt_windows = tw.get();
     if (sharded && !(d->flags & MCQ_DB_LOCS_64)) c.flags |= MCQ_DB_LOCS_GW;
-    int rc = mcq_db_create(&c, out);
-    (void)hipFree(tw);
+    const int rc = mcq_db_create(&c, out);
     if (rc != MCQ_OK) g_berr = mcq_last_error();
-    (void)hipFree(t2t);
-    mcq_table_free(T);
-    return rc;
+    return rc;                                                   // (tw, t2t and the table go in that order, as they always did)
 }
 
 // ---- one reference rank's table out of the union table (mcq_table_rank_split of include/mcq.h) ----------------------------------
@@ -916,40 +916,52 @@ __global__ void __launch_bounds__(256) k_split_scatter(const u32* keys, const u6
 }
 }  // namespace
 
+// ---- what the two filters of a table share (this one and -remove-ambig-features below) ----
+// *out = t without some of its locations and without the keys that lose their whole list; win_off is t's.  count(grid, cnt, alive)
+// enqueues the kernel that writes what every key keeps (cnt[key] locations, alive[key] = 0 / 1), scatter(grid, alive, key_pos,
+// loc_pos, n_keys_out, n_locs_out, keys, list_off, locs) the one that writes the output from the two scans; neither is called
+// for a table without keys.
+template <class Count, class Scatter>
+static int filter_table(const mcq_table* t, Count count, Scatter scatter, mcq_table** out, uint64_t* n_kept_keys) {
+    const u64 nk = t->n_keys;
+    TablePtr R(new mcq_table());
+    R->device = t->device; R->n_targets = t->n_targets;
+    BCHK(R->win_off.alloc((u64)t->n_targets + 1));
+    BCHK(hipMemcpy(R->win_off.get(), t->win_off.get(), ((u64)t->n_targets + 1) * 8, hipMemcpyDeviceToDevice));
+    Dev<u32> cnt, alive; Dev<u64> key_pos, loc_pos;
+    BCHK(cnt.alloc(nk)); BCHK(alive.alloc(nk)); BCHK(key_pos.alloc(nk)); BCHK(loc_pos.alloc(nk));
+    const dim3 grid = grid_for((nk + 3) / 4 * 64);               // four keys per wave of 64 lanes
+    u64 n_keys_out = 0, n_locs_out = 0;
+    if (nk) count(grid, cnt.get(), alive.get());
+    MCHK(excl_scan(cnt.get(), loc_pos.get(), nk, &n_locs_out));
+    MCHK(excl_scan(alive.get(), key_pos.get(), nk, &n_keys_out));
+    R->n_keys = n_keys_out; R->n_locs = n_locs_out;
+    BCHK(R->keys.alloc(n_keys_out)); BCHK(R->list_off.alloc(n_keys_out + 1)); BCHK(R->locs.alloc(n_locs_out));
+    if (nk) scatter(grid, (const u32*)alive.get(), (const u64*)key_pos.get(), (const u64*)loc_pos.get(), n_keys_out, n_locs_out,
+                    R->keys.get(), R->list_off.get(), R->locs.get());
+    else BCHK(hipMemset(R->list_off.get(), 0, 8));
+    BCHK(hipDeviceSynchronize());
+    BCHK(hipGetLastError());
+    *n_kept_keys = n_keys_out;
+    *out = R.release();
+    return MCQ_OK;
+}
+
 extern "C" int mcq_table_rank_split(const mcq_table* t, uint32_t n_ranks, uint32_t rank, mcq_table** out) {
     if (!t || !out) return bfail(MCQ_E_ARG, "null argument");
     if (n_ranks < 1 || rank >= n_ranks) return bfail(MCQ_E_ARG, "rank >= n_ranks");
     BCHK(hipSetDevice(t->device));
     const u64 nk = t->n_keys;
-    mcq_table* R = new mcq_table();
-    std::memset(R, 0, sizeof(*R));
-    R->device = t->device; R->n_targets = t->n_targets;
-    struct TableGuard { mcq_table*& t; ~TableGuard() { if (t) mcq_table_free(t); } } guard{R};
-    BCHK(hipMalloc(&R->win_off, ((u64)t->n_targets + 1) * 8));
-    BCHK(hipMemcpy(R->win_off, t->win_off, ((u64)t->n_targets + 1) * 8, hipMemcpyDeviceToDevice));
-    u32 *cnt = nullptr, *alive = nullptr; u64 *key_pos = nullptr, *loc_pos = nullptr;
-    struct Tmp { void** p; ~Tmp() { (void)hipFree(*p); } };
-    BCHK(hipMalloc(&cnt, (nk ? nk : 1) * 4)); Tmp f1{(void**)&cnt};
-    BCHK(hipMalloc(&alive, (nk ? nk : 1) * 4)); Tmp f2{(void**)&alive};
-    BCHK(hipMalloc(&key_pos, (nk ? nk : 1) * 8)); Tmp f3{(void**)&key_pos};
-    BCHK(hipMalloc(&loc_pos, (nk ? nk : 1) * 8)); Tmp f4{(void**)&loc_pos};
-    const dim3 grid = grid_for((nk + 3) / 4 * 64);               // four keys per wave of 64 lanes
-    u64 n_keys_out = 0, n_locs_out = 0;
-    if (nk) hipLaunchKernelGGL(k_split_count, grid, dim3(TB), 0, 0, (const u64*)t->list_off, (const u64*)t->locs, nk, n_ranks, rank, cnt, alive);
-    MCHK(excl_scan(cnt, loc_pos, nk, &n_locs_out));
-    MCHK(excl_scan(alive, key_pos, nk, &n_keys_out));
-    R->n_keys = n_keys_out; R->n_locs = n_locs_out;
-    BCHK(hipMalloc(&R->keys, (n_keys_out ? n_keys_out : 1) * 4));
-    BCHK(hipMalloc(&R->list_off, (n_keys_out + 1) * 8));
-    BCHK(hipMalloc(&R->locs, (n_locs_out ? n_locs_out : 1) * 8));
-    if (nk) hipLaunchKernelGGL(k_split_scatter, grid, dim3(TB), 0, 0, (const u32*)t->keys, (const u64*)t->list_off, (const u64*)t->locs, nk, n_ranks, rank,
-                               (const u32*)alive, (const u64*)key_pos, (const u64*)loc_pos, n_keys_out, n_locs_out, R->keys, R->list_off, R->locs);
-    else BCHK(hipMemset(R->list_off, 0, 8));
-    BCHK(hipDeviceSynchronize());
-    BCHK(hipGetLastError());
-    *out = R;
-    R = nullptr;
-    return MCQ_OK;
+    const u32* keys = t->keys.get(); const u64 *list_off = t->list_off.get(), *locs = t->locs.get();
+    u64 n_kept = 0;
+    return filter_table(t,
+        [&](dim3 grid, u32* cnt, u32* alive) {
+            hipLaunchKernelGGL(k_split_count, grid, dim3(TB), 0, 0, list_off, locs, nk, n_ranks, rank, cnt, alive);
+        },
+        [&](dim3 grid, const u32* alive, const u64* key_pos, const u64* loc_pos, u64 n_keys_out, u64 n_locs_out, u32* okeys, u64* ooff, u64* olocs) {
+            hipLaunchKernelGGL(k_split_scatter, grid, dim3(TB), 0, 0, keys, list_off, locs, nk, n_ranks, rank, alive, key_pos, loc_pos,
+                               n_keys_out, n_locs_out, okeys, ooff, olocs);
+        }, out, &n_kept);
 }
 
 // ---- -remove-ambig-features: keys whose list names more than max_keys distinct clades (mcq_table_remove_ambiguous of include/mcq.h) ----
@@ -1049,48 +1061,28 @@ extern "C" int mcq_table_remove_ambiguous(const mcq_table* t, const uint32_t* tg
     if (max_keys < 1 || max_keys > 255) return bfail(MCQ_E_ARG, "max_keys must be 1..255");
     BCHK(hipSetDevice(t->device));
     const u64 nk = t->n_keys;
-    mcq_table* R = new mcq_table();
-    std::memset(R, 0, sizeof(*R));
-    R->device = t->device; R->n_targets = t->n_targets;
-    struct TableGuard { mcq_table*& t; ~TableGuard() { if (t) mcq_table_free(t); } } guard{R};
-    BCHK(hipMalloc(&R->win_off, ((u64)t->n_targets + 1) * 8));
-    BCHK(hipMemcpy(R->win_off, t->win_off, ((u64)t->n_targets + 1) * 8, hipMemcpyDeviceToDevice));
-    u32 *cnt = nullptr, *alive = nullptr, *d_key = nullptr; u64 *key_pos = nullptr, *loc_pos = nullptr;
-    struct Tmp { void** p; ~Tmp() { (void)hipFree(*p); } };
-    Tmp f0{(void**)&d_key};
+    const u32* keys = t->keys.get(); const u64 *list_off = t->list_off.get(), *locs = t->locs.get();
+    Dev<u32> d_key;
     const u32* keyp = tgt_key;
     if (!(flags & MCQ_DEVICE_PTRS)) {
-        BCHK(hipMalloc(&d_key, (u64)n_targets * 4));
-        BCHK(hipMemcpy(d_key, tgt_key, (u64)n_targets * 4, hipMemcpyHostToDevice));
-        keyp = d_key;
+        BCHK(d_key.alloc(n_targets));
+        BCHK(hipMemcpy(d_key.get(), tgt_key, (u64)n_targets * 4, hipMemcpyHostToDevice));
+        keyp = d_key.get();
     }
-    BCHK(hipMalloc(&cnt, (nk ? nk : 1) * 4)); Tmp f1{(void**)&cnt};
-    BCHK(hipMalloc(&alive, (nk ? nk : 1) * 4)); Tmp f2{(void**)&alive};
-    BCHK(hipMalloc(&key_pos, (nk ? nk : 1) * 8)); Tmp f3{(void**)&key_pos};
-    BCHK(hipMalloc(&loc_pos, (nk ? nk : 1) * 8)); Tmp f4{(void**)&loc_pos};
-    const dim3 grid = grid_for((nk + 3) / 4 * 64);               // four keys per wave of 64 lanes
-    u64 n_keys_out = 0, n_locs_out = 0;
-    if (nk) {
-        if (max_keys == 1)
-            hipLaunchKernelGGL(k_ambig_count<true>, grid, dim3(TB), 0, 0, (const u64*)t->list_off, (const u64*)t->locs, nk, keyp, n_targets, max_keys, cnt, alive);
-        else
-            hipLaunchKernelGGL(k_ambig_count<false>, grid, dim3(TB), (TB / SPLIT_GROUP) * (max_keys + 1) * 4, 0, (const u64*)t->list_off, (const u64*)t->locs, nk,
-                               keyp, n_targets, max_keys, cnt, alive);
-    }
-    MCHK(excl_scan(cnt, loc_pos, nk, &n_locs_out));
-    MCHK(excl_scan(alive, key_pos, nk, &n_keys_out));
-    R->n_keys = n_keys_out; R->n_locs = n_locs_out;
-    BCHK(hipMalloc(&R->keys, (n_keys_out ? n_keys_out : 1) * 4));
-    BCHK(hipMalloc(&R->list_off, (n_keys_out + 1) * 8));
-    BCHK(hipMalloc(&R->locs, (n_locs_out ? n_locs_out : 1) * 8));
-    if (nk) hipLaunchKernelGGL(k_ambig_scatter, grid, dim3(TB), 0, 0, (const u32*)t->keys, (const u64*)t->list_off, (const u64*)t->locs, nk,
-                               (const u32*)alive, (const u64*)key_pos, (const u64*)loc_pos, n_keys_out, n_locs_out, R->keys, R->list_off, R->locs);
-    else BCHK(hipMemset(R->list_off, 0, 8));
-    BCHK(hipDeviceSynchronize());
-    BCHK(hipGetLastError());
-    *n_removed = nk - n_keys_out;
-    *out = R;
-    R = nullptr;
+    u64 n_kept = 0;
+    MCHK(filter_table(t,
+        [&](dim3 grid, u32* cnt, u32* alive) {
+            if (max_keys == 1)
+                hipLaunchKernelGGL(k_ambig_count<true>, grid, dim3(TB), 0, 0, list_off, locs, nk, keyp, n_targets, max_keys, cnt, alive);
+            else
+                hipLaunchKernelGGL(k_ambig_count<false>, grid, dim3(TB), (TB / SPLIT_GROUP) * (max_keys + 1) * 4, 0, list_off, locs, nk,
+                                   keyp, n_targets, max_keys, cnt, alive);
+        },
+        [&](dim3 grid, const u32* alive, const u64* key_pos, const u64* loc_pos, u64 n_keys_out, u64 n_locs_out, u32* okeys, u64* ooff, u64* olocs) {
+            hipLaunchKernelGGL(k_ambig_scatter, grid, dim3(TB), 0, 0, keys, list_off, locs, nk, alive, key_pos, loc_pos,
+                               n_keys_out, n_locs_out, okeys, ooff, olocs);
+        }, out, &n_kept));
+    *n_removed = nk - n_kept;
     return MCQ_OK;
 }
 
@@ -1098,7 +1090,7 @@ extern "C" int mcq_table_tgt_windows(const mcq_table* t, uint32_t* out) {
     if (!t || !out) return bfail(MCQ_E_ARG, "null argument");
     BCHK(hipSetDevice(t->device));
     std::vector<u64> w((size_t)t->n_targets + 1);
-    BCHK(hipMemcpy(w.data(), t->win_off, w.size() * 8, hipMemcpyDeviceToHost));
+    BCHK(hipMemcpy(w.data(), t->win_off.get(), w.size() * 8, hipMemcpyDeviceToHost));
     for (u32 i = 0; i < t->n_targets; ++i) out[i] = (u32)(w[i + 1] - w[i]);
     return MCQ_OK;
 }
