@@ -656,7 +656,9 @@ int mcq_target_slots(const mcq_result* cands, uint64_t n_queries, uint32_t max_c
  * src/querying.h:88-106): match_off[q..q+1) into matches (capacity cap; pass matches = NULL first to
  * learn the sizes).  path_flags = 0 taps every query on the path it takes in mcq_query (first or second
  * wave stage, workgroup kernel); MCQ_FORCE_BLOCK_PATH / MCQ_FORCE_RAW_SORT / MCQ_NO_WAVE16 tap the path
- * those hooks select.  The taps live in separate instantiations of the kernels.                     */
+ * those hooks select.  The taps live in separate instantiations of the kernels.  The batch is a plain
+ * ASCII host batch, held to the rules of mcq_query's host batches: seq_off[0] must be 0 (MCQ_E_ARG
+ * otherwise), and a packed or ranges batch is refused before anything is copied.                    */
 int mcq_debug_matches(const mcq_db* db, mcq_ws* ws, const mcq_batch* in, uint32_t path_flags,
                       uint64_t* match_off /* host [n_queries+1] */, uint64_t* matches /* host */, uint64_t cap);
 

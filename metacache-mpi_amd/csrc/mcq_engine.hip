@@ -1740,15 +1740,11 @@ extern "C" int mcq_ws_create(const mcq_db* db, uint64_t max_queries, uint64_t ma
     u64 lmax = max_locs_per_query ? pow2ceil64(max_locs_per_query) : (1ull << 18);
     if (lmax > (1ull << 30)) return fail(MCQ_E_UNSUPPORTED, "max_locs_per_query too large");
     HIPCHK(hipSetDevice(db->device));
-    mcq_ws* ws = new mcq_ws();
-    memset(ws, 0, sizeof(*ws));
+    std::unique_ptr<mcq_ws> ws(new mcq_ws());     // (a failure below gives back what was made so far)
     ws->device = db->device; ws->max_queries = max_queries; ws->max_bases = max_bases;
-    ws->sc.lmax = (u32)lmax;
-    ws->sc.fmax = 1u << 15;
+    ws->sc.lmax = (u32)lmax; ws->sc.fmax = 1u << 15;
     ws->n_block_wgs = MCQ_BLOCK_WGS_DEFAULT;   // two resident workgroups per CU (32-bit keys: 64 KB of LDS, 64 VGPRs)
     if (const char* e = getenv("MCQ_BLOCK_WGS")) ws->n_block_wgs = std::max(1, atoi(e));      // tuning knob
-    ws->ev_used = new std::vector<TimedLaunch>();
-    ws->ev_free = new std::vector<TimedLaunch>();
     with_loc_form(db, [&](auto L) {     // (every cap_* measured on the BSH = 2 instantiation, whatever the table's layout)
         constexpr bool GW = decltype(L)::gw;
         ws->cap_wave = resident_blocks(k_query_wave<typename decltype(L)::Key, 512, false, false, GW, 2>, 256, db->device);
@@ -1758,71 +1754,41 @@ extern "C" int mcq_ws_create(const mcq_db* db, uint64_t max_queries, uint64_t ma
         ws->cap_wave32 = resident_blocks(k_query_wave32<false, GW, 2>, 256, db->device);
     });
     const u64 nb = (u64)ws->n_block_wgs;
-#define WSCHK(expr) HIPCHK_OR(expr, (void)mcq_ws_destroy(ws))
-    WSCHK(hipMalloc(&ws->ctr, sizeof(CountersDev)));
-    WSCHK(hipHostMalloc(&ws->ctr_host, sizeof(CountersDev)));
-    WSCHK(hipMalloc(&ws->ovf_list, ovf_capacity(max_queries) * 4));
+    HIPCHK(ws->ctr.alloc(1));
+    HIPCHK(ws->ctr_host.alloc(1));
+    HIPCHK(ws->ovf_list.alloc(ovf_capacity(max_queries)));
     // back-queue rows (first-stage pushes: below max_queries + MCQ_OVF_TAIL), then front-queue rows (first-stage front pushes AND the
     // second stage's hand-ons, each set of waves with its reservation tails: below max_queries + 2 x MCQ_OVF_TAIL)
     const u64 probe_rows = 2 * max_queries + 3 * (u64)MCQ_OVF_TAIL;
-    WSCHK(hipMalloc(&ws->probe_buf, probe_rows * 64 * 8));
-    WSCHK(hipMemset(ws->ctr, 0, sizeof(CountersDev)));
-    WSCHK(hipMemcpy(&ws->ctr->probe_buf, &ws->probe_buf, sizeof(ws->probe_buf), hipMemcpyHostToDevice));
-    WSCHK(hipMemset(ws->probe_buf, 0, probe_rows * 64 * 8));        // (a row never written reads as 64 empty lists)
-    {
-        unsigned long long* front = ws->probe_buf + (max_queries + (u64)MCQ_OVF_TAIL) * 64;
-        WSCHK(hipMemcpy(&ws->ctr->probe_front, &front, sizeof(front), hipMemcpyHostToDevice));
-    }
-    WSCHK(hipMalloc(&ws->sc.feat, nb * ws->sc.fmax * 4));
-    WSCHK(hipMalloc(&ws->sc.fpos, nb * ((u64)ws->sc.fmax + 1) * 4));
-    WSCHK(hipMalloc(&ws->sc.foff, nb * ws->sc.fmax * 8));
-    WSCHK(hipMalloc(&ws->sc.gbuf, nb * lmax * 8));
-    WSCHK(hipMalloc(&ws->sc.ghits, nb * lmax * 8));
-#undef WSCHK
-    *out = ws;
+    HIPCHK(ws->probe_buf.alloc(probe_rows * 64));
+    CountersDev* ctr = ws->ctr.get();
+    unsigned long long *back = ws->probe_buf.get(), *front = back + (max_queries + (u64)MCQ_OVF_TAIL) * 64;
+    HIPCHK(hipMemset(ctr, 0, sizeof(CountersDev)));
+    HIPCHK(hipMemcpy(&ctr->probe_buf, &back, sizeof(back), hipMemcpyHostToDevice));
+    HIPCHK(hipMemset(back, 0, probe_rows * 64 * 8));        // (a row never written reads as 64 empty lists)
+    HIPCHK(hipMemcpy(&ctr->probe_front, &front, sizeof(front), hipMemcpyHostToDevice));
+    HIPCHK(ws->sc_feat.alloc(nb * ws->sc.fmax));             ws->sc.feat = ws->sc_feat.get();
+    HIPCHK(ws->sc_fpos.alloc(nb * ((u64)ws->sc.fmax + 1)));  ws->sc.fpos = ws->sc_fpos.get();
+    HIPCHK(ws->sc_foff.alloc(nb * ws->sc.fmax));             ws->sc.foff = ws->sc_foff.get();
+    HIPCHK(ws->sc_gbuf.alloc(nb * lmax));                    ws->sc.gbuf = ws->sc_gbuf.get();
+    HIPCHK(ws->sc_ghits.alloc(nb * lmax));                   ws->sc.ghits = ws->sc_ghits.get();
+    *out = ws.release();
     return MCQ_OK;
 }
 
 extern "C" int mcq_ws_destroy(mcq_ws* ws) {
     if (!ws) return MCQ_OK;
     (void)hipSetDevice(ws->device);
-    (void)hipFree(ws->ctr); (void)hipHostFree(ws->ctr_host); (void)hipFree(ws->ovf_list); (void)hipFree(ws->probe_buf);
-    (void)hipFree(ws->sc.feat); (void)hipFree(ws->sc.fpos); (void)hipFree(ws->sc.foff); (void)hipFree(ws->sc.gbuf); (void)hipFree(ws->sc.ghits);
-    if (ws->d_bases) (void)hipFree(ws->d_bases);
-    if (ws->d_seq_off) (void)hipFree(ws->d_seq_off);
-    if (ws->d_cands) (void)hipFree(ws->d_cands);
-    if (ws->d_ncand) (void)hipFree(ws->d_ncand);
-    if (ws->pipe.ready) {
-        for (int k = 0; k < 2; ++k) {
-            (void)hipFree(ws->pipe.d_bases[k]); (void)hipFree(ws->pipe.d_seq_off[k]); (void)hipFree(ws->pipe.d_cands[k]); (void)hipFree(ws->pipe.d_ncand[k]);
-            (void)hipEventDestroy(ws->pipe.ev_in[k]); (void)hipEventDestroy(ws->pipe.ev_k[k]); (void)hipEventDestroy(ws->pipe.ev_out[k]);
-        }
-        (void)hipStreamDestroy(ws->pipe.s_in); (void)hipStreamDestroy(ws->pipe.s_k); (void)hipStreamDestroy(ws->pipe.s_out);
-    }
-    if (ws->cls_counts) (void)hipFree(ws->cls_counts);
-    if (ws->cls_ev) (void)hipEventDestroy(ws->cls_ev);
-    if (ws->excl_tgt) (void)hipFree(ws->excl_tgt);
-    for (auto& sl : ws->qc_slot) {
-        if (sl.pinned) (void)hipHostFree(sl.pinned);
-        if (sl.dev) (void)hipFree(sl.dev);
-        if (sl.ev) (void)hipEventDestroy(sl.ev);
-    }
-    delete ws->qc_host;
-    for (auto* v : {ws->ev_used, ws->ev_free}) {
-        if (!v) continue;
-        for (auto& t : *v) for (auto e : t.ev) (void)hipEventDestroy(e);
-        delete v;
-    }
-    delete ws;
+    delete ws;                  // (the order its members go in: mcq_internal.hpp)
     return MCQ_OK;
 }
 
-static int ensure_staging(mcq_ws* ws) {
-    if (ws->d_bases) return MCQ_OK;
-    HIPCHK(hipMalloc(&ws->d_bases, std::max<u64>(1, ws->max_bases) + 16));
-    HIPCHK(hipMalloc(&ws->d_seq_off, (2 * ws->max_queries + 2) * 8));
-    HIPCHK(hipMalloc(&ws->d_cands, std::max<u64>(1, ws->max_queries) * 16 * 16));
-    HIPCHK(hipMalloc(&ws->d_ncand, std::max<u64>(1, ws->max_queries) * 4));
+int Staging::alloc(const mcq_ws* ws) {
+    if (d_ncand.get()) return MCQ_OK;
+    HIPCHK(d_bases.alloc(std::max<u64>(1, ws->max_bases) + 16));
+    HIPCHK(d_seq_off.alloc(2 * ws->max_queries + 2));
+    HIPCHK(d_cands.alloc(std::max<u64>(1, ws->max_queries) * 16 * 4));     // 16 candidates of 16 bytes
+    HIPCHK(d_ncand.alloc(ws->max_queries));
     return MCQ_OK;
 }
 
@@ -1839,15 +1805,15 @@ struct LaunchTimer {
     LaunchTimer(mcq_ws* w, hipStream_t s) : ws(w), st(s), n(0), on(w->timing != 0) {}
     int begin() {
         if (!on) return MCQ_OK;
-        if (!ws->ev_free->empty()) { t = ws->ev_free->back(); ws->ev_free->pop_back(); }
-        else for (auto& e : t.ev) HIPCHK(hipEventCreate(&e));
+        if (!ws->ev_free.empty()) { t = std::move(ws->ev_free.back()); ws->ev_free.pop_back(); }
+        else for (auto& e : t.ev) HIPCHK(e.create(hipEventDefault));
         return mark();
     }
     int mark() { if (on && n <= MCQ_N_TIMED) HIPCHK(hipEventRecord(t.ev[n++], st)); return MCQ_OK; }
     int end() {                                 // kernels that were not launched take no time: repeat the last event
         if (!on) return MCQ_OK;
         while (n <= MCQ_N_TIMED) { int rc = mark(); if (rc) return rc; }
-        ws->ev_used->push_back(t);
+        ws->ev_used.push_back(std::move(t));
         return MCQ_OK;
     }
 };
@@ -1924,7 +1890,7 @@ static int plan_launch(const mcq_db* db, const OptDev& od_req, bool tap, bool sh
 // received location buffer); the counters are then zeroed by the caller (the sketch kernel has already counted)
 int mcq::launch_query(const mcq_db* db, mcq_ws* ws, const BatchDev& b, const OptDev& od_in, const OutDev& o,
                       hipStream_t st, LeanReq lean_req, const DebugDev& dbg, const ShardDev* shp, const DbDev* dbd, const ExclDev* exp) {
-    if (!shp) HIPCHK(hipMemsetAsync(ws->ctr, 0, MCQ_CTR_ZEROED, st));
+    if (!shp) HIPCHK(hipMemsetAsync(ws->ctr.get(), 0, MCQ_CTR_ZEROED, st));
     if (b.nq == 0) return MCQ_OK;
     const ShardDev sh = shp ? *shp : ShardDev{};
     const DbDev& D = dbd ? *dbd : db->d;
@@ -1951,7 +1917,7 @@ int mcq::launch_query(const mcq_db* db, mcq_ws* ws, const BatchDev& b, const Opt
         using Key = typename decltype(L)::Key;
         constexpr bool GW = decltype(L)::gw;
         auto first = [&](auto TAP, auto SH, auto BSH, auto NL, auto LEAN, auto EX, u32 g, auto PAIRED, auto PACKED) {
-            hipLaunchKernelGGL((k_query_wave<Key, kLcapWave, TAP, SH, GW, BSH, NL, LEAN, EX, PAIRED, PACKED>), dim3(g), dim3(256), 0, st, D, b, p.first, o, ws->ctr, ws->ovf_list, dbg, sh, db->g, ex);
+            hipLaunchKernelGGL((k_query_wave<Key, kLcapWave, TAP, SH, GW, BSH, NL, LEAN, EX, PAIRED, PACKED>), dim3(g), dim3(256), 0, st, D, b, p.first, o, ws->ctr.get(), ws->ovf_list.get(), dbg, sh, db->g, ex);
         };
         if (p.full) by_role([&](auto TAP, auto SH, auto BSH, auto EX) { first(TAP, SH, BSH, IntC<1>{}, No{}, EX, grid, No{}, No{}); });
         if constexpr (sizeof(Key) == 4) {   // the NL and LEAN instantiations: 32-bit words, plain launches
@@ -1966,13 +1932,13 @@ int mcq::launch_query(const mcq_db* db, mcq_ws* ws, const BatchDev& b, const Opt
         rc = tm.mark(); if (rc) return rc;
         if constexpr (sizeof(Key) == 4) {   // second wave stage (back queue); no queue for 64-bit keys
             by_role([&](auto TAP, auto SH, auto BSH, auto EX) {
-                hipLaunchKernelGGL((k_query_wave16<TAP, SH, GW, BSH, EX>), dim3(grid_for(ws->cap_wave16, want)), dim3(256), 0, st, D, b, od, o, ws->ctr,
-                                   ws->ovf_list, dbg, sh, db->g, ex);
+                hipLaunchKernelGGL((k_query_wave16<TAP, SH, GW, BSH, EX>), dim3(grid_for(ws->cap_wave16, want)), dim3(256), 0, st, D, b, od, o, ws->ctr.get(),
+                                   ws->ovf_list.get(), dbg, sh, db->g, ex);
             });
             // third wave stage: front-queue entries of up to 2048 locations (see k_query_wave32); counts the narrow ones it leaves
             if (p.with_tc) by_role([&](auto TAP, auto SH, auto BSH, auto EX) {     // (no tap or exclusion form: with_tc excludes both)
                 if constexpr (!TAP && !EX) hipLaunchKernelGGL((k_query_wave32<SH, GW, BSH>), dim3(grid_for(ws->cap_wave32, want)), dim3(256), 0, st, D, b, od, o,
-                                                       ws->ctr, ws->ovf_list, sh, db->g);
+                                                       ws->ctr.get(), ws->ovf_list.get(), sh, db->g);
             });
         }
         rc = tm.mark(); if (rc) return rc;
@@ -1980,8 +1946,8 @@ int mcq::launch_query(const mcq_db* db, mcq_ws* ws, const BatchDev& b, const Opt
         constexpr int lcap = sizeof(Key) == 4 ? MCQ_BLOCK_LCAP : kLcapBlock, nt = sizeof(Key) == 4 ? MCQ_BLOCK_NT : 1024;
         auto block = [&](auto TC, auto BIG) {
             auto launch = [&](auto SH, auto EX) {
-                if constexpr (!(EX && TC)) hipLaunchKernelGGL((k_query_block<Key, lcap, nt, BIG, SH, GW, TC, EX>), dim3(ws->n_block_wgs), dim3(nt), 0, st, D, b, od, o, ws->ctr,
-                                   (const u32*)ws->ovf_list, ws->sc, dbg, sh, db->g, ex);
+                if constexpr (!(EX && TC)) hipLaunchKernelGGL((k_query_block<Key, lcap, nt, BIG, SH, GW, TC, EX>), dim3(ws->n_block_wgs), dim3(nt), 0, st, D, b, od, o, ws->ctr.get(),
+                                   (const u32*)ws->ovf_list.get(), ws->sc, dbg, sh, db->g, ex);
             };
             if (shp) launch(Yes{}, No{}); else if (exp) launch(No{}, Yes{}); else launch(No{}, No{});
         };
@@ -1991,8 +1957,8 @@ int mcq::launch_query(const mcq_db* db, mcq_ws* ws, const BatchDev& b, const Opt
     });
     if (rc) return rc;
     rc = tm.end(); if (rc) return rc;
-    if (p.next_mode) hipLaunchKernelGGL(k_next_mode, dim3(1), dim3(1), 0, st, ws->ctr, b.nq, (p.full && p.lean) ? 1u : 0u);
-    else HIPCHK(hipMemsetAsync(&ws->ctr->direct_mode, 0, 4, st));
+    if (p.next_mode) hipLaunchKernelGGL(k_next_mode, dim3(1), dim3(1), 0, st, ws->ctr.get(), b.nq, (p.full && p.lean) ? 1u : 0u);
+    else HIPCHK(hipMemsetAsync(&ws->ctr.get()->direct_mode, 0, 4, st));
     HIPCHK(hipGetLastError());
     ws->last_nq = b.nq;
     return MCQ_OK;
@@ -2003,7 +1969,7 @@ int mcq::launch_query(const mcq_db* db, mcq_ws* ws, const BatchDev& b, const Opt
 static int classify_batch(mcq_ws* ws, const OutDev& o, u64 nq, u32 max_cand, hipStream_t st) {
     if (!ws->cls_tx || !nq) return MCQ_OK;
     mcq_result r; r.cands = (mcq_cand*)o.cands; r.n_cand = o.ncand; r.flags = MCQ_DEVICE_PTRS;
-    const int rc = mcq_classify(ws->cls_tx, &r, nq, max_cand, &ws->cls_opt, nullptr, (uint64_t*)ws->cls_counts, st);
+    const int rc = mcq_classify(ws->cls_tx, &r, nq, max_cand, &ws->cls_opt, nullptr, (uint64_t*)ws->cls_counts.get(), st);
     if (rc) return rc;
     HIPCHK(hipEventRecord(ws->cls_ev, st));
     return MCQ_OK;
@@ -2016,11 +1982,11 @@ extern "C" int mcq_ws_set_classify(mcq_ws* ws, const mcq_taxonomy* tx, const mcq
     if (rc) return rc;
     if (tx->device != ws->device) return fail(MCQ_E_ARG, "the taxonomy lives on another device than the workspace");
     HIPCHK(hipSetDevice(ws->device));
-    if (!ws->cls_ev) HIPCHK(hipEventCreateWithFlags(&ws->cls_ev, hipEventDisableTiming));
-    if (!ws->cls_counts || ws->cls_n != tx->n_taxa + 1) {
-        if (ws->cls_counts) { HIPCHK(hipEventSynchronize(ws->cls_ev)); (void)hipFree(ws->cls_counts); ws->cls_counts = nullptr; }
-        HIPCHK(hipMalloc(&ws->cls_counts, ((u64)tx->n_taxa + 1) * 8));
-        HIPCHK(hipMemsetAsync(ws->cls_counts, 0, ((u64)tx->n_taxa + 1) * 8, nullptr));
+    HIPCHK(ws->cls_ev.create());
+    if (!ws->cls_counts.get() || ws->cls_n != tx->n_taxa + 1) {
+        if (ws->cls_counts.get()) HIPCHK(hipEventSynchronize(ws->cls_ev));       // (the last batch that added into the counts that go)
+        HIPCHK(ws->cls_counts.alloc((u64)tx->n_taxa + 1));
+        HIPCHK(hipMemsetAsync(ws->cls_counts.get(), 0, ((u64)tx->n_taxa + 1) * 8, nullptr));
         HIPCHK(hipStreamSynchronize(nullptr));
         ws->cls_n = tx->n_taxa + 1;
     }
@@ -2030,12 +1996,12 @@ extern "C" int mcq_ws_set_classify(mcq_ws* ws, const mcq_taxonomy* tx, const mcq
 
 extern "C" int mcq_ws_taxon_counts(mcq_ws* ws, uint64_t* host_out, int reset) {
     if (!ws || !host_out) return fail(MCQ_E_ARG, "null argument");
-    if (!ws->cls_counts) return fail(MCQ_E_ARG, "no taxonomy was ever attached to this workspace (mcq_ws_set_classify)");
+    if (!ws->cls_counts.get()) return fail(MCQ_E_ARG, "no taxonomy was ever attached to this workspace (mcq_ws_set_classify)");
     HIPCHK(hipSetDevice(ws->device));
     HIPCHK(hipEventSynchronize(ws->cls_ev));
-    HIPCHK(hipMemcpy(host_out, ws->cls_counts, (u64)ws->cls_n * 8, hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(host_out, ws->cls_counts.get(), (u64)ws->cls_n * 8, hipMemcpyDeviceToHost));
     if (reset) {
-        HIPCHK(hipMemsetAsync(ws->cls_counts, 0, (u64)ws->cls_n * 8, nullptr));
+        HIPCHK(hipMemsetAsync(ws->cls_counts.get(), 0, (u64)ws->cls_n * 8, nullptr));
         HIPCHK(hipStreamSynchronize(nullptr));
     }
     return MCQ_OK;
@@ -2047,15 +2013,15 @@ extern "C" int mcq_ws_set_exclusion(mcq_ws* ws, const uint32_t* tgt_clade, uint3
     if (flags & ~(u32)MCQ_DEVICE_PTRS) return fail(MCQ_E_ARG, "unknown bits in flags");
     HIPCHK(hipSetDevice(ws->device));
     HIPCHK(hipDeviceSynchronize());              // (batches in flight read the table that goes)
-    if (ws->excl_tgt) { (void)hipFree(ws->excl_tgt); ws->excl_tgt = nullptr; ws->excl_n = 0; }
+    ws->excl_tgt.reset(); ws->excl_n = 0;
     ws->qc_kind = 0;
     if (!tgt_clade) return MCQ_OK;
     if (!n_targets) return fail(MCQ_E_ARG, "a clade table of no targets");
     if (!(flags & MCQ_DEVICE_PTRS))
         for (u32 t = 0; t < n_targets; ++t)
             if (tgt_clade[t] == MCQ_CLADE_KEEP_ALL) return fail(MCQ_E_ARG, "MCQ_CLADE_KEEP_ALL is a query's value, not a target's");
-    HIPCHK(hipMalloc(&ws->excl_tgt, (u64)n_targets * 4));
-    HIPCHK(hipMemcpy(ws->excl_tgt, tgt_clade, (u64)n_targets * 4, (flags & MCQ_DEVICE_PTRS) ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice));
+    HIPCHK(ws->excl_tgt.alloc(n_targets));
+    HIPCHK(hipMemcpy(ws->excl_tgt.get(), tgt_clade, (u64)n_targets * 4, (flags & MCQ_DEVICE_PTRS) ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice));
     ws->excl_n = n_targets;
     return MCQ_OK;
 }
@@ -2063,12 +2029,11 @@ extern "C" int mcq_ws_set_exclusion(mcq_ws* ws, const uint32_t* tgt_clade, uint3
 extern "C" int mcq_ws_set_query_clades(mcq_ws* ws, const uint32_t* query_clade, uint64_t n_queries, uint32_t flags) {
     if (!ws || !query_clade) return fail(MCQ_E_ARG, "null argument");
     if (flags & ~(u32)MCQ_DEVICE_PTRS) return fail(MCQ_E_ARG, "unknown bits in flags");
-    if (!ws->excl_tgt) return fail(MCQ_E_ARG, "no clade table is attached to this workspace (mcq_ws_set_exclusion)");
+    if (!ws->excl_tgt.get()) return fail(MCQ_E_ARG, "no clade table is attached to this workspace (mcq_ws_set_exclusion)");
     if (n_queries > ws->max_queries) return fail(MCQ_E_ARG, "more clade keys than the workspace has queries");
     if (flags & MCQ_DEVICE_PTRS) { ws->qc_dev = query_clade; ws->qc_kind = 1; }
     else {
-        if (!ws->qc_host) ws->qc_host = new std::vector<u32>();
-        ws->qc_host->assign(query_clade, query_clade + n_queries);
+        ws->qc_host.assign(query_clade, query_clade + n_queries);
         ws->qc_kind = 2;
     }
     ws->qc_n = n_queries;
@@ -2076,35 +2041,51 @@ extern "C" int mcq_ws_set_query_clades(mcq_ws* ws, const uint32_t* query_clade, 
 }
 
 // The clade keys of the batch that is being enqueued, as the kernels take them: consumes what mcq_ws_set_query_clades handed over.
-// A host array goes through staging set `slot` (pinned + device) on stream `up`, which the batch's kernels are ordered behind.
+// A host array goes through the slot of staging set `s` (pinned + device) on stream `up`, which the batch's kernels are ordered behind.
 // on == false: the workspace has no exclusion attached, the batch runs as ever.
-static int take_query_clades(const mcq_db* db, mcq_ws* ws, u64 nq, int slot, hipStream_t up, ExclDev& ex, bool& on) {
-    on = ws->excl_tgt != nullptr;
+static int take_query_clades(const mcq_db* db, mcq_ws* ws, u64 nq, Staging& s, hipStream_t up, ExclDev& ex, bool& on) {
+    on = ws->excl_tgt.get() != nullptr;
     if (!on) return MCQ_OK;
     if (ws->excl_n != db->d.n_targets) return fail(MCQ_E_ARG, "the attached clade table has another number of targets than the database");
     if (ws->qc_kind == 0) return fail(MCQ_E_ARG, "clade exclusion is attached but no clade keys were handed over for this batch (mcq_ws_set_query_clades)");
     if (ws->qc_n != nq) return fail(MCQ_E_ARG, "the clade keys handed over are not one per query of this batch");
-    ex.tgt_clade = ws->excl_tgt;
+    ex.tgt_clade = ws->excl_tgt.get();
     if (ws->qc_kind == 1) ex.query_clade = ws->qc_dev;
     else {
-        auto& sl = ws->qc_slot[slot];
-        if (!sl.pinned) {
-            const u64 bytes = std::max<u64>(1, ws->max_queries) * 4;
-            HIPCHK(hipHostMalloc(&sl.pinned, bytes));
-            HIPCHK(hipMalloc(&sl.dev, bytes));
-            HIPCHK(hipEventCreateWithFlags(&sl.ev, hipEventDisableTiming));
+        if (!s.qc_ev) {
+            HIPCHK(s.qc_pinned.alloc(ws->max_queries));
+            HIPCHK(s.qc_dev.alloc(ws->max_queries));
+            HIPCHK(s.qc_ev.create());
         }
-        if (sl.used) HIPCHK(hipEventSynchronize(sl.ev));       // the upload before this one has read the pinned words
+        if (s.qc_used) HIPCHK(hipEventSynchronize(s.qc_ev));   // the upload before this one has read the pinned words
         if (nq) {
-            memcpy(sl.pinned, ws->qc_host->data(), nq * 4);
-            HIPCHK(hipMemcpyAsync(sl.dev, sl.pinned, nq * 4, hipMemcpyHostToDevice, up));
+            memcpy(s.qc_pinned.get(), ws->qc_host.data(), nq * 4);
+            HIPCHK(hipMemcpyAsync(s.qc_dev.get(), s.qc_pinned.get(), nq * 4, hipMemcpyHostToDevice, up));
         }
-        HIPCHK(hipEventRecord(sl.ev, up));
-        sl.used = true;
-        ex.query_clade = sl.dev;
+        HIPCHK(hipEventRecord(s.qc_ev, up));
+        s.qc_used = true;
+        ex.query_clade = s.qc_dev.get();
     }
     ws->qc_kind = 0;
     return MCQ_OK;
+}
+
+// a host batch against the workspace -> its number of bases (a batch that breaks several rules reports the first of them)
+static int check_host_batch(const mcq_ws* ws, const mcq_batch* in, u64& nbases) {
+    nbases = in->n_seqs ? in->seq_off[in->n_seqs] - in->seq_off[0] : 0;
+    if (nbases > ws->max_bases) return fail(MCQ_E_ARG, "batch has more bases than the workspace allows");
+    if (in->n_seqs && in->seq_off[0] != 0) return fail(MCQ_E_ARG, "host batches must start at offset 0");
+    if ((in->flags & MCQ_BATCH_PACKED) && in->n_bases && in->n_bases != nbases) return fail(MCQ_E_ARG, "mcq_batch.n_bases must equal seq_off[n_seqs] for a packed batch");
+    return MCQ_OK;
+}
+
+// ... and into staging set `s` on stream `st`, described as the kernels take it
+static int upload_host_batch(const mcq_batch* in, u64 nbases, const Staging& s, hipStream_t st, BatchDev& b) {
+    const u64 bytes = (in->flags & MCQ_BATCH_PACKED) ? mcq_packed_bytes(nbases) : nbases;     // (a packed batch is at most as large as its ASCII form + 16 B)
+    if (bytes) HIPCHK(hipMemcpyAsync(s.d_bases.get(), in->bases, bytes, hipMemcpyHostToDevice, st));
+    HIPCHK(hipMemcpyAsync(s.d_seq_off.get(), in->seq_off, (in->n_seqs + 1) * 8, hipMemcpyHostToDevice, st));
+    mcq_batch hin = *in; hin.n_bases = nbases;
+    return batch_dev(&hin, s.d_bases.get(), s.d_seq_off.get(), b);
 }
 
 extern "C" int mcq_query(const mcq_db* db, mcq_ws* ws, const mcq_batch* in, const mcq_query_opts* opt,
@@ -2118,39 +2099,25 @@ extern "C" int mcq_query(const mcq_db* db, mcq_ws* ws, const mcq_batch* in, cons
     const u64 nq = in->paired ? in->n_seqs / 2 : in->n_seqs;
     if (nq > ws->max_queries) return fail(MCQ_E_ARG, "batch has more queries than the workspace allows");
     const bool dev_in = (in->flags & MCQ_DEVICE_PTRS) != 0, dev_out = (out->flags & MCQ_DEVICE_PTRS) != 0;
-    const bool packed = (in->flags & MCQ_BATCH_PACKED) != 0;
     if ((in->flags & MCQ_BATCH_RANGES) && !dev_in) return fail(MCQ_E_ARG, "MCQ_BATCH_RANGES needs device pointers");
-    OutDev o;
+    Staging& s = ws->staging[2];
     u64 nbases = 0;
-    if (!dev_in) {
-        nbases = in->n_seqs ? in->seq_off[in->n_seqs] - in->seq_off[0] : 0;
-        if (nbases > ws->max_bases) return fail(MCQ_E_ARG, "batch has more bases than the workspace allows");
-        if (in->n_seqs && in->seq_off[0] != 0) return fail(MCQ_E_ARG, "host batches must start at offset 0");
-        if (packed && in->n_bases && in->n_bases != nbases) return fail(MCQ_E_ARG, "mcq_batch.n_bases must equal seq_off[n_seqs] for a packed batch");
-    }
-    if (!dev_in || !dev_out) { rc = ensure_staging(ws); if (rc) return rc; }
+    if (!dev_in) { rc = check_host_batch(ws, in, nbases); if (rc) return rc; }
+    if (!dev_in || !dev_out) { rc = s.alloc(ws); if (rc) return rc; }
     BatchDev b;
-    if (!dev_in) {
-        const u64 bytes = packed ? mcq_packed_bytes(nbases) : nbases;      // (a packed batch is at most as large as its ASCII form + 16 B)
-        if (bytes) HIPCHK(hipMemcpyAsync(ws->d_bases, in->bases, bytes, hipMemcpyHostToDevice, st));
-        HIPCHK(hipMemcpyAsync(ws->d_seq_off, in->seq_off, (in->n_seqs + 1) * 8, hipMemcpyHostToDevice, st));
-        mcq_batch hin = *in; hin.n_bases = nbases;
-        rc = batch_dev(&hin, ws->d_bases, ws->d_seq_off, b);
-    } else rc = batch_dev(in, in->bases, in->seq_off, b);
+    rc = dev_in ? batch_dev(in, in->bases, in->seq_off, b) : upload_host_batch(in, nbases, s, st, b);
     if (rc) return rc;
-    if (!dev_out) { o.cands = ws->d_cands; o.ncand = ws->d_ncand; }
+    OutDev o;
+    if (!dev_out) { o.cands = s.d_cands.get(); o.ncand = s.d_ncand.get(); }
     else { o.cands = (u32*)out->cands; o.ncand = out->n_cand; }
     DebugDev dbg; memset(&dbg, 0, sizeof(dbg));
     ExclDev ex; bool excl;
-    rc = take_query_clades(db, ws, nq, 2, st, ex, excl);
-    if (rc) return rc;
-    rc = launch_query(db, ws, b, od, o, st, lean_request(opt->flags), dbg, nullptr, nullptr, excl ? &ex : nullptr);
-    if (rc) return rc;
-    rc = classify_batch(ws, o, nq, od.max_cand, st);
-    if (rc) return rc;
+    rc = take_query_clades(db, ws, nq, s, st, ex, excl); if (rc) return rc;
+    rc = launch_query(db, ws, b, od, o, st, lean_request(opt->flags), dbg, nullptr, nullptr, excl ? &ex : nullptr); if (rc) return rc;
+    rc = classify_batch(ws, o, nq, od.max_cand, st); if (rc) return rc;
     if (!dev_out && nq) {
-        HIPCHK(hipMemcpyAsync(out->cands, ws->d_cands, nq * od.max_cand * 16, hipMemcpyDeviceToHost, st));
-        HIPCHK(hipMemcpyAsync(out->n_cand, ws->d_ncand, nq * 4, hipMemcpyDeviceToHost, st));
+        HIPCHK(hipMemcpyAsync(out->cands, o.cands, nq * od.max_cand * 16, hipMemcpyDeviceToHost, st));
+        HIPCHK(hipMemcpyAsync(out->n_cand, o.ncand, nq * 4, hipMemcpyDeviceToHost, st));
     }
     if (!dev_in || !dev_out) return mcq_ws_sync(ws, stream, nullptr);
     return MCQ_OK;
@@ -2165,17 +2132,10 @@ static int pipe_init(mcq_ws* ws) {
     auto& p = ws->pipe;
     if (p.ready) return MCQ_OK;
     for (int k = 0; k < 2; ++k) {
-        HIPCHK(hipMalloc(&p.d_bases[k], std::max<u64>(1, ws->max_bases) + 16));
-        HIPCHK(hipMalloc(&p.d_seq_off[k], (2 * ws->max_queries + 2) * 8));
-        HIPCHK(hipMalloc(&p.d_cands[k], std::max<u64>(1, ws->max_queries) * 16 * 16));
-        HIPCHK(hipMalloc(&p.d_ncand[k], std::max<u64>(1, ws->max_queries) * 4));
-        HIPCHK(hipEventCreateWithFlags(&p.ev_in[k], hipEventDisableTiming));
-        HIPCHK(hipEventCreateWithFlags(&p.ev_k[k], hipEventDisableTiming));
-        HIPCHK(hipEventCreateWithFlags(&p.ev_out[k], hipEventDisableTiming));
+        int rc = ws->staging[k].alloc(ws); if (rc) return rc;
+        for (Event* e : {&p.ev_in[k], &p.ev_k[k], &p.ev_out[k]}) HIPCHK(e->create());
     }
-    HIPCHK(hipStreamCreateWithFlags(&p.s_in, hipStreamNonBlocking));
-    HIPCHK(hipStreamCreateWithFlags(&p.s_k, hipStreamNonBlocking));
-    HIPCHK(hipStreamCreateWithFlags(&p.s_out, hipStreamNonBlocking));
+    for (Stream* st : {&p.s_in, &p.s_k, &p.s_out}) HIPCHK(st->create());
     p.issued = 0; p.ready = true;
     return MCQ_OK;
 }
@@ -2190,29 +2150,21 @@ extern "C" int mcq_query_pipelined(const mcq_db* db, mcq_ws* ws, const mcq_batch
     HIPCHK(hipSetDevice(db->device));
     const u64 nq = in->paired ? in->n_seqs / 2 : in->n_seqs;
     if (nq > ws->max_queries) return fail(MCQ_E_ARG, "batch has more queries than the workspace allows");
-    const u64 nbases = in->n_seqs ? in->seq_off[in->n_seqs] - in->seq_off[0] : 0;
-    if (nbases > ws->max_bases) return fail(MCQ_E_ARG, "batch has more bases than the workspace allows");
-    if (in->n_seqs && in->seq_off[0] != 0) return fail(MCQ_E_ARG, "host batches must start at offset 0");
-    const bool packed = (in->flags & MCQ_BATCH_PACKED) != 0;
-    if (packed && in->n_bases && in->n_bases != nbases) return fail(MCQ_E_ARG, "mcq_batch.n_bases must equal seq_off[n_seqs] for a packed batch");
+    u64 nbases; rc = check_host_batch(ws, in, nbases); if (rc) return rc;
     rc = pipe_init(ws); if (rc) return rc;
     auto& p = ws->pipe;
     const u64 i = p.issued;
-    const int k = (int)(i & 1);
+    const int k = (int)(i & 1); Staging& s = ws->staging[k];
     // in: this staging set was last read by the kernels of call i - 2
     if (i >= 2) HIPCHK(hipStreamWaitEvent(p.s_in, p.ev_k[k], 0));
-    const u64 bytes = packed ? mcq_packed_bytes(nbases) : nbases;
-    if (bytes) HIPCHK(hipMemcpyAsync(p.d_bases[k], in->bases, bytes, hipMemcpyHostToDevice, p.s_in));
-    HIPCHK(hipMemcpyAsync(p.d_seq_off[k], in->seq_off, (in->n_seqs + 1) * 8, hipMemcpyHostToDevice, p.s_in));
+    BatchDev b; rc = upload_host_batch(in, nbases, s, p.s_in, b); if (rc) return rc;
     ExclDev ex; bool excl;
-    rc = take_query_clades(db, ws, nq, k, p.s_in, ex, excl); if (rc) return rc;    // (this batch's own array: staging set k, as its bases)
+    rc = take_query_clades(db, ws, nq, s, p.s_in, ex, excl); if (rc) return rc;    // (this batch's own array: staging set k, as its bases)
     HIPCHK(hipEventRecord(p.ev_in[k], p.s_in));
     // compute: after its input arrived and its result set was copied out (call i - 2)
     HIPCHK(hipStreamWaitEvent(p.s_k, p.ev_in[k], 0));
     if (i >= 2) HIPCHK(hipStreamWaitEvent(p.s_k, p.ev_out[k], 0));
-    mcq_batch hin = *in; hin.n_bases = nbases;
-    BatchDev b; rc = batch_dev(&hin, p.d_bases[k], p.d_seq_off[k], b); if (rc) return rc;
-    OutDev o; o.cands = p.d_cands[k]; o.ncand = p.d_ncand[k];
+    OutDev o; o.cands = s.d_cands.get(); o.ncand = s.d_ncand.get();
     DebugDev dbg; memset(&dbg, 0, sizeof(dbg));
     rc = launch_query(db, ws, b, od, o, p.s_k, lean_request(opt->flags), dbg, nullptr, nullptr, excl ? &ex : nullptr); if (rc) return rc;
     rc = classify_batch(ws, o, nq, od.max_cand, p.s_k); if (rc) return rc;
@@ -2220,8 +2172,8 @@ extern "C" int mcq_query_pipelined(const mcq_db* db, mcq_ws* ws, const mcq_batch
     // out
     HIPCHK(hipStreamWaitEvent(p.s_out, p.ev_k[k], 0));
     if (nq) {
-        HIPCHK(hipMemcpyAsync(out->cands, p.d_cands[k], nq * od.max_cand * 16, hipMemcpyDeviceToHost, p.s_out));
-        HIPCHK(hipMemcpyAsync(out->n_cand, p.d_ncand[k], nq * 4, hipMemcpyDeviceToHost, p.s_out));
+        HIPCHK(hipMemcpyAsync(out->cands, o.cands, nq * od.max_cand * 16, hipMemcpyDeviceToHost, p.s_out));
+        HIPCHK(hipMemcpyAsync(out->n_cand, o.ncand, nq * 4, hipMemcpyDeviceToHost, p.s_out));
     }
     HIPCHK(hipEventRecord(p.ev_out[k], p.s_out));
     *ticket = i;
@@ -2246,20 +2198,21 @@ extern "C" int mcq_ws_sync(mcq_ws* ws, void* stream, mcq_stats* stats) {
     HIPCHK(hipSetDevice(ws->device));
     hipStream_t st = (hipStream_t)stream;
     if (ws->pipe.ready && ws->pipe.issued) { HIPCHK(hipStreamSynchronize(ws->pipe.s_k)); HIPCHK(hipStreamSynchronize(ws->pipe.s_out)); }
-    HIPCHK(hipMemcpyAsync(ws->ctr_host, ws->ctr, sizeof(CountersDev), hipMemcpyDeviceToHost, st));
+    HIPCHK(hipMemcpyAsync(ws->ctr_host.get(), ws->ctr.get(), sizeof(CountersDev), hipMemcpyDeviceToHost, st));
     HIPCHK(hipStreamSynchronize(st));
+    const CountersDev* h = ws->ctr_host.get();
     if (stats) {
         stats->n_queries = ws->last_nq;
-        stats->n_features = ws->ctr_host->n_features; stats->n_hit_features = ws->ctr_host->n_hit_features;
-        stats->n_locations = ws->ctr_host->n_locations; stats->n_cands = ws->ctr_host->n_cands;
+        stats->n_features = h->n_features; stats->n_hit_features = h->n_hit_features;
+        stats->n_locations = h->n_locations; stats->n_cands = h->n_cands;
         // (direct mode: every query is queued; those the first stage would have kept are not counted -- nor are those its lean form handed on)
-        stats->n_overflow = ws->ctr_host->n_ovf - ws->ctr_host->n_short - ws->ctr_host->n_lean;
-        stats->n_lean_queued = ws->ctr_host->n_lean;
-        stats->n_two_class = ws->ctr_host->n_two_class; stats->n_two_class_retry = ws->ctr_host->n_two_class_retry;
-        stats->n_narrow_queued = ws->ctr_host->n_narrow;
+        stats->n_overflow = h->n_ovf - h->n_short - h->n_lean;
+        stats->n_lean_queued = h->n_lean;
+        stats->n_two_class = h->n_two_class; stats->n_two_class_retry = h->n_two_class_retry;
+        stats->n_narrow_queued = h->n_narrow;
     }
-    if (ws->ctr_host->err_count)
-        return fail(MCQ_E_CAPACITY, std::to_string(ws->ctr_host->err_count) + " queries exceeded the workspace's per-query capacity");
+    if (h->err_count)
+        return fail(MCQ_E_CAPACITY, std::to_string(h->err_count) + " queries exceeded the workspace's per-query capacity");
     return MCQ_OK;
 }
 
@@ -2267,7 +2220,7 @@ extern "C" int mcq_ws_sync(mcq_ws* ws, void* stream, mcq_stats* stats) {
 // synchronised by mcq_ws_sync (zeros in a normal build)
 extern "C" int mcq_debug_phase_clocks(mcq_ws* ws, uint64_t* out22) {
     if (!ws || !out22) return fail(MCQ_E_ARG, "null argument");
-    for (int i = 0; i < 22; ++i) out22[i] = i < 17 ? ws->ctr_host->pad_[i] : 0;
+    for (int i = 0; i < 22; ++i) out22[i] = i < 17 ? ws->ctr_host.get()->pad_[i] : 0;
     return MCQ_OK;
 }
 
@@ -2277,41 +2230,36 @@ extern "C" int mcq_debug_matches(const mcq_db* db, mcq_ws* ws, const mcq_batch* 
     if (!db || !ws || !in || !match_off) return fail(MCQ_E_ARG, "null argument");
     if (path_flags & ~(u32)(MCQ_FORCE_BLOCK_PATH | MCQ_FORCE_RAW_SORT | MCQ_NO_WAVE16)) return fail(MCQ_E_ARG, "path_flags: test hooks only");
     if (in->flags & MCQ_DEVICE_PTRS) return fail(MCQ_E_ARG, "debug tap takes host batches");
+    if (in->flags & (MCQ_BATCH_PACKED | MCQ_BATCH_RANGES)) return fail(MCQ_E_ARG, "debug tap takes plain ASCII batches");
+    mcq_query_opts qo; qo.max_cand = 1; qo.emulate_ranks = 1; qo.insert_size_max = 0; qo.flags = path_flags;
+    OptDev od; int rc = make_opt(&qo, od, db); if (rc) return rc;
     HIPCHK(hipSetDevice(db->device));
     const u64 nq = in->paired ? in->n_seqs / 2 : in->n_seqs;
-    if (nq > ws->max_queries) return fail(MCQ_E_ARG, "batch too large");
-    int rc = ensure_staging(ws); if (rc) return rc;
-    const u64 nbases = in->n_seqs ? in->seq_off[in->n_seqs] : 0;
-    if (nbases > ws->max_bases) return fail(MCQ_E_ARG, "batch too large");
-    if (nbases) HIPCHK(hipMemcpy(ws->d_bases, in->bases, nbases, hipMemcpyHostToDevice));
-    HIPCHK(hipMemcpy(ws->d_seq_off, in->seq_off, (in->n_seqs + 1) * 8, hipMemcpyHostToDevice));
-    mcq_query_opts qo; qo.max_cand = 1; qo.emulate_ranks = 1; qo.insert_size_max = 0; qo.flags = path_flags;
-    OptDev od; rc = make_opt(&qo, od, db); if (rc) return rc;
-    if (in->flags & (MCQ_BATCH_PACKED | MCQ_BATCH_RANGES)) return fail(MCQ_E_ARG, "debug tap takes plain ASCII batches");
-    BatchDev b; rc = batch_dev(in, ws->d_bases, ws->d_seq_off, b); if (rc) return rc;
-    OutDev o; o.cands = ws->d_cands; o.ncand = ws->d_ncand;
-    u64 *d_cnt = nullptr, *d_off = nullptr, *d_m = nullptr;
-    HIPCHK(hipMalloc(&d_cnt, std::max<u64>(1, nq) * 8));
-    HIPCHK(hipMemset(d_cnt, 0, std::max<u64>(1, nq) * 8));
-    HIPCHK(hipMalloc(&d_off, (nq + 1) * 8));
+    if (nq > ws->max_queries) return fail(MCQ_E_ARG, "batch has more queries than the workspace allows");
+    u64 nbases; rc = check_host_batch(ws, in, nbases); if (rc) return rc;
+    Staging& s = ws->staging[2]; rc = s.alloc(ws); if (rc) return rc;
+    BatchDev b; rc = upload_host_batch(in, nbases, s, 0, b); if (rc) return rc;
+    OutDev o; o.cands = s.d_cands.get(); o.ncand = s.d_ncand.get();
+    Dev<u64> d_cnt, d_off, d_m;       // (given back on every way out; hipFree waits for a launch that still uses them)
+    HIPCHK(d_cnt.alloc(nq));
+    HIPCHK(hipMemset(d_cnt.get(), 0, std::max<u64>(1, nq) * 8));
+    HIPCHK(d_off.alloc(nq + 1));
     DebugDev dbg; memset(&dbg, 0, sizeof(dbg));
-    dbg.mode = 1; dbg.match_cnt = d_cnt;
+    dbg.mode = 1; dbg.match_cnt = d_cnt.get();
     rc = launch_query(db, ws, b, od, o, 0, LeanReq::Auto, dbg); if (rc) return rc;
     HIPCHK(hipDeviceSynchronize());
     std::vector<u64> cnt(nq);
-    if (nq) HIPCHK(hipMemcpy(cnt.data(), d_cnt, nq * 8, hipMemcpyDeviceToHost));
+    if (nq) HIPCHK(hipMemcpy(cnt.data(), d_cnt.get(), nq * 8, hipMemcpyDeviceToHost));
     match_off[0] = 0;
     for (u64 q = 0; q < nq; ++q) match_off[q + 1] = match_off[q] + cnt[q];
     if (matches && match_off[nq] <= cap && match_off[nq] > 0) {
-        HIPCHK(hipMalloc(&d_m, match_off[nq] * 8));
-        HIPCHK(hipMemcpy(d_off, match_off, (nq + 1) * 8, hipMemcpyHostToDevice));
-        dbg.mode = 2; dbg.match_off = d_off; dbg.matches = d_m;
+        HIPCHK(d_m.alloc(match_off[nq]));
+        HIPCHK(hipMemcpy(d_off.get(), match_off, (nq + 1) * 8, hipMemcpyHostToDevice));
+        dbg.mode = 2; dbg.match_off = d_off.get(); dbg.matches = d_m.get();
         rc = launch_query(db, ws, b, od, o, 0, LeanReq::Auto, dbg); if (rc) return rc;
         HIPCHK(hipDeviceSynchronize());
-        HIPCHK(hipMemcpy(matches, d_m, match_off[nq] * 8, hipMemcpyDeviceToHost));
-        (void)hipFree(d_m);
+        HIPCHK(hipMemcpy(matches, d_m.get(), match_off[nq] * 8, hipMemcpyDeviceToHost));
     }
-    (void)hipFree(d_cnt); (void)hipFree(d_off);
     return MCQ_OK;
 }
 
@@ -2326,7 +2274,7 @@ extern "C" int mcq_reduce(const mcq_db* db, mcq_ws* ws, uint64_t n_queries, cons
     if (od.big) od.hooks |= MCQ_HOOK_BLOCK_ONLY;     // (the staged wave kernels keep the lists in a wave's lanes or not at all)
     HIPCHK(hipSetDevice(db->device));
     hipStream_t st = (hipStream_t)stream;
-    HIPCHK(hipMemsetAsync(ws->ctr, 0, MCQ_CTR_ZEROED, st));
+    HIPCHK(hipMemsetAsync(ws->ctr.get(), 0, MCQ_CTR_ZEROED, st));
     ws->last_nq = n_queries;
     if (n_queries == 0) return MCQ_OK;
     OutDev o; o.cands = (u32*)out->cands; o.ncand = out->n_cand;
@@ -2336,16 +2284,16 @@ extern "C" int mcq_reduce(const mcq_db* db, mcq_ws* ws, uint64_t n_queries, cons
     rc = with_loc_form(db, [&](auto L) -> int {
         using Key = typename decltype(L)::Key;
         constexpr bool GW = decltype(L)::gw;
-        hipLaunchKernelGGL((k_reduce_wave<Key, kLcapWave, GW>), dim3(grid), dim3(256), 0, st, db->d, od, o, ws->ctr, ws->ovf_list,
+        hipLaunchKernelGGL((k_reduce_wave<Key, kLcapWave, GW>), dim3(grid), dim3(256), 0, st, db->d, od, o, ws->ctr.get(), ws->ovf_list.get(),
                            n_queries, loc_off, (const Key*)locs, query_len, db->g);
         rc = tm.mark(); if (rc) return rc;
         if constexpr (sizeof(Key) == 4)     // (no second stage for 64-bit words: its timer slot stays empty)
-            hipLaunchKernelGGL(k_reduce_wave16<GW>, dim3(grid_for(ws->cap_reduce16, (n_queries + 3) / 4)), dim3(256), 0, st, db->d, od, o, ws->ctr,
-                               (const u32*)ws->ovf_list, n_queries, loc_off, (const u32*)locs, query_len, db->g);
+            hipLaunchKernelGGL(k_reduce_wave16<GW>, dim3(grid_for(ws->cap_reduce16, (n_queries + 3) / 4)), dim3(256), 0, st, db->d, od, o, ws->ctr.get(),
+                               (const u32*)ws->ovf_list.get(), n_queries, loc_off, (const u32*)locs, query_len, db->g);
         rc = tm.mark(); if (rc) return rc;
         auto block = [&](auto BIG) {
-            hipLaunchKernelGGL((k_reduce_block<Key, kLcapBlock, BIG, GW>), dim3(ws->n_block_wgs), dim3(1024), 0, st, db->d, od, o, ws->ctr,
-                               (const u32*)ws->ovf_list, ws->sc, loc_off, (const Key*)locs, query_len, db->g);
+            hipLaunchKernelGGL((k_reduce_block<Key, kLcapBlock, BIG, GW>), dim3(ws->n_block_wgs), dim3(1024), 0, st, db->d, od, o, ws->ctr.get(),
+                               (const u32*)ws->ovf_list.get(), ws->sc, loc_off, (const Key*)locs, query_len, db->g);
         };
         if (od.big) block(IntC<1>{}); else block(IntC<0>{});
         return MCQ_OK;
@@ -2358,7 +2306,7 @@ extern "C" int mcq_reduce(const mcq_db* db, mcq_ws* ws, uint64_t n_queries, cons
 
 // ------------------------------------------------------------------ per-kernel timing
 static int drain_events(mcq_ws* ws) {
-    for (auto& t : *ws->ev_used) {
+    for (auto& t : ws->ev_used) {
         HIPCHK(hipEventSynchronize(t.ev[MCQ_N_TIMED]));
         for (int i = 0; i < MCQ_N_TIMED; ++i) {
             float ms = 0;
@@ -2366,9 +2314,9 @@ static int drain_events(mcq_ws* ws) {
             ws->timed_ms[i] += ms;
         }
         ws->timed_launches += 1;
-        ws->ev_free->push_back(t);
+        ws->ev_free.push_back(std::move(t));
     }
-    ws->ev_used->clear();
+    ws->ev_used.clear();
     return MCQ_OK;
 }
 

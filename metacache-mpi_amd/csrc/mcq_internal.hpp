@@ -1,13 +1,14 @@
 #pragma once
 // mcq_internal.hpp -- what more than one unit of libmcq_hip.so needs on the host side: the handle structs behind the
-// C ABI, error reporting, a few inline helpers, and the declarations of the functions that cross a unit boundary
-// (hidden visibility: none of them is part of the ABI).  The units: mcq_engine.hip (workspace, fused query, reduce),
-// mcq_table.hip (mcq_db_*), mcq_stages.hip (staged and routing entry points, batch preparation), mcq_shard.hip
-// (mcq_shard_*).  Kernels are not declared here: each is defined in the unit that launches it.
+// C ABI, the owners of their GPU resources, error reporting, a few inline helpers, and the declarations of the functions that
+// cross a unit boundary (hidden visibility: none is part of the ABI).  The units: mcq_engine.hip (workspace, fused query, reduce),
+// mcq_table.hip (mcq_db_*), mcq_stages.hip (staged and routing entry points, batch preparation), mcq_shard.hip (mcq_shard_*),
+// mcq_target_hits.hip (mcq_target_*).  Kernels are not declared here: each is defined in the unit that launches it.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <stdio.h>
 #include <string.h>
+#include <memory>
 #include <string>
 #include <vector>
 #include <algorithm>
@@ -62,47 +63,97 @@ struct DebugDev {
     u64* matches;
 };
 
+// ------------------------------------------------------------------ owners
+// move-only; the destructor gives back what is held, so every way out of a function frees and a handle is destroyed by `delete`.
+// Dev<T> has the shape of the build unit's (mcq_build.hip keeps its own for now: DESIGN.md 20)
+template <class T> struct Dev {                 // n elements of T from hipMalloc, never fewer than one
+    T* p = nullptr;
+    Dev() = default;
+    Dev(Dev&& o) noexcept : p(o.release()) {}
+    Dev& operator=(Dev&& o) noexcept { if (this != &o) { reset(); p = o.release(); } return *this; }
+    ~Dev() { reset(); }
+    hipError_t alloc(u64 n) { reset(); return hipMalloc(&p, (n ? n : 1) * sizeof(T)); }
+    T* get() const { return p; }
+    void reset() { if (p) (void)hipFree(p); p = nullptr; }
+    T* release() { T* q = p; p = nullptr; return q; }
+};
+template <class T> struct Pinned {              // the same from hipHostMalloc
+    T* p = nullptr;
+    Pinned() = default;
+    Pinned(Pinned&& o) noexcept : p(o.p) { o.p = nullptr; }
+    Pinned& operator=(Pinned&& o) noexcept { std::swap(p, o.p); return *this; }
+    ~Pinned() { if (p) (void)hipHostFree(p); }
+    hipError_t alloc(u64 n) { return p ? hipSuccess : hipHostMalloc(&p, (n ? n : 1) * sizeof(T)); }
+    T* get() const { return p; }
+};
+struct Event {                                  // created once, on demand; converts to the runtime's handle
+    hipEvent_t e = nullptr;
+    Event() = default;
+    Event(Event&& o) noexcept : e(o.e) { o.e = nullptr; }
+    Event& operator=(Event&& o) noexcept { std::swap(e, o.e); return *this; }
+    ~Event() { if (e) (void)hipEventDestroy(e); }
+    hipError_t create(unsigned flags = hipEventDisableTiming) { return e ? hipSuccess : hipEventCreateWithFlags(&e, flags); }
+    operator hipEvent_t() const { return e; }
+};
+struct Stream {                                 // a non-blocking stream of the workspace's own
+    hipStream_t s = nullptr;
+    Stream() = default;
+    Stream(Stream&& o) noexcept : s(o.s) { o.s = nullptr; }
+    Stream& operator=(Stream&& o) noexcept { std::swap(s, o.s); return *this; }
+    ~Stream() { if (s) (void)hipStreamDestroy(s); }
+    hipError_t create() { return s ? hipSuccess : hipStreamCreateWithFlags(&s, hipStreamNonBlocking); }
+    operator hipStream_t() const { return s; }
+};
+
 #define MCQ_N_TIMED 3           // kernels of one batch that are timed separately: first wave stage, second wave stage, workgroup kernel
-struct TimedLaunch { hipEvent_t ev[MCQ_N_TIMED + 1]; };
+struct TimedLaunch { Event ev[MCQ_N_TIMED + 1]; };
+struct mcq_ws;
+// One staging set for calls with host pointers: the batch's bases and offsets, its candidate lists, and the slot a host array of
+// clade keys goes through (mcq_ws_set_query_clades), guarded by the event behind its last upload.  The four arrays come with
+// alloc(), at the first call that needs this set; the slot comes with the first host clade array (take_query_clades).
+struct Staging {
+    Event qc_ev; bool qc_used = false; Pinned<u32> qc_pinned; Dev<u32> qc_dev;
+    Dev<char> d_bases; Dev<u64> d_seq_off; Dev<u32> d_cands, d_ncand;
+    int alloc(const mcq_ws* ws);                // (mcq_engine.hip)
+};
+// Members are destroyed last to first, and the order matters: device memory goes first (the first hipFree is what waits for the
+// work in flight), then the events, then the streams.  So streams are declared before events, events before device memory.
 struct mcq_ws {
-    int device;
-    u64 max_queries, max_bases;
-    CountersDev* ctr;         // device
-    CountersDev* ctr_host;    // pinned
-    u32* ovf_list;            // [ovf_capacity(max_queries)]
-    unsigned long long* probe_buf;   // [(2 x max_queries + 3 x MCQ_OVF_TAIL) x 64]: rows of the back queue, then of the front queue; see CountersDev
-    ScratchDev sc;
-    int n_block_wgs;
-    u32 cap_wave, cap_wave16, cap_reduce16, cap_wave32, cap_wave_many;   // resident workgroups of the wave-per-query kernels on this device
-    // staging for host-pointer calls
-    char* d_bases; u64* d_seq_off; u32* d_cands; u32* d_ncand;
-    u64 last_nq;
-    // host-buffer pipeline (mcq_query_pipelined): two staging sets, copy streams on both sides of the compute stream
+    int device = 0, n_block_wgs = 0;
+    u64 max_queries = 0, max_bases = 0;
+    u32 cap_wave = 0, cap_wave16 = 0, cap_reduce16 = 0, cap_wave32 = 0, cap_wave_many = 0;   // resident workgroups of the wave-per-query kernels on this device
+    u64 last_nq = 0;
+    // host-buffer pipeline (mcq_query_pipelined): staging sets 0 and 1, copy streams on both sides of the compute stream
     struct Pipe {
-        char* d_bases[2]; u64* d_seq_off[2]; u32* d_cands[2]; u32* d_ncand[2];
-        hipStream_t s_in, s_k, s_out;
-        hipEvent_t ev_in[2], ev_k[2], ev_out[2];
-        u64 issued;             // calls so far; call i uses set i & 1
-        bool ready;
+        Stream s_in, s_k, s_out;
+        Event ev_in[2], ev_k[2], ev_out[2];
+        u64 issued = 0;         // calls so far; call i uses set i & 1
+        bool ready = false;
     } pipe;
     // optional per-launch timing of the path's kernels (events between them on the call's stream)
-    int timing;
-    std::vector<TimedLaunch>* ev_used;
-    std::vector<TimedLaunch>* ev_free;
-    double timed_ms[MCQ_N_TIMED]; u64 timed_launches;
+    int timing = 0;
+    std::vector<TimedLaunch> ev_used, ev_free;
+    double timed_ms[MCQ_N_TIMED] = {}; u64 timed_launches = 0;
     // classification of every batch while a taxonomy is attached (mcq_ws_set_classify): counts [cls_n] on the device,
     // cls_ev recorded behind the last batch that added into them
-    const mcq_taxonomy* cls_tx;
-    mcq_classify_opts cls_opt;
-    unsigned long long* cls_counts;
-    u32 cls_n;
-    hipEvent_t cls_ev;
-    // clade exclusion (mcq_ws_set_exclusion): the targets' clade keys on the device while attached; the query keys handed over for
-    // the NEXT batch (mcq_ws_set_query_clades: a device pointer as it came, or a copy of the host array), and where host arrays are
-    // staged -- one set per staging set of the pipelined call and one for mcq_query, each guarded by the event behind its last upload
-    u32* excl_tgt; u32 excl_n;
-    const u32* qc_dev; std::vector<u32>* qc_host; u64 qc_n; int qc_kind;      // qc_kind: 0 nothing handed over, 1 device pointer, 2 host copy
-    struct QcSlot { u32* pinned; u32* dev; hipEvent_t ev; bool used; } qc_slot[3];
+    const mcq_taxonomy* cls_tx = nullptr;
+    mcq_classify_opts cls_opt = {};
+    u32 cls_n = 0;
+    Event cls_ev;
+    // clade exclusion (mcq_ws_set_exclusion): the targets' clade keys on the device while attached (excl_tgt [excl_n]); the query
+    // keys handed over for the NEXT batch (mcq_ws_set_query_clades: a device pointer as it came, or a copy of the host array)
+    u32 excl_n = 0;
+    const u32* qc_dev = nullptr; std::vector<u32> qc_host; u64 qc_n = 0; int qc_kind = 0;    // qc_kind: 0 nothing handed over, 1 device pointer, 2 host copy
+    Staging staging[3];       // [0], [1]: the pipeline's; [2]: mcq_query's and mcq_debug_matches'
+    // device and pinned memory, declared in the reverse of the order it is given back in
+    Dev<u32> excl_tgt;
+    Dev<unsigned long long> cls_counts;
+    ScratchDev sc = {};       // the five arrays below as the workgroup kernels take them
+    Dev<u64> sc_ghits, sc_gbuf, sc_foff; Dev<u32> sc_fpos, sc_feat;
+    Dev<unsigned long long> probe_buf;   // [(2 x max_queries + 3 x MCQ_OVF_TAIL) x 64]: rows of the back queue, then of the front queue; see CountersDev
+    Dev<u32> ovf_list;        // [ovf_capacity(max_queries)]
+    Pinned<CountersDev> ctr_host;
+    Dev<CountersDev> ctr;
 };
 
 // ------------------------------------------------------------------ a handle's form as template arguments

@@ -698,7 +698,7 @@ extern "C" int mcq_shard_query(mcq_shard* c, const mcq_batch* in, const mcq_quer
     HIPCHK(hipStreamWaitEvent(st, c->ev_x[k], 0));
 
     // ---- S3: home side, the fused kernels fed from the exchange
-    HIPCHK(hipMemsetAsync(ws->ctr, 0, MCQ_CTR_ZEROED, st));
+    HIPCHK(hipMemsetAsync(ws->ctr.get(), 0, MCQ_CTR_ZEROED, st));
     hipLaunchKernelGGL(k_shard_fold_err, dim3(1), dim3(1), 0, st, c->err, (const u32*)(c->err + 1 + k));
     const bool alias = shard_alias(c);
     u32* const recvR = alias ? b.sendR : b.recvR;
@@ -710,7 +710,7 @@ extern "C" int mcq_shard_query(mcq_shard* c, const mcq_batch* in, const mcq_quer
     OutDev o; o.cands = (u32*)out->cands; o.ncand = out->n_cand;
     DebugDev dbg; memset(&dbg, 0, sizeof(dbg));
     rc = launch_query(c->db, ws, bd, od, o, st, lean_request(opt->flags), dbg, &sh, &dbd); if (rc) return rc;
-    hipLaunchKernelGGL(k_shard_add_count, dim3(1), dim3(1), 0, st, &ws->ctr->n_features, (const unsigned long long*)b.feat_cnt);
+    hipLaunchKernelGGL(k_shard_add_count, dim3(1), dim3(1), 0, st, &ws->ctr.get()->n_features, (const unsigned long long*)b.feat_cnt);
     HIPCHK(hipEventRecord(c->ev_done[k], st));            // this buffer set may be overwritten
     c->last_nq = nq;
     const int k2 = (k + 1) % MCQ_SHARD_SETS;

@@ -318,7 +318,7 @@ extern "C" int mcq_target_hits(const mcq_db* db, mcq_ws* ws, const mcq_batch* in
     a.targets = targets; a.n_slots = n_slots; a.range_cap = range_cap; a.insert_size_max = insert_size_max;
     a.ranges = reinterpret_cast<u32*>(out_ranges); a.counts = out_counts; a.status = status;
     hipStream_t st = (hipStream_t)stream;
-    const DbDev d = db->d; const GwDev g = db->g; CountersDev* ctr = ws->ctr;
+    const DbDev d = db->d; const GwDev g = db->g; CountersDev* ctr = ws->ctr.get();
     const int device = db->device;
     with_loc_form(db, [&](auto lf) {
         using LF = decltype(lf);
