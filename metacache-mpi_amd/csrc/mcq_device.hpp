@@ -866,6 +866,154 @@ __device__ __forceinline__ u32 wave_sketch_b(const BatchDev& b, u64 at, u32 n, u
     return wave_sketch_words(w, am, n, k, s, lane, tmp, dst);
 }
 
+// ---- both windows of a short read in one pass (default geometry: k 16, s 16, windows 128 / 113) ---------------------------
+// A read of 129..160 bases has two windows, A = bases [0, 128) with 113 k-mer positions and B = [113, n) with n - 128 <= 32 of
+// them.  The stride is winlen - k + 1, so a k-mer that starts at p <= 112 lies in A and one at p >= 113 in B: the read's k-mers
+// partition, and what wave_sketch does once per window (load, encode, OR-reduce, shuffle, hash, ballot, compact, sort,
+// de-duplicate, write) is done once per read here.  Writes A's features (ascending), then B's, to dst and returns their number:
+// exactly what two calls of wave_sketch on [0, 128) and [113, n) write (tests/native/fused_sketch.hip).
+//
+// Decode: four bases per lane out of one (unaligned) 32-bit load; no byte outside [seq, seq + n) is loaded -- the lane that
+// straddles the end loads the read's last four bytes and shifts (n >= 129), the zero bytes that come in encode as ambiguous.
+// 4 lanes form a 16-base word, 8 lanes a 32-base ambiguity word.  Hash: lane l owns the k-mers at l, l + 64 and l + 128.
+// Select: A's hashes below E / c_A of the hash range (c_A = A's valid k-mers; all of them if c_A <= 32) compact to tmp[0..32),
+// all of B's to tmp[32..64), one 32-lane-block sort orders both.  E is lower than wave_sketch's 40 because A's survivors have
+// to fit 32 lanes, not 64.  Retries (wave-uniform, from the hashes in registers): 33..64 survivors -> A alone through the
+// 64-lane sort; more than 64, or fewer than 16 distinct ones below the threshold -> the exact repeated-wave-min selection; B
+// then sorts alone.  The result is the same whatever E is.
+#ifndef MCQ_SKETCH_EXPECT_FUSED
+#define MCQ_SKETCH_EXPECT_FUSED 25    // expected number of A's hashes below the threshold
+#endif
+struct __attribute__((packed)) PackedU32 { u32 v; };
+// four ASCII bases (first in the low byte) -> code8: their 2-bit codes, first base in the top bits; amb4: their ambiguity bits,
+// first base in the top bit.  The same classes as wave_words_of_chars: A/a C/c G/g T/t are bases, every other byte is ambiguous.
+__device__ __forceinline__ void encode_chars4(u32 c, u32& code8, u32& amb4) {
+    const u32 z = (c & 0xDFDFDFDFu) ^ 0x41414141u;                   // per byte: A 0x00, C 0x02, G 0x06, T 0x15
+    const u32 r = (z >> 1) & 0x03030303u;                            // A 0, C 1, G 3, T 2
+    const u32 t = r & ~(r << 1) & 0x02020202u;                       // 0x02 where r == 2
+    const u32 bad = (z & 0xF9F9F9F9u) ^ ((t >> 1) | (t << 3));       // a base leaves 0x00 (T: 0x11 ^ 0x11)
+    const u32 f = ((((bad & 0x7F7F7F7Fu) + 0x7F7F7F7Fu) | bad) >> 7) & 0x01010101u;      // 1 per non-zero byte
+    const u32 x = r ^ ((r >> 1) & 0x01010101u);                      // A 0, C 1, G 2, T 3
+    const u32 px = (x << 2) | (x >> 8);
+    code8 = ((px << 4) | (px >> 16)) & 0xFFu;
+    const u32 pf = (f << 1) | (f >> 8);
+    amb4 = ((pf << 2) | (pf >> 16)) & 0xFu;
+}
+// sort the cnt values compacted in tmp[0..cnt) (WIDE: cnt <= 64, else <= 32), de-duplicate, write the min(distinct, cap) smallest
+// to dst; returns the number of distinct values (the caller decides whether that many suffice)
+template <bool WIDE>
+__device__ __forceinline__ u32 sketch_sorted_prefix(const u32* tmp, u32 cnt, u32 cap, u32 lane, u32* dst) {
+    u32 v = lane < cnt ? tmp[lane] : MCQ_EMPTY;
+    v = WIDE ? wave_sort64_1(v) : wave_sort_blocks32_1(v);
+    asm("s_nop 1" : "+v"(v));                     // v was written inside an asm block: 2 wait states before a DPP read
+    const u32 prev = (u32)__builtin_amdgcn_update_dpp(0, (int)v, 0x138, 0xF, 0xF, false);    // wave_shr:1
+    const bool keep = (v != MCQ_EMPTY) && (lane == 0 || v != prev);
+    const u64 km = __ballot(keep);
+    const u32 rank = lane_rank(km);
+    if (keep && rank < cap) dst[rank] = v;
+    return (u32)__builtin_popcountll(km);
+}
+// path: 0 = the one-sort pass, 1 = A through the 64-lane sort, 2 = A by the exact selection (for the test program; dead otherwise)
+// REMAT: the shifts and shuffle addresses that depend on the lane alone are computed per call instead of living in registers
+// across the caller's loop (a dozen VGPRs; for a kernel that has none to spare)
+template <u32 E = MCQ_SKETCH_EXPECT_FUSED, bool REMAT = false>
+__device__ __forceinline__ u32 wave_sketch_two_windows(const char* __restrict__ seq, u32 n, u32 lane, u32* tmp, u32* dst, u32& path) {
+    if constexpr (REMAT) asm volatile("" : "+v"(lane));
+    constexpr u32 K = MCQ_GEOM_DEFAULT_K, S = MCQ_GEOM_DEFAULT_S, W = MCQ_GEOM_DEFAULT_WINLEN, ST = MCQ_GEOM_DEFAULT_STRIDE;
+    static_assert(K == 16 && S == 16 && W == 128 && ST == W - K + 1, "the two windows' k-mers partition; a k-mer is one 32-bit word");
+    // ---- decode once
+    const u32 p4 = 4 * lane;
+    const u32 la = p4 < n - 4 ? p4 : n - 4;                           // (n >= 129)
+    u32 c = reinterpret_cast<const PackedU32*>(seq + la)->v >> (8 * ((p4 - la) & 3u));
+    if (p4 >= n) c = 0;
+    u32 code8, amb4;
+    encode_chars4(c, code8, amb4);
+    u32 w = code8 << (24 - 8 * (lane & 3));
+    w |= xor_lane<1>(w, lane); w |= xor_lane<2>(w, lane);
+    u32 am = amb4 << (28 - 4 * (lane & 7));
+    am |= xor_lane<1>(am, lane); am |= xor_lane<2>(am, lane); am |= xor_lane<4>(am, lane);
+    // ---- hash once: k-mers at lane, lane + 64, lane + 128 (word i of the read sits in lanes 4i.., ambiguity word i in lanes 8i..)
+    const u32 sh = (lane & 15) * 2, ash = lane & 31;
+    const u32 wsrc = (lane & 0x30u), asrc = (lane & 0x20u);           // ds_bpermute addresses (lane x 4) of word lane / 16, ambiguity word lane / 32
+    u32 h[3];
+#pragma unroll
+    for (int i = 0; i < 3; ++i) {
+        const u32 pos = lane + 64 * i;
+        const u32 w0 = (u32)__builtin_amdgcn_ds_bpermute((int)(wsrc + 64 * i), (int)w);
+        const u32 w1 = (u32)__builtin_amdgcn_ds_bpermute((int)(wsrc + 64 * i + 16), (int)w);
+        const u32 kmer = (u32)((((u64)w0 << 32) | w1) >> (32 - sh));
+        const u32 m0 = (u32)__builtin_amdgcn_ds_bpermute((int)(asrc + 64 * i), (int)am);
+        const u32 m1 = (u32)__builtin_amdgcn_ds_bpermute((int)(asrc + 64 * i + 32), (int)am);
+        const u32 amb32 = (u32)((((u64)m0 << 32) | m1) >> (32 - ash));
+        // a k-mer ends inside its own window: p <= 112 always does (window A: p + 16 <= 128 < n), p >= 113 if p + 16 <= n (window B)
+        const bool ok = (i == 0 || pos + K <= n) && (amb32 >> (32 - K)) == 0;
+        h[i] = ok ? tmh(canonical(kmer, K)) : MCQ_EMPTY;
+    }
+    const bool b1 = lane >= ST - 64;                                  // slot 1 from position 113 on belongs to B
+    const u32 ha0 = h[0], ha1 = b1 ? MCQ_EMPTY : h[1], hb = b1 ? h[1] : h[2];
+    // ---- select both windows together
+    const u32 cA = (u32)__builtin_popcountll(__ballot(ha0 != MCQ_EMPTY)) + (u32)__builtin_popcountll(__ballot(ha1 != MCQ_EMPTY));
+    const bool all_in = cA <= 32;
+    const u32 thr = all_in ? MCQ_EMPTY : (u32)fminf(__builtin_amdgcn_rcpf((float)cA) * (4294967296.0f * E), 4294967040.0f);
+    const bool s0 = ha0 < thr, s1 = ha1 < thr, sb = hb != MCQ_EMPTY;
+    const u64 m0 = __ballot(s0), m1 = __ballot(s1), mb = __ballot(sb);
+    const u32 n0 = (u32)__builtin_popcountll(m0), cntA = n0 + (u32)__builtin_popcountll(m1), cntB = (u32)__builtin_popcountll(mb);
+    const u32 capB = n - W;                                           // B's k-mer positions: 1..32, at most S of them are kept
+    const u32 slB = capB < S ? capB : S;
+    path = 0;
+    if (cntA <= 32) {
+        if (s0) tmp[lane_rank(m0)] = ha0;
+        if (s1) tmp[n0 + lane_rank(m1)] = ha1;
+        if (sb) tmp[32 + lane_rank(mb)] = hb;
+        wave_sync();
+        const bool hi = lane >= 32;
+        u32 v = lane < (hi ? 32 + cntB : cntA) ? tmp[lane] : MCQ_EMPTY;
+        v = wave_sort_blocks32_1(v);
+        asm("s_nop 1" : "+v"(v));                 // v was written inside an asm block: 2 wait states before a DPP read
+        const u32 prev = (u32)__builtin_amdgcn_update_dpp(0, (int)v, 0x138, 0xF, 0xF, false);    // wave_shr:1
+        const bool keep = (v != MCQ_EMPTY) && ((lane & 31) == 0 || v != prev);
+        const u64 km = __ballot(keep);
+        const u32 DA = (u32)__builtin_popcount((u32)km), DB = (u32)__builtin_popcount((u32)(km >> 32));
+        if (all_in || DA >= S) {
+            const u32 mA = DA < S ? DA : S, mB = DB < slB ? DB : slB;
+            const u32 rank = lane_rank(km) - (hi ? DA : 0u);
+            if (keep && rank < (hi ? mB : mA)) dst[rank + (hi ? mA : 0u)] = v;
+            wave_sync();
+            return mA + mB;
+        }
+        wave_sync();                              // tmp[] is compacted into again below
+    }
+    // ---- retries: A alone, then B alone
+    u32 mA = 0;
+    bool exact = cntA > 64 || cntA <= 32;         // (<= 32: the pass above found fewer than S distinct hashes below the threshold)
+    if (!exact) {
+        path = 1;
+        if (s0) tmp[lane_rank(m0)] = ha0;
+        if (s1) tmp[n0 + lane_rank(m1)] = ha1;
+        wave_sync();
+        const u32 DA = sketch_sorted_prefix<true>(tmp, cntA, S, lane, dst);
+        if (DA < S) exact = true; else mA = S;    // (not all_in here: c_A >= cntA > 32)
+        wave_sync();
+    }
+    if (exact) {
+        path = 2;
+        u32 a0 = ha0, a1 = ha1;
+        for (mA = 0; mA < S; ++mA) {              // repeated wave-min, equal values retire together
+            const u32 lo = a0 < a1 ? a0 : a1;
+            const u32 mn = wave_min_u32(lo);
+            if (mn == MCQ_EMPTY) break;
+            if (lane == 0) dst[mA] = mn;
+            if (a0 == mn) a0 = MCQ_EMPTY;
+            if (a1 == mn) a1 = MCQ_EMPTY;
+        }
+    }
+    if (sb) tmp[lane_rank(mb)] = hb;
+    wave_sync();
+    const u32 DB = sketch_sorted_prefix<false>(tmp, cntB, slB, lane, dst + mA);
+    wave_sync();
+    return mA + (DB < slB ? DB : slB);
+}
+
 // ------------------------------------------------------------------ row 6: probe
 // Linear probing over 64-B buckets; one 16-B load returns key and list length -- and, for the short lists most features
 // have, the bucket IS the list: its locations are in the same 64-B sector the probe has just brought in, so the gather

@@ -614,6 +614,9 @@ __device__ __forceinline__ void tap_distinct(const DebugDev& dbg, const u32* SK,
 // The lean form is also compiled for one sketch geometry and one form of batch: GeomDefault (k, s, window length and both strides
 // of the reference's default build as literals) and BatchForm<PAIRED, PACKED>, where every other instantiation reads the table's and
 // the batch's words (GeomRt, BatchRt).  plan_launch gives a table of any other geometry the full form alone.
+// Its single, unpacked instantiations sketch a read of 129..160 bases -- two windows, the second with at most 32 k-mers -- in one
+// pass over both (wave_sketch_two_windows: one decode, one round of hashes, one sort) instead of once per window; every other
+// length, pairs and packed batches keep the loop over the windows.
 // Which form runs is the batch before's word (CountersDev::direct_mode bit MCQ_MODE_LEAN; both are launched and the other one
 // returns at once) unless MCQ_HOOK_ONLY_LAUNCH says this launch is the only one.
 template <class KeyT, int LCAP, bool TAP = false, bool SH = false, bool GW = false, int BSH = -1, int NL = 1, bool LEAN = false, bool EXCL = false,
@@ -705,6 +708,16 @@ __global__ __launch_bounds__(256, sizeof(KeyT) == 4 ? (NL > 1 ? 5 : MCQ_WAVE_OCC
                 nfeat = (g.nw1 + g.nw2) * db.s;          // feature slots (unused ones have no list)
                 if (lane < nfeat) shard_fetch(sh, sh.win_off[b.paired ? 2 * q : q] * db.s + lane, off, len);
             } else {
+            if constexpr (LEAN && !PAIRED && !PACKED) {
+                // a single read of 129..160 bases (150: two windows, the second with at most 32 k-mers): both windows in one pass.
+                // (The global-window instantiations have no VGPR to spare for the pass's lane constants: they recompute them.)
+                if (g.n1 - 129u <= 31u) { u32 path; nfeat = wave_sketch_two_windows<MCQ_SKETCH_EXPECT_FUSED, GW>(b.bases + g.o0, g.n1, lane, sk_tmp, feat, path); }
+                else for (u32 w = 0; w < g.nw1; ++w) {
+                    u64 at; u32 wl;
+                    window_span<G>(db, g, w, at, wl);
+                    nfeat += wave_sketch_b<F>(b, at, wl, geo.k(), geo.s(), lane, sk_tmp, feat + nfeat);
+                }
+            } else
             for (u32 w = 0; w < g.nw1 + g.nw2; ++w) {
                 u64 at; u32 wl;
                 window_span<G>(db, g, w, at, wl);
