@@ -650,6 +650,47 @@ int mcq_target_hits(const mcq_db* db, mcq_ws* ws, const mcq_batch* in, const uin
 int mcq_target_slots(const mcq_result* cands, uint64_t n_queries, uint32_t max_cand, uint32_t hits_min,
                      const uint32_t* tax2tgt, uint32_t n_taxa, uint32_t* targets, uint32_t n_slots, void* stream);
 
+/* ---- read-to-candidate alignment: what `-align` prints (csrc/mcq_align.hip) ------------------------------------------------------
+ * make_semi_global_alignment (src/classification.cpp:77-103) of every query of a batch against one subject each: align_semi_global
+ * with default_alignment_scheme (src/alignment.h: match +2, mismatch -1, gap -1; row 0 and column 0 are 0 and end the backtrace; a
+ * cell takes diag, then above if strictly greater, then left if strictly greater; the end cell is the corner, then the last column at
+ * rows 1 .. len_q-1, then the last row at columns 1 .. len_s-1, each only if strictly greater).  Mate 1 is aligned forward and as its
+ * reverse complement (reverse_complement, src/dna_encoding.h:146-165: only ACGTacgt change); a second mate that is not empty adds its
+ * two scores to the two sums, which are std::size_t there: a negative sum compares as a huge number, and so it does here.  Forward
+ * wins only if strictly greater.  What comes back is mate 1's chosen alignment: its score, the orientation, and the two aligned
+ * strings in reading order ('_' = gap).  Characters are compared raw: case matters, N equals N.  An empty mate 1 or an empty subject
+ * gives score 0 and the one pair '_' / '_'.
+ *   in          a batch as mcq_query takes it, device pointers only (MCQ_DEVICE_PTRS), ASCII, offsets or MCQ_BATCH_RANGES, paired or
+ *               not.  MCQ_BATCH_PACKED has lost the case of the bases: MCQ_E_UNSUPPORTED.
+ *   subjects    device, raw bases; jobs[q] (device, [n_queries]) names query q's slice of it.  on = 0: no alignment for this query.
+ *   out         device, [n_queries].  length = bytes of each of the two strings, 0 for a query without `on` and for one beyond a capacity.
+ *   out_query, out_subject   device, [n_queries * text_cap]: query q's strings start at q * text_cap.  Only [0, length) is written.
+ * The capacities: a mate of more than max_query bases gets MCQ_ALIGN_QUERY_LONG in its status, a subject of more than max_subject bases
+ * MCQ_ALIGN_SUBJECT_LONG; such a query gets length 0 and nothing is written into its text slots.  max_query <= MCQ_ALIGN_MAX_QUERY and
+ * max_subject <= MCQ_ALIGN_MAX_SUBJECT are the caller's bounds for this call (MCQ_E_ARG beyond), text_cap >= max_query + max_subject and
+ * >= 1.  Jobs whose predecessor matrix (2 bits per cell) does not fit a wave's share of LDS keep it in scratch memory of the workspace:
+ * 256 MiB, made once by the first call whose bounds allow such a job (that one call allocates; every other call only enqueues work on
+ * `stream`); a call that needs it runs with as many waves as areas of max_query x max_subject cells fit into it.  The
+ * workspace's counters and its capacity count are not touched: status[] is the only report.                                        */
+enum { MCQ_ALIGN_MAX_QUERY = 2048u,      /* bases of one mate                                                    */
+       MCQ_ALIGN_MAX_SUBJECT = 4096u };  /* bases of one subject                                                 */
+enum { MCQ_ALIGN_QUERY_LONG = 1u,        /* status: a mate has more than max_query bases                         */
+       MCQ_ALIGN_SUBJECT_LONG = 2u };    /* ... the subject has more than max_subject bases                      */
+typedef struct {
+    uint64_t sub_off;           /* first base of the subject in `subjects`                 */
+    uint32_t sub_len;
+    uint32_t on;                /* 0: no alignment for this query                          */
+} mcq_align_job;
+typedef struct {
+    int32_t score;              /* of mate 1's chosen alignment                            */
+    uint32_t length;            /* aligned length L: bytes of each string                  */
+    uint32_t reverse;           /* 1: the reverse complement of mate 1 was chosen          */
+    uint32_t status;            /* 0 or MCQ_ALIGN_* bits                                    */
+} mcq_alignment;
+int mcq_align(mcq_ws* ws, const mcq_batch* in, const char* subjects, const mcq_align_job* jobs,
+              uint32_t max_query, uint32_t max_subject, mcq_alignment* out,
+              char* out_query, char* out_subject, uint32_t text_cap, void* stream);
+
 /* ---- debug / parity taps ------------------------------------------------------------
  * Row 5 in isolation is mcq_count_windows + mcq_sketch above (the sketches of every window).
  * Rows 7-8 in isolation: the sorted match list of every query (what merge_sort returns,

@@ -14,6 +14,7 @@ _UNITS = {
     os.path.join(_CSRC, "mcq_stages.hip"): _INTERNAL,      # staged and routing entry points, batch preparation
     os.path.join(_CSRC, "mcq_shard.hip"): _INTERNAL,       # mcq_shard_*
     os.path.join(_CSRC, "mcq_target_hits.hip"): _INTERNAL, # per-target window hit lists (-hits-per-seq)
+    os.path.join(_CSRC, "mcq_align.hip"): _INTERNAL,       # read-to-candidate alignment (-align)
     os.path.join(_CSRC, "mcq_build.hip"): [_HDR],          # table construction (rocPRIM sorts)
     os.path.join(_CSRC, "mcq_classify.hip"): [os.path.join(_CSRC, "mcq_classify.hpp"), _HDR],   # classification + taxon counts
 }
@@ -79,7 +80,7 @@ def build_host(force=False, verbose=False):
     # what both programs depend on besides their own source: the two libraries and every header they include
     shared = [out, lib_path(), _HDR, hdr, os.path.join(os.path.dirname(_HERE), "include", "mcq_open.hpp")] + \
              [os.path.join(_HERE, "csrc", "host", h) for h in ("mcq_cli_common.hpp", "mcq_cli_buffers.hpp", "mcq_read_unit.hpp")]
-    cli_deps = shared + [cli_src, os.path.join(_HERE, "csrc", "host", "mcq_read_batches.hpp")]
+    cli_deps = shared + [cli_src] + [os.path.join(_HERE, "csrc", "host", h) for h in ("mcq_read_batches.hpp", "mcq_align_subjects.hpp")]
     if force or not os.path.exists(cli) or os.path.getmtime(cli) < max(os.path.getmtime(f) for f in cli_deps):
         hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
         cmd = [hipcc, "-std=c++14", "-O2", "-pthread", cli_src, "-o", cli, "-L" + _HERE, "-lmcq_hip", "-lmcq_host", "-Wl,-rpath,$ORIGIN"]

@@ -18,6 +18,10 @@
 //   * -hits-per-seq [FILE] (mcq_query_cli only)  show_matches_per_targets src/printing.cpp:437-469 (mcq_hits_table_text) after the
 //         mapping lines and in front of the abundance tables (src/classification.cpp:847-862), into the -out file or FILE; the
 //         query_id column of the TABLE_LAYOUT and of every mapping line, two parameter lines
+//   * -align (mcq_query_cli only)               show_alignment src/classification.cpp:437-477 behind the classification column of a
+//         classified read whose first candidate is a sequence (mcq_align on the GPU, mcq_align_subjects.hpp), one parameter line
+//         (src/printing.cpp:91-93); -align-candidate-range, written into no output, aligns against the candidate's real window range
+//         where the fold has zeroed it
 //   * the summary                              show_summary             src/printing.cpp:622-641,
 //                                              show_taxon_statistics    src/printing.cpp:522-600 (mcq_eval_stats_text)
 //   * -exclude RANK / -ground-truth / -precision (mcq_query_cli only; get_evaluation_options, src/query_options.cpp:190-213):
@@ -34,7 +38,7 @@
 //            [-maxcand N] [-hitmin N] [-hitdiff X] [-insertsize N] [-threads N] [-tophits] [-taxids] [-taxids-only] [-omit-ranks]
 //            [-lineage] [-mapped-only] [-nomap] [-noquirks] [-abundances [FILE]] [-abundance-per R] [-out FILE] [-batch N]
 //            [-batch-bases N] [-read-chunk BYTES] [-reader gpu|host] [-exclude RANK] [-ground-truth] [-precision] [-hits-per-seq [FILE]]
-//            [-help]
+//            [-align] [-align-candidate-range] [-help]
 // (inputs: every argument up to the first option; a directory stands for the files in it (files_in_directory below).  -pairseq
 //  without -pairfiles comes first: every file is interleaved pairs, also the two of `r1 r2` and the one of `r1 -`.  Without it,
 //  `r1 r2` alone is one pair of files in the given order and `r1 -` one single-end file.  Otherwise -pairfiles sorts the names and pairs
@@ -89,6 +93,8 @@ struct Options {
     std::string abundance_file;          // ... its FILE (cleared when it names the -out file: src/query_options.cpp:355)
     uint32_t abundance_rank = MCQ_RANK_NONE;   // -abundance-per R: the estimate to rank R (< root)
     bool tax_counts() const { return abundances || abundance_rank != MCQ_RANK_NONE; }
+    bool align = false;                  // -align: the alignment block behind the line of a read classified to a sequence
+    bool align_range = false;            // -align-candidate-range: align against the candidate's real window range, not the folded (0,0)
     bool hits_per_seq = false;           // -hits-per-seq [FILE]: the per-reference window hit lists, and the query_id column
     std::string hits_file;               // ... its FILE (cleared when it names the -out file: src/query_options.cpp:353)
     uint32_t exclude_rank = MCQ_RANK_NONE;     // -exclude R (< root): drop the hits on the read's own clade at R
@@ -181,6 +187,17 @@ static const char* const kQueryUsage =
     "                   front of every mapping line.  Rows in ascending target order.  Host memory grows with the input (one\n"
     "                   entry per read and candidate is kept until the end, as in the reference).  A read with more than %u\n"
     "                   distinct (sequence, window) pairs on its candidates ends the run with an ABORT line that names it.\n"
+    "alignment:\n"
+    "  -align           (mcq_query_cli only; mcq_query_mpi rejects it and names mcq_query_cli; aliases -alignment, -showalignment) with\n"
+    "                   -lowest sequence: behind the line of a read classified to a sequence, its semi-global alignment to the top\n"
+    "                   candidate's window range (score, source file and record, range, the two aligned strings), computed on the GPU.\n"
+    "                   A mate of more than 2048 bases or a window range of more than 4096 bases ends the run with an ABORT line\n"
+    "                   that names the read.  The genome files the database names are read once at the start, relative to the\n"
+    "                   working directory, and stay in host memory: it grows with the genomes.  A file that cannot be read is\n"
+    "                   reported once and its sequences get no alignment.  Above -lowest sequence only the parameter line is written.\n"
+    "  -align-candidate-range  (written into no output) with n_ranks > 1 the merged candidates carry no positions and -align aligns\n"
+    "                   to window 0 of the target, as the reference's MPI program does; this option aligns to the candidate's real\n"
+    "                   window range instead\n"
     "rejected:        -taxon-coverage (both programs): the coverage statistics are not reproduced\n";
 
 static bool parse_options(int argc, char** argv, Options& o) {
@@ -235,6 +252,8 @@ static bool parse_options(int argc, char** argv, Options& o) {
             o.hits_per_seq = true;
             if (i + 1 < argc && argv[i + 1][0] != '-') o.hits_file = argv[++i];
         }
+        else if (opt_named(a, {"-align", "-alignment", "-showalignment"})) o.align = true;                                      // src/query_options.cpp:329-331
+        else if (a == "-align-candidate-range") o.align_range = true;
         else if (a == "-exclude") { const uint32_t r = mcq_rank_from_name(next()); if (r < MCQ_RANK_ROOT) o.exclude_rank = r; }   // src/query_options.cpp:205-210
         else if (opt_named(a, {"-ground-truth", "-ground_truth", "-groundtruth"})) o.ground_truth = true;                       // :196-198
         else if (a == "-precision") o.precision = true;                                                                         // :203
@@ -314,6 +333,7 @@ static void write_head(std::ostream& os, const Out& o, uint32_t hitmin) {
                                         << cm << "  Max insert size considered " << p.insertsize << ".\n";
     else if (p.pairing == Options::SEQUENCES) os << cm << "Per file paired-end mode:\n" << cm << "  Reads from two consecutive sequences in each file will be paired up.\n"
                                                  << cm << "  Max insert size considered " << p.insertsize << ".\n";
+    if (p.align) os << cm << "Query sequences will be aligned to best candidate target => SLOW!\n";   // src/printing.cpp:91-93
     if (p.hits_per_seq)                                                     // (both lines hang on -hits-per-seq in the reference: the second one is its quirk, :95-103)
         os << cm << "A list of hits per reference sequence will be generated after the read mapping.\n"
            << cm << "A list of absolute and relative abundances per taxon will be generated after the read mapping.\n";
@@ -374,9 +394,16 @@ static std::vector<Options> output_runs(const Options& p) {
 // src/classification_statistics.h:69-78) and its mapping line (show_query_mapping, src/classification.cpp:583-632)
 // (token: the header up to its first ' ', what the line prints; truth: the read's ground truth or MCQ_NO_TAXON, for the truth_
 //  column and, with `ev`, evaluate_classification's assign_known_correct, src/classification.cpp:329-353)
+// -align: what show_alignment (src/classification.cpp:437-477) prints of a read, or nothing (length 0)
+struct AlignBlock {
+    int32_t score = 0; uint32_t length = 0;              // length: of the two aligned strings; 0 = no block
+    const char* file = ""; uint64_t index = 0;           // the target's source
+    uint64_t range_beg = 0, range_end = 0;               // w * beg, w * end + w
+    const char* query = nullptr; const char* target = nullptr;
+};
 static void write_query(std::ostream& os, const Out& o, uint32_t hitmin, const char* token, size_t token_len,
                         const mcq_cand* cands, uint32_t ncand, uint64_t* assigned /* [MCQ_RANK_NONE + 1] */,
-                        uint32_t truth = MCQ_NO_TAXON, mcq_eval_stats* ev = nullptr, uint64_t query_id = 0) {
+                        uint32_t truth = MCQ_NO_TAXON, mcq_eval_stats* ev = nullptr, uint64_t query_id = 0, const AlignBlock* al = nullptr) {
     mcq_refdb* rdb = o.db; const Options& p = o.p;
     const uint32_t best = mcq_refdb_classify(rdb, reinterpret_cast<const uint32_t*>(cands), ncand, hitmin, p.hitdiff, p.highest);
     if (best == MCQ_NO_TAXON) ++assigned[MCQ_RANK_NONE];
@@ -402,6 +429,12 @@ static void write_query(std::ostream& os, const Out& o, uint32_t hitmin, const c
         os << o.col;
     }
     o.best(os, best);
+    if (al && al->length && best != MCQ_NO_TAXON) {                          // opt.showAlignment && cls.best, src/classification.cpp:627-629
+        os << '\n' << o.comment << "  score  " << al->score << "  aligned to " << al->file << " #" << al->index
+           << " in range [" << al->range_beg << ',' << al->range_end << "]\n" << o.comment << "  query  ";
+        os.write(al->query, al->length) << '\n' << o.comment << "  target ";
+        os.write(al->target, al->length);
+    }
     os << '\n';
 }
 static void write_query(std::ostream& os, const Out& o, uint32_t hitmin, const std::string& header,

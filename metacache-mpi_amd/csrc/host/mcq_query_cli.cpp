@@ -17,8 +17,17 @@
 // width of the count rows is the range width of the batch's longest query, so the batch's offsets are looked at on the host first
 // (Run::stage_hits).  The writer threads feed one accumulator each (mcq_hits_table_*), merged and written after the last
 // mapping line; host memory grows with the input, as the reference's does.  A read beyond the kernel's capacity ends the run.
+//
+// -align (with -lowest sequence; above it only the parameter line is written and nothing of this runs): the genome files the
+// database names are read once at the start (mcq_align_subjects.hpp).  Behind a batch's query, on the same stream, the host waits
+// for the batch's candidates, builds one job per read that is classified, whose first candidate is a sequence and whose target's
+// bases are known -- the slice comes from that candidate's window range, which after a fold (n_ranks > 1) is (0,0) as in the
+// reference's MPI program; -align-candidate-range first asks mcq_target_slots / mcq_target_hits (one slot) for the real range --,
+// gathers the slices into a pinned buffer, copies them in, calls mcq_align and copies the results back (Run::stage_align).  This
+// host round trip between the query and the alignment is paid by -align alone.  A read beyond the kernel's capacities ends the run.
 #include "mcq_cli_common.hpp"
 #include "mcq_read_batches.hpp"
+#include "mcq_align_subjects.hpp"
 
 #include <array>
 #include <sstream>
@@ -34,6 +43,7 @@ struct Slot : ReadSlot {
     DeviceBuf<uint32_t> d_tgt, d_cnt, d_hst; DeviceBuf<mcq_target_range> d_rng;
     PinnedBuf<uint32_t> cnt, hst; PinnedBuf<mcq_target_range> rng; PinnedBuf<uint64_t> seq_off;
     uint32_t range_cap = 0; bool hits = false;
+    AlignSlot al;                                                                        // -align
     uint64_t first_id = 0;                                                               // query id of the batch's first query
 };
 constexpr int NS = 3;
@@ -55,6 +65,7 @@ struct Run {
     uint64_t next_id = 1;                                        // query ids: the 1-based running number of the read (pair) over all units of this output
     std::vector<mcq_hits_table*> hit_acc;                        // -hits-per-seq: one accumulator per writer thread
     DeviceBuf<uint32_t> d_tax2tgt; uint32_t n_taxa = 0, n_slots = 0;
+    AlignSubjects subjects;                                      // -align: the sequences the database names, in host memory
 
     Run(const Options& p_, const Database& db_) : p(p_), db(db_), o(make_out(db_.rdb, p_)), co(classify_opts(p_, db_.hitmin)) { std::memset(&eval, 0, sizeof(eval)); }
     ~Run() { if (pending.valid()) pending.wait(); mcq_ws_destroy(ws); mcq_taxonomy_destroy(tx); for (mcq_hits_table* t : hit_acc) mcq_hits_table_free(t); }
@@ -73,7 +84,8 @@ struct Run {
             hit_acc.assign(std::max(1u, p.threads), nullptr);
             for (mcq_hits_table*& t : hit_acc) if (mcq_hits_table_create(&t)) return false;
         }
-        if (hits_on()) {                                         // candidates above sequence level are skipped: no kernel, no rows
+        if (align_on() && !subjects.load(db.rdb)) return false;
+        if (hits_on() || (align_on() && p.align_range && p.P > 1)) {   // candidates above sequence level are skipped: no kernel, no rows
             mcq_refdb_info rinfo; mcq_refdb_get_info(db.rdb, &rinfo);
             std::vector<uint32_t> t2g(rinfo.n_taxa);
             if (mcq_refdb_tax2tgt(db.rdb, t2g.data())) { std::fprintf(stderr, "ABORT: %s\n", mcq_host_last_error()); return false; }
@@ -90,6 +102,94 @@ struct Run {
 
     bool excluding() const { return p.exclude_rank != MCQ_RANK_NONE; }
     bool hits_on() const { return p.hits_per_seq && p.lowest == MCQ_RANK_SEQUENCE; }
+    bool align_on() const { return p.align && !p.nomap && p.lowest == MCQ_RANK_SEQUENCE; }   // (no mapping lines, no blocks: nothing is aligned)
+    // -align: behind the batch's query and the copies of its candidates on s_k.  The host waits for the candidates, makes the jobs,
+    // gathers their subjects, and enqueues the copies in, mcq_align and the copies out on s_k (`st` has prepared the batch).
+    bool stage_align(Slot& S, const mcq_batch& in, const mcq_result& res, hipStream_t st) {
+        AlignSlot& A = S.al;
+        const uint64_t n = S.n, ns = in.n_seqs;
+        A.on = false;
+        MCQ_HIP(hipStreamSynchronize(s_k), return false);       // the candidates are on the host
+        const uint64_t* off = S.h_seq_off.data();
+        if (!S.host_parsed) {
+            if (!S.seq_off.grow(ns + 1)) return false;
+            MCQ_HIP(hipMemcpyAsync(S.seq_off.p, S.d_seq_off.p, (ns + 1) * 8, hipMemcpyDeviceToHost, st), return false);
+            MCQ_HIP(hipStreamSynchronize(st), return false);
+            off = S.seq_off.p;
+        }
+        uint64_t longest_mate = 0, longest_query = 0;
+        const uint64_t m = in.paired ? 2 : 1;
+        for (uint64_t s = 0; s < ns; ++s) longest_mate = std::max(longest_mate, off[s + 1] - off[s]);
+        for (uint64_t q = 0; q < n; ++q) longest_query = std::max(longest_query, off[m * q + m] - off[m * q]);
+        if (!A.jobs.grow(n) || !A.d_jobs.grow(n) || !A.res.grow(n) || !A.d_res.grow(n)) return false;
+        A.beg.assign(n, 0); A.end.assign(n, 0);
+        // who is aligned, and to which windows
+        std::vector<uint32_t> tgt(n, MCQ_NO_TAXON);
+        uint64_t n_on = 0;
+        for (uint64_t q = 0; q < n; ++q) {
+            const mcq_cand* c = &S.cands.p[q * p.maxcand];
+            const uint32_t nc = S.ncand.p[q];
+            if (nc == 0 || mcq_refdb_classify(db.rdb, reinterpret_cast<const uint32_t*>(c), nc, db.hitmin, p.hitdiff, p.highest) == MCQ_NO_TAXON) continue;
+            if (mcq_refdb_taxon_rank(db.rdb, c[0].tax) != MCQ_RANK_SEQUENCE) continue;
+            tgt[q] = subjects.target_of(c[0].tax);
+            if (tgt[q] == MCQ_NO_TAXON) continue;
+            A.beg[q] = c[0].win_beg; A.end[q] = c[0].win_end;
+            ++n_on;
+        }
+        if (n_on == 0) return true;
+        if (p.align_range && p.P > 1) {                         // the fold has zeroed the positions: the top target's range once more
+            const uint32_t cap = mcq_target_hits_range_cap(db.edb, longest_query, p.insertsize);
+            if (!A.d_tgt.grow(n) || !A.d_rng.grow(n) || !A.rng.grow(n) || !A.d_cnt.grow(n * cap) || !A.d_hst.grow(n) || !A.hst.grow(n)) return false;
+            if (mcq_target_slots(&res, n, p.maxcand, db.hitmin, d_tax2tgt.p, n_taxa, A.d_tgt.p, 1, s_k) ||
+                mcq_target_hits(db.edb, ws, &in, A.d_tgt.p, 1, p.insertsize, cap, A.d_rng.p, A.d_cnt.p, A.d_hst.p, s_k)) {
+                std::fprintf(stderr, "FAIL: %s\n", mcq_last_error()); return false;
+            }
+            MCQ_HIP(hipMemcpyAsync(A.rng.p, A.d_rng.p, n * sizeof(mcq_target_range), hipMemcpyDeviceToHost, s_k), return false);
+            MCQ_HIP(hipMemcpyAsync(A.hst.p, A.d_hst.p, n * 4, hipMemcpyDeviceToHost, s_k), return false);
+            MCQ_HIP(hipStreamSynchronize(s_k), return false);
+            for (uint64_t q = 0; q < n; ++q) {
+                if (tgt[q] == MCQ_NO_TAXON) continue;
+                if (A.hst.p[q]) {
+                    std::fprintf(stderr, "ABORT: -align-candidate-range: read %llu is beyond what mcq_target_hits takes\n", (unsigned long long)(S.first_id + q));
+                    return false;
+                }
+                const mcq_target_range& r = A.rng.p[q];
+                if (r.tgt == tgt[q] && r.n_win) { A.beg[q] = r.win_beg; A.end[q] = r.win_beg + r.n_win - 1; }
+            }
+        }
+        uint64_t total = 0, longest_sub = 0;
+        for (uint64_t q = 0; q < n; ++q) {
+            mcq_align_job& j = A.jobs.p[q];
+            j.sub_off = total; j.sub_len = 0; j.on = 0;
+            if (tgt[q] == MCQ_NO_TAXON) continue;
+            uint64_t o, l;
+            subjects.slice(tgt[q], A.beg[q], A.end[q], o, l);
+            j.on = 1; j.sub_len = (uint32_t)std::min<uint64_t>(l, 0xFFFFFFFFu);
+            if (l <= MCQ_ALIGN_MAX_SUBJECT) { total += l; longest_sub = std::max(longest_sub, l); }     // (a longer one is reported by the kernel and never read)
+        }
+        if (!A.sub.grow(total + 1) || !A.d_sub.grow(total + 1)) return false;
+        for (uint64_t q = 0; q < n; ++q) {
+            const mcq_align_job& j = A.jobs.p[q];
+            if (!j.on || j.sub_len > MCQ_ALIGN_MAX_SUBJECT) continue;
+            uint64_t o, l;
+            subjects.slice(tgt[q], A.beg[q], A.end[q], o, l);
+            std::memcpy(A.sub.p + j.sub_off, subjects.bases.data() + o, l);
+        }
+        const uint32_t max_query = (uint32_t)std::min<uint64_t>(longest_mate, MCQ_ALIGN_MAX_QUERY), max_subject = (uint32_t)longest_sub;
+        A.text_cap = std::max(1u, max_query + max_subject);
+        const uint64_t text = n * (uint64_t)A.text_cap;
+        if (!A.text_q.grow(text) || !A.text_s.grow(text) || !A.d_text_q.grow(text) || !A.d_text_s.grow(text)) return false;
+        MCQ_HIP(hipMemcpyAsync(A.d_sub.p, A.sub.p, total, hipMemcpyHostToDevice, s_k), return false);
+        MCQ_HIP(hipMemcpyAsync(A.d_jobs.p, A.jobs.p, n * sizeof(mcq_align_job), hipMemcpyHostToDevice, s_k), return false);
+        if (mcq_align(ws, &in, A.d_sub.p, A.d_jobs.p, max_query, max_subject, A.d_res.p, A.d_text_q.p, A.d_text_s.p, A.text_cap, s_k)) {
+            std::fprintf(stderr, "FAIL: %s\n", mcq_last_error()); return false;
+        }
+        MCQ_HIP(hipMemcpyAsync(A.res.p, A.d_res.p, n * sizeof(mcq_alignment), hipMemcpyDeviceToHost, s_k), return false);
+        MCQ_HIP(hipMemcpyAsync(A.text_q.p, A.d_text_q.p, text, hipMemcpyDeviceToHost, s_k), return false);
+        MCQ_HIP(hipMemcpyAsync(A.text_s.p, A.d_text_s.p, text, hipMemcpyDeviceToHost, s_k), return false);
+        A.on = true;
+        return true;
+    }
     // -hits-per-seq: behind the batch's query on s_k, its slot targets, their ranges and window counts, and the copies out.  The count
     // rows are as wide as the range of the batch's longest query: its offsets come to the host first (`st` has prepared the batch).
     bool stage_hits(Slot& S, const mcq_batch& in, const mcq_result& res, hipStream_t st) {
@@ -168,6 +268,13 @@ struct Run {
                                                              : "is beyond what mcq_target_hits takes (range width, window ids of 2^28 and more, 2^31 bases)");
             return false;
         }
+        if (S.al.on) for (uint64_t q = 0; q < n; ++q) if (S.al.res.p[q].status) {   // beyond mcq_align's capacity: reported, never dropped in silence
+            std::fprintf(stderr, "ABORT: -align: read %llu (%.*s) %s\n", (unsigned long long)(S.first_id + q),
+                         (int)(S.hdr.p[2 * q + 1] - S.hdr.p[2 * q]), S.text[0].p + S.hdr.p[2 * q],
+                         (S.al.res.p[q].status & MCQ_ALIGN_QUERY_LONG) ? ("has a mate of more than " + std::to_string(MCQ_ALIGN_MAX_QUERY) + " (MCQ_ALIGN_MAX_QUERY) bases").c_str()
+                                                                      : ("has a candidate window range of more than " + std::to_string(MCQ_ALIGN_MAX_SUBJECT) + " (MCQ_ALIGN_MAX_SUBJECT) bases").c_str());
+            return false;
+        }
         const unsigned T = (unsigned)std::min<uint64_t>(std::max(1u, p.threads), std::max<uint64_t>(1, n / 64));
         std::vector<std::string> out(T);
         std::vector<std::array<uint64_t, MCQ_RANK_NONE + 1>> asg(T);
@@ -179,8 +286,19 @@ struct Run {
             std::memset(&evs[t], 0, sizeof(evs[t]));
             for (uint64_t q = n * t / T; q < n * (t + 1) / T; ++q) {
                 const uint32_t truth = !p.wants_truth() ? MCQ_NO_TAXON : (excluding() ? S.truth[q] : truth_of(S, q));
+                AlignBlock ab;
+                if (S.al.on && S.al.res.p[q].length) {
+                    const mcq_alignment& r = S.al.res.p[q];
+                    const uint32_t key = S.cands.p[q * p.maxcand].tax;
+                    const uint64_t w = subjects.winstride;
+                    ab.score = r.score; ab.length = r.length;
+                    ab.file = mcq_refdb_taxon_file(db.rdb, key); ab.index = mcq_refdb_taxon_index(db.rdb, key);
+                    ab.range_beg = w * S.al.beg[q]; ab.range_end = w * S.al.end[q] + w;
+                    ab.query = S.al.text_q.p + q * (uint64_t)S.al.text_cap; ab.target = S.al.text_s.p + q * (uint64_t)S.al.text_cap;
+                }
                 write_query(ss, o, db.hitmin, S.text[0].p + S.hdr.p[2 * q], (size_t)(S.hdr.p[2 * q + 1] - S.hdr.p[2 * q]),
-                            &S.cands.p[q * p.maxcand], S.ncand.p[q], asg[t].data(), truth, p.precision ? &evs[t] : nullptr, S.first_id + q);
+                            &S.cands.p[q * p.maxcand], S.ncand.p[q], asg[t].data(), truth, p.precision ? &evs[t] : nullptr, S.first_id + q,
+                            ab.length ? &ab : nullptr);
                 if (S.hits) for (uint32_t s = 0; s < n_slots; ++s) {        // matches_per_target::insert of this read's candidates
                     const mcq_target_range& r = S.rng.p[q * n_slots + s];
                     if (r.tgt != MCQ_TARGET_UNUSED && r.n_win &&
@@ -281,6 +399,8 @@ static int run_queries(const Options& p, const Database& db) {
         MCQ_HIP(hipMemcpyAsync(S.ncand.p, S.d_ncand.p, n * 4, hipMemcpyDeviceToHost, run.s_k), return 1);
         if (!S.host_parsed && !run.excluding()) MCQ_HIP(hipMemcpyAsync(S.hdr.p, S.d_hdr.p, 2 * n * 8, hipMemcpyDeviceToHost, run.s_k), return 1);
         if (S.hits && !run.stage_hits(S, in, res, reads.stream())) return 1;
+        S.al.on = false;
+        if (run.align_on() && !run.stage_align(S, in, res, reads.stream())) return 1;
         MCQ_HIP(hipEventRecord(S.done, run.s_k), return 1);
         ++run.issued;
     }

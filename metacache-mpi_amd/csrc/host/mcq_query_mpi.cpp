@@ -23,6 +23,7 @@
 //
 // usage: mpiexec -n N mcq_query_mpi <dbprefix> <P> <file|directory>... [options of mcq_query_cli] [-transport rccl|mpi]
 //                                   [-batch N] [-batch-bases N]
+// -align (and its aliases) is rejected the same way.
 // -exclude, -ground-truth and -precision are rejected with a line that names mcq_query_cli: the sharded kernels have no exclusion.
 // -hits-per-seq is rejected the same way: mcq_target_hits is a kernel of the one-GPU path.
 #include <mpi.h>
@@ -119,6 +120,10 @@ int main(int argc, char** argv) {
     }
     if (p.hits_per_seq) {                                                   // (before any GPU work)
         if (rank == 0) std::fprintf(stderr, "ABORT: -hits-per-seq is an option of mcq_query_cli; mcq_query_mpi keeps no window hit lists (the sharded path has none)\n");
+        MPI_Finalize(); return 2;
+    }
+    if (p.align || p.align_range) {                                         // (before any GPU work)
+        if (rank == 0) std::fprintf(stderr, "ABORT: -align is an option of mcq_query_cli; mcq_query_mpi aligns no reads (its ranks hold neither the candidates' positions nor the genomes)\n");
         MPI_Finalize(); return 2;
     }
     int n_dev = 0;

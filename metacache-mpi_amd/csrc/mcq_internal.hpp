@@ -3,7 +3,7 @@
 // C ABI, the owners of their GPU resources, error reporting, a few inline helpers, and the declarations of the functions that
 // cross a unit boundary (hidden visibility: none is part of the ABI).  The units: mcq_engine.hip (workspace, fused query, reduce),
 // mcq_table.hip (mcq_db_*), mcq_stages.hip (staged and routing entry points, batch preparation), mcq_shard.hip (mcq_shard_*),
-// mcq_target_hits.hip (mcq_target_*).  Kernels are not declared here: each is defined in the unit that launches it.
+// mcq_target_hits.hip (mcq_target_*), mcq_align.hip (mcq_align).  Kernels are not declared here: each is defined in the unit that launches it.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <stdio.h>
@@ -146,6 +146,7 @@ struct mcq_ws {
     const u32* qc_dev = nullptr; std::vector<u32> qc_host; u64 qc_n = 0; int qc_kind = 0;    // qc_kind: 0 nothing handed over, 1 device pointer, 2 host copy
     Staging staging[3];       // [0], [1]: the pipeline's; [2]: mcq_query's and mcq_debug_matches'
     // device and pinned memory, declared in the reverse of the order it is given back in
+    Dev<unsigned short> align_scratch; u64 align_scratch_words = 0;   // mcq_align: predecessor matrices too large for LDS; made once, divided among a call's waves
     Dev<u32> excl_tgt;
     Dev<unsigned long long> cls_counts;
     ScratchDev sc = {};       // the five arrays below as the workgroup kernels take them

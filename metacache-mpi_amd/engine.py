@@ -33,6 +33,11 @@ MCQ_TARGET_HITS_MAX_SLOTS = 16   # mcq_target_hits: slot targets per query
 MCQ_TARGET_HITS_MAX_KEYS = 1024  # ... distinct (target, window) pairs of one query over all its slot targets
 MCQ_TARGET_UNUSED = 0xFFFFFFFF   # ... an unused slot
 MCQ_TARGET_HITS_RANGE, MCQ_TARGET_HITS_KEYS, MCQ_TARGET_HITS_WINDOW = 1, 2, 4    # ... status bits of a query beyond a capacity
+MCQ_ALIGN_MAX_QUERY = 2048       # mcq_align: bases of one mate
+MCQ_ALIGN_MAX_SUBJECT = 4096     # ... bases of one subject
+MCQ_ALIGN_QUERY_LONG, MCQ_ALIGN_SUBJECT_LONG = 1, 2    # ... status bits of a query beyond a capacity
+ALIGN_JOB = np.dtype([("sub_off", "<u8"), ("sub_len", "<u4"), ("on", "<u4")])     # mcq_align_job
+ALIGNMENT = np.dtype([("score", "<i4"), ("length", "<u4"), ("reverse", "<u4"), ("status", "<u4")])   # mcq_alignment
 
 MCQ_OK, MCQ_E_ARG, MCQ_E_HIP, MCQ_E_CAPACITY, MCQ_E_UNSUPPORTED = 0, -1, -2, -3, -4
 
@@ -190,6 +195,9 @@ def lib():
                                           C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
             L.mcq_target_slots.argtypes = [C.POINTER(Result), C.c_uint64, C.c_uint32, C.c_uint32, C.c_void_p, C.c_uint32, C.c_void_p,
                                            C.c_uint32, C.c_void_p]
+        if hasattr(L, "mcq_align"):
+            L.mcq_align.argtypes = [C.c_void_p, C.POINTER(Batch), C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p,
+                                    C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p]
         L.mcq_shard_create.argtypes = [C.c_void_p, C.POINTER(ShardCfg), C.POINTER(C.c_void_p)]
         L.mcq_shard_destroy.argtypes = [C.c_void_p]
         L.mcq_shard_unique_id.argtypes = [C.c_void_p]
@@ -475,6 +483,66 @@ class Workspace:
         if sync:
             self.sync(st)
         return out
+
+    # ---- read-to-candidate alignment (mcq_align): what -align prints
+    def align_device(self, bases_ptr, seq_off_ptr, n_seqs, paired, subjects_ptr, jobs_ptr, max_query, max_subject, out_ptr,
+                     out_query_ptr, out_subject_ptr, text_cap, stream=None, ranges=False, packed_bases=0):
+        """device pointers, enqueue only: jobs mcq_align_job [nq] (ALIGN_JOB) -> out mcq_alignment [nq] (ALIGNMENT) and the two aligned
+        strings of query q at out_query / out_subject + q * text_cap.  A query beyond a capacity gets a status bit and length 0."""
+        b = Batch(n_seqs, bases_ptr, seq_off_ptr, 1 if paired else 0,
+                  MCQ_DEVICE_PTRS | (MCQ_BATCH_RANGES if ranges else 0) | (MCQ_BATCH_PACKED if packed_bases else 0), packed_bases)
+        _chk(lib().mcq_align(self.h, C.byref(b), subjects_ptr, jobs_ptr, max_query, max_subject, out_ptr, out_query_ptr,
+                             out_subject_ptr, text_cap, stream))
+
+    def align(self, bases, seq_off, paired, subjects, jobs, max_query=None, max_subject=None, text_cap=None, ranges=False,
+              packed=False, fill=0x2E):
+        """numpy in, numpy out (the copies go through torch; waits for the device).  bases / subjects: bytes or u8 arrays; jobs: rows
+        of (sub_off, sub_len, on).  max_query / max_subject None: what the longest mate / subject of the batch needs, within the
+        kernel's capacities; text_cap None: their sum.  Returns a dict: score i32 [nq], reverse u32 [nq], status u32 [nq], length
+        u32 [nq], query / subject: the aligned strings (bytes) per query, text_query / text_subject: the raw u8 [nq, text_cap]
+        buffers, which held `fill` before the call.  Every output has 64 guard bytes behind it; a changed one raises."""
+        import torch
+        dev = torch.device("cuda", self.db.device)
+        seq_off = np.ascontiguousarray(seq_off, np.uint64)
+        n_seqs = len(seq_off) // 2 if ranges else len(seq_off) - 1
+        nq = n_seqs // 2 if paired else n_seqs
+        j = np.zeros(max(nq, 1), ALIGN_JOB)
+        for i, (o, n, on) in enumerate(jobs):
+            j[i] = (o, n, on)
+        lens = (seq_off[1::2].astype(np.int64) - seq_off[0::2].astype(np.int64)) if ranges else np.diff(seq_off.astype(np.int64))
+        if max_query is None:
+            max_query = min(int(lens.max()) if len(lens) else 0, MCQ_ALIGN_MAX_QUERY)
+        if max_subject is None:
+            max_subject = min(int(j["sub_len"][:nq].max()) if nq else 0, MCQ_ALIGN_MAX_SUBJECT)
+        if text_cap is None:
+            text_cap = max(1, max_query + max_subject)
+
+        def u8(x):
+            return (np.frombuffer(x, dtype=np.uint8) if not isinstance(x, np.ndarray) else x.view(np.uint8))
+        d_bases = torch.from_numpy(np.concatenate([u8(bases), np.zeros(8, np.uint8)])).to(dev)
+        d_sub = torch.from_numpy(np.concatenate([u8(subjects), np.zeros(8, np.uint8)])).to(dev)
+        d_off = torch.from_numpy(seq_off.view(np.int64)).to(dev) if len(seq_off) else torch.zeros(1, dtype=torch.int64, device=dev)
+        d_jobs = torch.from_numpy(j.view(np.uint8)).to(dev)
+        G, guard = 64, 0xA5
+        h_out = np.full(max(nq, 1) * ALIGNMENT.itemsize + G, guard, np.uint8)
+        h_q = np.full(nq * text_cap + G, fill, np.uint8); h_q[nq * text_cap:] = guard
+        h_s = h_q.copy()
+        d_out, d_q, d_s = (torch.from_numpy(h).to(dev) for h in (h_out, h_q, h_s))
+        st = torch.cuda.current_stream(dev).cuda_stream
+        self.align_device(d_bases.data_ptr(), d_off.data_ptr(), n_seqs, paired, d_sub.data_ptr(), d_jobs.data_ptr(), max_query,
+                          max_subject, d_out.data_ptr(), d_q.data_ptr(), d_s.data_ptr(), text_cap, stream=st, ranges=ranges,
+                          packed_bases=int(seq_off[-1]) if packed else 0)
+        torch.cuda.synchronize(dev)
+        g_out, g_q, g_s = (d.cpu().numpy() for d in (d_out, d_q, d_s))
+        for g, n in ((g_out, nq * ALIGNMENT.itemsize), (g_q, nq * text_cap), (g_s, nq * text_cap)):
+            if not (g[n:n + G] == guard).all() or (nq == 0 and not (g[:G] == guard).all()):
+                raise AssertionError("mcq_align wrote behind an output")
+        res = g_out[:nq * ALIGNMENT.itemsize].view(ALIGNMENT)
+        tq, ts = g_q[:nq * text_cap].reshape(nq, text_cap), g_s[:nq * text_cap].reshape(nq, text_cap)
+        return {"score": res["score"].copy(), "reverse": res["reverse"].copy(), "status": res["status"].copy(),
+                "length": res["length"].copy(), "text_query": tq, "text_subject": ts,
+                "query": [tq[q, :res["length"][q]].tobytes() for q in range(nq)],
+                "subject": [ts[q, :res["length"][q]].tobytes() for q in range(nq)]}
 
     def timing(self, enable):
         _chk(lib().mcq_ws_timing(self.h, 1 if enable else 0))
