@@ -160,6 +160,14 @@ __device__ __forceinline__ void seq_bounds(const u64* seq_off, u32 ranges, u64 a
     if (ranges) { beg = seq_off[2 * a]; end = seq_off[2 * a + 1]; }
     else { beg = seq_off[a]; end = seq_off[a + 1]; }
 }
+// the same for a wave-uniform a, as scalar loads (the offsets are the batch's input: written before the launch, never by a kernel of
+// the query path, which is what lets them come through the constant cache).  One s_load_dwordx4 where the vector form takes a load,
+// a wait for every outstanding vector load and four v_readfirstlane.
+__device__ __forceinline__ void seq_bounds_uniform(const u64* seq_off, u32 ranges, u64 a, u64& beg, u64& end) {
+    typedef const u64 __attribute__((address_space(4))) * ConstU64;
+    const ConstU64 p = (ConstU64)(uintptr_t)seq_off + (ranges ? 2 * a : a);
+    beg = p[0]; end = p[1];
+}
 
 struct OptDev {
     u32 max_cand;            // M
@@ -447,12 +455,15 @@ struct BatchRt {
     __device__ __forceinline__ explicit BatchRt(const BatchDev& x) : b(x) {}
     __device__ __forceinline__ bool paired() const { return b.paired != 0; }
     __device__ __forceinline__ bool packed() const { return b.packed != 0; }
+    __device__ __forceinline__ static void seq_bounds(const u64* seq_off, u32 ranges, u64 a, u64& beg, u64& end) { mcq::seq_bounds(seq_off, ranges, a, beg, end); }
 };
 template <bool PAIRED, bool PACKED>
 struct BatchForm {
     __device__ __forceinline__ explicit BatchForm(const BatchDev&) {}
     __device__ __forceinline__ static constexpr bool paired() { return PAIRED; }
     __device__ __forceinline__ static constexpr bool packed() { return PACKED; }
+    // (the lean form asks per wave, never per lane: read_geom's q is wave-uniform there)
+    __device__ __forceinline__ static void seq_bounds(const u64* seq_off, u32 ranges, u64 a, u64& beg, u64& end) { seq_bounds_uniform(seq_off, ranges, a, beg, end); }
 };
 
 // ------------------------------------------------------------------ wave primitives
@@ -916,7 +927,7 @@ __device__ __forceinline__ u32 sketch_sorted_prefix(const u32* tmp, u32 cnt, u32
 // path: 0 = the one-sort pass, 1 = A through the 64-lane sort, 2 = A by the exact selection (for the test program; dead otherwise)
 // REMAT: the shifts and shuffle addresses that depend on the lane alone are computed per call instead of living in registers
 // across the caller's loop (a dozen VGPRs; for a kernel that has none to spare)
-template <u32 E = MCQ_SKETCH_EXPECT_FUSED, bool REMAT = false>
+template <u32 E = MCQ_SKETCH_EXPECT_FUSED, bool REMAT = false, bool REMAT_MASKS = false>
 __device__ __forceinline__ u32 wave_sketch_two_windows(const char* __restrict__ seq, u32 n, u32 lane, u32* tmp, u32* dst, u32& path) {
     if constexpr (REMAT) asm volatile("" : "+v"(lane));
     constexpr u32 K = MCQ_GEOM_DEFAULT_K, S = MCQ_GEOM_DEFAULT_S, W = MCQ_GEOM_DEFAULT_WINLEN, ST = MCQ_GEOM_DEFAULT_STRIDE;
@@ -949,7 +960,11 @@ __device__ __forceinline__ u32 wave_sketch_two_windows(const char* __restrict__ 
         const bool ok = (i == 0 || pos + K <= n) && (amb32 >> (32 - K)) == 0;
         h[i] = ok ? tmh(canonical(kmer, K)) : MCQ_EMPTY;
     }
-    const bool b1 = lane >= ST - 64;                                  // slot 1 from position 113 on belongs to B
+    // REMAT_MASKS: the lane predicates of the selection are computed here, per call, from a lane the compiler cannot see through --
+    // hoisted out of the caller's loop they are scalar pairs that get spilled, and a restore is two v_readlane where this is one v_cmp
+    u32 ln = lane;
+    if constexpr (REMAT_MASKS) asm volatile("" : "+v"(ln));
+    const bool b1 = ln >= ST - 64;                                    // slot 1 from position 113 on belongs to B
     const u32 ha0 = h[0], ha1 = b1 ? MCQ_EMPTY : h[1], hb = b1 ? h[1] : h[2];
     // ---- select both windows together
     const u32 cA = (u32)__builtin_popcountll(__ballot(ha0 != MCQ_EMPTY)) + (u32)__builtin_popcountll(__ballot(ha1 != MCQ_EMPTY));
@@ -966,12 +981,12 @@ __device__ __forceinline__ u32 wave_sketch_two_windows(const char* __restrict__ 
         if (s1) tmp[n0 + lane_rank(m1)] = ha1;
         if (sb) tmp[32 + lane_rank(mb)] = hb;
         wave_sync();
-        const bool hi = lane >= 32;
+        const bool hi = ln >= 32;
         u32 v = lane < (hi ? 32 + cntB : cntA) ? tmp[lane] : MCQ_EMPTY;
         v = wave_sort_blocks32_1(v);
         asm("s_nop 1" : "+v"(v));                 // v was written inside an asm block: 2 wait states before a DPP read
         const u32 prev = (u32)__builtin_amdgcn_update_dpp(0, (int)v, 0x138, 0xF, 0xF, false);    // wave_shr:1
-        const bool keep = (v != MCQ_EMPTY) && ((lane & 31) == 0 || v != prev);
+        const bool keep = (v != MCQ_EMPTY) && ((ln & 31) == 0 || v != prev);
         const u64 km = __ballot(keep);
         const u32 DA = (u32)__builtin_popcount((u32)km), DB = (u32)__builtin_popcount((u32)(km >> 32));
         if (all_in || DA >= S) {

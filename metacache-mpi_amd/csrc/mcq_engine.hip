@@ -243,11 +243,15 @@ __device__ __forceinline__ u32 dedup_count(const u32* tabkey, const u32* tabcnt,
 
 // Insertion half (depends on the number of registers E): counts the keys in the table and leaves the distinct
 // ones in the compaction list; returns their number D.
-template <int E>
+// LIT (the lean first wave stage): the empty quad of the table clear comes from a literal too, like the zero quad below -- else the
+// constant lives in a scalar register across the caller's per-read loop, which has none to spare
+template <int E, bool LIT = false>
 __device__ __forceinline__ u32 dedup_insert(const u32 (&r)[E], u32* buf, u32* hits, u32 T, u32 lane) {
     u32* tabkey = buf; u32* tabcnt = hits; u32* list = hits + 256;
-    reinterpret_cast<uint4*>(tabkey)[lane] = make_uint4(MCQ_EMPTY, MCQ_EMPTY, MCQ_EMPTY, MCQ_EMPTY);
-    reinterpret_cast<uint4*>(tabkey)[64 + lane] = make_uint4(MCQ_EMPTY, MCQ_EMPTY, MCQ_EMPTY, MCQ_EMPTY);
+    u32 empty = MCQ_EMPTY;
+    if constexpr (LIT) asm volatile("v_mov_b32 %0, -1" : "=v"(empty));
+    reinterpret_cast<uint4*>(tabkey)[lane] = make_uint4(empty, empty, empty, empty);
+    reinterpret_cast<uint4*>(tabkey)[64 + lane] = make_uint4(empty, empty, empty, empty);
     u32 zero;
     asm volatile("v_mov_b32 %0, 0" : "=v"(zero));     // not hoistable: a loop-invariant zero quad gets spilled to scratch otherwise
     reinterpret_cast<uint4*>(tabcnt)[lane] = make_uint4(zero, zero, zero, zero);
@@ -323,7 +327,7 @@ __device__ __forceinline__ u32 dedup_finish(u32 D, u32* buf, u32* hits, u32 lane
     return D;
 }
 // gather (or load) + insertion; the caller finishes with dedup_finish.  ~1u: stage-ablation stop after the gather.
-template <int E>
+template <int E, bool LIT = false>
 __device__ __forceinline__ u32 gather_dedup_insert(const DbDev& db, u32* buf, u32* hits, u32 T, u32 pos, u32 len, u64 off, u32 lane, int stop) {
     u32 r[E];
     gather_regs<u32, E>(db, r, T, pos, len, off, lane, hits);
@@ -334,7 +338,7 @@ __device__ __forceinline__ u32 gather_dedup_insert(const DbDev& db, u32* buf, u3
         buf[lane] = x;
         return ~1u;
     }
-    return dedup_insert<E>(r, buf, hits, T, lane);
+    return dedup_insert<E, LIT>(r, buf, hits, T, lane);
 }
 // the same with two lists per lane (second wave stage, reads of 65..128 features)
 template <int E>
@@ -506,8 +510,8 @@ __device__ __forceinline__ ReadGeom read_geom(const DbDev& db, const BatchDev& b
     const G geo(db); const F form(b);
     const u64 a = form.paired() ? 2 * q : q;
     u64 e0, e1;
-    seq_bounds(b.seq_off, b.ranges, a, g.o0, e0);
-    if (form.paired()) seq_bounds(b.seq_off, b.ranges, a + 1, g.o1, e1); else { g.o1 = e0; e1 = e0; }
+    F::seq_bounds(b.seq_off, b.ranges, a, g.o0, e0);
+    if (form.paired()) F::seq_bounds(b.seq_off, b.ranges, a + 1, g.o1, e1); else { g.o1 = e0; e1 = e0; }
     const u64 l1 = e0 - g.o0, l2 = e1 - g.o1;
     g.qlen = l1 + l2;
     g.ovf = block_only || ((l1 | l2) >> 20) != 0;
@@ -644,8 +648,13 @@ __global__ __launch_bounds__(256, sizeof(KeyT) == 4 ? (NL > 1 ? 5 : MCQ_WAVE_OCC
     u32* hits = s_hits[wave];
     u32* sk_tmp = hits;                // sketch scratch aliases the (not yet used) hit words
     u32* feat = hits + 64;
-    const u64 nwaves = (u64)gridDim.x * 4;
-    unsigned long long st_feat = 0, st_hit = 0, st_loc = 0, st_cand = 0;
+    // The lean form counts its reads and its statistics in 32 bits (QI, ST): nq < 2^31 (mcq_ws_create), and a wave takes at most
+    // 2^22 + 1 reads of the batch (launch_query: the lean grid), each with at most 64 features, 256 locations and 64 candidates
+    // -- below 2^31 per wave; the sums are folded into the 64-bit counters when the kernel ends, as in the full form.
+    using QI = std::conditional_t<LEAN, u32, u64>;
+    using ST = std::conditional_t<LEAN, u32, unsigned long long>;
+    const QI nwaves = (QI)gridDim.x * 4;
+    ST st_feat = 0, st_hit = 0, st_loc = 0, st_cand = 0;
     u32 st_geom = 0, st_long = 0;
 #ifdef MCQ_PROFILE_HOOKS
     const int stop = (int)(hooks >> MCQ_HOOK_STOP_SHIFT);   // profiling builds: stop after stage 1..5 (results invalid); 0 = run everything
@@ -698,7 +707,11 @@ __global__ __launch_bounds__(256, sizeof(KeyT) == 4 ? (NL > 1 ? 5 : MCQ_WAVE_OCC
             return;
         }
     }
-    for (u64 q = (u64)blockIdx.x * 4 + wave; q < b.nq; q += nwaves) {
+    const QI nq = (QI)b.nq;
+    // (lean: what range_width needs of the launch's insert_size_max, once -- a read that reaches this stage is shorter than 2^21 bases)
+    const bool ism_huge = LEAN && opt.insert_size_max >= (1ull << 31);
+    const u32 nw_ism = LEAN ? geo.range_width(0, opt.insert_size_max) : 0u;
+    for (QI q = (QI)blockIdx.x * 4 + wave; q < nq; q += nwaves) {
         const ReadGeom g = read_geom<G, F>(db, b, q, (hooks & MCQ_HOOK_BLOCK_ONLY) != 0);
         bool ovf = g.ovf;
         u32 myf = MCQ_EMPTY, nfeat = 0, T = 0, len = 0, pos = 0;
@@ -711,7 +724,7 @@ __global__ __launch_bounds__(256, sizeof(KeyT) == 4 ? (NL > 1 ? 5 : MCQ_WAVE_OCC
             if constexpr (LEAN && !PAIRED && !PACKED) {
                 // a single read of 129..160 bases (150: two windows, the second with at most 32 k-mers): both windows in one pass.
                 // (The global-window instantiations have no VGPR to spare for the pass's lane constants: they recompute them.)
-                if (g.n1 - 129u <= 31u) { u32 path; nfeat = wave_sketch_two_windows<MCQ_SKETCH_EXPECT_FUSED, GW>(b.bases + g.o0, g.n1, lane, sk_tmp, feat, path); }
+                if (g.n1 - 129u <= 31u) { u32 path; nfeat = wave_sketch_two_windows<MCQ_SKETCH_EXPECT_FUSED, GW, true>(b.bases + g.o0, g.n1, lane, sk_tmp, feat, path); }
                 else for (u32 w = 0; w < g.nw1; ++w) {
                     u64 at; u32 wl;
                     window_span<G>(db, g, w, at, wl);
@@ -761,16 +774,20 @@ __global__ __launch_bounds__(256, sizeof(KeyT) == 4 ? (NL > 1 ? 5 : MCQ_WAVE_OCC
         if (T == 0) { if (lane == 0) out.ncand[q] = 0; continue; }
 
         wave_sync();                                   // feat[] (aliasing hits) has been consumed
-        const u32 numWindows = geo.range_width(g.qlen, opt.insert_size_max);
+        u32 numWindows;
+        if constexpr (LEAN) {       // 2 + max(qlen, insert_size_max) / stride: the division is monotone, and qlen < 2^21 < 2^31 <= a huge insert size
+            const u32 nw_q = 2 + (u32)g.qlen / G::S;
+            numWindows = (ism_huge || nw_ism > nw_q) ? nw_ism : nw_q;
+        } else numWindows = geo.range_width(g.qlen, opt.insert_size_max);
         const auto& hdb = heads_db<EXCL>(db, exd, q);  // what the top lists read the heads' taxa from (EXCL: without the query's own clade)
         if constexpr (sizeof(KeyT) == 4) {
             if (LEAN || (T <= MCQ_DEDUP_MAX_T && !(hooks & MCQ_HOOK_RAW_SORT))) {
                 u32 D = 0, k1 = MCQ_EMPTY, incl1 = 0, t1 = 0, tb1 = 0;
                 bool skipped = false;
-                if (T <= 64)       D = gather_dedup_insert<1>(db, buf, hits, T, pos, len, off, lane, stop);
-                else if (T <= 128) D = gather_dedup_insert<2>(db, buf, hits, T, pos, len, off, lane, stop);
-                else if (T <= 192) D = gather_dedup_insert<3>(db, buf, hits, T, pos, len, off, lane, stop);
-                else if (LEAN || T <= 256) D = gather_dedup_insert<4>(db, buf, hits, T, pos, len, off, lane, stop);      // (lean: T <= 256 here)
+                if (T <= 64)       D = gather_dedup_insert<1, LEAN>(db, buf, hits, T, pos, len, off, lane, stop);
+                else if (T <= 128) D = gather_dedup_insert<2, LEAN>(db, buf, hits, T, pos, len, off, lane, stop);
+                else if (T <= 192) D = gather_dedup_insert<3, LEAN>(db, buf, hits, T, pos, len, off, lane, stop);
+                else if (LEAN || T <= 256) D = gather_dedup_insert<4, LEAN>(db, buf, hits, T, pos, len, off, lane, stop);      // (lean: T <= 256 here)
                 else if constexpr (!LEAN) {
                     if (lane == 0) s_lean[wave] += 1;       // (the lean form would have handed it on)
                     const u32 t_fail = s_tfail[wave];
@@ -833,10 +850,10 @@ __global__ __launch_bounds__(256, sizeof(KeyT) == 4 ? (NL > 1 ? 5 : MCQ_WAVE_OCC
     if (lane == 0 && st_geom) atomicAdd(&ctr->n_geom, (unsigned long long)st_geom);
     if (lane == 0 && st_long) atomicAdd(&ctr->n_long, (unsigned long long)st_long);
     if (lane == 0 && (st_feat | st_loc | st_hit)) {
-        if (st_feat) atomicAdd(&ctr->n_features, st_feat);
-        atomicAdd(&ctr->n_hit_features, st_hit);
-        atomicAdd(&ctr->n_locations, st_loc);
-        atomicAdd(&ctr->n_cands, st_cand);
+        if (st_feat) atomicAdd(&ctr->n_features, (unsigned long long)st_feat);
+        atomicAdd(&ctr->n_hit_features, (unsigned long long)st_hit);
+        atomicAdd(&ctr->n_locations, (unsigned long long)st_loc);
+        atomicAdd(&ctr->n_cands, (unsigned long long)st_cand);
     }
 }
 
@@ -1937,7 +1954,9 @@ int mcq::launch_query(const mcq_db* db, mcq_ws* ws, const BatchDev& b, const Opt
             if (p.many) with_layout(db, [&](auto BSH) { first(No{}, No{}, BSH, IntC<4>{}, No{}, No{}, grid_for(ws->cap_wave_many, want), No{}, No{}); });
             // the lean form knows the batch's form too: one instantiation per (layout, paired, packed)
             if (p.lean) with_layout(db, [&](auto BSH) {
-                auto lean = [&](auto PAIRED, auto PACKED) { first(No{}, No{}, BSH, IntC<1>{}, Yes{}, No{}, grid, PAIRED, PACKED); };
+                // (at most 2^22 + 1 reads per wave, on a device of any size: the lean form's statistics are 32-bit sums)
+                const u32 lean_grid = std::max<u32>(grid, (u32)(want >> 22) + 1);
+                auto lean = [&](auto PAIRED, auto PACKED) { first(No{}, No{}, BSH, IntC<1>{}, Yes{}, No{}, lean_grid, PAIRED, PACKED); };
                 if (b.paired) { if (b.packed) lean(Yes{}, Yes{}); else lean(Yes{}, No{}); }
                 else { if (b.packed) lean(No{}, Yes{}); else lean(No{}, No{}); }
             });
