@@ -92,6 +92,7 @@ def _reduce_against_oracle(make_lists):
     import torch
     from golden_util import Fixture
     from oracle import dbfile
+    from reduce_lists import to_native
     eng = importlib.import_module("metacache-mpi_amd.engine")
     dev = torch.device("cuda", 0)
     fx = Fixture("mini", 2)
@@ -103,24 +104,18 @@ def _reduce_against_oracle(make_lists):
     lists = make_lists(locs)
     loc_off = np.zeros(len(lists) + 1, np.int64); loc_off[1:] = np.cumsum([len(x) for x in lists])
     allv = np.concatenate(lists)
-    # global-window form: windows per target = 1 + its largest window id in the table (what the handle derives)
-    ext = np.zeros(len(t2t), np.int64)
-    np.maximum.at(ext, (locs >> np.uint64(32)).astype(np.int64), (locs & np.uint64(0xFFFFFFFF)).astype(np.int64) + 1)
-    gw_off = np.concatenate([[0], np.cumsum(ext)]).astype(np.uint64)
     qlen = torch.full((len(lists),), 150, dtype=torch.int32, device=dev)
     doff = torch.from_numpy(loc_off).to(dev)
-    for dbflags in (0, eng.MCQ_DB_LOCS_GW):           # the staged reduce kernels in both 32-bit location forms
+    for dbflags in (0, eng.MCQ_DB_LOCS_GW, eng.MCQ_DB_LOCS_64):      # the staged reduce kernels in all three location forms
         db = eng.Database(keys, off, locs, t2t, k=p["qk"], sketch_size=p["qs"], winlen=p["qwinlen"], winstride=p["qwinstride"],
                           tgt_winstride=p["winstride"], flags=dbflags)
-        wb = db.win_bits()
-        if db.layout()["loc_format"] == eng.MCQ_LOC_GLOBAL_WINDOW:
-            dl = torch.from_numpy((gw_off[(allv >> np.uint64(32)).astype(np.int64)] + (allv & np.uint64(0xFFFFFFFF))).astype(np.uint32).view(np.int32)).to(dev)
-        elif db.loc_bytes() == 4:
-            dl = torch.from_numpy((((allv >> np.uint64(32)) << np.uint64(wb)) | (allv & np.uint64(0xFFFFFFFF))).astype(np.uint32).view(np.int32)).to(dev)
-        else:
-            dl = torch.from_numpy(allv.view(np.int64)).to(dev)
+        native = to_native(allv, db)
+        dl = torch.from_numpy(native.view(np.int32 if db.loc_bytes() == 4 else np.int64)).to(dev)
         ws = eng.Workspace(db, len(lists), 1)
-        for P, M in ((1, 4), (2, 2), (32, 4)):          # (32, 4): lists in the workgroup kernel's LDS
+        # (32, 4): 128 list entries do not fit a wave's lanes, but make_opt folds every P > 1 as one selection (OptDev::lin,
+        # big = 0) unless MCQ_FOLD_BY_LISTS or MCQ_QUIRK_SEQ_DROP on sequence-level taxa asks for the P lists: the wave
+        # kernels take these lists too.  The workgroup kernel's LDS lists (BIG = 1): tests/test_gpu_reduce_edges.py
+        for P, M in ((1, 4), (2, 2), (32, 4)):
             for flags in (0, eng.MCQ_FORCE_RAW_SORT):
                 cands = torch.zeros((len(lists), M, 4), dtype=torch.int32, device=dev)
                 ncand = torch.zeros(len(lists), dtype=torch.int32, device=dev)
