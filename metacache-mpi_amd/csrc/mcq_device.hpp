@@ -2350,4 +2350,209 @@ __device__ __forceinline__ u32 topk_block(const DB& db, const OptDev& opt, const
     return n;
 }
 
+// ---- rows 8-9 on DISTINCT (tgt,win) keys (32-bit keys, T <= 512) ------------------------------
+// A read's match list repeats the same (target, window) many times (C2: 107 locations, 33 distinct;
+// 2x150 bp pairs: 214 / 65; on an 8 x larger table 218 / 140), and everything after the gather only needs
+// the distinct keys and how often each occurs.  The wave counts them in a 512-slot open-addressing table
+// in its LDS segment (ds_cmpst claims a slot, ds_add counts in a 16-bit lane), the lanes that claimed a
+// slot compact their keys, <= 256 distinct keys are sorted in one, two or four registers per lane instead
+// of 64*E raw locations, and the multiplicities come back by probing the table with the sorted keys.
+// Output: SK[0..D) sorted distinct keys, WP[0..D) inclusive prefix sums of the multiplicities (for
+// sweep_targets_weighted).  Returns D, or ~0u when there are more than 256 distinct keys (the caller then
+// sorts the raw list); the insertion stops at the first register that takes D past 256, so the table never
+// holds more than 320 keys.
+//   LDS (u32 words): buf[0..512) table keys, later the sweep's H in buf[0..256) and the top lists' scratch
+//   behind it;  hits[0..256) table counts (16 bits per slot: any multiset of up to 512 locations is counted
+//   exactly, whatever the caller of mcq_reduce hands over), later WP;  hits[256..512) compaction list, later SK.
+#ifndef MCQ_DEDUP_MAX_T
+#define MCQ_DEDUP_MAX_T 512u    // tuning knobs: -DMCQ_DEDUP_MAX_T=384u -DMCQ_DEDUP_MAX_D=128u is the two-register form
+#endif
+#ifndef MCQ_DEDUP_MAX_D
+#define MCQ_DEDUP_MAX_D 256u
+#endif
+__device__ __forceinline__ u32 dedup_slot(u32 key) { return (key * 0x9E3779B1u) >> 23; }
+__device__ __forceinline__ u32* dedup_sk(u32* hits) { return hits + 256; }
+__device__ __forceinline__ u32* dedup_wp(u32* hits) { return hits; }
+__device__ __forceinline__ u32 dedup_count(const u32* tabkey, const u32* tabcnt, u32 k) {
+    u32 slot = dedup_slot(k);
+    while (tabkey[slot] != k) slot = (slot + 1) & 511u;
+    return (tabcnt[slot >> 1] >> (16 * (slot & 1))) & 0xFFFFu;
+}
+
+// Insertion half (depends on the number of registers E): counts the keys in the table and leaves the distinct
+// ones in the compaction list; returns their number D.
+// LIT (the lean first wave stage): the empty quad of the table clear comes from a literal too, like the zero quad below -- else the
+// constant lives in a scalar register across the caller's per-read loop, which has none to spare
+template <int E, bool LIT = false>
+__device__ __forceinline__ u32 dedup_insert(const u32 (&r)[E], u32* buf, u32* hits, u32 T, u32 lane) {
+    u32* tabkey = buf; u32* tabcnt = hits; u32* list = hits + 256;
+    u32 empty = MCQ_EMPTY;
+    if constexpr (LIT) asm volatile("v_mov_b32 %0, -1" : "=v"(empty));
+    reinterpret_cast<uint4*>(tabkey)[lane] = make_uint4(empty, empty, empty, empty);
+    reinterpret_cast<uint4*>(tabkey)[64 + lane] = make_uint4(empty, empty, empty, empty);
+    u32 zero;
+    asm volatile("v_mov_b32 %0, 0" : "=v"(zero));     // not hoistable: a loop-invariant zero quad gets spilled to scratch otherwise
+    reinterpret_cast<uint4*>(tabcnt)[lane] = make_uint4(zero, zero, zero, zero);
+    wave_sync();
+    u32 D = 0;
+#pragma unroll
+    for (int e = 0; e < E; ++e) {
+        if (e > 0 && (u32)(e * 64) >= T) break;  // wave-uniform: nothing left in the higher registers
+        const u32 key = r[e];
+        bool created = false;
+        if ((u32)(e * 64) + lane < T) {
+            u32 slot = dedup_slot(key);
+            while (true) {                       // <= 320 keys in 512 slots: an empty slot always exists
+                const u32 old = atomicCAS(&tabkey[slot], MCQ_EMPTY, key);
+                created = old == MCQ_EMPTY;
+                if (created || old == key) { atomicAdd(&tabcnt[slot >> 1], 1u << (16 * (slot & 1))); break; }
+                slot = (slot + 1) & 511u;
+            }
+        }
+        const u64 cm = __ballot(created);
+        const u32 rank = D + lane_rank(cm);
+        if (created && rank < MCQ_DEDUP_MAX_D) list[rank] = key;
+        D += (u32)__builtin_popcountll(cm);
+        if (D > MCQ_DEDUP_MAX_D) break;          // wave-uniform: the raw list gets sorted instead
+    }
+    wave_sync();
+    return D;
+}
+// Second half, the same code for every E: sort the D distinct keys, fetch their multiplicities, prefix sums.
+// k1/incl1: the sorted keys and inclusive sums one per lane when D <= 64 (for sweep_targets_regs); t1/tb1: target and
+// first word of the target of k1 -- looked up here, right behind the sort, so that a format that has to go to memory
+// for them (LocGW) does so once per read and under the LDS work that follows.
+// Returns D, or ~0u when D > 256.
+template <class LF>
+__device__ __forceinline__ u32 dedup_finish(u32 D, u32* buf, u32* hits, u32 lane, const LF& lf, u32& k1, u32& incl1, u32& t1, u32& tb1) {
+    u32* tabkey = buf; u32* tabcnt = hits; u32* list = hits + 256; u32* SK = dedup_sk(hits); u32* WP = dedup_wp(hits);
+    k1 = MCQ_EMPTY; incl1 = 0; t1 = 0; tb1 = 0;
+    if (D > MCQ_DEDUP_MAX_D) return ~0u;
+    if (D <= 64) {
+        u32 k = lane < D ? list[lane] : MCQ_EMPTY;
+        k = (D <= 32) ? wave_sort_blocks32_1(k) : wave_sort64_1(k);
+        if constexpr (LF::lookup) lf.locate(lane < D ? k : list[0], t1, tb1);      // (padding lanes look up a real word)
+        const u32 c = lane < D ? dedup_count(tabkey, tabcnt, k) : 0u;
+        const u32 incl = wave_incl_scan_dpp(c);
+        wave_sync();                             // counts consumed: WP overwrites them
+        SK[lane] = k; WP[lane] = incl;
+        k1 = k; incl1 = incl;
+    } else if (D <= 128) {
+        u32 k[2];
+        k[0] = list[lane]; k[1] = (64 + lane < D) ? list[64 + lane] : MCQ_EMPTY;
+        wave_regsort<u32, 2>(k, lane);
+        const u32 c0 = dedup_count(tabkey, tabcnt, k[0]);
+        const u32 c1 = (64 + lane < D) ? dedup_count(tabkey, tabcnt, k[1]) : 0u;
+        const u32 i0 = wave_incl_scan_dpp(c0);
+        const u32 i1 = wave_incl_scan_dpp(c1) + bcast(i0, 63);
+        wave_sync();
+        SK[lane] = k[0]; SK[64 + lane] = k[1]; WP[lane] = i0; WP[64 + lane] = i1;
+    } else {
+        u32 k[4], c[4];
+#pragma unroll
+        for (int e = 0; e < 4; ++e) k[e] = ((u32)(64 * e) + lane < D) ? list[64 * e + lane] : MCQ_EMPTY;
+        wave_regsort<u32, 4>(k, lane);
+#pragma unroll
+        for (int e = 0; e < 4; ++e) c[e] = ((u32)(64 * e) + lane < D) ? dedup_count(tabkey, tabcnt, k[e]) : 0u;
+        u32 carry = 0;
+#pragma unroll
+        for (int e = 0; e < 4; ++e) { c[e] = wave_incl_scan_dpp(c[e]) + carry; carry = bcast(c[e], 63); }
+        wave_sync();                             // list and counts consumed: SK and WP overwrite them
+#pragma unroll
+        for (int e = 0; e < 4; ++e) { SK[64 * e + lane] = k[e]; WP[64 * e + lane] = c[e]; }
+    }
+    wave_sync();                                 // table dead from here: buf[] becomes the sweep's H
+    return D;
+}
+
+// ---- rows 8-11 without a sort: one selection (OptDev::lin), at most 64 distinct keys, a window range of at most
+// MCQ_NARROW_NWR windows, bit-field words (the lean first wave stage's usual read: 150 bp against a small table gives 33
+// distinct keys and a range of 3).  Runs behind dedup_insert in place of dedup_finish + sweep_targets_regs + topk_lin_write,
+// on the table in buf / hits and the D unsorted distinct keys in hits[256..).  The sorted order served two ends there:
+//   - the range that ends at key k holds k and its predecessors of the same target among the last numWindows - 1 keys.  Those are
+//     the WORDS k - 1 .. k - (numWindows - 1) as far as they stay inside the target (k - tbeg(k) >= i: what range_low expresses),
+//     and the table says how often any word occurs -- dedup_count with an exit at the first empty slot for a word that is absent
+//     (at most 320 keys in 512 slots: there is one).  A lane's look-ups do not depend on one another: their first reads go out
+//     together.
+//   - ties by position.  Position among the sorted distinct keys is key order.
+// The selection is the same word for word: there a run head carries the maximum of (hits, -j) over its target's run, heads compete
+// on (hits, -rank, -j), and the rank is constant inside a run -- so the head that wins a round is the lane that maximises
+// (hits, -rank, -j) over ALL lanes not yet retired, j order is key order, a winner retires every lane of its taxon in both forms
+// (a run has one taxon), and only (taxon, hits) are written.  Here every valid lane enters with hits << 6 | 63 - rank; among the
+// lanes that hold the maximum the smallest key wins, which takes a second reduction only when they hold different taxa (behind a
+// ballot: most rounds have one winner or one taxon).
+// The taxon keys are loaded first, under the look-ups (the sorted form would hold them across the sort and the sweep: topk_dedup).
+// TIES (tests): *tie_seen = 1 when a round took the second reduction.  Returns the number of candidates written.
+#define MCQ_NARROW_NWR 4u
+template <bool TIES = false, class LF, class DB>
+__device__ __forceinline__ u32 narrow_tail_lin(const DB& db, const OptDev& opt, const OutDev& out, const u32* buf, const u32* hits, u32 D,
+                                               u32 numWindows, const LF& lf, u64 q, u32 lane, u32* tie_seen = nullptr) {
+    static_assert(!LF::lookup, "predecessor words by arithmetic: bit-field locations");
+    constexpr u32 NWR = MCQ_NARROW_NWR;
+    const u32* tabkey = buf; const u32* tabcnt = hits; const u32* list = hits + 256;
+    const bool valid = lane < D;
+    const u32 k = valid ? list[lane] : MCQ_EMPTY;
+    const u32 tgt = lf.tgt(k);
+    // Nothing is in flight here (the gather's loads were consumed by the insertion), but the compiler cannot know: the lanes past
+    // the list's end skipped the blocks that waited for them.  Said once, in a form its counter bookkeeping reads, or it waits for
+    // ALL vector loads -- the taxon keys' among them -- in front of the first table read below.
+    __builtin_amdgcn_s_waitcnt(0x0F70);              // vmcnt(0) alone
+    u32 ctax = MCQ_EMPTY;
+    if (valid && tgt < db.n_targets) ctax = head_tax(db, tgt);
+    const u32 win = k - lf.tbeg(k);
+    u32 slot[NWR], kk[NWR];
+    bool live[NWR];
+    live[0] = valid; slot[0] = dedup_slot(k); kk[0] = MCQ_EMPTY;
+    if (valid) kk[0] = tabkey[slot[0]];
+#pragma unroll
+    for (u32 i = 1; i < NWR; ++i) {
+        live[i] = false; slot[i] = 0; kk[i] = MCQ_EMPTY;
+        if (i < numWindows) {                        // wave-uniform
+            live[i] = valid && win >= i;
+            slot[i] = dedup_slot(k - i);
+            if (live[i]) kk[i] = tabkey[slot[i]];
+        }
+    }
+#pragma unroll
+    for (u32 i = 0; i < NWR; ++i) {
+        if (i > 0 && i >= numWindows) break;         // wave-uniform
+        while (kk[i] != k - i && kk[i] != MCQ_EMPTY) { slot[i] = (slot[i] + 1) & 511u; kk[i] = tabkey[slot[i]]; }
+    }
+    u32 c[NWR];
+#pragma unroll
+    for (u32 i = 0; i < NWR; ++i) {
+        c[i] = 0;
+        if (i > 0 && i >= numWindows) continue;      // wave-uniform
+        if (live[i] && kk[i] == k - i) c[i] = tabcnt[slot[i] >> 1];
+    }
+    u32 h = 0;
+#pragma unroll
+    for (u32 i = 0; i < NWR; ++i) h += (c[i] >> (16 * (slot[i] & 1))) & 0xFFFFu;
+    const u32 cr = lin_rank(opt, tgt);
+    u32 v = (ctax == MCQ_EMPTY || cr >= opt.keep) ? 0u : (h << 6) | (63u - cr);
+    const u32 M = opt.max_cand;
+    u32 Ltax = MCQ_EMPTY, Lh = 0;                    // lanes < M: the list
+    for (u32 i = 0; i < M; ++i) {
+        const u32 m = wave_max_u32(v);
+        if (m == 0) break;
+        const bool top = v == m;
+        u32 wtax = bcast(ctax, (u32)__builtin_ctzll(__ballot(top)));
+        if (__ballot(top && ctax != wtax)) {         // several taxa hold the maximum: the smallest key's (keys are distinct)
+            const u32 kmin = wave_min_u32(top ? k : MCQ_EMPTY);
+            wtax = bcast(ctax, (u32)__builtin_ctzll(__ballot(top && k == kmin)));
+            if constexpr (TIES) { if (lane == 0) *tie_seen = 1; }
+        }
+        if (lane == i) { Ltax = wtax; Lh = m >> 6; }
+        if (ctax == wtax) v = 0;                     // every lane of the winner's taxon retires
+    }
+    const u32 n = (u32)__builtin_popcountll(__ballot(lane < M && Lh != 0));
+    if (lane < n) {
+        u32 ln = lane;
+        asm volatile("" : "+v"(ln));               // (see topk_fold_write)
+        reinterpret_cast<uint4*>(out.cands)[q * M + ln] = make_uint4(Ltax, Lh, 0u, 0u);
+    }
+    if (lane == 0) out.ncand[q] = n;
+    return n;
+}
+
 } // namespace mcq

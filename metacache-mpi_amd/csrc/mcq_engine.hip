@@ -178,26 +178,6 @@ __device__ __forceinline__ void gather_sort_store(const DbDev& db, KeyT* buf, u3
     for (int e = 0; e < E; ++e) buf[e * 64 + lane] = r[e];
 }
 
-// ---- rows 8-9 on DISTINCT (tgt,win) keys (32-bit keys, T <= 512) ------------------------------
-// A read's match list repeats the same (target, window) many times (C2: 107 locations, 33 distinct;
-// 2x150 bp pairs: 214 / 65; on an 8 x larger table 218 / 140), and everything after the gather only needs
-// the distinct keys and how often each occurs.  The wave counts them in a 512-slot open-addressing table
-// in its LDS segment (ds_cmpst claims a slot, ds_add counts in a 16-bit lane), the lanes that claimed a
-// slot compact their keys, <= 256 distinct keys are sorted in one, two or four registers per lane instead
-// of 64*E raw locations, and the multiplicities come back by probing the table with the sorted keys.
-// Output: SK[0..D) sorted distinct keys, WP[0..D) inclusive prefix sums of the multiplicities (for
-// sweep_targets_weighted).  Returns D, or ~0u when there are more than 256 distinct keys (the caller then
-// sorts the raw list); the insertion stops at the first register that takes D past 256, so the table never
-// holds more than 320 keys.
-//   LDS (u32 words): buf[0..512) table keys, later the sweep's H in buf[0..256) and the top lists' scratch
-//   behind it;  hits[0..256) table counts (16 bits per slot: any multiset of up to 512 locations is counted
-//   exactly, whatever the caller of mcq_reduce hands over), later WP;  hits[256..512) compaction list, later SK.
-#ifndef MCQ_DEDUP_MAX_T
-#define MCQ_DEDUP_MAX_T 512u    // tuning knobs: -DMCQ_DEDUP_MAX_T=384u -DMCQ_DEDUP_MAX_D=128u is the two-register form
-#endif
-#ifndef MCQ_DEDUP_MAX_D
-#define MCQ_DEDUP_MAX_D 256u
-#endif
 // top lists of the dedup path: more than 64 distinct keys (two to four rounds of 64 run heads) take all heads at once
 // t1 (D <= 64): the target of sorted key j in lane j, as dedup_finish looked it up
 template <class LF, class DB>
@@ -232,100 +212,6 @@ __shared__ u64 g_wph[4][12];
 #else
 #define WCLK(i) do { } while (0)
 #endif
-__device__ __forceinline__ u32 dedup_slot(u32 key) { return (key * 0x9E3779B1u) >> 23; }
-__device__ __forceinline__ u32* dedup_sk(u32* hits) { return hits + 256; }
-__device__ __forceinline__ u32* dedup_wp(u32* hits) { return hits; }
-__device__ __forceinline__ u32 dedup_count(const u32* tabkey, const u32* tabcnt, u32 k) {
-    u32 slot = dedup_slot(k);
-    while (tabkey[slot] != k) slot = (slot + 1) & 511u;
-    return (tabcnt[slot >> 1] >> (16 * (slot & 1))) & 0xFFFFu;
-}
-
-// Insertion half (depends on the number of registers E): counts the keys in the table and leaves the distinct
-// ones in the compaction list; returns their number D.
-// LIT (the lean first wave stage): the empty quad of the table clear comes from a literal too, like the zero quad below -- else the
-// constant lives in a scalar register across the caller's per-read loop, which has none to spare
-template <int E, bool LIT = false>
-__device__ __forceinline__ u32 dedup_insert(const u32 (&r)[E], u32* buf, u32* hits, u32 T, u32 lane) {
-    u32* tabkey = buf; u32* tabcnt = hits; u32* list = hits + 256;
-    u32 empty = MCQ_EMPTY;
-    if constexpr (LIT) asm volatile("v_mov_b32 %0, -1" : "=v"(empty));
-    reinterpret_cast<uint4*>(tabkey)[lane] = make_uint4(empty, empty, empty, empty);
-    reinterpret_cast<uint4*>(tabkey)[64 + lane] = make_uint4(empty, empty, empty, empty);
-    u32 zero;
-    asm volatile("v_mov_b32 %0, 0" : "=v"(zero));     // not hoistable: a loop-invariant zero quad gets spilled to scratch otherwise
-    reinterpret_cast<uint4*>(tabcnt)[lane] = make_uint4(zero, zero, zero, zero);
-    wave_sync();
-    u32 D = 0;
-#pragma unroll
-    for (int e = 0; e < E; ++e) {
-        if (e > 0 && (u32)(e * 64) >= T) break;  // wave-uniform: nothing left in the higher registers
-        const u32 key = r[e];
-        bool created = false;
-        if ((u32)(e * 64) + lane < T) {
-            u32 slot = dedup_slot(key);
-            while (true) {                       // <= 320 keys in 512 slots: an empty slot always exists
-                const u32 old = atomicCAS(&tabkey[slot], MCQ_EMPTY, key);
-                created = old == MCQ_EMPTY;
-                if (created || old == key) { atomicAdd(&tabcnt[slot >> 1], 1u << (16 * (slot & 1))); break; }
-                slot = (slot + 1) & 511u;
-            }
-        }
-        const u64 cm = __ballot(created);
-        const u32 rank = D + lane_rank(cm);
-        if (created && rank < MCQ_DEDUP_MAX_D) list[rank] = key;
-        D += (u32)__builtin_popcountll(cm);
-        if (D > MCQ_DEDUP_MAX_D) break;          // wave-uniform: the raw list gets sorted instead
-    }
-    wave_sync();
-    return D;
-}
-// Second half, the same code for every E: sort the D distinct keys, fetch their multiplicities, prefix sums.
-// k1/incl1: the sorted keys and inclusive sums one per lane when D <= 64 (for sweep_targets_regs); t1/tb1: target and
-// first word of the target of k1 -- looked up here, right behind the sort, so that a format that has to go to memory
-// for them (LocGW) does so once per read and under the LDS work that follows.
-// Returns D, or ~0u when D > 256.
-template <class LF>
-__device__ __forceinline__ u32 dedup_finish(u32 D, u32* buf, u32* hits, u32 lane, const LF& lf, u32& k1, u32& incl1, u32& t1, u32& tb1) {
-    u32* tabkey = buf; u32* tabcnt = hits; u32* list = hits + 256; u32* SK = dedup_sk(hits); u32* WP = dedup_wp(hits);
-    k1 = MCQ_EMPTY; incl1 = 0; t1 = 0; tb1 = 0;
-    if (D > MCQ_DEDUP_MAX_D) return ~0u;
-    if (D <= 64) {
-        u32 k = lane < D ? list[lane] : MCQ_EMPTY;
-        k = (D <= 32) ? wave_sort_blocks32_1(k) : wave_sort64_1(k);
-        if constexpr (LF::lookup) lf.locate(lane < D ? k : list[0], t1, tb1);      // (padding lanes look up a real word)
-        const u32 c = lane < D ? dedup_count(tabkey, tabcnt, k) : 0u;
-        const u32 incl = wave_incl_scan_dpp(c);
-        wave_sync();                             // counts consumed: WP overwrites them
-        SK[lane] = k; WP[lane] = incl;
-        k1 = k; incl1 = incl;
-    } else if (D <= 128) {
-        u32 k[2];
-        k[0] = list[lane]; k[1] = (64 + lane < D) ? list[64 + lane] : MCQ_EMPTY;
-        wave_regsort<u32, 2>(k, lane);
-        const u32 c0 = dedup_count(tabkey, tabcnt, k[0]);
-        const u32 c1 = (64 + lane < D) ? dedup_count(tabkey, tabcnt, k[1]) : 0u;
-        const u32 i0 = wave_incl_scan_dpp(c0);
-        const u32 i1 = wave_incl_scan_dpp(c1) + bcast(i0, 63);
-        wave_sync();
-        SK[lane] = k[0]; SK[64 + lane] = k[1]; WP[lane] = i0; WP[64 + lane] = i1;
-    } else {
-        u32 k[4], c[4];
-#pragma unroll
-        for (int e = 0; e < 4; ++e) k[e] = ((u32)(64 * e) + lane < D) ? list[64 * e + lane] : MCQ_EMPTY;
-        wave_regsort<u32, 4>(k, lane);
-#pragma unroll
-        for (int e = 0; e < 4; ++e) c[e] = ((u32)(64 * e) + lane < D) ? dedup_count(tabkey, tabcnt, k[e]) : 0u;
-        u32 carry = 0;
-#pragma unroll
-        for (int e = 0; e < 4; ++e) { c[e] = wave_incl_scan_dpp(c[e]) + carry; carry = bcast(c[e], 63); }
-        wave_sync();                             // list and counts consumed: SK and WP overwrite them
-#pragma unroll
-        for (int e = 0; e < 4; ++e) { SK[64 * e + lane] = k[e]; WP[64 * e + lane] = c[e]; }
-    }
-    wave_sync();                                 // table dead from here: buf[] becomes the sweep's H
-    return D;
-}
 // gather (or load) + insertion; the caller finishes with dedup_finish.  ~1u: stage-ablation stop after the gather.
 template <int E, bool LIT = false>
 __device__ __forceinline__ u32 gather_dedup_insert(const DbDev& db, u32* buf, u32* hits, u32 T, u32 pos, u32 len, u64 off, u32 lane, int stop) {
@@ -798,6 +684,13 @@ __global__ __launch_bounds__(256, sizeof(KeyT) == 4 ? (NL > 1 ? 5 : MCQ_WAVE_OCC
                     }
                     else if (T <= 384) D = gather_dedup_insert<6>(db, buf, hits, T, pos, len, off, lane, stop);
                     else               D = gather_dedup_insert<8>(db, buf, hits, T, pos, len, off, lane, stop);
+                }
+                if constexpr (LEAN && !GW) {       // one selection, <= 64 distinct keys, a narrow range: no sort, no sweep (narrow_tail_lin)
+                    if (stop == 0 && opt.lin != 0 && D <= 64 && numWindows <= MCQ_NARROW_NWR) {
+                        st_cand += narrow_tail_lin(hdb, opt, out, reinterpret_cast<const u32*>(buf), hits, D, numWindows, lf, q, lane);
+                        wave_sync();
+                        continue;
+                    }
                 }
                 if (D != ~1u) D = dedup_finish(D, buf, hits, lane, lf, k1, incl1, t1, tb1);
                 if (stop == 3 || stop == 4) { if (buf[lane] == 0x1234u && D == 77u) out.ncand[q] = 1; wave_sync(); continue; }
