@@ -535,6 +535,46 @@ int mcq_parts_builder_create(const mcq_parts_builder_desc* desc, mcq_parts_build
 int mcq_parts_builder_add(mcq_parts_builder* b, const uint32_t* feat, const uint32_t* tgt, const uint32_t* win, uint64_t n, uint32_t flags);
 int mcq_parts_builder_finish(mcq_parts_builder* b, mcq_parts** out);
 int mcq_parts_builder_free(mcq_parts_builder* b);
+
+/* ---- extending a table: `metacache_mpi modify DB GENOMES...` (main_mode_build_modify, src/mode_build.cpp:1117-1136) ----------
+ * The locations an existing database holds and the sketches of new sequences go through the pipeline of mcq_build_table together.
+ * mcq_table_extend_add takes the chunks mcq_shard_stream_next (include/mcq_host.h) hands out, as host pointers or as device
+ * pointers with MCQ_DEVICE_PTRS: every (feature, target, window) becomes the pipeline's pair, key = feature * n_ranks +
+ * target % n_ranks, value = global window of old_tgt_windows' prefix sums, appended on the device to one buffer in the order
+ * given.  Files may come in any order; the chunks of one file keep their order (a (feature, rank) group lies in one file, in one
+ * key record).  mcq_table_extend_finish counts the windows of the n_new_targets new sequences and sketches them (mcq_count_windows,
+ * mcq_sketch, with the descriptor's parameters: the database's), gives them the target ids n_old_targets, n_old_targets + 1, ...
+ * and global windows behind the old ones, puts their pairs BEHIND the old pairs and runs the pipeline: the sort is stable, so per
+ * (feature, rank) the old entries come first in their order and the first max_locs stay -- a bucket of the reference that is full
+ * takes nothing (add_all_window_sketches, src/sketch_database.h:1079-1097); a max_locs below the database's own shrinks every old
+ * bucket to its first max_locs entries (max_locations_per_feature, src/sketch_database.h:356-368); MCQ_BUILD_REMOVE_OVERPOPULATED
+ * is applied to old and new together.  *out is a table of n_old_targets + n_new_targets targets, as from mcq_build_table of all
+ * of them when the old database was built from the old ones in this order: win_off covers all targets, mcq_table_tgt_windows,
+ * mcq_table_rank_split and mcq_table_remove_ambiguous work on it unchanged.  n_new_targets = 0 (bases and seq_off may be NULL)
+ * gives the old table back, after the limit and the flag.  finish releases the handle when it succeeds.
+ * Limits: the one-piece pipeline only (no build in parts); old + new windows below 2^32 (MCQ_E_UNSUPPORTED); the pair buffer is
+ * sized once from expected_old_locations and grows by a sixteenth, by a copy, only when more arrive.  Device memory: 12 B per old
+ * location while the chunks are added; in finish 12 B per pair (old locations + new feature slots) twice while the old pairs are
+ * copied in front of the new ones, then the pipeline's ~44 B per pair at its peak.
+ * MCQ_E_ARG: a null argument, no rank, a triple that names a target or a window the descriptor does not have, an empty feature
+ * (0xFFFFFFFF); text in mcq_build_last_error.                                                                               */
+typedef struct {
+    uint32_t k, sketch_size, winlen, winstride;   /* the database's target sketcher                                         */
+    uint32_t n_ranks;                             /* P of the database (0 = 1)                                              */
+    uint32_t max_locs;                            /* per (feature, rank); 0 = 254                                           */
+    uint32_t flags;                               /* MCQ_BUILD_REMOVE_OVERPOPULATED                                         */
+    int32_t device;
+    uint32_t n_old_targets;
+    const uint32_t* old_tgt_windows;              /* host [n_old_targets]: mcq_refdb_tgt_windows                            */
+    uint64_t expected_old_locations;              /* sum of the shard files' location counts: sizes the pair buffer once    */
+} mcq_table_extend_desc;
+typedef struct mcq_table_extend mcq_table_extend;
+int mcq_table_extend_create(const mcq_table_extend_desc* desc, mcq_table_extend** out);
+int mcq_table_extend_add(mcq_table_extend* x, const uint32_t* feat, const uint32_t* tgt, const uint32_t* win, uint64_t n, uint32_t flags);
+int mcq_table_extend_finish(mcq_table_extend* x, const char* bases, const uint64_t* seq_off /* [n_new_targets + 1] */,
+                            uint32_t n_new_targets, uint32_t flags /* MCQ_DEVICE_PTRS: bases and seq_off are on the device */,
+                            mcq_table** out);
+int mcq_table_extend_free(mcq_table_extend* x);
 const char* mcq_build_last_error(void);
 
 /* ---- classification and per-taxon read counts on the device (csrc/mcq_classify.hip) ------------------------------------

@@ -18,6 +18,7 @@
  *   mcq_target_name / mcq_target_parent_taxid   extract_accession_string / extract_taxon_id   src/sequence_io.cpp:705-748
  *   mcq_genome_files    sequence_filenames               src/args_handling.cpp:50-90, src/filesys_utility.cpp:32-73
  *   mcq_genome_reader_* fasta_reader + add_targets_to_database   src/sequence_io.cpp:121-170, src/mode_build.cpp:559-647
+ *   mcq_genome_reader_open_after + mcq_refdb_taxa   the same on a database that was read (`modify`)   src/mode_build.cpp:1117-1136
  *
  * A taxon *key* is the index of the taxon in the database's taxon list; bit 31 marks a
  * sequence-level taxon (rank Sequence), 0xFFFFFFFF is "no taxon".  These are the keys
@@ -316,6 +317,19 @@ int mcq_genome_reader_next(mcq_genome_reader* r, char* bases, uint64_t cap, uint
 uint32_t mcq_genome_reader_n_targets(const mcq_genome_reader* r);
 int mcq_genome_reader_target(const mcq_genome_reader* r, uint32_t target, mcq_taxon_rec* rec, uint64_t* length);
 int mcq_genome_reader_close(mcq_genome_reader* r);
+/* The reader for sequences that are ADDED to a database (`modify`: add_to_database on a database that was read,
+ * src/mode_build.cpp:1117-1136): the names of the database's sequence-level taxa are taken before the first file is read
+ * (name2tax_, src/sketch_database.h:533-534, :938-943), and the target ids go on behind the database's: target i of this reader
+ * (i from 0, as mcq_genome_reader_target counts them) has the id n_old + i and the taxon id -(n_old + i + 1), n_old =
+ * info.n_targets of `existing` (from either opener; only read during this call).  mcq_genome_reader_n_skipped: records with
+ * sequence text that were passed over so far because their name was taken, by the database or earlier in this run.        */
+int mcq_genome_reader_open_after(const char* const* files, uint32_t n_files, uint64_t io_bytes, const mcq_refdb* existing,
+                                 mcq_genome_reader** out);
+uint64_t mcq_genome_reader_n_skipped(const mcq_genome_reader* r);
+/* every taxon record of an opened database in file order, as rank 0's file holds it (`windows` of a sequence-level taxon is
+ * non-zero only for the targets rank 0 owns; mcq_refdb_tgt_windows has every target's): out[n_taxa]; name and file point into
+ * the handle.  What a `modify` carries forward into the files it writes.                                                  */
+int mcq_refdb_taxa(const mcq_refdb* db, mcq_taxon_rec* out /* [n_taxa] */);
 
 /* default of -hitmin when unset: src/mode_query.cpp:247-259 */
 uint32_t mcq_default_hits_min(uint32_t sketch_size);

@@ -25,6 +25,19 @@
 // reads back the same), and the mapping of sequences to taxa through assembly_summary.txt / *.accession2taxid files: a target's
 // parent is the N of "taxid|N" in its header, or 0.  The sequences and the temporaries of the one-piece build must fit the
 // GPU (about 60 B per feature slot: tens of Gbp on one MI355X); MCQ_BUILD_TRACE=1 prints the times of the phases.
+//
+// -modify: `metacache_mpi modify DB NEW_GENOMES...` (main_mode_build_modify, src/mode_build.cpp:1117-1136: the database is read, its
+// build options are taken from it, then the same add_to_database runs) on DB.db_0 .. DB.db_<P-1> -- which the reference's own MPI
+// program cannot do on its sharded files (every rank opens DB.db).  The files are opened with mcq_refdb_open_meta: sketch parameters
+// and bucket limit come from there; every file is streamed into mcq_table_extend_* (include/mcq.h), the new genomes are read as above
+// by a reader that knows the database's names and target count (mcq_genome_reader_open_after), the extender's finish gives the union
+// table of old and new, and step 2b and 3 go on as in a build.  The taxon list: old and new sequence-level taxa, last target first,
+// then the dump's taxa with -taxonomy (reset_taxa_above_sequence_level), else the database's own above the sequences; the old
+// sequence-level taxa keep name, parent, file and index.  -max-locations-per-feature N > 0 becomes the files' limit (below the
+// database's value the old buckets are cut to their first N entries); without it the database's value stays.
+// DIVERGENCES of -modify: -kmerlen, -sketchlen, -winlen, -winstride that differ from the database's end the run before anything is
+// written (the reference parses them and goes on with the database's); every file is written as <name>.tmp and renamed once the last
+// one is written, so a run that fails leaves the database as it was; -out NEWDB writes a second database.
 #include "mcq_cli_common.hpp"
 #include "mcq_cli_buffers.hpp"
 
@@ -39,6 +52,8 @@ struct BuildOptions {
     bool remove_overpopulated = false;
     uint32_t ambig_rank = MCQ_RANK_NONE; int max_ambig = 1;                             // src/mode_build.cpp:74-75, :124-131
     int device = 0; uint32_t ranks_per_pass = 1; uint64_t read_buffer = 64u << 20;
+    bool modify = false; std::string out_db;                                            // -modify [-out NEWDB]
+    bool set_kmerlen = false, set_sketchlen = false, set_winlen = false, set_winstride = false, set_max_locs = false;
 };
 
 const char* kUsage =
@@ -55,8 +70,21 @@ const char* kUsage =
     "                 count as one); `none` or an unknown RANK leaves it off.  Divergence: the reference's `mpiexec -n P metacache_mpi\n"
     "                 build` accepts the options and ignores them; here they do what the reference documents\n"
     "  -ranks-per-pass R   ranks whose tables are in host memory at a time (default 1); -read-buffer: bytes of each of the two read buffers\n"
+    "       mcq_build_cli DB P NEW_GENOMES... -modify [-taxonomy DIR] [-remove-overpopulated-features] [-max-locations-per-feature N]\n"
+    "           [-remove-ambig-features RANK [-max-ambig-per-feature N]] [-out NEWDB] [-device D] [-ranks-per-pass R] [-read-buffer BYTES]\n"
+    "  -modify        adds the sequences of NEW_GENOMES to the existing DB.db_0 .. DB.db_<P-1> (`metacache_mpi modify DB GENOMES...`): the files\n"
+    "                 then hold what a build of the old and the new genomes together writes.  New sequences get the target ids behind the\n"
+    "                 old ones; a sequence whose name the database has, or that came earlier in this run, is skipped; a bucket keeps its first\n"
+    "                 -max-locations-per-feature entries, the old ones first (N below the database's value shrinks the old buckets, N becomes\n"
+    "                 the files' value; default: the database's); -remove-overpopulated-features works on old and new together; with -taxonomy\n"
+    "                 the taxa above the sequences are replaced by the dump's, without it they are kept.  k, sketch size, window length and\n"
+    "                 stride are the database's.  Divergences: -kmerlen / -sketchlen / -winlen / -winstride that differ from the database's\n"
+    "                 end the run (the reference parses and ignores them); the files are written under temporary names and renamed after\n"
+    "                 the last one, so a run that fails leaves DB as it was; -out NEWDB writes NEWDB.db_* and leaves DB untouched.\n"
+    "                 Limits: the old locations and the new sketches go through the one-piece build on the GPU together (about 12 B per old\n"
+    "                 location, then about 44 B per old location and new feature slot); fewer than 2^32 windows in all\n"
     "not supported: assembly_summary.txt / *.accession2taxid mapping files (a target's parent is the N of 'taxid|N' in its\n"
-    "header, else none), FASTQ genome files, adding to an existing database; the key order inside a file is not the reference's\n";
+    "header, else none), FASTQ genome files; the key order inside a file is not the reference's\n";
 
 bool parse(int argc, char** argv, BuildOptions& o) {
     for (int i = 1; i < argc; ++i) if (opt_named(argv[i], {"-help", "--help", "-h"})) { std::fputs(kUsage, stdout); return false; }
@@ -70,11 +98,13 @@ bool parse(int argc, char** argv, BuildOptions& o) {
         const std::string a = argv[i];
         auto next = [&]() -> const char* { return (i + 1 < argc) ? argv[++i] : ""; };
         if (opt_named(a, {"-taxonomy"})) o.taxonomy = next();
-        else if (opt_named(a, {"-kmerlen"})) o.kmerlen = std::atoi(next());
-        else if (opt_named(a, {"-sketchlen"})) o.sketchlen = std::atoi(next());
-        else if (opt_named(a, {"-winlen"})) o.winlen = std::atoi(next());
-        else if (opt_named(a, {"-winstride"})) o.winstride = std::atoi(next());
-        else if (opt_named(a, {"-max-locations-per-feature", "-max_locations_per_feature"})) o.max_locs = std::atoi(next());
+        else if (opt_named(a, {"-kmerlen"})) { o.kmerlen = std::atoi(next()); o.set_kmerlen = true; }
+        else if (opt_named(a, {"-sketchlen"})) { o.sketchlen = std::atoi(next()); o.set_sketchlen = true; }
+        else if (opt_named(a, {"-winlen"})) { o.winlen = std::atoi(next()); o.set_winlen = true; }
+        else if (opt_named(a, {"-winstride"})) { o.winstride = std::atoi(next()); o.set_winstride = true; }
+        else if (opt_named(a, {"-max-locations-per-feature", "-max_locations_per_feature"})) { o.max_locs = std::atoi(next()); o.set_max_locs = o.max_locs > 0; }
+        else if (opt_named(a, {"-modify"})) o.modify = true;
+        else if (opt_named(a, {"-out"})) o.out_db = next();
         else if (opt_named(a, {"-remove-overpopulated-features", "-remove_overpopulated_features"})) o.remove_overpopulated = true;
         else if (opt_named(a, {"-remove-ambig-features", "-remove_ambig_features"})) {
             const std::string name = next();
@@ -89,7 +119,9 @@ bool parse(int argc, char** argv, BuildOptions& o) {
     }
     if (o.P < 1 || o.P > 64) { std::fprintf(stderr, "ABORT: P must be 1..64\n"); return false; }
     if (o.inputs.empty()) { std::fprintf(stderr, "ABORT: Nothing to do - no reference sequences provided.\n"); return false; }
-    if (o.taxonomy.empty()) { std::fprintf(stderr, "ABORT: -taxonomy DIR is required\n"); return false; }
+    if (o.taxonomy.empty() && !o.modify) { std::fprintf(stderr, "ABORT: -taxonomy DIR is required\n"); return false; }
+    if (!o.out_db.empty() && !o.modify) { std::fprintf(stderr, "ABORT: -out NEWDB goes with -modify\n"); return false; }
+    if (!o.out_db.empty() && o.out_db.find(".db") == std::string::npos) o.out_db += ".db";
     if (o.winstride < 0) o.winstride = o.winlen - o.kmerlen + 1;             // src/mode_build.cpp:111
     if (o.winstride < 1) o.winstride = 1;                                    // src/sketch_database.h:321-324
     // -max-locations-per-feature N as the reference takes it: applied only if N > 0 (src/mode_build.cpp:658-660), then narrowed to
@@ -117,6 +149,24 @@ struct TaxDump { mcq_taxdump* h = nullptr; ~TaxDump() { mcq_taxdump_free(h); } }
 struct FileList { mcq_file_list* h = nullptr; ~FileList() { mcq_file_list_free(h); } };
 struct GenomeReader { mcq_genome_reader* h = nullptr; ~GenomeReader() { mcq_genome_reader_close(h); } };
 struct Table { mcq_table* h = nullptr; ~Table() { mcq_table_free(h); } void reset() { mcq_table_free(h); h = nullptr; } };
+struct RefDb { mcq_refdb* h = nullptr; ~RefDb() { mcq_refdb_close(h); } };
+struct ShardStream { mcq_shard_stream* h = nullptr; ~ShardStream() { mcq_shard_stream_close(h); } };
+struct Extender { mcq_table_extend* h = nullptr; ~Extender() { mcq_table_extend_free(h); } };
+// -modify writes its files under temporary names; they get their own once the last one is written: a run that ends before that
+// takes its temporary files away and leaves the database that was there.  (A build writes under the final names, as it always did.)
+struct OutFiles {
+    const bool temporary;
+    std::vector<std::pair<std::string, std::string>> names;      // (temporary, final)
+    bool kept = false;
+    explicit OutFiles(bool t) : temporary(t) {}
+    std::string add(const std::string& path) { if (!temporary) return path; names.emplace_back(path + ".tmp", path); return names.back().first; }
+    bool commit() {
+        for (const auto& n : names)
+            if (std::rename(n.first.c_str(), n.second.c_str())) { std::fprintf(stderr, "ABORT: can't rename %s to %s\n", n.first.c_str(), n.second.c_str()); return false; }
+        return kept = true;
+    }
+    ~OutFiles() { if (!kept) for (const auto& n : names) std::remove(n.first.c_str()); }
+};
 
 // one rank's table and taxon list in host memory
 struct RankOut {
@@ -133,6 +183,25 @@ int main(int argc, char** argv) {
     if (!parse(argc, argv, o)) return 2;
     Phases phase;
     MCQ_HIP(hipSetDevice(o.device), return 1);
+    // ---- 0. -modify: the database that is there -- its sketch parameters and bucket limit are the run's (get_build_options_from_db,
+    // src/mode_build.cpp:1117-1136); an option that asks for another sketch ends the run here, where the reference goes on with the
+    // database's value in silence
+    RefDb old;
+    mcq_refdb_info old_info; std::memset(&old_info, 0, sizeof(old_info));
+    if (o.modify) {
+        if (o.db.size() < 3 || o.db.compare(o.db.size() - 3, 3, ".db") != 0) { std::fprintf(stderr, "ABORT: -modify: the database name must end in .db (%s)\n", o.db.c_str()); return 1; }
+        if (mcq_refdb_open_meta(o.db.substr(0, o.db.size() - 3).c_str(), o.P, &old.h) || mcq_refdb_get_info(old.h, &old_info)) return host_fail();
+        const struct { const char* name; bool set; int asked; uint32_t has; } sk[] = {
+            {"-kmerlen", o.set_kmerlen, o.kmerlen, old_info.k}, {"-sketchlen", o.set_sketchlen, o.sketchlen, old_info.sketch_size},
+            {"-winlen", o.set_winlen, o.winlen, old_info.winlen}, {"-winstride", o.set_winstride, o.winstride, old_info.winstride}};
+        for (const auto& x : sk)
+            if (x.set && (int64_t)x.asked != (int64_t)x.has) {
+                std::fprintf(stderr, "ABORT: %s %d differs from the database's %u: -modify sketches with the database's parameters\n", x.name, x.asked, x.has);
+                return 1;
+            }
+        o.kmerlen = (int)old_info.k; o.sketchlen = (int)old_info.sketch_size; o.winlen = (int)old_info.winlen; o.winstride = (int)old_info.winstride;
+        if (!o.set_max_locs) o.max_locs = (int)std::min<uint32_t>(std::max<uint32_t>(old_info.max_locs_per_feature, 1), 254);
+    }
     {   // the kernels' limits, before anything is read or written: a key-less handle carries the sketching parameters
         mcq_db_desc sd; std::memset(&sd, 0, sizeof(sd));
         sd.k = (uint32_t)o.kmerlen; sd.sketch_size = (uint32_t)o.sketchlen; sd.winlen = (uint32_t)o.winlen; sd.winstride = (uint32_t)o.winstride;
@@ -143,7 +212,7 @@ int main(int argc, char** argv) {
         mcq_db_destroy(probe);
     }
     TaxDump tax;
-    if (mcq_taxdump_read(o.taxonomy.c_str(), &tax.h)) return host_fail();
+    if (!o.taxonomy.empty() && mcq_taxdump_read(o.taxonomy.c_str(), &tax.h)) return host_fail();      // (optional with -modify)
 
     // ---- 1. the sequences: files -> two pinned buffers in turn -> device memory, back to back
     FileList files;
@@ -160,7 +229,9 @@ int main(int argc, char** argv) {
         if (::stat(paths.back(), &st) == 0 && S_ISREG(st.st_mode)) total_bytes += (uint64_t)st.st_size;     // (a file holds at least its bases)
     }
     GenomeReader reader;
-    if (mcq_genome_reader_open(paths.data(), (uint32_t)paths.size(), std::min<uint64_t>(o.read_buffer, 16u << 20), &reader.h)) return host_fail();
+    const uint64_t io_bytes = std::min<uint64_t>(o.read_buffer, 16u << 20);
+    if (o.modify ? mcq_genome_reader_open_after(paths.data(), (uint32_t)paths.size(), io_bytes, old.h, &reader.h)
+                 : mcq_genome_reader_open(paths.data(), (uint32_t)paths.size(), io_bytes, &reader.h)) return host_fail();
     DeviceBuf<char> d_bases; PinnedBuf<char> stage[2]; Event copied[2]; Stream s_in;
     if (!d_bases.grow(total_bytes + 1) || !stage[0].grow(o.read_buffer) || !stage[1].grow(o.read_buffer) || !s_in.create() ||
         !copied[0].create() || !copied[1].create()) return 1;
@@ -177,24 +248,63 @@ int main(int argc, char** argv) {
         if (done) break;
     }
     MCQ_HIP(hipStreamSynchronize(s_in), return 1);
-    const uint32_t nt = mcq_genome_reader_n_targets(reader.h);
-    if (nt < 1) { std::fprintf(stderr, "ABORT: no reference sequence found in the genome files\n"); return 1; }
-    std::vector<mcq_taxon_rec> targets(nt);
-    std::vector<uint64_t> seq_off((size_t)nt + 1, 0);
-    for (uint32_t t = 0; t < nt; ++t) {
+    // targets: the database's (-modify), then the ones read now, with the ids that go on behind them
+    const uint32_t n_old = old_info.n_targets, n_new = mcq_genome_reader_n_targets(reader.h);
+    if ((uint64_t)n_old + n_new >= 0xFFFFFFFFull) { std::fprintf(stderr, "ABORT: more targets than a 32-bit target id holds\n"); return 1; }
+    const uint32_t nt = n_old + n_new;
+    if (nt < 1 || (!o.modify && n_new < 1)) { std::fprintf(stderr, "ABORT: no reference sequence found in the genome files\n"); return 1; }
+    std::vector<mcq_taxon_rec> targets(nt), old_taxa(old_info.n_taxa);
+    if (o.modify) {
+        if (mcq_refdb_taxa(old.h, old_taxa.data())) return host_fail();
+        std::vector<bool> seen(n_old, false);
+        for (const mcq_taxon_rec& x : old_taxa)
+            if (x.id < 0 && (uint64_t)(-x.id - 1) < n_old) { targets[(size_t)(-x.id - 1)] = x; targets[(size_t)(-x.id - 1)].windows = 0; seen[(size_t)(-x.id - 1)] = true; }
+        for (uint32_t t = 0; t < n_old; ++t)
+            if (!seen[t]) { std::fprintf(stderr, "ABORT: the database holds no taxon for its target %u\n", t); return 1; }
+    }
+    std::vector<uint64_t> seq_off((size_t)n_new + 1, 0);
+    for (uint32_t t = 0; t < n_new; ++t) {
         uint64_t len = 0;
-        if (mcq_genome_reader_target(reader.h, t, &targets[t], &len)) return host_fail();
+        if (mcq_genome_reader_target(reader.h, t, &targets[n_old + t], &len)) return host_fail();
         seq_off[t + 1] = seq_off[t] + len;
     }
     DeviceBuf<uint64_t> d_seq_off;
-    if (!d_seq_off.grow((uint64_t)nt + 1)) return 1;
-    MCQ_HIP(hipMemcpy(d_seq_off.p, seq_off.data(), ((size_t)nt + 1) * 8, hipMemcpyHostToDevice), return 1);
+    if (!d_seq_off.grow((uint64_t)n_new + 1)) return 1;
+    MCQ_HIP(hipMemcpy(d_seq_off.p, seq_off.data(), ((size_t)n_new + 1) * 8, hipMemcpyHostToDevice), return 1);
     stage[0] = PinnedBuf<char>(); stage[1] = PinnedBuf<char>();              // (the read buffers are not needed any more)
     phase("read");
 
     // ---- 2. the union of the P rank tables
     Table table;
-    {
+    if (o.modify) {
+        // what the files hold goes to the extender file by file, chunk by chunk (mcq_shard_stream_*), then the new sequences
+        std::vector<uint32_t> old_windows(n_old);
+        if (mcq_refdb_tgt_windows(old.h, old_windows.data())) return host_fail();
+        mcq_table_extend_desc d; std::memset(&d, 0, sizeof(d));
+        d.k = old_info.k; d.sketch_size = old_info.sketch_size; d.winlen = old_info.winlen; d.winstride = old_info.winstride;
+        d.n_ranks = o.P; d.max_locs = (uint32_t)o.max_locs; d.flags = o.remove_overpopulated ? MCQ_BUILD_REMOVE_OVERPOPULATED : 0; d.device = o.device;
+        d.n_old_targets = n_old; d.old_tgt_windows = old_windows.data(); d.expected_old_locations = old_info.n_locs;
+        Extender ext;
+        if (mcq_table_extend_create(&d, &ext.h)) { std::fprintf(stderr, "ABORT: %s\n", mcq_build_last_error()); return 1; }
+        uint64_t largest = 0;
+        for (uint32_t r = 0; r < o.P; ++r) { uint64_t nl = 0; if (mcq_refdb_file_stats(old.h, r, nullptr, nullptr, &nl)) return host_fail(); largest = std::max(largest, nl); }
+        const uint64_t chunk = std::min<uint64_t>(largest + 255, 1u << 22);           // (a chunk takes whole key records: at most 255 locations each)
+        PinnedBuf<uint32_t> cf, ct, cw;
+        if (!cf.grow(chunk) || !ct.grow(chunk) || !cw.grow(chunk)) return 1;
+        for (uint32_t r = 0; r < o.P; ++r) {
+            ShardStream in;
+            if (mcq_shard_stream_open(old.h, r, &in.h)) return host_fail();
+            for (;;) {
+                uint64_t n = 0;
+                if (mcq_shard_stream_next(in.h, cf.p, ct.p, cw.p, chunk, &n)) return host_fail();
+                if (!n) break;
+                if (mcq_table_extend_add(ext.h, cf.p, ct.p, cw.p, n, 0)) { std::fprintf(stderr, "ABORT: %s_%u: %s\n", o.db.c_str(), r, mcq_build_last_error()); return 1; }
+            }
+        }
+        phase("old locations");
+        if (mcq_table_extend_finish(ext.h, d_bases.p, d_seq_off.p, n_new, MCQ_DEVICE_PTRS, &table.h)) { std::fprintf(stderr, "ABORT: %s\n", mcq_build_last_error()); return 1; }
+        ext.h = nullptr;                                                         // (finish has released it)
+    } else {
         mcq_build_desc d; std::memset(&d, 0, sizeof(d));
         d.k = (uint32_t)o.kmerlen; d.sketch_size = (uint32_t)o.sketchlen; d.winlen = (uint32_t)o.winlen; d.winstride = (uint32_t)o.winstride;
         d.n_targets = nt; d.bases = d_bases.p; d.seq_off = d_seq_off.p; d.emulate_ranks = o.P; d.max_locs = (uint32_t)o.max_locs;
@@ -210,11 +320,14 @@ int main(int argc, char** argv) {
     // (src/taxonomy.h:290-294, :348)
     std::vector<mcq_taxon_rec> taxa;
     for (uint32_t t = nt; t-- > 0;) taxa.push_back(targets[t]);
-    for (uint64_t i = 0; i < mcq_taxdump_count(tax.h); ++i) taxa.push_back(mcq_taxdump_taxa(tax.h)[i]);
+    // (-modify: the taxa above the sequences are the dump's if one is given, reset_taxa_above_sequence_level; else the database's own)
+    if (tax.h) for (uint64_t i = 0; i < mcq_taxdump_count(tax.h); ++i) taxa.push_back(mcq_taxdump_taxa(tax.h)[i]);
+    else for (const mcq_taxon_rec& x : old_taxa) if (x.id >= 0) taxa.push_back(x);
+    const uint64_t n_above = taxa.size() - nt;
 
     // ---- 2b. -remove-ambig-features: once, on the union table (non_target_taxon_count() > 1, src/mode_build.cpp:729-730)
     std::string ambig_line;
-    if (o.ambig_rank < MCQ_RANK_NONE && mcq_taxdump_count(tax.h) > 1) {
+    if (o.ambig_rank < MCQ_RANK_NONE && n_above > 1) {
         std::vector<uint32_t> tgt_key(nt);
         if (o.ambig_rank == MCQ_RANK_SEQUENCE) for (uint32_t t = 0; t < nt; ++t) tgt_key[t] = t;
         else if (mcq_taxa_clade_keys(taxa.data(), taxa.size(), nt, o.ambig_rank, tgt_key.data())) return host_fail();
@@ -232,9 +345,12 @@ int main(int argc, char** argv) {
     }
 
     // ---- 3. rank by rank: split on the device, copy, write
+    const std::string& out_db = o.out_db.empty() ? o.db : o.out_db;
+    OutFiles files_out(o.modify);
     mcq_shard_params sp;
     sp.k = sp.q_k = (uint64_t)o.kmerlen; sp.sketch_size = sp.q_sketch_size = (uint64_t)o.sketchlen;     // the query sketcher starts as the target
     sp.winlen = sp.q_winlen = (uint64_t)o.winlen; sp.winstride = sp.q_winstride = (uint64_t)o.winstride;   // sketcher (src/sketch_database.h:247-260)
+    if (o.modify) { sp.q_sketch_size = old_info.q_sketch_size; sp.q_winlen = old_info.q_winlen; sp.q_winstride = old_info.q_winstride; }     // (the query sketcher stays the database's)
     sp.max_locs_per_feature = (uint64_t)o.max_locs;
     double t_split = 0, t_write = 0;
     uint64_t keys_total = 0, locs_total = 0;
@@ -255,7 +371,7 @@ int main(int argc, char** argv) {
             if (R.n_locs) MCQ_HIP(hipMemcpy(R.locs.p, dl, R.n_locs * 8, hipMemcpyDeviceToHost), return 1);
             R.taxa = taxa;
             for (uint32_t t = r; t < nt; t += o.P) R.taxa[nt - 1 - t].windows = windows[t];
-            R.path = o.db + "_" + std::to_string(r);                         // src/mode_build.cpp:1079-1082
+            R.path = files_out.add(out_db + "_" + std::to_string(r));      // src/mode_build.cpp:1079-1082
             keys_total += R.n_keys; locs_total += R.n_locs;
         }
         const auto tb = std::chrono::steady_clock::now();
@@ -272,8 +388,10 @@ int main(int argc, char** argv) {
         t_split += std::chrono::duration<double>(tb - ta).count(); t_write += std::chrono::duration<double>(tc - tb).count();
     }
     if (phase.on) std::fprintf(stderr, "[mcq_build_cli] %-28s %8.3f s\n[mcq_build_cli] %-28s %8.3f s\n", "rank split", t_split, "write", t_write);
+    if (!files_out.commit()) return 1;
+    if (o.modify) std::printf("%u sequences added to %u, %llu skipped (their names were taken)\n", n_new, n_old, (unsigned long long)mcq_genome_reader_n_skipped(reader.h));
     std::fputs(ambig_line.c_str(), stdout);
-    std::printf("%u targets, %llu bases -> %u files %s_0 .. _%u: %llu keys, %llu locations\n", nt, (unsigned long long)n_bases, o.P, o.db.c_str(),
+    std::printf("%u targets, %llu bases -> %u files %s_0 .. _%u: %llu keys, %llu locations\n", nt, (unsigned long long)n_bases, o.P, out_db.c_str(),
                 o.P - 1, (unsigned long long)keys_total, (unsigned long long)locs_total);
     return 0;
 }

@@ -385,6 +385,15 @@ extern "C" int64_t mcq_refdb_taxon_parent(const mcq_refdb* db, uint32_t key) { r
 extern "C" const char* mcq_refdb_taxon_file(const mcq_refdb* db, uint32_t key) { return valid_key(db, key) ? db->taxa[key & 0x7FFFFFFFu].file.c_str() : ""; }
 extern "C" uint64_t mcq_refdb_taxon_index(const mcq_refdb* db, uint32_t key) { return valid_key(db, key) ? db->taxa[key & 0x7FFFFFFFu].index : 0; }
 extern "C" uint64_t mcq_refdb_taxon_windows(const mcq_refdb* db, uint32_t key) { return valid_key(db, key) ? db->taxa[key & 0x7FFFFFFFu].windows : 0; }
+extern "C" int mcq_refdb_taxa(const mcq_refdb* db, mcq_taxon_rec* out) {
+    if (!db || (!out && !db->taxa.empty())) return fail("bad argument");
+    for (size_t i = 0; i < db->taxa.size(); ++i) {
+        const Taxon& t = db->taxa[i];
+        out[i].id = t.id; out[i].parent = t.parent; out[i].rank = t.rank; out[i].name = t.name.c_str(); out[i].file = t.file.c_str();
+        out[i].index = t.index; out[i].windows = t.windows;
+    }
+    return 0;
+}
 extern "C" uint32_t mcq_refdb_ancestor(const mcq_refdb* db, uint32_t key, uint32_t rank) {
     if (!valid_key(db, key) || rank >= (uint32_t)kNumRanks) return MCQ_NO_TAXON;
     return db->lineage[(size_t)(key & 0x7FFFFFFFu) * kNumRanks + rank];

@@ -318,6 +318,8 @@ struct mcq_genome_reader {
     struct Target { std::string name; int64_t parent; uint32_t file; uint64_t index, length; };
     std::vector<Target> targets;
     std::set<std::string> names;
+    uint32_t first_target = 0;         // mcq_genome_reader_open_after: the targets of the database come before this reader's
+    uint64_t n_skipped = 0;
     ~mcq_genome_reader() { if (fd >= 0) ::close(fd); }
     void leave_file() { if (fd >= 0) ::close(fd); fd = -1; }
     bool open_next() {                 // false: no file left
@@ -340,6 +342,20 @@ extern "C" int mcq_genome_reader_open(const char* const* files, uint32_t n_files
     *out = r;
     return 0;
 }
+
+extern "C" int mcq_genome_reader_open_after(const char* const* files, uint32_t n_files, uint64_t io_bytes, const mcq_refdb* existing,
+                                            mcq_genome_reader** out) {
+    mcq_refdb_info info;
+    if (!existing || mcq_refdb_get_info(existing, &info)) return fail("null argument");
+    mcq_genome_reader* r = nullptr;
+    if (mcq_genome_reader_open(files, n_files, io_bytes, &r)) return -1;
+    for (uint32_t i = 0; i < info.n_taxa; ++i)                                 // name2tax_ of a database that was read (src/sketch_database.h:938-943)
+        if (mcq_refdb_taxon_rank(existing, i) == MCQ_RANK_SEQUENCE) r->names.insert(mcq_refdb_taxon_name(existing, i));
+    r->first_target = info.n_targets;
+    *out = r;
+    return 0;
+}
+extern "C" uint64_t mcq_genome_reader_n_skipped(const mcq_genome_reader* r) { return r ? r->n_skipped : 0; }
 
 extern "C" int mcq_genome_reader_next(mcq_genome_reader* r, char* bases, uint64_t cap, uint64_t* n_bases, int32_t* done) {
     if (!r || (cap && !bases) || !n_bases || !done) return fail("null argument");
@@ -390,9 +406,9 @@ extern "C" int mcq_genome_reader_next(mcq_genome_reader* r, char* bases, uint64_
         if (stop > r->pos) {
             if (r->rec == mcq_genome_reader::PENDING) {
                 std::string name = target_name(r->header);
-                if (r->names.count(name)) r->rec = mcq_genome_reader::SKIPPED;
+                if (r->names.count(name)) { r->rec = mcq_genome_reader::SKIPPED; ++r->n_skipped; }
                 else {
-                    if (r->targets.size() >= 0xFFFFFFFFull) return fail("more targets than a 32-bit target id holds");
+                    if ((uint64_t)r->first_target + r->targets.size() >= 0xFFFFFFFFull) return fail("more targets than a 32-bit target id holds");
                     r->names.insert(name);
                     const int64_t parent = header_taxid(r->header);
                     r->targets.push_back({std::move(name), parent < 1 ? 0 : parent, (uint32_t)(r->next_file - 1), r->index, 0});
@@ -417,7 +433,7 @@ extern "C" int mcq_genome_reader_target(const mcq_genome_reader* r, uint32_t t, 
     if (!r || t >= r->targets.size()) return fail("no such target");
     const mcq_genome_reader::Target& x = r->targets[t];
     if (rec) {
-        rec->id = -(int64_t)t - 1; rec->parent = x.parent; rec->rank = (uint8_t)MCQ_RANK_SEQUENCE; rec->name = x.name.c_str();
+        rec->id = -((int64_t)r->first_target + t) - 1; rec->parent = x.parent; rec->rank = (uint8_t)MCQ_RANK_SEQUENCE; rec->name = x.name.c_str();
         rec->file = r->files[x.file].c_str(); rec->index = x.index; rec->windows = 0;
     }
     if (length) *length = x.length;

@@ -46,6 +46,20 @@ template <class T> struct Dev {
     void reset() { if (p) (void)hipFree(p); p = nullptr; }
     T* release() { T* q = p; p = nullptr; return q; }
 };
+// The same from the device's default memory pool, in stream 0: what a handle gathers over several calls and then hands to a
+// pipeline whose temporaries come from that pool (Scratch below) -- given back, its memory serves the pipeline's next buffer instead
+// of being unmapped by a hipFree in the middle of a build.
+template <class T> struct PoolDev {
+    T* p = nullptr;
+    PoolDev() = default;
+    PoolDev(PoolDev&& o) noexcept : p(o.release()) {}
+    PoolDev& operator=(PoolDev&& o) noexcept { if (this != &o) { reset(); p = o.release(); } return *this; }
+    ~PoolDev() { reset(); }
+    hipError_t alloc(u64 n) { reset(); return hipMallocAsync((void**)&p, (n ? n : 1) * sizeof(T), 0); }
+    T* get() const { return p; }
+    void reset() { if (p) (void)hipFreeAsync(p, 0); p = nullptr; }
+    T* release() { T* q = p; p = nullptr; return q; }
+};
 // a half-built handle: freed by its own *_free / mcq_db_destroy unless released into *out
 template <class H, int (*Free)(H*)> struct HandleFree { void operator()(H* h) const { (void)Free(h); } };
 typedef std::unique_ptr<mcq_table, HandleFree<mcq_table, mcq_table_free>> TablePtr;
@@ -783,6 +797,219 @@ extern "C" int mcq_parts_builder_finish(mcq_parts_builder* b, mcq_parts** out) {
     }
     *out = R.release();
     mcq_parts_builder_free(b);
+    return MCQ_OK;
+}
+
+// ---- a table extended by new sequences: `modify` (mcq_table_extend_* of include/mcq.h) ------------------------------------------
+// What the database holds arrives as the triples of its shard files and becomes the pairs of the pipeline above, appended in
+// the order given: a (feature, rank) group lies in one file, inside one key record, so it stays in the order of its bucket.
+// finish() sketches the new sequences, makes their pairs with target ids and global windows that go on behind the old ones,
+// puts them behind the old pairs and runs sort_truncate: the stable sort keeps the old entries of a group first, the cut at
+// max_locs is the reference's bucket limit on an append (src/sketch_database.h:1090-1092).
+struct mcq_table_extend {
+    int device = 0; u32 k = 0, s = 0, winlen = 0, winstride = 0, P = 1, max_locs = 254, flags = 0;
+    u32 n_old = 0; u64 n_old_win = 0;
+    Dev<u32> tgt_windows;             // device [n_old]
+    Dev<u64> win_off;                 // device [n_old + 1]: first global window of every old target
+    PoolDev<u64> key; PoolDev<u32> val; u64 n = 0, cap = 0;     // the old pairs
+    Dev<u32> d_feat, d_tgt, d_win; u64 stage_cap = 0;
+    Dev<u32> d_bad;                   // triples of a chunk that name nothing the database has
+};
+typedef std::unique_ptr<mcq_table_extend, HandleFree<mcq_table_extend, mcq_table_extend_free>> ExtendPtr;
+namespace {
+__global__ void k_win_off(const u32* tgt_windows, u32 nt, u64* win_off) {      // (one thread, as k_gwoff)
+    if (blockIdx.x || threadIdx.x) return;
+    u64 acc = 0;
+    for (u32 t = 0; t < nt; ++t) { win_off[t] = acc; acc += tgt_windows[t]; }
+    win_off[nt] = acc;
+}
+// triple i of a chunk -> pair at + i (the caller has made room for the whole chunk)
+__global__ void k_triple_pairs(const u32* feat, const u32* tgt, const u32* win, u64 n, const u32* tgt_windows, const u64* win_off, u32 nt, u32 P,
+                               u64* key, u32* val, u32* bad) {
+    const u64 stride = (u64)gridDim.x * blockDim.x;
+    for (u64 i = (u64)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) {
+        const u32 f = feat[i], t = tgt[i], w = win[i];
+        if (f == 0xFFFFFFFFu || t >= nt || w >= tgt_windows[t]) { key[i] = ~0ull; val[i] = 0; atomicAdd(bad, 1u); continue; }
+        key[i] = (u64)f * P + (t % P);
+        val[i] = (u32)(win_off[t] + w);
+    }
+}
+// k_make_pairs for sequences that go on behind others: win_off counts from the first new window, target ids from tgt_base,
+// global windows from win_base (a kernel of its own: the from-scratch build keeps the one it has)
+__global__ void k_make_pairs_after(const u32* feat, u64 n_slots, u32 s, const u64* win_off, u32 n_targets, u32 P, u32 tgt_base, u64 win_base,
+                                   u64* key, u32* val) {
+    const u64 stride = (u64)gridDim.x * blockDim.x;
+    for (u64 i = (u64)blockIdx.x * blockDim.x + threadIdx.x; i < n_slots; i += stride) {
+        const u32 f = feat[i];
+        const u64 w = i / s;
+        if (f == 0xFFFFFFFFu) { key[i] = ~0ull; val[i] = 0; continue; }
+        const u32 t = tgt_base + target_of(win_off, n_targets, w);
+        key[i] = (u64)f * P + (t % P);
+        val[i] = (u32)(win_base + w);
+    }
+}
+__global__ void k_shift_up(const u64* in, u64 n, u64 base, u64* out) {
+    const u64 i = (u64)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < n) out[i] = in[i] + base;
+}
+}  // namespace
+
+extern "C" int mcq_table_extend_free(mcq_table_extend* x) {
+    if (!x) return MCQ_OK;
+    (void)hipSetDevice(x->device);
+    delete x;
+    (void)hipStreamSynchronize(0);                              // (the pair buffer goes back to the pool in stream 0)
+    return MCQ_OK;
+}
+
+extern "C" int mcq_table_extend_create(const mcq_table_extend_desc* d, mcq_table_extend** out) {
+    if (!d || !out || (d->n_old_targets && !d->old_tgt_windows)) return bfail(MCQ_E_ARG, "null argument");
+    if (d->flags & ~(uint32_t)MCQ_BUILD_REMOVE_OVERPOPULATED) return bfail(MCQ_E_ARG, "flags other than MCQ_BUILD_REMOVE_OVERPOPULATED");
+    u64 total = 0;
+    for (u32 t = 0; t < d->n_old_targets; ++t) total += d->old_tgt_windows[t];
+    if (total >= (1ull << 32)) return bfail(MCQ_E_UNSUPPORTED, "more than 2^32 windows");
+    if (d->expected_old_locations >= (1ull << 40)) return bfail(MCQ_E_UNSUPPORTED, "2^40 locations or more: the one-piece pipeline does not hold them");
+    {   // the sketch parameters are refused here, before the database is read
+        mcq_build_desc bd; std::memset(&bd, 0, sizeof(bd));
+        bd.k = d->k; bd.sketch_size = d->sketch_size; bd.winlen = d->winlen; bd.winstride = d->winstride; bd.device = d->device;
+        BCHK(hipSetDevice(d->device));
+        if (!make_sketch_handle(&bd)) return MCQ_E_ARG;
+    }
+    ExtendPtr x(new mcq_table_extend());
+    x->device = d->device; x->k = d->k; x->s = d->sketch_size; x->winlen = d->winlen; x->winstride = d->winstride;
+    x->P = d->n_ranks ? d->n_ranks : 1; x->max_locs = d->max_locs ? d->max_locs : 254; x->flags = d->flags;
+    x->n_old = d->n_old_targets; x->n_old_win = total;
+    BCHK(x->tgt_windows.alloc(x->n_old)); BCHK(x->win_off.alloc((u64)x->n_old + 1)); BCHK(x->d_bad.alloc(1));
+    if (x->n_old) BCHK(hipMemcpy(x->tgt_windows.get(), d->old_tgt_windows, (u64)x->n_old * 4, hipMemcpyHostToDevice));
+    hipLaunchKernelGGL(k_win_off, dim3(1), dim3(1), 0, 0, (const u32*)x->tgt_windows.get(), x->n_old, x->win_off.get());
+    x->cap = d->expected_old_locations;
+    BCHK(x->key.alloc(x->cap)); BCHK(x->val.alloc(x->cap));
+    BCHK(hipDeviceSynchronize());
+    BCHK(hipGetLastError());
+    *out = x.release();
+    return MCQ_OK;
+}
+
+extern "C" int mcq_table_extend_add(mcq_table_extend* x, const uint32_t* feat, const uint32_t* tgt, const uint32_t* win, uint64_t n, uint32_t flags) {
+    if (!x || (n && (!feat || !tgt || !win))) return bfail(MCQ_E_ARG, "null argument");
+    if (!n) return MCQ_OK;
+    if (n >= (1ull << 31)) return bfail(MCQ_E_ARG, "a chunk holds fewer than 2^31 triples");
+    BCHK(hipSetDevice(x->device));
+    if (x->n + n > x->cap) {
+        // more than the caller expected: room for this chunk and a sixteenth more, the pairs so far copied over
+        const u64 ncap = x->n + n + std::max<u64>(x->cap / 16, 1u << 20);
+        PoolDev<u64> nk; PoolDev<u32> nv;
+        BCHK(nk.alloc(ncap)); BCHK(nv.alloc(ncap));
+        if (x->n) {
+            BCHK(hipMemcpyAsync(nk.get(), x->key.get(), x->n * 8, hipMemcpyDeviceToDevice, 0));
+            BCHK(hipMemcpyAsync(nv.get(), x->val.get(), x->n * 4, hipMemcpyDeviceToDevice, 0));
+        }
+        x->key = std::move(nk); x->val = std::move(nv);           // (gives the old ones back, behind the copies in stream 0)
+        x->cap = ncap;
+    }
+    const u32 *df = feat, *dt = tgt, *dw = win;
+    if (!(flags & MCQ_DEVICE_PTRS)) {
+        if (n > x->stage_cap) {
+            x->d_feat.reset(); x->d_tgt.reset(); x->d_win.reset(); x->stage_cap = 0;      // (all three go before the larger ones come)
+            BCHK(x->d_feat.alloc(n)); BCHK(x->d_tgt.alloc(n)); BCHK(x->d_win.alloc(n));
+            x->stage_cap = n;
+        }
+        df = x->d_feat.get(); dt = x->d_tgt.get(); dw = x->d_win.get();
+        BCHK(hipMemcpyAsync(x->d_feat.get(), feat, n * 4, hipMemcpyHostToDevice, 0));
+        BCHK(hipMemcpyAsync(x->d_tgt.get(), tgt, n * 4, hipMemcpyHostToDevice, 0));
+        BCHK(hipMemcpyAsync(x->d_win.get(), win, n * 4, hipMemcpyHostToDevice, 0));
+    }
+    BCHK(hipMemsetAsync(x->d_bad.get(), 0, 4, 0));
+    hipLaunchKernelGGL(k_triple_pairs, grid_for(n), dim3(TB), 0, 0, df, dt, dw, n, (const u32*)x->tgt_windows.get(), (const u64*)x->win_off.get(),
+                       x->n_old, x->P, x->key.get() + x->n, x->val.get() + x->n, x->d_bad.get());
+    u32 bad = 0;
+    BCHK(hipMemcpy(&bad, x->d_bad.get(), 4, hipMemcpyDeviceToHost));      // (waits for the kernel: the caller's buffers are free again)
+    BCHK(hipGetLastError());
+    if (bad) return bfail(MCQ_E_ARG, std::to_string(bad) + " triples name a target or a window the database does not have");
+    x->n += n;
+    return MCQ_OK;
+}
+
+extern "C" int mcq_table_extend_finish(mcq_table_extend* x, const char* bases, const uint64_t* seq_off, uint32_t n_new_targets, uint32_t flags,
+                                       mcq_table** out) {
+    if (!x || !out || (n_new_targets && (!seq_off || !bases))) return bfail(MCQ_E_ARG, "null argument");
+    const u32 nn = n_new_targets;
+    if ((u64)x->n_old + nn >= 0xFFFFFFFFull) return bfail(MCQ_E_UNSUPPORTED, "more targets than a 32-bit target id holds");
+    BCHK(hipSetDevice(x->device));
+    Scratch tmpbuf;
+    BCHK(tmpbuf.init(x->device));
+    PhaseTrace phase;
+    x->d_feat.reset(); x->d_tgt.reset(); x->d_win.reset(); x->stage_cap = 0;
+    const u32 nt = x->n_old + nn, s = x->s;
+
+    TablePtr T(new mcq_table());
+    T->device = x->device; T->n_targets = nt;
+    BCHK(T->win_off.alloc((u64)nt + 1));
+    u64* const win_off = T->win_off.get();
+    BCHK(hipMemcpy(win_off, x->win_off.get(), ((u64)x->n_old + 1) * 8, hipMemcpyDeviceToDevice));
+
+    // the new sequences: windows and sketches, counted from their own first window
+    u64 n_new_win = 0;
+    u32* feat = nullptr; u64* new_off = nullptr;
+    char* t_bases = nullptr; u64* t_off = nullptr;
+    if (nn) {
+        if (!(flags & MCQ_DEVICE_PTRS)) {
+            const u64 nb = seq_off[nn];
+            BCHK(tmpbuf.get(&t_bases, nb ? nb : 1)); BCHK(tmpbuf.get(&t_off, (u64)(nn + 1) * 8));
+            if (nb) BCHK(hipMemcpy(t_bases, bases, nb, hipMemcpyHostToDevice));
+            BCHK(hipMemcpy(t_off, seq_off, (u64)(nn + 1) * 8, hipMemcpyHostToDevice));
+            bases = t_bases; seq_off = t_off;
+        }
+        mcq_build_desc bd; std::memset(&bd, 0, sizeof(bd));
+        bd.k = x->k; bd.sketch_size = s; bd.winlen = x->winlen; bd.winstride = x->winstride; bd.device = x->device;
+        DbPtr sk = make_sketch_handle(&bd);
+        if (!sk) return MCQ_E_ARG;
+        BCHK(tmpbuf.get(&new_off, (u64)(nn + 1) * 8));
+        mcq_batch b; b.n_seqs = nn; b.bases = bases; b.seq_off = seq_off; b.paired = 0; b.flags = MCQ_DEVICE_PTRS; b.n_bases = 0;
+        MCHK(mcq_count_windows(sk.get(), &b, new_off, nullptr));
+        BCHK(hipMemcpy(&n_new_win, new_off + nn, 8, hipMemcpyDeviceToHost));
+        if (x->n_old_win + n_new_win >= (1ull << 32)) return bfail(MCQ_E_UNSUPPORTED, "more than 2^32 windows");
+        u32* nfeat = nullptr;
+        BCHK(tmpbuf.get(&feat, std::max<u64>(1, n_new_win * s) * 4)); BCHK(tmpbuf.get(&nfeat, std::max<u64>(1, n_new_win) * 4));
+        MCHK(mcq_sketch(sk.get(), &b, new_off, feat, nfeat, nullptr));
+        hipLaunchKernelGGL(k_shift_up, dim3((nn + 1 + TB - 1) / TB), dim3(TB), 0, 0, (const u64*)new_off, (u64)nn + 1, x->n_old_win, win_off + x->n_old);
+        BCHK(hipDeviceSynchronize());
+        tmpbuf.put(nfeat);
+    }
+    phase("windows + sketches (new)");
+
+    // old pairs, then the new ones, in one buffer of the pipeline's own kind
+    const u64 n_new = n_new_win * s, n = x->n + n_new;
+    u64* key = nullptr; u32* val = nullptr;
+    BCHK(tmpbuf.get(&key, (n ? n : 1) * 8)); BCHK(tmpbuf.get(&val, (n ? n : 1) * 4));
+    if (x->n) {
+        BCHK(hipMemcpyAsync(key, x->key.get(), x->n * 8, hipMemcpyDeviceToDevice, 0));
+        BCHK(hipMemcpyAsync(val, x->val.get(), x->n * 4, hipMemcpyDeviceToDevice, 0));
+    }
+    if (n_new) hipLaunchKernelGGL(k_make_pairs_after, grid_for(n_new), dim3(TB), 0, 0, (const u32*)feat, n_new, s, (const u64*)new_off, nn, x->P,
+                                  x->n_old, x->n_old_win, key + x->n, val + x->n);
+    BCHK(hipDeviceSynchronize());
+    BCHK(hipGetLastError());
+    x->key.reset(); x->val.reset(); x->cap = 0; x->n = 0;        // (the pipeline owns the pairs from here on: an error below ends the extension)
+    if (feat) tmpbuf.put(feat);
+    if (new_off) tmpbuf.put(new_off);
+    if (t_bases) tmpbuf.put(t_bases);
+    if (t_off) tmpbuf.put(t_off);
+    phase("pairs (old + new)");
+    Lists L;
+    MCHK(sort_truncate(tmpbuf, key, val, n, x->P, x->max_locs, (x->flags & MCQ_BUILD_REMOVE_OVERPOPULATED) != 0, L, phase));
+    // keys, offsets, (target, window) locations over all targets (as mcq_build_table ends, whose text stays what it was)
+    T->n_keys = L.n_keys; T->n_locs = L.n_kept;
+    BCHK(T->keys.alloc(L.n_keys)); BCHK(T->list_off.alloc(L.n_keys + 1));
+    BCHK(T->locs.alloc(L.n_kept));
+    if (L.n_kept) hipLaunchKernelGGL(k_emit, grid_for(L.n_kept), dim3(TB), 0, 0, L.fw, L.head, L.kid, L.n_kept, L.n_keys, win_off, nt, T->keys.get(), T->list_off.get(), T->locs.get());
+    else BCHK(hipMemset(T->list_off.get(), 0, 8));
+    BCHK(hipDeviceSynchronize());
+    BCHK(hipGetLastError());
+    tmpbuf.put(L.fw); tmpbuf.put(L.head); tmpbuf.put(L.kid);
+    phase("emit keys / offsets / locations");
+    *out = T.release();
+    mcq_table_extend_free(x);
     return MCQ_OK;
 }
 

@@ -105,6 +105,12 @@ class PartsBuilderDesc(C.Structure):
                 ("n_ranges", C.c_uint32), ("n_shards", C.c_uint32), ("shard_id", C.c_uint32), ("device", C.c_int32)]
 
 
+class TableExtendDesc(C.Structure):
+    _fields_ = [("k", C.c_uint32), ("sketch_size", C.c_uint32), ("winlen", C.c_uint32), ("winstride", C.c_uint32),
+                ("n_ranks", C.c_uint32), ("max_locs", C.c_uint32), ("flags", C.c_uint32), ("device", C.c_int32),
+                ("n_old_targets", C.c_uint32), ("old_tgt_windows", C.c_void_p), ("expected_old_locations", C.c_uint64)]
+
+
 class ShardCfg(C.Structure):
     _fields_ = [("n_ranks", C.c_uint32), ("rank", C.c_uint32), ("max_queries", C.c_uint64), ("max_seqs", C.c_uint64),
                 ("max_bases", C.c_uint64), ("max_locs_per_query", C.c_uint64), ("max_features_per_peer", C.c_uint64),
@@ -177,6 +183,11 @@ def lib():
             L.mcq_parts_builder_add.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint32]
             L.mcq_parts_builder_finish.argtypes = [C.c_void_p, C.POINTER(C.c_void_p)]
             L.mcq_parts_builder_free.argtypes = [C.c_void_p]
+        if hasattr(L, "mcq_table_extend_create"):           # (as above: a parent's library in a same-box A/B has none)
+            L.mcq_table_extend_create.argtypes = [C.POINTER(TableExtendDesc), C.POINTER(C.c_void_p)]
+            L.mcq_table_extend_add.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint32]
+            L.mcq_table_extend_finish.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.POINTER(C.c_void_p)]
+            L.mcq_table_extend_free.argtypes = [C.c_void_p]
         L.mcq_reduce.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p,
                                  C.POINTER(QueryOpts), C.POINTER(Result), C.c_void_p]
         L.mcq_packed_bytes.restype = C.c_uint64; L.mcq_packed_bytes.argtypes = [C.c_uint64]
@@ -897,6 +908,54 @@ class PartsBuilder:
     def close(self):
         if getattr(self, "h", None):
             lib().mcq_parts_builder_free(self.h); self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class TableExtend:
+    """mcq_table_extend_*: the locations of an existing database (chunks of (feature, target, window) triples, as
+    host.RefDb(meta_only=True).stream() yields them) and new sequences through the build pipeline together -- `modify`.
+    finish() returns a Table of the old and the new targets."""
+
+    def __init__(self, old_tgt_windows, n_ranks=1, k=16, sketch_size=16, winlen=128, winstride=113, max_locs=0, flags=0,
+                 expected_old_locations=0, device=0):
+        tw = np.ascontiguousarray(old_tgt_windows, np.uint32)
+        d = TableExtendDesc(k, sketch_size, winlen, winstride, n_ranks, max_locs, flags, device, len(tw),
+                            tw.ctypes.data_as(C.c_void_p) if len(tw) else None, expected_old_locations)
+        h = C.c_void_p()
+        rc = lib().mcq_table_extend_create(C.byref(d), C.byref(h))
+        if rc != 0:
+            raise McqError(rc, (lib().mcq_build_last_error() or b"").decode())
+        self.h, self.n_old_targets, self.device = h, len(tw), device
+
+    def add(self, feat, tgt, win, n=None):
+        """a chunk: three numpy u32 arrays (host), or three raw device pointers (int) and the count n"""
+        if n is None:
+            f, t, w = (np.ascontiguousarray(x, np.uint32) for x in (feat, tgt, win))
+            ptrs, n, flags = [x.ctypes.data_as(C.c_void_p) for x in (f, t, w)], len(f), 0
+        else:
+            ptrs, flags = [C.c_void_p(int(x)) for x in (feat, tgt, win)], MCQ_DEVICE_PTRS
+        rc = lib().mcq_table_extend_add(self.h, ptrs[0], ptrs[1], ptrs[2], n, flags)
+        if rc != 0:
+            raise McqError(rc, (lib().mcq_build_last_error() or b"").decode())
+
+    def finish(self, bases_ptr, seq_off_ptr, n_new_targets, device_ptrs=True):
+        th = C.c_void_p()
+        rc = lib().mcq_table_extend_finish(self.h, bases_ptr, seq_off_ptr, n_new_targets, MCQ_DEVICE_PTRS if device_ptrs else 0, C.byref(th))
+        if rc != 0:
+            raise McqError(rc, (lib().mcq_build_last_error() or b"").decode())
+        self.h = None                                           # (released by the call)
+        t = Table.__new__(Table)
+        t._adopt(th, self.n_old_targets + n_new_targets, self.device)
+        return t
+
+    def close(self):
+        if getattr(self, "h", None):
+            lib().mcq_table_extend_free(self.h); self.h = None
 
     def __del__(self):
         try:

@@ -146,6 +146,9 @@ def lib():
         L.mcq_genome_reader_n_targets.restype = C.c_uint32; L.mcq_genome_reader_n_targets.argtypes = [C.c_void_p]
         L.mcq_genome_reader_target.argtypes = [C.c_void_p, C.c_uint32, C.POINTER(TaxonRec), C.POINTER(C.c_uint64)]
         L.mcq_genome_reader_close.argtypes = [C.c_void_p]
+        L.mcq_genome_reader_open_after.argtypes = [C.POINTER(C.c_char_p), C.c_uint32, C.c_uint64, C.c_void_p, C.POINTER(C.c_void_p)]
+        L.mcq_genome_reader_n_skipped.restype = C.c_uint64; L.mcq_genome_reader_n_skipped.argtypes = [C.c_void_p]
+        L.mcq_refdb_taxa.argtypes = [C.c_void_p, C.POINTER(TaxonRec)]
         _lib = L
     return _lib
 
@@ -238,6 +241,13 @@ class RefDb:
         """(file, index, windows) of a taxon record: the source of a sequence-level taxon"""
         return (lib().mcq_refdb_taxon_file(self.h, int(key)).decode("latin-1"), int(lib().mcq_refdb_taxon_index(self.h, int(key))),
                 int(lib().mcq_refdb_taxon_windows(self.h, int(key))))
+
+    def taxa(self):
+        """mcq_refdb_taxa: every taxon record in file order, as dicts (what write_shard takes), as rank 0's file holds them"""
+        arr = (TaxonRec * max(1, self.info.n_taxa))()
+        if lib().mcq_refdb_taxa(self.h, arr) != 0:
+            raise RuntimeError(lib().mcq_host_last_error().decode())
+        return [_rec(arr[i]) for i in range(self.info.n_taxa)]
 
     def ancestor(self, key, rank):
         return int(lib().mcq_refdb_ancestor(self.h, int(key), int(rank)))
@@ -547,12 +557,14 @@ def genome_files(args):
         lib().mcq_file_list_free(h)
 
 
-def read_genomes(files, cap, io_bytes=1 << 20):
+def read_genomes(files, cap, io_bytes=1 << 20, after=None, skipped=None):
     """mcq_genome_reader_* over `files` with a buffer of `cap` bases: (bases of all targets back to back as bytes, taxon records of
-    the targets as dicts, lengths, number of fills)"""
+    the targets as dicts, lengths, number of fills).  after: a RefDb -- mcq_genome_reader_open_after, the sequences are added to
+    that database (its names are taken, ids go on behind its targets); skipped: a list that gets mcq_genome_reader_n_skipped."""
     arr = (C.c_char_p * len(files))(*[str(f).encode() for f in files])
     h = C.c_void_p()
-    if lib().mcq_genome_reader_open(arr, len(files), io_bytes, C.byref(h)) != 0:
+    if (lib().mcq_genome_reader_open(arr, len(files), io_bytes, C.byref(h)) if after is None else
+            lib().mcq_genome_reader_open_after(arr, len(files), io_bytes, after.h, C.byref(h))) != 0:
         raise _err()
     try:
         buf = C.create_string_buffer(max(1, cap))
@@ -569,6 +581,8 @@ def read_genomes(files, cap, io_bytes=1 << 20):
             if lib().mcq_genome_reader_target(h, t, C.byref(r), C.byref(ln)) != 0:
                 raise _err()
             recs.append(_rec(r)); lens.append(int(ln.value))
+        if skipped is not None:
+            skipped.append(int(lib().mcq_genome_reader_n_skipped(h)))
         return b"".join(out), recs, lens, fills
     finally:
         lib().mcq_genome_reader_close(h)
