@@ -510,6 +510,39 @@ int mcq_parts_info(const mcq_parts* parts, uint64_t* n_keys, uint64_t* n_locs, u
 int mcq_db_from_parts(const mcq_parts* parts, const uint32_t* tgt2tax, uint32_t n_shards, uint32_t shard_id, uint32_t flags, mcq_db** out);
 int mcq_parts_free(mcq_parts* parts);
 
+/* The build in feature ranges that keeps (target, window) lists: the union table of mcq_build_table, one range of it at a time, for
+ * sequences whose one-piece temporaries do not fit (what mcq_build_cli -ranges writes shard files from).  Range r holds the features
+ * with (h2(feature) * n_ranges) >> 32 == r, the hash of mcq_owner and of mcq_build_parts, whose pass over the sequences this is.
+ * create: device pointers only (MCQ_DEVICE_PTRS; bases and seq_off must stay valid until free; n_shards must be 0 or 1); counts the
+ *   windows once; n_ranges = 0 derives the count from the free device memory (93 B per feature slot of a range against a third of
+ *   it: DESIGN.md section 27).  MCQ_E_UNSUPPORTED: 2^32 - 1 windows or more, more than 2^20 ranges.
+ * next: *out = the table of the next range, an ordinary mcq_table (mcq_table_free releases it): exactly the keys of mcq_build_table's
+ *   table whose feature falls into the range, in ascending feature order, each with the identical list (per-(feature, rank) limit,
+ *   MCQ_BUILD_REMOVE_OVERPOPULATED, (target, window) order); win_off over all targets.  mcq_table_rank_split,
+ *   mcq_table_remove_ambiguous, mcq_table_shard_records, mcq_table_tgt_windows and mcq_table_info work on it unchanged.  With
+ *   n_ranges = 1 the one table equals mcq_build_table's array for array.  A range without features gives an empty table.  Behind
+ *   the last range *out = NULL and MCQ_OK.  Device memory of a call: 44 B per feature slot of the range plus the chunk buffers, then
+ *   the table; free the table of a range before the next call unless it is known to fit beside a pass.
+ * tgt_windows: windows of every target to host memory [n_targets] (known after create).                                        */
+typedef struct mcq_range_build mcq_range_build;
+int mcq_range_build_create(const mcq_build_desc* desc, uint32_t n_ranges /* 0 = from the free memory */, mcq_range_build** out);
+int mcq_range_build_info(const mcq_range_build* b, uint32_t* n_ranges, uint32_t* next_range, uint64_t* n_windows);
+int mcq_range_build_tgt_windows(const mcq_range_build* b, uint32_t* out /* host [n_targets] */);
+int mcq_range_build_next(mcq_range_build* b, mcq_table** out);
+int mcq_range_build_free(mcq_range_build* b);
+
+/* One reference rank's key records of a table as the bytes of its shard file, made on the device: for every key of t that has at
+ * least one location with tgt % n_ranks == rank, in t's key order, the record `u32 key, u8 n, u64 n, u32 tgt[n], u64 n, u32 win[n]`
+ * (21 + 8 n bytes, little-endian, no padding; the rank's locations in list order) -- exactly what mcq_refdb_write_shard
+ * (include/mcq_host.h) writes behind its two counts for mcq_table_rank_split(t, n_ranks, rank), and what mcq_shard_writer_append
+ * takes.  out: device memory of cap_bytes bytes, or NULL to get the three sizes only; *n_bytes, *n_keys, *n_locs are the sizes of
+ * the rank's records (set on MCQ_E_CAPACITY too).  A rank that owns no target, and an empty table, give 0 bytes.
+ * MCQ_E_CAPACITY: cap_bytes < *n_bytes, nothing is written.  MCQ_E_UNSUPPORTED: a list with more than 255 locations of the rank
+ * (the file's count is 8 bits; the build's limit of 254 never makes one).  MCQ_E_ARG: a null argument, rank >= n_ranks.
+ * Device memory: 24 B per key of t of temporaries.                                                                            */
+int mcq_table_shard_records(const mcq_table* t, uint32_t n_ranks, uint32_t rank, void* out /* device, may be NULL */,
+                            uint64_t cap_bytes, uint64_t* n_bytes, uint64_t* n_keys, uint64_t* n_locs);
+
 /* ---- parts from streamed (feature, target, window) triples: a table of any size from the REFERENCE'S OWN shard files --------
  * (row f1 at scale: sketch_database::read + hash_multimap::deserialize, src/sketch_database.h:858-952, src/hash_multimap.h:923-964,
  * without the host-side union of mcq_refdb_open -- 16 B per location and a sort on the host: 240 GB for a RefSeq build.)

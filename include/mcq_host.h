@@ -72,6 +72,17 @@ typedef struct {
 int mcq_refdb_write_shard(const char* path, const mcq_shard_params* params, const mcq_taxon_rec* taxa, uint64_t n_taxa,
                           uint32_t n_targets, const uint32_t* keys, const uint64_t* list_off, const uint64_t* locs,
                           uint64_t n_keys);
+/* The same file written in blocks, for a table that is never in host memory as a whole (mcq_build_cli -ranges): open writes the head
+ * of mcq_refdb_write_shard and two zero counts; append takes host bytes that hold whole key records (`u32 key, u8 n, u64 n, u32 tgt[n],
+ * u64 n, u32 win[n]`, 21 + 8 n bytes each: what mcq_table_shard_records of include/mcq.h makes on the GPU) with their numbers of keys
+ * and locations -- n_bytes must be 21 n_keys + 8 n_locs, an empty block is allowed --; close patches the two counts and closes (a
+ * null handle is allowed; the handle is gone after close, whatever it returns).  Given the same records in the same order the file
+ * is byte-identical to mcq_refdb_write_shard's.  Errors (text: mcq_host_last_error): a file that cannot be opened, a write error.   */
+typedef struct mcq_shard_writer mcq_shard_writer;
+int mcq_shard_writer_open(const char* path, const mcq_shard_params* params, const mcq_taxon_rec* taxa, uint64_t n_taxa,
+                          uint32_t n_targets, mcq_shard_writer** out);
+int mcq_shard_writer_append(mcq_shard_writer* w, const void* records, uint64_t n_bytes, uint64_t n_keys, uint64_t n_locs);
+int mcq_shard_writer_close(mcq_shard_writer* w);
 
 /* reads <prefix>.db_0 .. <prefix>.db_<n_ranks-1> and unions their tables */
 int mcq_refdb_open(const char* prefix, uint32_t n_ranks, mcq_refdb** out);

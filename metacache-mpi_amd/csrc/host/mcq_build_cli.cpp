@@ -13,7 +13,9 @@
 //
 // usage: mcq_build_cli DB P GENOMES... -taxonomy DIR [-kmerlen K] [-sketchlen S] [-winlen W] [-winstride X]
 //            [-max-locations-per-feature N] [-remove-overpopulated-features] [-remove-ambig-features RANK] [-max-ambig-per-feature N]
-//            [-device D] [-ranks-per-pass R] [-read-buffer BYTES]
+//            [-device D] [-ranks-per-pass R] [-read-buffer BYTES] [-ranges N]
+// -ranges N, and by itself a build whose one-piece temporaries do not fit: steps 2 and 3 run once per feature-hash range
+// (build_in_ranges below): the sequences stay on the device and are sketched once per range.
 // -remove-ambig-features RANK [-max-ambig-per-feature N, default 1]: a feature whose locations, over all P ranks and after the limit
 // and -remove-overpopulated-features, name more than N distinct taxa at RANK (targets without one count as one taxon; the targets
 // themselves for `sequence`) is left out of every file: remove_ambiguous_features (src/sketch_database.h:428-470) as the
@@ -23,8 +25,8 @@
 // post_process_features_distributed, src/mode_build.cpp:770-789, at every P): there is no reference file to compare with.
 // Not reproduced: the order of the keys inside a file (the reference's hash table order; its reader inserts key by key, any order
 // reads back the same), and the mapping of sequences to taxa through assembly_summary.txt / *.accession2taxid files: a target's
-// parent is the N of "taxid|N" in its header, or 0.  The sequences and the temporaries of the one-piece build must fit the
-// GPU (about 60 B per feature slot: tens of Gbp on one MI355X); MCQ_BUILD_TRACE=1 prints the times of the phases.
+// parent is the N of "taxid|N" in its header, or 0.  The sequences must fit the GPU, and so must the temporaries of the one-piece
+// build (about 60 B per feature slot: tens of Gbp on one MI355X) or of one range; MCQ_BUILD_TRACE=1 prints the times of the phases.
 //
 // -modify: `metacache_mpi modify DB NEW_GENOMES...` (main_mode_build_modify, src/mode_build.cpp:1117-1136: the database is read, its
 // build options are taken from it, then the same add_to_database runs) on DB.db_0 .. DB.db_<P-1> -- which the reference's own MPI
@@ -53,13 +55,14 @@ struct BuildOptions {
     uint32_t ambig_rank = MCQ_RANK_NONE; int max_ambig = 1;                             // src/mode_build.cpp:74-75, :124-131
     int device = 0; uint32_t ranks_per_pass = 1; uint64_t read_buffer = 64u << 20;
     bool modify = false; std::string out_db;                                            // -modify [-out NEWDB]
+    int64_t ranges = 0;                                                                 // -ranges N (0: not given)
     bool set_kmerlen = false, set_sketchlen = false, set_winlen = false, set_winstride = false, set_max_locs = false;
 };
 
 const char* kUsage =
     "usage: mcq_build_cli DB P GENOMES... -taxonomy DIR [-kmerlen K] [-sketchlen S] [-winlen W] [-winstride X]\n"
     "           [-max-locations-per-feature N] [-remove-overpopulated-features] [-remove-ambig-features RANK] [-max-ambig-per-feature N]\n"
-    "           [-device D] [-ranks-per-pass R] [-read-buffer BYTES]\n"
+    "           [-device D] [-ranks-per-pass R] [-read-buffer BYTES] [-ranges N]\n"
     "writes DB.db_0 .. DB.db_<P-1>: the files `mpiexec -n P metacache_mpi build DB GENOMES... -taxonomy DIR` writes\n"
     "  GENOMES        FASTA files or directories of them (before the first option); directories are read recursively\n"
     "  -taxonomy DIR  nodes.dmp, names.dmp and, if present, merged.dmp\n"
@@ -70,6 +73,12 @@ const char* kUsage =
     "                 count as one); `none` or an unknown RANK leaves it off.  Divergence: the reference's `mpiexec -n P metacache_mpi\n"
     "                 build` accepts the options and ignores them; here they do what the reference documents\n"
     "  -ranks-per-pass R   ranks whose tables are in host memory at a time (default 1); -read-buffer: bytes of each of the two read buffers\n"
+    "  -ranges N      builds the table in N ranges of the feature hash, one after the other: every range sketches the sequences again, its\n"
+    "                 key records are made on the GPU and appended to the P files, which are written under temporary names and renamed after\n"
+    "                 the last range.  For genomes whose one-piece build does not fit the GPU (about 60 B per feature slot); without the\n"
+    "                 option the program goes this way by itself when it does not fit, with a number of ranges from the free memory.  The\n"
+    "                 files hold what the one-piece build's hold; for N > 1 the keys inside a file come in another order.  -ranks-per-pass\n"
+    "                 has no meaning here (host memory: one rank's records of one range); not with -modify\n"
     "       mcq_build_cli DB P NEW_GENOMES... -modify [-taxonomy DIR] [-remove-overpopulated-features] [-max-locations-per-feature N]\n"
     "           [-remove-ambig-features RANK [-max-ambig-per-feature N]] [-out NEWDB] [-device D] [-ranks-per-pass R] [-read-buffer BYTES]\n"
     "  -modify        adds the sequences of NEW_GENOMES to the existing DB.db_0 .. DB.db_<P-1> (`metacache_mpi modify DB GENOMES...`): the files\n"
@@ -115,12 +124,17 @@ bool parse(int argc, char** argv, BuildOptions& o) {
         else if (opt_named(a, {"-device"})) o.device = std::atoi(next());
         else if (opt_named(a, {"-ranks-per-pass"})) o.ranks_per_pass = (uint32_t)std::max(1, std::atoi(next()));
         else if (opt_named(a, {"-read-buffer"})) o.read_buffer = std::max<uint64_t>(1, std::strtoull(next(), nullptr, 10));
+        else if (opt_named(a, {"-ranges"})) {
+            o.ranges = std::strtoll(next(), nullptr, 10);
+            if (o.ranges < 1 || o.ranges > 0xFFFFFFFFll) { std::fprintf(stderr, "ABORT: -ranges N needs N >= 1\n"); return false; }
+        }
         else { std::fprintf(stderr, "ABORT: unknown option %s\n%s", a.c_str(), kUsage); return false; }
     }
     if (o.P < 1 || o.P > 64) { std::fprintf(stderr, "ABORT: P must be 1..64\n"); return false; }
     if (o.inputs.empty()) { std::fprintf(stderr, "ABORT: Nothing to do - no reference sequences provided.\n"); return false; }
     if (o.taxonomy.empty() && !o.modify) { std::fprintf(stderr, "ABORT: -taxonomy DIR is required\n"); return false; }
     if (!o.out_db.empty() && !o.modify) { std::fprintf(stderr, "ABORT: -out NEWDB goes with -modify\n"); return false; }
+    if (o.modify && o.ranges) { std::fprintf(stderr, "ABORT: -modify works on the whole table: -ranges goes with a build\n"); return false; }
     if (!o.out_db.empty() && o.out_db.find(".db") == std::string::npos) o.out_db += ".db";
     if (o.winstride < 0) o.winstride = o.winlen - o.kmerlen + 1;             // src/mode_build.cpp:111
     if (o.winstride < 1) o.winstride = 1;                                    // src/sketch_database.h:321-324
@@ -175,6 +189,131 @@ struct RankOut {
 };
 
 int host_fail() { std::fprintf(stderr, "ABORT: %s\n", mcq_host_last_error()); return 1; }
+int build_fail() { std::fprintf(stderr, "ABORT: %s\n", mcq_build_last_error()); return 1; }
+
+// The taxon list: sequence-level taxa (id -(target + 1): the last target first) before the taxonomy's, both in ascending id
+// (src/taxonomy.h:290-294, :348).  -modify: the taxa above the sequences are the dump's if one is given
+// (reset_taxa_above_sequence_level), else the database's own.
+std::vector<mcq_taxon_rec> taxon_list(const std::vector<mcq_taxon_rec>& targets, const mcq_taxdump* dump, const std::vector<mcq_taxon_rec>& old_taxa) {
+    std::vector<mcq_taxon_rec> taxa;
+    for (size_t t = targets.size(); t-- > 0;) taxa.push_back(targets[t]);
+    if (dump) for (uint64_t i = 0; i < mcq_taxdump_count(dump); ++i) taxa.push_back(mcq_taxdump_taxa(dump)[i]);
+    else for (const mcq_taxon_rec& x : old_taxa) if (x.id >= 0) taxa.push_back(x);
+    return taxa;
+}
+// -remove-ambig-features: is it on (non_target_taxon_count() > 1, src/mode_build.cpp:729-730), and the targets' keys at the rank
+bool ambig_on(const BuildOptions& o, const std::vector<mcq_taxon_rec>& taxa, uint32_t nt) { return o.ambig_rank < MCQ_RANK_NONE && taxa.size() - nt > 1; }
+bool ambig_keys(const BuildOptions& o, const std::vector<mcq_taxon_rec>& taxa, uint32_t nt, std::vector<uint32_t>& tgt_key) {
+    tgt_key.resize(nt);
+    if (o.ambig_rank == MCQ_RANK_SEQUENCE) { for (uint32_t t = 0; t < nt; ++t) tgt_key[t] = t; return true; }
+    return mcq_taxa_clade_keys(taxa.data(), taxa.size(), nt, o.ambig_rank, tgt_key.data()) == 0;
+}
+std::string ambig_text(const BuildOptions& o, uint64_t removed, uint64_t keys_before) {
+    return "ambiguous features on rank " + std::string(mcq_rank_name(o.ambig_rank)) + " (more than " + std::to_string(o.max_ambig) +
+           " taxa): " + std::to_string(removed) + " of " + std::to_string(keys_before) + " removed\n";
+}
+// the sketch parameters of a file: the query sketcher starts as the target sketcher (src/sketch_database.h:247-260)
+mcq_shard_params shard_params(const BuildOptions& o) {
+    mcq_shard_params sp;
+    sp.k = sp.q_k = (uint64_t)o.kmerlen; sp.sketch_size = sp.q_sketch_size = (uint64_t)o.sketchlen;
+    sp.winlen = sp.q_winlen = (uint64_t)o.winlen; sp.winstride = sp.q_winstride = (uint64_t)o.winstride;
+    sp.max_locs_per_feature = (uint64_t)o.max_locs;
+    return sp;
+}
+
+struct RangeBuild { mcq_range_build* h = nullptr; ~RangeBuild() { mcq_range_build_free(h); } };
+struct ShardWriters {
+    std::vector<mcq_shard_writer*> w;
+    ~ShardWriters() { for (mcq_shard_writer* x : w) mcq_shard_writer_close(x); }
+    bool close() {                       // every file is closed, whatever the ones before it said
+        bool ok = true;
+        for (mcq_shard_writer*& x : w) { if (mcq_shard_writer_close(x)) ok = false; x = nullptr; }
+        return ok;
+    }
+};
+
+// ---- the build in feature ranges (-ranges N, or by itself when the one-piece build does not fit): steps 2 and 3 of a build, one
+// range of the union table at a time (mcq_range_build_* of include/mcq.h: every range sketches the sequences again).  All P files are
+// open from the start, under temporary names; a range's table is filtered (-remove-ambig-features: a per-feature filter, so per range it
+// is the same filter), then every rank's key records are made on the GPU as the bytes of its file (mcq_table_shard_records), copied to
+// a pinned block and appended (mcq_shard_writer_*).  The files get their names after the last range: a run that fails leaves none.
+// Host memory: one rank's records of one range.  The keys of a file come range by range, in ascending feature order inside a range.
+int build_in_ranges(const BuildOptions& o, const mcq_build_desc& d, uint32_t n_ranges, const std::vector<mcq_taxon_rec>& targets,
+                    const mcq_taxdump* dump, uint64_t n_bases, Phases& phase) {
+    const uint32_t nt = d.n_targets;
+    RangeBuild build;
+    if (mcq_range_build_create(&d, n_ranges, &build.h) || mcq_range_build_info(build.h, &n_ranges, nullptr, nullptr)) return build_fail();
+    std::vector<uint32_t> windows(nt);
+    if (mcq_range_build_tgt_windows(build.h, windows.data())) return build_fail();
+    const std::vector<mcq_taxon_rec> taxa = taxon_list(targets, dump, {});
+    std::vector<uint32_t> tgt_key;
+    const bool ambig = ambig_on(o, taxa, nt);
+    if (ambig && !ambig_keys(o, taxa, nt, tgt_key)) return host_fail();
+    phase("windows");
+
+    const mcq_shard_params sp = shard_params(o);
+    OutFiles files_out(true);
+    ShardWriters writers;
+    writers.w.assign(o.P, nullptr);
+    {
+        for (uint32_t r = 0; r < o.P; ++r) {
+            std::vector<mcq_taxon_rec> mine = taxa;
+            for (uint32_t t = r; t < nt; t += o.P) mine[nt - 1 - t].windows = windows[t];                    // `windows` is set for the targets the rank owns
+            const std::string path = files_out.add(o.db + "_" + std::to_string(r));                          // src/mode_build.cpp:1079-1082
+            if (mcq_shard_writer_open(path.c_str(), &sp, mine.data(), mine.size(), nt, &writers.w[r])) return host_fail();
+        }
+    }
+    DeviceBuf<unsigned char> d_rec; PinnedBuf<unsigned char> h_rec;
+    uint64_t keys_total = 0, locs_total = 0, keys_before = 0, removed_total = 0;
+    double t_build = 0, t_ambig = 0, t_records = 0, t_write = 0;
+    auto seconds = [](std::chrono::steady_clock::time_point a) { return std::chrono::duration<double>(std::chrono::steady_clock::now() - a).count(); };
+    for (uint32_t range = 0; range < n_ranges; ++range) {
+        auto t0 = std::chrono::steady_clock::now();
+        Table table;
+        if (mcq_range_build_next(build.h, &table.h)) return build_fail();
+        if (!table.h) { std::fprintf(stderr, "ABORT: the build ended after %u of %u ranges\n", range, n_ranges); return 1; }
+        t_build += seconds(t0); t0 = std::chrono::steady_clock::now();
+        if (ambig) {
+            uint64_t before = 0, removed = 0;
+            Table kept;
+            if (mcq_table_info(table.h, &before, nullptr, nullptr, nullptr, nullptr, nullptr) ||
+                mcq_table_remove_ambiguous(table.h, tgt_key.data(), nt, (uint32_t)o.max_ambig, 0, &kept.h, &removed)) return build_fail();
+            table.reset();
+            std::swap(table.h, kept.h);
+            keys_before += before; removed_total += removed;
+            t_ambig += seconds(t0);
+        }
+        for (uint32_t r = 0; r < o.P; ++r) {
+            t0 = std::chrono::steady_clock::now();
+            uint64_t nb = 0, nk = 0, nl = 0;
+            if (mcq_table_shard_records(table.h, o.P, r, nullptr, 0, &nb, &nk, &nl)) return build_fail();
+            if (!d_rec.grow(nb) || !h_rec.grow(nb)) return 1;
+            if (nb) {
+                if (mcq_table_shard_records(table.h, o.P, r, d_rec.p, d_rec.cap, &nb, &nk, &nl)) return build_fail();
+                MCQ_HIP(hipMemcpy(h_rec.p, d_rec.p, nb, hipMemcpyDeviceToHost), return 1);
+            }
+            t_records += seconds(t0); t0 = std::chrono::steady_clock::now();
+            if (mcq_shard_writer_append(writers.w[r], h_rec.p, nb, nk, nl)) return host_fail();
+            t_write += seconds(t0);
+            keys_total += nk; locs_total += nl;
+        }
+    }
+    const auto t0 = std::chrono::steady_clock::now();
+    if (!writers.close()) return host_fail();
+    t_write += seconds(t0);
+    if (phase.on) {
+        const struct { const char* name; double t; } rows[] = {{"sketch + sort (ranges)", t_build}, {"remove ambiguous features", t_ambig},
+                                                                 {"key records", t_records}, {"write", t_write}};
+        for (const auto& x : rows) std::fprintf(stderr, "[mcq_build_cli] %-28s %8.3f s\n", x.name, x.t);
+    }
+    if (!files_out.commit()) return 1;
+    if (ambig) std::fputs(ambig_text(o, removed_total, keys_before).c_str(), stdout);
+    std::printf("%u targets, %llu bases -> %u files %s_0 .. _%u: %llu keys, %llu locations", nt, (unsigned long long)n_bases, o.P, o.db.c_str(),
+                o.P - 1, (unsigned long long)keys_total, (unsigned long long)locs_total);
+    if (phase.on) std::printf(" (%u ranges)", n_ranges);
+    std::printf("\n");
+    return 0;
+}
 
 }  // namespace
 
@@ -309,6 +448,16 @@ int main(int argc, char** argv) {
         d.k = (uint32_t)o.kmerlen; d.sketch_size = (uint32_t)o.sketchlen; d.winlen = (uint32_t)o.winlen; d.winstride = (uint32_t)o.winstride;
         d.n_targets = nt; d.bases = d_bases.p; d.seq_off = d_seq_off.p; d.emulate_ranks = o.P; d.max_locs = (uint32_t)o.max_locs;
         d.flags = MCQ_DEVICE_PTRS | (o.remove_overpopulated ? MCQ_BUILD_REMOVE_OVERPOPULATED : 0); d.device = o.device;
+        // in feature ranges when asked to (-ranges N), or when the one-piece temporaries (about 60 B per feature slot) would not leave
+        // room for the table: mcq_db_build's test, with the sequences on the device; the library then derives the number of ranges
+        bool in_ranges = o.ranges > 0;
+        if (!in_ranges) {
+            size_t mem_free = 0, mem_total = 0;
+            MCQ_HIP(hipMemGetInfo(&mem_free, &mem_total), return 1);
+            const uint64_t slots = n_bases / (uint64_t)o.winstride * (uint64_t)o.sketchlen;
+            in_ranges = slots * 60 > mem_free / 2;
+        }
+        if (in_ranges) return build_in_ranges(o, d, (uint32_t)o.ranges, targets, tax.h, n_bases, phase);
         if (mcq_build_table(&d, &table.h)) { std::fprintf(stderr, "ABORT: %s\n", mcq_build_last_error()); return 1; }
     }
     d_bases = DeviceBuf<char>();
@@ -316,21 +465,13 @@ int main(int argc, char** argv) {
     if (mcq_table_tgt_windows(table.h, windows.data())) { std::fprintf(stderr, "ABORT: %s\n", mcq_build_last_error()); return 1; }
     phase("sketch + sort");
 
-    // The taxon list: sequence-level taxa (id -(target + 1): the last target first) before the taxonomy's, both in ascending id
-    // (src/taxonomy.h:290-294, :348)
-    std::vector<mcq_taxon_rec> taxa;
-    for (uint32_t t = nt; t-- > 0;) taxa.push_back(targets[t]);
-    // (-modify: the taxa above the sequences are the dump's if one is given, reset_taxa_above_sequence_level; else the database's own)
-    if (tax.h) for (uint64_t i = 0; i < mcq_taxdump_count(tax.h); ++i) taxa.push_back(mcq_taxdump_taxa(tax.h)[i]);
-    else for (const mcq_taxon_rec& x : old_taxa) if (x.id >= 0) taxa.push_back(x);
-    const uint64_t n_above = taxa.size() - nt;
+    const std::vector<mcq_taxon_rec> taxa = taxon_list(targets, tax.h, old_taxa);
 
-    // ---- 2b. -remove-ambig-features: once, on the union table (non_target_taxon_count() > 1, src/mode_build.cpp:729-730)
+    // ---- 2b. -remove-ambig-features: once, on the union table
     std::string ambig_line;
-    if (o.ambig_rank < MCQ_RANK_NONE && n_above > 1) {
-        std::vector<uint32_t> tgt_key(nt);
-        if (o.ambig_rank == MCQ_RANK_SEQUENCE) for (uint32_t t = 0; t < nt; ++t) tgt_key[t] = t;
-        else if (mcq_taxa_clade_keys(taxa.data(), taxa.size(), nt, o.ambig_rank, tgt_key.data())) return host_fail();
+    if (ambig_on(o, taxa, nt)) {
+        std::vector<uint32_t> tgt_key;
+        if (!ambig_keys(o, taxa, nt, tgt_key)) return host_fail();
         uint64_t keys_before = 0, removed = 0;
         Table kept;
         if (mcq_table_info(table.h, &keys_before, nullptr, nullptr, nullptr, nullptr, nullptr) ||
@@ -339,19 +480,15 @@ int main(int argc, char** argv) {
         }
         table.reset();                                                       // (the unfiltered table goes before the rank split)
         std::swap(table.h, kept.h);
-        ambig_line = "ambiguous features on rank " + std::string(mcq_rank_name(o.ambig_rank)) + " (more than " + std::to_string(o.max_ambig) +
-                     " taxa): " + std::to_string(removed) + " of " + std::to_string(keys_before) + " removed\n";
+        ambig_line = ambig_text(o, removed, keys_before);
         phase("remove ambiguous features");
     }
 
     // ---- 3. rank by rank: split on the device, copy, write
     const std::string& out_db = o.out_db.empty() ? o.db : o.out_db;
     OutFiles files_out(o.modify);
-    mcq_shard_params sp;
-    sp.k = sp.q_k = (uint64_t)o.kmerlen; sp.sketch_size = sp.q_sketch_size = (uint64_t)o.sketchlen;     // the query sketcher starts as the target
-    sp.winlen = sp.q_winlen = (uint64_t)o.winlen; sp.winstride = sp.q_winstride = (uint64_t)o.winstride;   // sketcher (src/sketch_database.h:247-260)
+    mcq_shard_params sp = shard_params(o);
     if (o.modify) { sp.q_sketch_size = old_info.q_sketch_size; sp.q_winlen = old_info.q_winlen; sp.q_winstride = old_info.q_winstride; }     // (the query sketcher stays the database's)
-    sp.max_locs_per_feature = (uint64_t)o.max_locs;
     double t_split = 0, t_write = 0;
     uint64_t keys_total = 0, locs_total = 0;
     std::vector<RankOut> outs(std::min(o.ranks_per_pass, o.P));

@@ -313,17 +313,8 @@ struct Writer {
         if (ok && n && std::fwrite(s, 1, n, f) != n) ok = false;
     }
 };
-}  // namespace
-
-extern "C" int mcq_refdb_write_shard(const char* path, const mcq_shard_params* p, const mcq_taxon_rec* taxa, uint64_t n_taxa,
-                                     uint32_t n_targets, const uint32_t* keys, const uint64_t* list_off, const uint64_t* locs,
-                                     uint64_t n_keys) {
-    if (!path || !p || (n_taxa && !taxa) || (n_keys && (!keys || !list_off || !locs))) return fail("bad argument");
-    for (uint64_t i = 0; i < n_keys; ++i)
-        if (list_off[i + 1] < list_off[i] || list_off[i + 1] - list_off[i] > 255)
-            return fail("a list has more than 255 locations (bucket size type is uint8, src/config.h:77)");
-    Writer w; w.f = std::fopen(path, "wb");
-    if (!w.f) return fail(std::string("can't open file ") + path);
+// what a shard file holds in front of its table: version, type widths, sketch parameters, taxon list, target count
+void write_head(Writer& w, const mcq_shard_params* p, const mcq_taxon_rec* taxa, uint64_t n_taxa, uint32_t n_targets) {
     w.put<uint64_t>(kDbVersion);
     const uint8_t widths[6] = {4, 4, 4, 1, 8, (uint8_t)kNumRanks};
     for (uint8_t x : widths) w.put<uint8_t>(x);
@@ -337,6 +328,63 @@ extern "C" int mcq_refdb_write_shard(const char* path, const mcq_shard_params* p
         w.put<uint64_t>(taxa[i].index); w.put<uint64_t>(taxa[i].windows);
     }
     w.put<uint32_t>(n_targets);
+}
+}  // namespace
+
+// ---- the same file written in blocks: the head and two zero counts, key records as the caller has them (mcq_table_shard_records of
+// include/mcq.h makes them on the GPU), the counts patched in at the end
+struct mcq_shard_writer {
+    Writer w; std::string path;
+    long counts_pos = -1;                // where the two counts stand; -1: a file without targets has none
+    uint64_t n_keys = 0, n_locs = 0;
+};
+extern "C" int mcq_shard_writer_open(const char* path, const mcq_shard_params* p, const mcq_taxon_rec* taxa, uint64_t n_taxa,
+                                     uint32_t n_targets, mcq_shard_writer** out) {
+    if (!path || !p || (n_taxa && !taxa) || !out) return fail("bad argument");
+    FILE* f = std::fopen(path, "wb");
+    if (!f) return fail(std::string("can't open file ") + path);
+    mcq_shard_writer* s = new mcq_shard_writer();
+    s->w.f = f; s->path = path;
+    write_head(s->w, p, taxa, n_taxa, n_targets);
+    if (n_targets >= 1) {
+        s->counts_pos = std::ftell(f);
+        s->w.put<uint64_t>(0); s->w.put<uint64_t>(0);
+    }
+    if (!s->w.ok || (n_targets >= 1 && s->counts_pos < 0)) { std::fclose(f); delete s; return fail(std::string("write error on ") + path); }
+    *out = s;
+    return 0;
+}
+extern "C" int mcq_shard_writer_append(mcq_shard_writer* s, const void* records, uint64_t n_bytes, uint64_t n_keys, uint64_t n_locs) {
+    if (!s || (n_bytes && !records)) return fail("bad argument");
+    if (n_bytes != 21 * n_keys + 8 * n_locs) return fail("key records of n_keys keys and n_locs locations take 21 n_keys + 8 n_locs bytes");
+    if (n_bytes && s->counts_pos < 0) return fail("a shard file without targets holds no key records");
+    if (s->w.ok && n_bytes && std::fwrite(records, 1, n_bytes, s->w.f) != n_bytes) s->w.ok = false;
+    if (!s->w.ok) return fail("write error on " + s->path);
+    s->n_keys += n_keys; s->n_locs += n_locs;
+    return 0;
+}
+extern "C" int mcq_shard_writer_close(mcq_shard_writer* s) {
+    if (!s) return 0;
+    if (s->w.ok && s->counts_pos >= 0) {
+        if (std::fseek(s->w.f, s->counts_pos, SEEK_SET) != 0) s->w.ok = false;
+        s->w.put<uint64_t>(s->n_keys); s->w.put<uint64_t>(s->n_locs);
+    }
+    const bool ok = (std::fclose(s->w.f) == 0) && s->w.ok;
+    const std::string path = s->path;
+    delete s;
+    return ok ? 0 : fail("write error on " + path);
+}
+
+extern "C" int mcq_refdb_write_shard(const char* path, const mcq_shard_params* p, const mcq_taxon_rec* taxa, uint64_t n_taxa,
+                                     uint32_t n_targets, const uint32_t* keys, const uint64_t* list_off, const uint64_t* locs,
+                                     uint64_t n_keys) {
+    if (!path || !p || (n_taxa && !taxa) || (n_keys && (!keys || !list_off || !locs))) return fail("bad argument");
+    for (uint64_t i = 0; i < n_keys; ++i)
+        if (list_off[i + 1] < list_off[i] || list_off[i + 1] - list_off[i] > 255)
+            return fail("a list has more than 255 locations (bucket size type is uint8, src/config.h:77)");
+    Writer w; w.f = std::fopen(path, "wb");
+    if (!w.f) return fail(std::string("can't open file ") + path);
+    write_head(w, p, taxa, n_taxa, n_targets);
     if (n_targets >= 1) {
         uint64_t nonempty = 0;
         for (uint64_t i = 0; i < n_keys; ++i) nonempty += list_off[i + 1] > list_off[i];

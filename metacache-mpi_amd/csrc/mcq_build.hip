@@ -304,6 +304,21 @@ static int sort_truncate(Scratch& tmpbuf, u64* key, u32* val, u64 n, u32 P, u32 
     return MCQ_OK;
 }
 
+// What mcq_build_table ends in, for a pass of the range build (the one-piece builds keep the text they have): keys, offsets and
+// (target, window) locations of T (win_off and n_targets are set) from the sorted lists; gives fw / head / kid back to tmpbuf.
+static int emit_table(Scratch& tmpbuf, mcq_table& T, const Lists& L) {
+    T.n_keys = L.n_keys; T.n_locs = L.n_kept;
+    BCHK(T.keys.alloc(L.n_keys)); BCHK(T.list_off.alloc(L.n_keys + 1));
+    BCHK(T.locs.alloc(L.n_kept));
+    if (L.n_kept) hipLaunchKernelGGL(k_emit, grid_for(L.n_kept), dim3(TB), 0, 0, (const u64*)L.fw, (const u32*)L.head, (const u64*)L.kid, L.n_kept, L.n_keys,
+                                     (const u64*)T.win_off.get(), T.n_targets, T.keys.get(), T.list_off.get(), T.locs.get());
+    else BCHK(hipMemset(T.list_off.get(), 0, 8));
+    BCHK(hipDeviceSynchronize());
+    BCHK(hipGetLastError());
+    tmpbuf.put(L.fw); tmpbuf.put(L.head); tmpbuf.put(L.kid);
+    return MCQ_OK;
+}
+
 struct PhaseTrace {
     bool on; std::chrono::steady_clock::time_point last;
     PhaseTrace() : on(getenv("MCQ_BUILD_TRACE") != nullptr), last(std::chrono::steady_clock::now()) {}
@@ -501,12 +516,100 @@ static int emit_part(Scratch& tmpbuf, mcq_parts& R, u64* fw, u32* head, u64* kid
     return MCQ_OK;
 }
 
+// ---- one pass over the sequences for one feature range: what mcq_build_parts and mcq_range_build_next share ----
+// The windows of every target (device: win_off, host: h_win) and the chunks of whole targets the sequences are sketched in
+// (MCQ_BUILD_CHUNK_WINDOWS: tuning knob / test hook).
+struct RangePlan {
+    std::vector<u64> h_win; std::vector<u32> cut; u64 largest = 0, n_win = 0;
+    u64 chunk_bytes(u32 s) const { return largest * s * 16 + largest * 4; }     // feat, flag, pos of a chunk's slots; nfeat
+};
+static int plan_ranges(mcq_db* sk, const mcq_build_desc* d, u64* win_off, RangePlan& pl) {
+    const u32 nt = d->n_targets;
+    mcq_batch b; b.n_seqs = nt; b.bases = d->bases; b.seq_off = d->seq_off; b.paired = 0; b.flags = MCQ_DEVICE_PTRS; b.n_bases = 0;
+    MCHK(mcq_count_windows(sk, &b, win_off, nullptr));
+    pl.h_win.resize((size_t)nt + 1);
+    BCHK(hipMemcpy(pl.h_win.data(), win_off, (u64)(nt + 1) * 8, hipMemcpyDeviceToHost));
+    pl.n_win = pl.h_win[nt];
+    if (pl.n_win >= 0xFFFFFFFFull) return bfail(MCQ_E_UNSUPPORTED, "2^32 - 1 windows or more");
+    u64 chunk_win = 1ull << 24;
+    if (const char* e = getenv("MCQ_BUILD_CHUNK_WINDOWS")) chunk_win = std::max<u64>(1, strtoull(e, nullptr, 10));
+    pl.cut.assign(1, 0u);
+    pl.largest = 0;
+    for (u32 t = 0; t < nt;) {
+        u32 e = t + 1;
+        while (e < nt && pl.h_win[e + 1] - pl.h_win[t] <= chunk_win) ++e;
+        pl.largest = std::max(pl.largest, pl.h_win[e] - pl.h_win[t]);
+        pl.cut.push_back(e); t = e;
+    }
+    return MCQ_OK;
+}
+// what one pass may keep in flight: a third of the free memory without the chunk's buffers, at least 1 GiB
+static int pass_budget(u64 chunk_bytes, u64* budget) {
+    size_t mem_free = 0, mem_total = 0;
+    BCHK(hipMemGetInfo(&mem_free, &mem_total));
+    *budget = mem_free / 3 > chunk_bytes + (1ull << 30) ? mem_free / 3 - chunk_bytes : (1ull << 30);
+    return MCQ_OK;
+}
+// the buffers of one chunk: sketches, features per window, range flags and their scan, the chunk's own window offsets
+struct ChunkBufs {
+    u32 *feat = nullptr, *nfeat = nullptr, *flag = nullptr; u64 *pos = nullptr, *woff = nullptr;
+    int get(Scratch& tmpbuf, u64 largest, u32 s, u32 nt) {
+        BCHK(tmpbuf.get(&feat, std::max<u64>(1, largest * s) * 4)); BCHK(tmpbuf.get(&nfeat, std::max<u64>(1, largest) * 4));
+        BCHK(tmpbuf.get(&flag, std::max<u64>(1, largest * s) * 4)); BCHK(tmpbuf.get(&pos, std::max<u64>(1, largest * s) * 8));
+        BCHK(tmpbuf.get(&woff, ((u64)nt + 1) * 8));
+        return MCQ_OK;
+    }
+    void put(Scratch& tmpbuf) { tmpbuf.put(feat); tmpbuf.put(nfeat); tmpbuf.put(flag); tmpbuf.put(pos); tmpbuf.put(woff); }
+};
+// Range `range` of n_ranges: every target is sketched again, chunk by chunk; the slots whose feature falls into the range are kept
+// (flags, scan, scatter: (target, window) order stays) in pair arrays that start with room for `cap` pairs (MCQ_BUILD_PART_CAP: test
+// hook) and grow; sort_truncate leaves the range's lists in L.
+template <class Phase>
+static int range_pass(Scratch& tmpbuf, mcq_db* sk, const mcq_build_desc* d, const u64* win_off, const RangePlan& pl, const ChunkBufs& cb,
+                      u32 n_ranges, u32 range, u64 cap, Lists& L, Phase& phase) {
+    const u32 P = d->emulate_ranks ? d->emulate_ranks : 1, max_locs = d->max_locs ? d->max_locs : 254;
+    const u32 nt = d->n_targets, s = d->sketch_size;
+    u64* key = nullptr; u32* val = nullptr;
+    u64 cap_p = cap;
+    if (const char* e = getenv("MCQ_BUILD_PART_CAP")) cap_p = std::max<u64>(1, strtoull(e, nullptr, 10));      // test hook: start small, grow
+    BCHK(tmpbuf.get(&key, cap_p * 8)); BCHK(tmpbuf.get(&val, cap_p * 4));
+    u64 cursor = 0;
+    for (size_t c = 0; c + 1 < pl.cut.size(); ++c) {
+        const u32 t0 = pl.cut[c], t1 = pl.cut[c + 1];
+        const u64 w0 = pl.h_win[t0], nw = pl.h_win[t1] - w0, ns = nw * s;
+        if (!nw) continue;
+        hipLaunchKernelGGL(k_shift_off, dim3((t1 - t0 + 1 + TB - 1) / TB), dim3(TB), 0, 0, (const u64*)(win_off + t0), (u64)(t1 - t0) + 1, w0, cb.woff);
+        mcq_batch b; b.n_seqs = t1 - t0; b.bases = d->bases; b.seq_off = d->seq_off + t0; b.paired = 0; b.flags = MCQ_DEVICE_PTRS; b.n_bases = 0;
+        MCHK(mcq_sketch(sk, &b, cb.woff, cb.feat, cb.nfeat, nullptr));
+        hipLaunchKernelGGL(k_part_flags, grid_for(ns), dim3(TB), 0, 0, (const u32*)cb.feat, ns, n_ranges, range, cb.flag);
+        u64 kept = 0;
+        MCHK(excl_scan(cb.flag, cb.pos, ns, &kept));
+        if (cursor + kept > cap_p) {
+            // more than the even share + 3 %: real data is not uniform -- features that repeat millions of times (low-complexity
+            // minimisers, rRNA, IS copies) all land in ONE range before the 254-per-feature limit applies.  The pair arrays of
+            // this range grow (half again, at least what is needed) instead of failing (until r04: MCQ_E_CAPACITY and the advice
+            // to ask for more parts, which shrinks the cap as well)
+            const u64 ncap = std::max<u64>(cursor + kept, cap_p + cap_p / 2);
+            u64* key2 = nullptr; u32* val2 = nullptr;
+            BCHK(tmpbuf.get(&key2, ncap * 8)); BCHK(tmpbuf.get(&val2, ncap * 4));
+            if (cursor) { BCHK(hipMemcpyAsync(key2, key, cursor * 8, hipMemcpyDeviceToDevice, 0)); BCHK(hipMemcpyAsync(val2, val, cursor * 4, hipMemcpyDeviceToDevice, 0)); }
+            BCHK(hipStreamSynchronize(0));
+            tmpbuf.put(key); tmpbuf.put(val);
+            key = key2; val = val2; cap_p = ncap;
+        }
+        hipLaunchKernelGGL(k_part_scatter, grid_for(ns), dim3(TB), 0, 0, (const u32*)cb.feat, (const u32*)cb.flag, (const u64*)cb.pos, ns, s, w0,
+                           win_off, nt, P, cursor, cap_p, key, val);
+        cursor += kept;
+    }
+    BCHK(hipDeviceSynchronize());
+    phase("  sketch + keep the range's features");
+    return sort_truncate(tmpbuf, key, val, cursor, P, max_locs, (d->flags & MCQ_BUILD_REMOVE_OVERPOPULATED) != 0, L, phase);
+}
+
 extern "C" int mcq_build_parts(const mcq_build_desc* d, mcq_parts** out) {
     if (!d || !out || !d->seq_off || (d->n_targets && !d->bases)) return bfail(MCQ_E_ARG, "null argument");
     if (d->n_targets < 1) return bfail(MCQ_E_ARG, "no targets");
     if (!(d->flags & MCQ_DEVICE_PTRS)) return bfail(MCQ_E_ARG, "mcq_build_parts takes device pointers (the sequences of such a table do not fit a staging copy)");
-    const u32 P = d->emulate_ranks ? d->emulate_ranks : 1;
-    const u32 max_locs = d->max_locs ? d->max_locs : 254;
     const u32 n_shards = d->n_shards ? d->n_shards : 1;
     if (d->shard_id >= n_shards) return bfail(MCQ_E_ARG, "shard_id >= n_shards");
     BCHK(hipSetDevice(d->device));
@@ -520,93 +623,131 @@ extern "C" int mcq_build_parts(const mcq_build_desc* d, mcq_parts** out) {
     PartsPtr R(new mcq_parts());
     R->device = d->device; R->n_targets = nt; R->k = d->k; R->s = s; R->winlen = d->winlen; R->winstride = d->winstride;
 
-    // windows of every target (device + host copy: the chunks are cut at target boundaries)
+    // windows of every target, chunks of whole targets for the sketch
     u64* win_off = nullptr;
     BCHK(tmpbuf.get(&win_off, (u64)(nt + 1) * 8));
-    mcq_batch b; b.n_seqs = nt; b.bases = d->bases; b.seq_off = d->seq_off; b.paired = 0; b.flags = MCQ_DEVICE_PTRS; b.n_bases = 0;
-    MCHK(mcq_count_windows(sk.get(), &b, win_off, nullptr));
-    std::vector<u64> h_win(nt + 1);
-    BCHK(hipMemcpy(h_win.data(), win_off, (u64)(nt + 1) * 8, hipMemcpyDeviceToHost));
-    const u64 n_win = h_win[nt];
-    if (n_win >= 0xFFFFFFFFull) return bfail(MCQ_E_UNSUPPORTED, "2^32 - 1 windows or more");
+    RangePlan plan;
+    MCHK(plan_ranges(sk.get(), d, win_off, plan));
+    const u64 n_win = plan.n_win;
     R->n_windows = n_win;
     BCHK(R->tgt_windows.alloc(nt));
     hipLaunchKernelGGL(k_windows_of, dim3((nt + TB - 1) / TB), dim3(TB), 0, 0, (const u64*)win_off, nt, R->tgt_windows.get());
     phase("windows");
 
-    // chunks of whole targets for the sketch (MCQ_BUILD_CHUNK_WINDOWS: tuning knob / test hook)
-    u64 chunk_win = 1ull << 24;
-    if (const char* e = getenv("MCQ_BUILD_CHUNK_WINDOWS")) chunk_win = std::max<u64>(1, strtoull(e, nullptr, 10));
-    std::vector<u32> cut{0};
-    u64 largest = 0;
-    for (u32 t = 0; t < nt;) {
-        u32 e = t + 1;
-        while (e < nt && h_win[e + 1] - h_win[t] <= chunk_win) ++e;
-        largest = std::max(largest, h_win[e] - h_win[t]);
-        cut.push_back(e); t = e;
-    }
     // number of parts: what one pass keeps in flight (44 B per pair at its peak, plus the chunk's buffers) against a third of the
     // free memory (MCQ_BUILD_PARTS: tuning knob / test hook)
-    size_t mem_free = 0, mem_total = 0;
-    BCHK(hipMemGetInfo(&mem_free, &mem_total));
     const u64 n_slots_mine = (n_win * s + n_shards - 1) / n_shards;
-    const u64 chunk_bytes = largest * s * 16 + largest * 4;
-    u64 budget = mem_free / 3 > chunk_bytes + (1ull << 30) ? mem_free / 3 - chunk_bytes : (1ull << 30);
+    u64 budget = 0;
+    MCHK(pass_budget(plan.chunk_bytes(s), &budget));
     u32 n_parts = (u32)std::max<u64>(1, (n_slots_mine * 44 + budget - 1) / budget);
     if (const char* e = getenv("MCQ_BUILD_PARTS")) n_parts = (u32)std::max<u64>(1, strtoull(e, nullptr, 10));
     if ((u64)n_parts * n_shards > (1u << 20)) return bfail(MCQ_E_UNSUPPORTED, "too many parts");
     const u32 n_ranges = n_parts * n_shards;
     // a range's share of the slots to start with: the hash spreads distinct features evenly (3 % and 2^20 slack; a range that holds
-    // more -- repeats -- grows, see below)
+    // more -- repeats -- grows, see range_pass)
     const u64 cap = (u64)((double)n_slots_mine / n_parts * 1.03) + (1ull << 20);
 
-    u32 *feat = nullptr, *nfeat = nullptr, *flag = nullptr; u64 *pos = nullptr, *woff = nullptr;
-    BCHK(tmpbuf.get(&feat, std::max<u64>(1, largest * s) * 4)); BCHK(tmpbuf.get(&nfeat, std::max<u64>(1, largest) * 4));
-    BCHK(tmpbuf.get(&flag, std::max<u64>(1, largest * s) * 4)); BCHK(tmpbuf.get(&pos, std::max<u64>(1, largest * s) * 8));
-    BCHK(tmpbuf.get(&woff, ((u64)nt + 1) * 8));
+    ChunkBufs cb;
+    MCHK(cb.get(tmpbuf, plan.largest, s, nt));
     for (u32 p = 0; p < n_parts; ++p) {
-        const u32 range = d->shard_id * n_parts + p;
-        u64* key = nullptr; u32* val = nullptr;
-        u64 cap_p = cap;
-        if (const char* e = getenv("MCQ_BUILD_PART_CAP")) cap_p = std::max<u64>(1, strtoull(e, nullptr, 10));      // test hook: start small, grow
-        BCHK(tmpbuf.get(&key, cap_p * 8)); BCHK(tmpbuf.get(&val, cap_p * 4));
-        u64 cursor = 0;
-        for (size_t c = 0; c + 1 < cut.size(); ++c) {
-            const u32 t0 = cut[c], t1 = cut[c + 1];
-            const u64 w0 = h_win[t0], nw = h_win[t1] - w0, ns = nw * s;
-            if (!nw) continue;
-            hipLaunchKernelGGL(k_shift_off, dim3((t1 - t0 + 1 + TB - 1) / TB), dim3(TB), 0, 0, (const u64*)(win_off + t0), (u64)(t1 - t0) + 1, w0, woff);
-            mcq_batch cb; cb.n_seqs = t1 - t0; cb.bases = d->bases; cb.seq_off = d->seq_off + t0; cb.paired = 0; cb.flags = MCQ_DEVICE_PTRS; cb.n_bases = 0;
-            MCHK(mcq_sketch(sk.get(), &cb, woff, feat, nfeat, nullptr));
-            hipLaunchKernelGGL(k_part_flags, grid_for(ns), dim3(TB), 0, 0, (const u32*)feat, ns, n_ranges, range, flag);
-            u64 kept = 0;
-            MCHK(excl_scan(flag, pos, ns, &kept));
-            if (cursor + kept > cap_p) {
-                // more than the even share + 3 %: real data is not uniform -- features that repeat millions of times (low-complexity
-                // minimisers, rRNA, IS copies) all land in ONE range before the 254-per-feature limit applies.  The pair arrays of
-                // this part grow (half again, at least what is needed) instead of failing (until r04: MCQ_E_CAPACITY and the advice
-                // to ask for more parts, which shrinks the cap as well)
-                const u64 ncap = std::max<u64>(cursor + kept, cap_p + cap_p / 2);
-                u64* key2 = nullptr; u32* val2 = nullptr;
-                BCHK(tmpbuf.get(&key2, ncap * 8)); BCHK(tmpbuf.get(&val2, ncap * 4));
-                if (cursor) { BCHK(hipMemcpyAsync(key2, key, cursor * 8, hipMemcpyDeviceToDevice, 0)); BCHK(hipMemcpyAsync(val2, val, cursor * 4, hipMemcpyDeviceToDevice, 0)); }
-                BCHK(hipStreamSynchronize(0));
-                tmpbuf.put(key); tmpbuf.put(val);
-                key = key2; val = val2; cap_p = ncap;
-            }
-            hipLaunchKernelGGL(k_part_scatter, grid_for(ns), dim3(TB), 0, 0, (const u32*)feat, (const u32*)flag, (const u64*)pos, ns, s, w0,
-                               (const u64*)win_off, nt, P, cursor, cap_p, key, val);
-            cursor += kept;
-        }
-        BCHK(hipDeviceSynchronize());
-        phase("  sketch + keep the part's features");
         Lists L;
-        MCHK(sort_truncate(tmpbuf, key, val, cursor, P, max_locs, (d->flags & MCQ_BUILD_REMOVE_OVERPOPULATED) != 0, L, phase));
+        MCHK(range_pass(tmpbuf, sk.get(), d, win_off, plan, cb, n_ranges, d->shard_id * n_parts + p, cap, L, phase));
         MCHK(emit_part(tmpbuf, *R, L.fw, L.head, L.kid, L.n_kept, L.n_keys));
         phase("  part emitted");
     }
-    tmpbuf.put(feat); tmpbuf.put(nfeat); tmpbuf.put(flag); tmpbuf.put(pos); tmpbuf.put(woff); tmpbuf.put(win_off);
+    cb.put(tmpbuf); tmpbuf.put(win_off);
     *out = R.release();
+    return MCQ_OK;
+}
+
+// ---- the build in ranges that keeps (target, window) lists: one mcq_table per feature range (mcq_range_build_* of include/mcq.h) ----
+// The ranges and the pass are those of mcq_build_parts (range_pass); a range ends in k_emit, as mcq_build_table does, so its table
+// has the rank structure that mcq_table_rank_split and mcq_table_shard_records need.  The handle keeps the windows of the targets,
+// the chunk cuts, the sketching handle and, as the one call of mcq_build_parts does for all its parts, ONE Scratch and one set of
+// chunk buffers for all its passes: what a pass gives back serves the next one, and the pool is trimmed once, when the handle goes.
+struct mcq_range_build {
+    mcq_build_desc d;                 // (bases and seq_off stay the caller's, on the device)
+    u32 n_ranges = 1, next = 0;
+    DbPtr sk;
+    Dev<u64> win_off;                 // device [n_targets + 1]
+    RangePlan plan;
+    u64 cap = 0;                      // pairs a pass makes room for to start with
+    Scratch tmpbuf;                   // the temporaries of every pass (what an error leaves in it goes with the handle)
+    ChunkBufs cb;
+};
+typedef std::unique_ptr<mcq_range_build, HandleFree<mcq_range_build, mcq_range_build_free>> RangeBuildPtr;
+
+extern "C" int mcq_range_build_free(mcq_range_build* b) {
+    if (!b) return MCQ_OK;
+    (void)hipSetDevice(b->d.device);
+    delete b;
+    return MCQ_OK;
+}
+
+extern "C" int mcq_range_build_create(const mcq_build_desc* d, uint32_t n_ranges, mcq_range_build** out) {
+    if (!d || !out || !d->seq_off || (d->n_targets && !d->bases)) return bfail(MCQ_E_ARG, "null argument");
+    if (d->n_targets < 1) return bfail(MCQ_E_ARG, "no targets");
+    if (!(d->flags & MCQ_DEVICE_PTRS)) return bfail(MCQ_E_ARG, "mcq_range_build_create takes device pointers (as mcq_build_parts)");
+    if (d->n_shards > 1) return bfail(MCQ_E_ARG, "mcq_range_build_* builds the whole table (n_shards must be 0 or 1)");
+    if (n_ranges > (1u << 20)) return bfail(MCQ_E_UNSUPPORTED, "too many ranges (at most 2^20)");
+    BCHK(hipSetDevice(d->device));
+    RangeBuildPtr b(new mcq_range_build());
+    b->d = *d;
+    b->sk = make_sketch_handle(d);
+    if (!b->sk) return MCQ_E_ARG;
+    BCHK(b->win_off.alloc((u64)d->n_targets + 1));
+    MCHK(plan_ranges(b->sk.get(), d, b->win_off.get(), b->plan));
+    const u64 n_slots = b->plan.n_win * d->sketch_size;
+    if (!n_ranges) {
+        // per pair of a range: 44 B of the pass at its peak, the range's table (12 B per key, 8 B per location: at most one key and
+        // one location per pair) and the record block of the largest rank (21 B per key, 8 B per location: all of them, at worst) --
+        // 93 B, against what mcq_build_parts allows one pass
+        u64 budget = 0;
+        MCHK(pass_budget(b->plan.chunk_bytes(d->sketch_size), &budget));
+        const u64 r = std::max<u64>(1, (n_slots * (44 + 20 + 29) + budget - 1) / budget);
+        if (r > (1u << 20)) return bfail(MCQ_E_UNSUPPORTED, "too many ranges (at most 2^20)");
+        n_ranges = (u32)r;
+    }
+    b->n_ranges = n_ranges;
+    b->cap = (u64)((double)n_slots / n_ranges * 1.03) + (1ull << 20);
+    BCHK(b->tmpbuf.init(d->device));
+    MCHK(b->cb.get(b->tmpbuf, b->plan.largest, d->sketch_size, d->n_targets));
+    BCHK(hipDeviceSynchronize());
+    *out = b.release();
+    return MCQ_OK;
+}
+
+extern "C" int mcq_range_build_info(const mcq_range_build* b, uint32_t* n_ranges, uint32_t* next_range, uint64_t* n_windows) {
+    if (!b) return bfail(MCQ_E_ARG, "null argument");
+    if (n_ranges) *n_ranges = b->n_ranges;
+    if (next_range) *next_range = b->next;
+    if (n_windows) *n_windows = b->plan.n_win;
+    return MCQ_OK;
+}
+
+extern "C" int mcq_range_build_tgt_windows(const mcq_range_build* b, uint32_t* out) {
+    if (!b || !out) return bfail(MCQ_E_ARG, "null argument");
+    for (u32 t = 0; t < b->d.n_targets; ++t) out[t] = (u32)(b->plan.h_win[t + 1] - b->plan.h_win[t]);
+    return MCQ_OK;
+}
+
+extern "C" int mcq_range_build_next(mcq_range_build* b, mcq_table** out) {
+    if (!b || !out) return bfail(MCQ_E_ARG, "null argument");
+    *out = nullptr;
+    if (b->next >= b->n_ranges) return MCQ_OK;
+    BCHK(hipSetDevice(b->d.device));
+    PhaseTrace phase;
+    const u32 nt = b->d.n_targets;
+    TablePtr T(new mcq_table());
+    T->device = b->d.device; T->n_targets = nt;
+    BCHK(T->win_off.alloc((u64)nt + 1));
+    BCHK(hipMemcpy(T->win_off.get(), b->win_off.get(), ((u64)nt + 1) * 8, hipMemcpyDeviceToDevice));
+    Lists L;
+    MCHK(range_pass(b->tmpbuf, b->sk.get(), &b->d, b->win_off.get(), b->plan, b->cb, b->n_ranges, b->next, b->cap, L, phase));
+    MCHK(emit_table(b->tmpbuf, *T, L));
+    phase("  range emitted");
+    ++b->next;
+    *out = T.release();
     return MCQ_OK;
 }
 
@@ -1189,6 +1330,98 @@ extern "C" int mcq_table_rank_split(const mcq_table* t, uint32_t n_ranks, uint32
             hipLaunchKernelGGL(k_split_scatter, grid, dim3(TB), 0, 0, keys, list_off, locs, nk, n_ranks, rank, alive, key_pos, loc_pos,
                                n_keys_out, n_locs_out, okeys, ooff, olocs);
         }, out, &n_kept);
+}
+
+// ---- one rank's key records as the bytes of its shard file (mcq_table_shard_records of include/mcq.h) --------------------------------
+// The rank split above, ending in file bytes instead of a table: for every key with at least one location of the rank, in key
+// order, `u32 key, u8 n, u64 n, u32 tgt[n], u64 n, u32 win[n]` -- 21 + 8 n bytes, little-endian, nothing aligned (what
+// mcq_refdb_write_shard of the host library writes per key; hash_multimap::serialize, src/hash_multimap.h).  Same traversal: a group of
+// 16 lanes per key, four keys per wave, trip counts uniform over the wave.  The count pass leaves n and the bytes of every key (0 or
+// 21 + 8 n) and raises a flag word for a list that an 8-bit count does not hold; a 64-bit scan of the bytes gives every record its
+// place; the emit pass writes the record's fixed fields from the group's first lane and the two columns at ballot-prefix positions.
+// No atomics.  Every field is written byte by byte: the target column starts at byte 13 of a record and the window column at
+// 21 + 4 n, records follow each other without padding, so no field has an alignment to rely on -- and the disk, not this kernel,
+// bounds the phase.
+namespace {
+__device__ __forceinline__ void put_le(unsigned char* p, u64 v, u32 n_bytes) {
+    for (u32 i = 0; i < n_bytes; ++i) p[i] = (unsigned char)(v >> (8 * i));
+}
+__global__ void __launch_bounds__(256) k_rec_count(const u64* list_off, const u64* locs, u64 n_keys, u32 P, u32 rank, u32* cnt, u32* bytes, u32* too_long) {
+    const u32 lane = threadIdx.x & 63, sub = lane % SPLIT_GROUP, shift = lane - sub;
+    const u64 wave = ((u64)blockIdx.x * blockDim.x + threadIdx.x) >> 6, n_waves = ((u64)gridDim.x * blockDim.x) >> 6;
+    for (u64 base = wave * 4; base < n_keys; base += n_waves * 4) {
+        const SplitKey s = split_key(list_off, n_keys, base, lane);
+        u32 n = 0;
+        for (u32 i = 0; i < s.steps; ++i) {
+            const u32 j = i * SPLIT_GROUP + sub;
+            const bool mine = j < s.len && (u32)(locs[s.beg + j] >> 32) % P == rank;
+            n += (u32)__builtin_popcountll((__ballot(mine) >> shift) & 0xFFFFull);
+        }
+        if (sub == 0 && s.kx < n_keys) {
+            cnt[s.kx] = n; bytes[s.kx] = n ? 21u + 8u * n : 0u;
+            if (n > 255u) *too_long = 1u;                        // (every writer stores the same word)
+        }
+    }
+}
+__global__ void __launch_bounds__(256) k_rec_emit(const u32* keys, const u64* list_off, const u64* locs, u64 n_keys, u32 P, u32 rank,
+                                                 const u32* cnt, const u64* byte_pos, u64 n_bytes, unsigned char* out) {
+    const u32 lane = threadIdx.x & 63, sub = lane % SPLIT_GROUP, shift = lane - sub;
+    const u64 wave = ((u64)blockIdx.x * blockDim.x + threadIdx.x) >> 6, n_waves = ((u64)gridDim.x * blockDim.x) >> 6;
+    for (u64 base = wave * 4; base < n_keys; base += n_waves * 4) {
+        const SplitKey s = split_key(list_off, n_keys, base, lane);
+        const u32 n = s.kx < n_keys ? cnt[s.kx] : 0u;
+        const u64 at = n ? byte_pos[s.kx] : 0;
+        const bool live = n && at + 21 + 8ull * n <= n_bytes;   // (the whole record lies inside the buffer, or nothing of it is written)
+        unsigned char* const rec = out + at;
+        if (live && sub == 0) {
+            put_le(rec, keys[s.kx], 4); put_le(rec + 4, n, 1); put_le(rec + 5, n, 8);
+            put_le(rec + 13 + 4ull * n, n, 8);
+        }
+        u32 done = 0;
+        for (u32 i = 0; i < s.steps; ++i) {
+            const u32 j = i * SPLIT_GROUP + sub;
+            u64 w = 0;
+            bool mine = false;
+            if (live && j < s.len) { w = locs[s.beg + j]; mine = (u32)(w >> 32) % P == rank; }
+            const u32 bits = (u32)((__ballot(mine) >> shift) & 0xFFFFull);
+            const u32 o = done + (u32)__builtin_popcount(bits & ((1u << sub) - 1u));
+            if (mine && o < n) { put_le(rec + 13 + 4ull * o, w >> 32, 4); put_le(rec + 21 + 4ull * n + 4ull * o, w & 0xFFFFFFFFull, 4); }
+            done += (u32)__builtin_popcount(bits);
+        }
+    }
+}
+}  // namespace
+
+extern "C" int mcq_table_shard_records(const mcq_table* t, uint32_t n_ranks, uint32_t rank, void* out, uint64_t cap_bytes,
+                                       uint64_t* n_bytes, uint64_t* n_keys, uint64_t* n_locs) {
+    if (!t || !n_bytes || !n_keys || !n_locs) return bfail(MCQ_E_ARG, "null argument");
+    if (n_ranks < 1 || rank >= n_ranks) return bfail(MCQ_E_ARG, "rank >= n_ranks");
+    *n_bytes = *n_keys = *n_locs = 0;
+    const u64 nk = t->n_keys;
+    if (!nk) return MCQ_OK;
+    BCHK(hipSetDevice(t->device));
+    Dev<u32> cnt, bytes, too_long; Dev<u64> byte_pos, loc_pos;
+    BCHK(cnt.alloc(nk)); BCHK(bytes.alloc(nk)); BCHK(too_long.alloc(1)); BCHK(byte_pos.alloc(nk)); BCHK(loc_pos.alloc(nk));
+    BCHK(hipMemset(too_long.get(), 0, 4));
+    const dim3 grid = grid_for((nk + 3) / 4 * 64);               // four keys per wave of 64 lanes
+    hipLaunchKernelGGL(k_rec_count, grid, dim3(TB), 0, 0, (const u64*)t->list_off.get(), (const u64*)t->locs.get(), nk, n_ranks, rank,
+                       cnt.get(), bytes.get(), too_long.get());
+    u64 total_bytes = 0, total_locs = 0;
+    MCHK(excl_scan(bytes.get(), byte_pos.get(), nk, &total_bytes));
+    MCHK(excl_scan(cnt.get(), loc_pos.get(), nk, &total_locs));       // (for its total)
+    loc_pos.reset();
+    u32 flagged = 0;
+    BCHK(hipMemcpy(&flagged, too_long.get(), 4, hipMemcpyDeviceToHost));
+    BCHK(hipGetLastError());
+    if (flagged) return bfail(MCQ_E_UNSUPPORTED, "a list has more than 255 locations of the rank (bucket size type is uint8, src/config.h:77)");
+    *n_bytes = total_bytes; *n_locs = total_locs; *n_keys = (total_bytes - 8 * total_locs) / 21;
+    if (!out) return MCQ_OK;
+    if (cap_bytes < total_bytes) return bfail(MCQ_E_CAPACITY, "the buffer holds " + std::to_string(cap_bytes) + " bytes, the records need " + std::to_string(total_bytes));
+    if (total_bytes) hipLaunchKernelGGL(k_rec_emit, grid, dim3(TB), 0, 0, (const u32*)t->keys.get(), (const u64*)t->list_off.get(), (const u64*)t->locs.get(), nk,
+                                        n_ranks, rank, (const u32*)cnt.get(), (const u64*)byte_pos.get(), total_bytes, (unsigned char*)out);
+    BCHK(hipDeviceSynchronize());
+    BCHK(hipGetLastError());
+    return MCQ_OK;
 }
 
 // ---- -remove-ambig-features: keys whose list names more than max_keys distinct clades (mcq_table_remove_ambiguous of include/mcq.h) ----

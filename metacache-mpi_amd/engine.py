@@ -188,6 +188,14 @@ def lib():
             L.mcq_table_extend_add.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint32]
             L.mcq_table_extend_finish.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.POINTER(C.c_void_p)]
             L.mcq_table_extend_free.argtypes = [C.c_void_p]
+        if hasattr(L, "mcq_range_build_create"):            # (as above)
+            L.mcq_range_build_create.argtypes = [C.POINTER(BuildDesc), C.c_uint32, C.POINTER(C.c_void_p)]
+            L.mcq_range_build_info.argtypes = [C.c_void_p, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), C.POINTER(C.c_uint64)]
+            L.mcq_range_build_tgt_windows.argtypes = [C.c_void_p, C.c_void_p]
+            L.mcq_range_build_next.argtypes = [C.c_void_p, C.POINTER(C.c_void_p)]
+            L.mcq_range_build_free.argtypes = [C.c_void_p]
+            L.mcq_table_shard_records.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64),
+                                                  C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
         L.mcq_reduce.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p,
                                  C.POINTER(QueryOpts), C.POINTER(Result), C.c_void_p]
         L.mcq_packed_bytes.restype = C.c_uint64; L.mcq_packed_bytes.argtypes = [C.c_uint64]
@@ -816,6 +824,37 @@ class Table:
         _chk(lib().mcq_table_tgt_windows(self.h, _np_ptr(out)))
         return out
 
+    def shard_records_into(self, n_ranks, rank, out_ptr, cap_bytes):
+        """mcq_table_shard_records as the header has it: the key records of reference rank `rank` as file bytes at the device
+        pointer out_ptr (None: the sizes only) -> (n_bytes, n_keys, n_locs)"""
+        nb, nk, nl = C.c_uint64(), C.c_uint64(), C.c_uint64()
+        rc = lib().mcq_table_shard_records(self.h, n_ranks, rank, out_ptr, cap_bytes, C.byref(nb), C.byref(nk), C.byref(nl))
+        if rc != 0:
+            raise McqError(rc, (lib().mcq_build_last_error() or b"").decode())
+        return int(nb.value), int(nk.value), int(nl.value)
+
+    def shard_records(self, n_ranks, rank):
+        """the key records of reference rank `rank` of `n_ranks` as the bytes of its shard file (numpy uint8): what
+        host.ShardWriter.append takes, with the sizes shard_records_into(n_ranks, rank, None, 0) gives"""
+        n_bytes = self.shard_records_into(n_ranks, rank, None, 0)[0]
+        out = np.empty(n_bytes, np.uint8)
+        if not n_bytes:
+            return out
+        hip = C.CDLL("libamdhip64.so")
+        hip.hipMalloc.argtypes = [C.POINTER(C.c_void_p), C.c_size_t]
+        hip.hipFree.argtypes = [C.c_void_p]
+        hip.hipMemcpy.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int]
+        dev = C.c_void_p()
+        if hip.hipMalloc(C.byref(dev), n_bytes) != 0:
+            raise McqError(MCQ_E_HIP, "hipMalloc of the record block failed")
+        try:
+            self.shard_records_into(n_ranks, rank, dev, n_bytes)
+            if hip.hipMemcpy(_np_ptr(out), dev, n_bytes, 2) != 0:       # hipMemcpyDeviceToHost
+                raise McqError(MCQ_E_HIP, "hipMemcpy of the record block failed")
+        finally:
+            hip.hipFree(dev)
+        return out
+
     def close(self):
         if getattr(self, "h", None):
             lib().mcq_table_free(self.h); self.h = None
@@ -860,6 +899,55 @@ class Parts:
     def close(self):
         if getattr(self, "h", None):
             lib().mcq_parts_free(self.h); self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class RangeBuild:
+    """mcq_range_build_*: the union table of Table(...) built one feature-hash range at a time -- an iterator of Table, each
+    holding the keys of its range in ascending feature order with the lists of the one-piece build.  n_ranges = 0 lets the
+    library derive the count from the free device memory.  The sequences (device pointers) must outlive the object."""
+
+    def __init__(self, bases_ptr, seq_off_ptr, n_targets, n_ranges=0, emulate_ranks=1, k=16, sketch_size=16, winlen=128, winstride=113,
+                 max_locs=0, device=0, flags=0):
+        d = _build_desc(bases_ptr, seq_off_ptr, None, n_targets, emulate_ranks, k, sketch_size, winlen, winstride,
+                        max_locs, 1, 0, device, flags, True)
+        h = C.c_void_p()
+        rc = lib().mcq_range_build_create(C.byref(d), n_ranges, C.byref(h))
+        if rc != 0:
+            raise McqError(rc, (lib().mcq_build_last_error() or b"").decode())
+        self.h, self.n_targets, self.device = h, n_targets, device
+        nr, nx, nw = C.c_uint32(), C.c_uint32(), C.c_uint64()
+        _chk(lib().mcq_range_build_info(h, C.byref(nr), C.byref(nx), C.byref(nw)))
+        self.n_ranges, self.n_windows = int(nr.value), int(nw.value)
+
+    def tgt_windows(self):
+        """windows of every target (u32 [n_targets])"""
+        out = np.zeros(self.n_targets, np.uint32)
+        _chk(lib().mcq_range_build_tgt_windows(self.h, _np_ptr(out)))
+        return out
+
+    def __iter__(self):
+        return self
+
+    def __next__(self):
+        h = C.c_void_p()
+        rc = lib().mcq_range_build_next(self.h, C.byref(h))
+        if rc != 0:
+            raise McqError(rc, (lib().mcq_build_last_error() or b"").decode())
+        if not h.value:
+            raise StopIteration
+        t = Table.__new__(Table)
+        t._adopt(h, self.n_targets, self.device)
+        return t
+
+    def close(self):
+        if getattr(self, "h", None):
+            lib().mcq_range_build_free(self.h); self.h = None
 
     def __del__(self):
         try:

@@ -39,22 +39,57 @@ class ShardParams(C.Structure):
 _lib = None
 
 
-def write_shard(path, params, taxa, n_targets, keys, list_off, locs):
-    """mcq_refdb_write_shard.  params: dict with the ShardParams field names; taxa: list of dicts
-    (id, parent, rank, name, file, index, windows); keys u32, list_off u64 [n+1], locs u64 (tgt<<32|win)."""
-    sp = ShardParams(**{k: int(v) for k, v in params.items()})
-    arr = (TaxonRec * len(taxa))()
+def _taxon_array(taxa):
+    """(TaxonRec array, the byte strings it points into) of a list of dicts (id, parent, rank, name, file, index, windows)"""
+    arr = (TaxonRec * max(1, len(taxa)))()
     keep = []
     for i, t in enumerate(taxa):
         nm, fl = t["name"].encode("latin-1"), t["file"].encode("latin-1")
         keep += [nm, fl]
         arr[i] = TaxonRec(t["id"], t["parent"], t["rank"], nm, fl, t["index"], t["windows"])
+    return arr, keep
+
+
+def write_shard(path, params, taxa, n_targets, keys, list_off, locs):
+    """mcq_refdb_write_shard.  params: dict with the ShardParams field names; taxa: list of dicts
+    (id, parent, rank, name, file, index, windows); keys u32, list_off u64 [n+1], locs u64 (tgt<<32|win)."""
+    sp = ShardParams(**{k: int(v) for k, v in params.items()})
+    arr, keep = _taxon_array(taxa)
     keys = np.ascontiguousarray(keys, np.uint32); list_off = np.ascontiguousarray(list_off, np.uint64)
     locs = np.ascontiguousarray(locs, np.uint64)
     rc = lib().mcq_refdb_write_shard(path.encode(), C.byref(sp), arr, len(taxa), n_targets, keys.ctypes.data_as(C.c_void_p),
                                      list_off.ctypes.data_as(C.c_void_p), locs.ctypes.data_as(C.c_void_p), len(keys))
     if rc != 0:
         raise RuntimeError(lib().mcq_host_last_error().decode())
+
+
+class ShardWriter:
+    """mcq_shard_writer_*: a shard file written in blocks -- the head of write_shard at once, then append(records, n_keys, n_locs)
+    with whole key records as bytes (engine.Table.shard_records makes them), the two counts patched in by close()"""
+
+    def __init__(self, path, params, taxa, n_targets):
+        sp = ShardParams(**{k: int(v) for k, v in params.items()})
+        arr, keep = _taxon_array(taxa)
+        h = C.c_void_p()
+        if lib().mcq_shard_writer_open(path.encode(), C.byref(sp), arr, len(taxa), n_targets, C.byref(h)) != 0:
+            raise RuntimeError(lib().mcq_host_last_error().decode())
+        self.h = h
+
+    def append(self, records, n_keys, n_locs):
+        rec = np.ascontiguousarray(records, np.uint8)
+        if lib().mcq_shard_writer_append(self.h, rec.ctypes.data_as(C.c_void_p), rec.nbytes, n_keys, n_locs) != 0:
+            raise RuntimeError(lib().mcq_host_last_error().decode())
+
+    def close(self):
+        h, self.h = getattr(self, "h", None), None
+        if h and lib().mcq_shard_writer_close(h) != 0:
+            raise RuntimeError(lib().mcq_host_last_error().decode())
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
 
 
 def lib():
@@ -115,6 +150,9 @@ def lib():
         L.mcq_host_last_error.restype = C.c_char_p
         L.mcq_refdb_write_shard.argtypes = [C.c_char_p, C.POINTER(ShardParams), C.POINTER(TaxonRec), C.c_uint64, C.c_uint32,
                                             C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64]
+        L.mcq_shard_writer_open.argtypes = [C.c_char_p, C.POINTER(ShardParams), C.POINTER(TaxonRec), C.c_uint64, C.c_uint32, C.POINTER(C.c_void_p)]
+        L.mcq_shard_writer_append.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint64, C.c_uint64]
+        L.mcq_shard_writer_close.argtypes = [C.c_void_p]
         L.mcq_refdb_open_meta.argtypes = [C.c_char_p, C.c_uint32, C.POINTER(C.c_void_p)]
         L.mcq_refdb_tgt_windows.argtypes = [C.c_void_p, C.c_void_p]
         L.mcq_refdb_file_stats.argtypes = [C.c_void_p, C.c_uint32, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
