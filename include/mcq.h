@@ -764,6 +764,36 @@ int mcq_align(mcq_ws* ws, const mcq_batch* in, const char* subjects, const mcq_a
               uint32_t max_query, uint32_t max_subject, mcq_alignment* out,
               char* out_query, char* out_subject, uint32_t text_cap, void* stream);
 
+/* ---- all hits of a read: what `-allhits` prints (csrc/mcq_all_hits.hip) ------------------------------------------------------------
+ * A read's sorted match list (what merge_sort returns, src/querying.h:88-106) run-length compressed: one mcq_hit per distinct
+ * (target, window) the read hits, in ascending (tgt, win) order, `hits` = how many of the read's locations lie there.  Two calls:
+ *   mcq_all_hits_count  sketches and probes every query and leaves in loc_off (device, [n_queries + 1]) the exclusive prefix sums of
+ *               the queries' location counts (the sums of the probed list lengths); loc_off[n_queries] is the total.  A query's
+ *               location count bounds the number of its entries and is the size of its segment of `hits`.  A query with a sequence
+ *               of 2^31 bases or more counts as 0.
+ *   mcq_all_hits  writes query q's entries to hits[loc_off[q] .. loc_off[q] + n_hits[q]); their `hits` fields sum to
+ *               loc_off[q + 1] - loc_off[q].  hits: device, [cap], 4-byte aligned; n_hits, status: device, [n_queries].
+ * mcq_all_hits never writes outside a query's segment nor at `cap` and beyond.  The part of a segment behind the query's entries
+ * is working space: what it holds afterwards is undefined.  A query whose status is not 0 gets n_hits = 0 and nothing is written
+ * into its segment: MCQ_ALL_HITS_LOCS -- it has more locations than the workspace's max_locs_per_query, or a sequence of 2^31
+ * bases or more; MCQ_ALL_HITS_SEGMENT -- its segment in loc_off is not its location count (or loc_off decreases there), or the segment
+ * of a query that has locations ends beyond cap.  So a loc_off that mcq_all_hits_count made for this batch on this table and a
+ * cap >= loc_off[n_queries] leave only MCQ_ALL_HITS_LOCS to happen.  Nothing is answered wrongly in silence.
+ * The kernel tiers by segment size: up to MCQ_ALL_HITS_REG_MAX locations one wavefront sorts in registers, up to
+ * MCQ_ALL_HITS_WAVE_MAX one wavefront sorts in LDS, beyond that a workgroup sorts inside the query's own segment.
+ * Batches as mcq_target_hits takes them (ASCII or MCQ_BATCH_PACKED, offsets or MCQ_BATCH_RANGES, paired or not; device pointers
+ * only: a host batch is MCQ_E_ARG); every location form and bucket layout; any sketch geometry the handle accepts.  Both calls only
+ * enqueue work on `stream`.  status[] is the only report: the workspace's counters and its capacity count are not touched.  A
+ * workspace under clade exclusion (mcq_ws_set_exclusion) is not looked at: the caller drops the entries of excluded targets.      */
+#define MCQ_ALL_HITS_REG_MAX 64u         /* locations of a query sorted in registers                       */
+#define MCQ_ALL_HITS_WAVE_MAX 2048u      /* ... sorted in LDS by one wavefront; more: the workgroup tier  */
+typedef struct { uint32_t tgt, win, hits; } mcq_hit;                 /* 12 bytes, no padding */
+enum { MCQ_ALL_HITS_LOCS = 1u,      /* status: more locations than the workspace's max_locs_per_query, or >= 2^31 bases */
+       MCQ_ALL_HITS_SEGMENT = 2u }; /* ... the query's segment in loc_off is not its location count, or ends beyond cap */
+int mcq_all_hits_count(const mcq_db* db, mcq_ws* ws, const mcq_batch* in, uint64_t* loc_off /* device [nq+1] */, void* stream);
+int mcq_all_hits(const mcq_db* db, mcq_ws* ws, const mcq_batch* in, const uint64_t* loc_off, mcq_hit* hits /* device [cap] */,
+                 uint64_t cap, uint32_t* n_hits /* device [nq] */, uint32_t* status /* device [nq] */, void* stream);
+
 /* ---- debug / parity taps ------------------------------------------------------------
  * Row 5 in isolation is mcq_count_windows + mcq_sketch above (the sketches of every window).
  * Rows 7-8 in isolation: the sorted match list of every query (what merge_sort returns,

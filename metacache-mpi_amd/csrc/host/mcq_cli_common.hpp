@@ -18,6 +18,15 @@
 //   * -hits-per-seq [FILE] (mcq_query_cli only)  show_matches_per_targets src/printing.cpp:437-469 (mcq_hits_table_text) after the
 //         mapping lines and in front of the abundance tables (src/classification.cpp:847-862), into the -out file or FILE; the
 //         query_id column of the TABLE_LAYOUT and of every mapping line, two parameter lines
+//   * -queryids                                the query_id column of the TABLE_LAYOUT and of every mapping line (showQueryIds,
+//         src/query_options.cpp:249-250, :308: -hits-per-seq sets the same flag)
+//   * -locations                               the candidate_locations column behind top_hits: show_candidate_ranges
+//         src/printing.cpp:422-432, `[w * win_beg,w * win_end + winlen] ` per candidate; after a fold (n_ranks > 1) the candidates
+//         carry (0,0) and every entry is `[0,<winlen>] `, as in the reference's MPI program
+//   * -allhits (mcq_query_cli only)             the all_hits column in front of top_hits: show_matches over match locations
+//         src/printing.cpp:365-416, one `name/win:count,` (-lowest sequence) or `ancestorname:count,` per distinct (target, window)
+//         of the read, from mcq_all_hits on the GPU; sets the map view mode to `all` (src/query_options.cpp:293-297); with -exclude
+//         the entries on the read's own clade are left out on the host
 //   * -align (mcq_query_cli only)               show_alignment src/classification.cpp:437-477 behind the classification column of a
 //         classified read whose first candidate is a sequence (mcq_align on the GPU, mcq_align_subjects.hpp), one parameter line
 //         (src/printing.cpp:91-93); -align-candidate-range, written into no output, aligns against the candidate's real window range
@@ -38,7 +47,7 @@
 //            [-maxcand N] [-hitmin N] [-hitdiff X] [-insertsize N] [-threads N] [-tophits] [-taxids] [-taxids-only] [-omit-ranks]
 //            [-lineage] [-mapped-only] [-nomap] [-noquirks] [-abundances [FILE]] [-abundance-per R] [-out FILE] [-batch N]
 //            [-batch-bases N] [-read-chunk BYTES] [-reader gpu|host] [-exclude RANK] [-ground-truth] [-precision] [-hits-per-seq [FILE]]
-//            [-align] [-align-candidate-range] [-help]
+//            [-align] [-align-candidate-range] [-queryids] [-locations] [-allhits] [-help]
 // (inputs: every argument up to the first option; a directory stands for the files in it (files_in_directory below).  -pairseq
 //  without -pairfiles comes first: every file is interleaved pairs, also the two of `r1 r2` and the one of `r1 -`.  Without it,
 //  `r1 r2` alone is one pair of files in the given order and `r1 -` one single-end file.  Otherwise -pairfiles sorts the names and pairs
@@ -95,6 +104,9 @@ struct Options {
     bool tax_counts() const { return abundances || abundance_rank != MCQ_RANK_NONE; }
     bool align = false;                  // -align: the alignment block behind the line of a read classified to a sequence
     bool align_range = false;            // -align-candidate-range: align against the candidate's real window range, not the folded (0,0)
+    bool query_ids = false;              // -queryids, and set by -hits-per-seq: the query_id column (showQueryIds)
+    bool locations = false;              // -locations: the candidate_locations column
+    bool allhits = false;                // -allhits: the all_hits column (mcq_query_cli)
     bool hits_per_seq = false;           // -hits-per-seq [FILE]: the per-reference window hit lists, and the query_id column
     std::string hits_file;               // ... its FILE (cleared when it names the -out file: src/query_options.cpp:353)
     uint32_t exclude_rank = MCQ_RANK_NONE;     // -exclude R (< root): drop the hits on the read's own clade at R
@@ -198,6 +210,17 @@ static const char* const kQueryUsage =
     "  -align-candidate-range  (written into no output) with n_ranks > 1 the merged candidates carry no positions and -align aligns\n"
     "                   to window 0 of the target, as the reference's MPI program does; this option aligns to the candidate's real\n"
     "                   window range instead\n"
+    "more columns:\n"
+    "  -queryids        (aliases -query-ids, -query_ids, -queryid, -query-id, -query_id) a query_id column in front of every mapping\n"
+    "                   line: the 1-based number of the read (pair)\n"
+    "  -locations       a candidate_locations column behind top_hits: `[begin,end] ` in bases of the target for every candidate; with\n"
+    "                   n_ranks > 1 the merged candidates carry no positions and every entry is `[0,<window length>] `\n"
+    "  -allhits         (mcq_query_cli only; mcq_query_mpi rejects it and names mcq_query_cli; alias -all-hits) an all_hits column in\n"
+    "                   front of top_hits: every (sequence, window) the read hits with its number of hits, as name/window:hits, with\n"
+    "                   -lowest sequence, else as ancestorname:hits, -- computed on the GPU.  Every read is shown (also with -nomap or\n"
+    "                   -mapped-only, unless -nomap -tophits).  With -exclude RANK the hits on the read's own clade are left out.  A\n"
+    "                   batch whose hits need more than 2 GiB, or a read with more locations than the workspace takes, ends the run\n"
+    "                   with an ABORT line.  Three batches are in flight: up to 6 GiB on the device and 6 GiB of pinned host memory.\n"
     "rejected:        -taxon-coverage (both programs): the coverage statistics are not reproduced\n";
 
 static bool parse_options(int argc, char** argv, Options& o) {
@@ -249,11 +272,14 @@ static bool parse_options(int argc, char** argv, Options& o) {
             const uint32_t r = mcq_rank_from_name(next()); if (r < MCQ_RANK_ROOT) o.abundance_rank = r;
         }
         else if (opt_named(a, {"-hits-per-seq", "-hitsperseq", "-hits_per_seq", "-hits-per-sequence", "-hitspersequence", "-hits_per_sequence"})) {   // src/query_options.cpp:299-306
-            o.hits_per_seq = true;
+            o.hits_per_seq = true; o.query_ids = true;                       // src/query_options.cpp:308
             if (i + 1 < argc && argv[i + 1][0] != '-') o.hits_file = argv[++i];
         }
         else if (opt_named(a, {"-align", "-alignment", "-showalignment"})) o.align = true;                                      // src/query_options.cpp:329-331
         else if (a == "-align-candidate-range") o.align_range = true;
+        else if (opt_named(a, {"-queryids", "-query-ids", "-query_ids", "-queryid", "-query-id", "-query_id"})) o.query_ids = true;   // src/query_options.cpp:249-250
+        else if (a == "-locations") o.locations = true;                                                                         // :257
+        else if (a == "-allhits" || a == "-all-hits") o.allhits = true;                                                         // :262-263
         else if (a == "-exclude") { const uint32_t r = mcq_rank_from_name(next()); if (r < MCQ_RANK_ROOT) o.exclude_rank = r; }   // src/query_options.cpp:205-210
         else if (opt_named(a, {"-ground-truth", "-ground_truth", "-groundtruth"})) o.ground_truth = true;                       // :196-198
         else if (a == "-precision") o.precision = true;                                                                         // :203
@@ -268,13 +294,15 @@ static bool parse_options(int argc, char** argv, Options& o) {
     if (o.hits_file == o.outfile) o.hits_file.clear();                       // src/query_options.cpp:353
     if (!make_units(named, pairfiles, pairseq, o)) return false;
     if (o.lowest > o.highest) o.lowest = o.highest;
-    if (o.nomap && o.tophits) { o.nomap = false; o.mapped_only = true; }   // "showing hits changes the mapping mode", src/query_options.cpp:289-292
+    if (o.nomap && o.tophits) { o.nomap = false; o.mapped_only = true; }   // "showing hits changes the mapping mode", src/query_options.cpp:293-297
+    else if (o.allhits) { o.nomap = false; o.mapped_only = false; }        // ... -allhits shows every read
     return true;
 }
 
 struct Out {
     mcq_refdb* db; const Options& p; Mode mode;
     const char* comment = "# "; const char* none = "--"; const char* col = "\t|\t";
+    uint64_t tgt_stride = 0, tgt_winlen = 0;             // -locations: the database's target window stride and window size
 
     // one taxon column entry: [prefix ':'] body, the body built from a name text and an id text
     template <class Name, class Id>
@@ -314,7 +342,10 @@ struct Out {
 };
 
 static Out make_out(mcq_refdb* rdb, const Options& p) {
-    return Out{rdb, p, Mode::make(p.show_ranks, p.taxids, p.taxids_only)};   // -taxids-only wins over -taxids (src/query_options.cpp:262-274)
+    Out o{rdb, p, Mode::make(p.show_ranks, p.taxids, p.taxids_only)};   // -taxids-only wins over -taxids (src/query_options.cpp:262-274)
+    mcq_refdb_info info; mcq_refdb_get_info(rdb, &info);
+    o.tgt_stride = info.winstride; o.tgt_winlen = info.winlen;
+    return o;
 }
 
 // show_query_parameters (src/printing.cpp:40-113) + show_query_mapping_header (src/classification.cpp:486-512)
@@ -343,10 +374,12 @@ static void write_head(std::ostream& os, const Out& o, uint32_t hitmin) {
     os << cm << "Using " << p.threads << " threads\n";
     if (!p.nomap) {
         os << cm << "TABLE_LAYOUT: ";
-        if (p.hits_per_seq) os << "query_id" << o.col;                       // showQueryIds, src/query_options.cpp:308, src/classification.cpp:495
+        if (p.query_ids) os << "query_id" << o.col;                          // showQueryIds, src/query_options.cpp:308, src/classification.cpp:495
         os << "query_header" << o.col;
         if (p.ground_truth) { o.header_taxon(os, "truth_"); os << o.col; }
+        if (p.allhits) os << "all_hits" << o.col;                            // src/classification.cpp:504-506
         if (p.tophits) os << "top_hits" << o.col;
+        if (p.locations) os << "candidate_locations" << o.col;
         o.header_taxon(os);
         os << '\n';
     }
@@ -395,6 +428,25 @@ static std::vector<Options> output_runs(const Options& p) {
 // (token: the header up to its first ' ', what the line prints; truth: the read's ground truth or MCQ_NO_TAXON, for the truth_
 //  column and, with `ev`, evaluate_classification's assign_known_correct, src/classification.cpp:329-353)
 // -align: what show_alignment (src/classification.cpp:437-477) prints of a read, or nothing (length 0)
+// -allhits: a read's entries (mcq_all_hits) and what turns them into the column.  tgt_key[t]: the taxon whose name stands for target t
+// (its ancestor at -lowest, or the sequence itself: mcq_refdb_tgt2tax).  tgt_clade / query_clade (-exclude): an entry on a target
+// whose clade key is the read's is left out, as remove_hits_on_rank drops its matches (src/classification.cpp:141-157)
+struct AllHits {
+    const mcq_hit* e = nullptr; uint32_t n = 0;
+    const uint32_t* tgt_key = nullptr;
+    const uint32_t* tgt_clade = nullptr; uint32_t query_clade = 0;
+};
+// show_matches over match locations, src/printing.cpp:365-416
+static void write_all_hits(std::ostream& os, const Out& o, const AllHits& h) {
+    const bool seq = o.p.lowest == MCQ_RANK_SEQUENCE;
+    for (uint32_t i = 0; i < h.n; ++i) {
+        const mcq_hit& m = h.e[i];
+        if (h.tgt_clade && h.tgt_clade[m.tgt] == h.query_clade) continue;
+        os << mcq_refdb_taxon_name(o.db, h.tgt_key[m.tgt]);
+        if (seq) os << '/' << (int)m.win;
+        os << ':' << (int)m.hits << ',';
+    }
+}
 struct AlignBlock {
     int32_t score = 0; uint32_t length = 0;              // length: of the two aligned strings; 0 = no block
     const char* file = ""; uint64_t index = 0;           // the target's source
@@ -403,7 +455,8 @@ struct AlignBlock {
 };
 static void write_query(std::ostream& os, const Out& o, uint32_t hitmin, const char* token, size_t token_len,
                         const mcq_cand* cands, uint32_t ncand, uint64_t* assigned /* [MCQ_RANK_NONE + 1] */,
-                        uint32_t truth = MCQ_NO_TAXON, mcq_eval_stats* ev = nullptr, uint64_t query_id = 0, const AlignBlock* al = nullptr) {
+                        uint32_t truth = MCQ_NO_TAXON, mcq_eval_stats* ev = nullptr, uint64_t query_id = 0, const AlignBlock* al = nullptr,
+                        const AllHits* all = nullptr) {
     mcq_refdb* rdb = o.db; const Options& p = o.p;
     const uint32_t best = mcq_refdb_classify(rdb, reinterpret_cast<const uint32_t*>(cands), ncand, hitmin, p.hitdiff, p.highest);
     if (best == MCQ_NO_TAXON) ++assigned[MCQ_RANK_NONE];
@@ -411,9 +464,10 @@ static void write_query(std::ostream& os, const Out& o, uint32_t hitmin, const c
     if (ev) mcq_eval_stats_assign_known_correct(ev, mcq_refdb_taxon_rank(rdb, best), mcq_refdb_taxon_rank(rdb, truth),
                                                 mcq_refdb_taxon_rank(rdb, mcq_refdb_ranked_lca(rdb, best, truth)));
     if (p.nomap || (p.mapped_only && best == MCQ_NO_TAXON)) return;
-    if (p.hits_per_seq) os << query_id << o.col;                             // showQueryIds, src/classification.cpp:537
+    if (p.query_ids) os << query_id << o.col;                                // showQueryIds, src/classification.cpp:537
     os.write(token, (std::streamsize)token_len) << o.col;
     if (p.ground_truth) { o.best(os, truth); os << o.col; }                  // show_taxon(os, db, opt, query.groundTruth), :611-614
+    if (p.allhits) { if (all) write_all_hits(os, o, *all); os << o.col; }    // src/classification.cpp:555-558
     if (p.tophits) {                                                         // show_matches, src/printing.cpp:333-360
         for (uint32_t i = 0; i < ncand && cands[i].hits > 0; ++i) {
             const mcq_cand& c = cands[i];
@@ -428,6 +482,11 @@ static void write_query(std::ostream& os, const Out& o, uint32_t hitmin, const c
         }
         os << o.col;
     }
+    if (p.locations) {                                                       // show_candidate_ranges, src/printing.cpp:422-432
+        for (uint32_t i = 0; i < ncand && cands[i].hits > 0; ++i)
+            os << '[' << o.tgt_stride * cands[i].win_beg << ',' << o.tgt_stride * cands[i].win_end + o.tgt_winlen << "] ";
+        os << o.col;
+    }
     o.best(os, best);
     if (al && al->length && best != MCQ_NO_TAXON) {                          // opt.showAlignment && cls.best, src/classification.cpp:627-629
         os << '\n' << o.comment << "  score  " << al->score << "  aligned to " << al->file << " #" << al->index
@@ -438,8 +497,8 @@ static void write_query(std::ostream& os, const Out& o, uint32_t hitmin, const c
     os << '\n';
 }
 static void write_query(std::ostream& os, const Out& o, uint32_t hitmin, const std::string& header,
-                        const mcq_cand* cands, uint32_t ncand, uint64_t* assigned) {
-    write_query(os, o, hitmin, header.data(), std::min(header.size(), header.find(' ')), cands, ncand, assigned);
+                        const mcq_cand* cands, uint32_t ncand, uint64_t* assigned, uint64_t query_id = 0) {
+    write_query(os, o, hitmin, header.data(), std::min(header.size(), header.find(' ')), cands, ncand, assigned, MCQ_NO_TAXON, nullptr, query_id);
 }
 
 // show_summary (src/printing.cpp:622-641) + show_taxon_statistics (:522-555)

@@ -18,6 +18,13 @@
 // (Run::stage_hits).  The writer threads feed one accumulator each (mcq_hits_table_*), merged and written after the last
 // mapping line; host memory grows with the input, as the reference's does.  A read beyond the kernel's capacity ends the run.
 //
+// -allhits: behind a batch's query, on the same stream, mcq_all_hits_count leaves the batch's segment offsets on the device; the host
+// waits for their total, grows the device and pinned entry buffers to it, and enqueues mcq_all_hits and the copies out
+// (Run::stage_all_hits).  The writer threads format the all_hits column from the pinned entries with the targets' names; with
+// -exclude they leave out the entries on the read's own clade.  This host round trip is paid by -allhits alone.  A batch whose
+// entries need more than 2 GiB, or a read beyond the kernel's capacity, ends the run.  Every slot has entry
+// buffers of its own: up to three times 2 GiB on the device, and as much pinned.
+//
 // -align (with -lowest sequence; above it only the parameter line is written and nothing of this runs): the genome files the
 // database names are read once at the start (mcq_align_subjects.hpp).  Behind a batch's query, on the same stream, the host waits
 // for the batch's candidates, builds one job per read that is classified, whose first candidate is a sequence and whose target's
@@ -43,10 +50,15 @@ struct Slot : ReadSlot {
     DeviceBuf<uint32_t> d_tgt, d_cnt, d_hst; DeviceBuf<mcq_target_range> d_rng;
     PinnedBuf<uint32_t> cnt, hst; PinnedBuf<mcq_target_range> rng; PinnedBuf<uint64_t> seq_off;
     uint32_t range_cap = 0; bool hits = false;
+    // -allhits: the batch's segment offsets, entries, entry counts and status words (mcq_all_hits)
+    DeviceBuf<uint64_t> d_ah_off; DeviceBuf<mcq_hit> d_ah; DeviceBuf<uint32_t> d_ah_n, d_ah_st;
+    PinnedBuf<uint64_t> ah_off; PinnedBuf<mcq_hit> ah; PinnedBuf<uint32_t> ah_n, ah_st;
+    bool all_hits = false;
     AlignSlot al;                                                                        // -align
     uint64_t first_id = 0;                                                               // query id of the batch's first query
 };
 constexpr int NS = 3;
+constexpr uint64_t kAllHitsMaxEntries = (2ull << 30) / sizeof(mcq_hit);                  // -allhits: entries of one batch, so of one slot: NS times that in flight
 
 // the batches in flight, the workspace they run in and what their lines add up to
 struct Run {
@@ -190,6 +202,26 @@ struct Run {
         A.on = true;
         return true;
     }
+    // -allhits: behind the batch's query on s_k.  Count, wait for the total, make room, emit, copy out.
+    bool stage_all_hits(Slot& S, const mcq_batch& in) {
+        const uint64_t n = S.n;
+        if (!S.d_ah_off.grow(n + 1) || !S.ah_off.grow(n + 1) || !S.d_ah_n.grow(n) || !S.ah_n.grow(n) || !S.d_ah_st.grow(n) || !S.ah_st.grow(n)) return false;
+        if (mcq_all_hits_count(db.edb, ws, &in, S.d_ah_off.p, s_k)) { std::fprintf(stderr, "FAIL: %s\n", mcq_last_error()); return false; }
+        MCQ_HIP(hipMemcpyAsync(S.ah_off.p, S.d_ah_off.p, (n + 1) * 8, hipMemcpyDeviceToHost, s_k), return false);
+        MCQ_HIP(hipStreamSynchronize(s_k), return false);
+        const uint64_t total = S.ah_off.p[n];
+        if (total > kAllHitsMaxEntries) {                        // 2 GiB of entries, on the device and pinned
+            std::fprintf(stderr, "ABORT: -allhits needs %llu MB for the hits of a batch of %llu reads: use a smaller -batch\n",
+                         (unsigned long long)((total * sizeof(mcq_hit)) >> 20), (unsigned long long)n);
+            return false;
+        }
+        if (!S.d_ah.grow(std::max<uint64_t>(total, 1)) || !S.ah.grow(std::max<uint64_t>(total, 1))) return false;   // (a batch without any hit: still a buffer to name)
+        if (mcq_all_hits(db.edb, ws, &in, S.d_ah_off.p, S.d_ah.p, total, S.d_ah_n.p, S.d_ah_st.p, s_k)) { std::fprintf(stderr, "FAIL: %s\n", mcq_last_error()); return false; }
+        if (total) MCQ_HIP(hipMemcpyAsync(S.ah.p, S.d_ah.p, total * sizeof(mcq_hit), hipMemcpyDeviceToHost, s_k), return false);
+        MCQ_HIP(hipMemcpyAsync(S.ah_n.p, S.d_ah_n.p, n * 4, hipMemcpyDeviceToHost, s_k), return false);
+        MCQ_HIP(hipMemcpyAsync(S.ah_st.p, S.d_ah_st.p, n * 4, hipMemcpyDeviceToHost, s_k), return false);
+        return true;
+    }
     // -hits-per-seq: behind the batch's query on s_k, its slot targets, their ranges and window counts, and the copies out.  The count
     // rows are as wide as the range of the batch's longest query: its offsets come to the host first (`st` has prepared the batch).
     bool stage_hits(Slot& S, const mcq_batch& in, const mcq_result& res, hipStream_t st) {
@@ -268,6 +300,13 @@ struct Run {
                                                              : "is beyond what mcq_target_hits takes (range width, window ids of 2^28 and more, 2^31 bases)");
             return false;
         }
+        if (S.all_hits) for (uint64_t q = 0; q < n; ++q) if (S.ah_st.p[q]) {      // beyond mcq_all_hits' capacity: reported, never dropped in silence
+            std::fprintf(stderr, "ABORT: -allhits: read %llu (%.*s) %s\n", (unsigned long long)(S.first_id + q),
+                         (int)(S.hdr.p[2 * q + 1] - S.hdr.p[2 * q]), S.text[0].p + S.hdr.p[2 * q],
+                         (S.ah_st.p[q] & MCQ_ALL_HITS_LOCS) ? "has more locations than the workspace takes (max_locs_per_query), or 2^31 bases or more"
+                                                            : "was not answered by mcq_all_hits (its segment of the entry buffer does not fit its locations)");
+            return false;
+        }
         if (S.al.on) for (uint64_t q = 0; q < n; ++q) if (S.al.res.p[q].status) {   // beyond mcq_align's capacity: reported, never dropped in silence
             std::fprintf(stderr, "ABORT: -align: read %llu (%.*s) %s\n", (unsigned long long)(S.first_id + q),
                          (int)(S.hdr.p[2 * q + 1] - S.hdr.p[2 * q]), S.text[0].p + S.hdr.p[2 * q],
@@ -296,9 +335,14 @@ struct Run {
                     ab.range_beg = w * S.al.beg[q]; ab.range_end = w * S.al.end[q] + w;
                     ab.query = S.al.text_q.p + q * (uint64_t)S.al.text_cap; ab.target = S.al.text_s.p + q * (uint64_t)S.al.text_cap;
                 }
+                AllHits ah;
+                if (S.all_hits) {
+                    ah.e = S.ah.p + S.ah_off.p[q]; ah.n = S.ah_n.p[q]; ah.tgt_key = db.t2t.data();
+                    if (excluding()) { ah.tgt_clade = tgt_clade.data(); ah.query_clade = S.clade.p[q]; }
+                }
                 write_query(ss, o, db.hitmin, S.text[0].p + S.hdr.p[2 * q], (size_t)(S.hdr.p[2 * q + 1] - S.hdr.p[2 * q]),
                             &S.cands.p[q * p.maxcand], S.ncand.p[q], asg[t].data(), truth, p.precision ? &evs[t] : nullptr, S.first_id + q,
-                            ab.length ? &ab : nullptr);
+                            ab.length ? &ab : nullptr, S.all_hits ? &ah : nullptr);
                 if (S.hits) for (uint32_t s = 0; s < n_slots; ++s) {        // matches_per_target::insert of this read's candidates
                     const mcq_target_range& r = S.rng.p[q * n_slots + s];
                     if (r.tgt != MCQ_TARGET_UNUSED && r.n_win &&
@@ -399,6 +443,8 @@ static int run_queries(const Options& p, const Database& db) {
         MCQ_HIP(hipMemcpyAsync(S.ncand.p, S.d_ncand.p, n * 4, hipMemcpyDeviceToHost, run.s_k), return 1);
         if (!S.host_parsed && !run.excluding()) MCQ_HIP(hipMemcpyAsync(S.hdr.p, S.d_hdr.p, 2 * n * 8, hipMemcpyDeviceToHost, run.s_k), return 1);
         if (S.hits && !run.stage_hits(S, in, res, reads.stream())) return 1;
+        S.all_hits = p.allhits && !p.nomap;
+        if (S.all_hits && !run.stage_all_hits(S, in)) return 1;
         S.al.on = false;
         if (run.align_on() && !run.stage_align(S, in, res, reads.stream())) return 1;
         MCQ_HIP(hipEventRecord(S.done, run.s_k), return 1);

@@ -25,7 +25,8 @@
 //                                   [-batch N] [-batch-bases N]
 // -align (and its aliases) is rejected the same way.
 // -exclude, -ground-truth and -precision are rejected with a line that names mcq_query_cli: the sharded kernels have no exclusion.
-// -hits-per-seq is rejected the same way: mcq_target_hits is a kernel of the one-GPU path.
+// -hits-per-seq is rejected the same way: mcq_target_hits is a kernel of the one-GPU path.  So is -allhits (mcq_all_hits).
+// -queryids and -locations come through the shared parser and writer.
 #include <mpi.h>
 #include <hip/hip_runtime_api.h>
 
@@ -126,6 +127,10 @@ int main(int argc, char** argv) {
         if (rank == 0) std::fprintf(stderr, "ABORT: -align is an option of mcq_query_cli; mcq_query_mpi aligns no reads (its ranks hold neither the candidates' positions nor the genomes)\n");
         MPI_Finalize(); return 2;
     }
+    if (p.allhits) {                                                        // (before any GPU work)
+        if (rank == 0) std::fprintf(stderr, "ABORT: -allhits is an option of mcq_query_cli; mcq_query_mpi lists no hits (mcq_all_hits is a kernel of the one-GPU path)\n");
+        MPI_Finalize(); return 2;
+    }
     int n_dev = 0;
     HIP_OR_DIE(hipGetDeviceCount(&n_dev));
     if (n_dev < 1) { std::fprintf(stderr, "ABORT: no GPU\n"); MPI_Abort(MPI_COMM_WORLD, 1); }
@@ -180,6 +185,7 @@ int main(int argc, char** argv) {
         std::string all;                                                        // rank 0: unit lines and mapping lines, in input order
         uint64_t assigned[MCQ_RANK_NONE + 1] = {0};                             // this rank's queries, over all units
         std::vector<uint64_t> counts((size_t)n_taxa + 1, 0), counts_u((size_t)n_taxa + 1), counts_all((size_t)n_taxa + 1);
+        uint64_t id_base = 1;                                                   // -queryids: the 1-based number of a unit's first query over all units of this output
         for (const ReadUnit& U : run.units) {
             // every rank reads the unit's files and keeps its contiguous slice of the queries
             std::vector<Rec> r1, r2;
@@ -224,7 +230,7 @@ int main(int argc, char** argv) {
                 const DevSet& S = set[j % NS];
                 HIP_OR_DIE(hipEventSynchronize(S.out));
                 for (size_t q = lo(j); q < hi(j); ++q)
-                    write_query(lines, o, db.hitmin, r1[q].header, &S.cands.p[(q - lo(j)) * p.maxcand], S.ncand.p[q - lo(j)], assigned_u);
+                    write_query(lines, o, db.hitmin, r1[q].header, &S.cands.p[(q - lo(j)) * p.maxcand], S.ncand.p[q - lo(j)], assigned_u, id_base + q);
             };
             // the first batch of a context exchanges exact sizes and learns the block sizes the others travel at; should a later
             // batch not fit them (MCQ_E_CAPACITY at the end), everything is repeated with exact sizes
@@ -273,6 +279,7 @@ int main(int argc, char** argv) {
             if (rank == 0) { int t = 0; for (int r = 0; r < N; ++r) { disp[r] = t; t += lens[r]; } unit_lines.resize((size_t)t); }
             MPI_Gatherv(mine_s.data(), len, MPI_CHAR, rank == 0 ? &unit_lines[0] : nullptr, lens.data(), disp.data(), MPI_CHAR, 0, MPI_COMM_WORLD);
             if (rank == 0) { std::ostringstream ul; write_unit_line(ul, o, U); all += ul.str(); all += unit_lines; }
+            id_base += nq_all;
         }
         // ... and the statistics, and writes
         unsigned long long a_loc[MCQ_RANK_NONE + 1], a_all[MCQ_RANK_NONE + 1];

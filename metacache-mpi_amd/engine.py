@@ -36,6 +36,10 @@ MCQ_TARGET_HITS_RANGE, MCQ_TARGET_HITS_KEYS, MCQ_TARGET_HITS_WINDOW = 1, 2, 4   
 MCQ_ALIGN_MAX_QUERY = 2048       # mcq_align: bases of one mate
 MCQ_ALIGN_MAX_SUBJECT = 4096     # ... bases of one subject
 MCQ_ALIGN_QUERY_LONG, MCQ_ALIGN_SUBJECT_LONG = 1, 2    # ... status bits of a query beyond a capacity
+MCQ_ALL_HITS_REG_MAX = 64        # mcq_all_hits: locations of a query sorted in registers
+MCQ_ALL_HITS_WAVE_MAX = 2048     # ... sorted in LDS by one wavefront; more: the workgroup tier
+MCQ_ALL_HITS_LOCS, MCQ_ALL_HITS_SEGMENT = 1, 2         # ... status bits of a query that was not answered
+HIT = np.dtype([("tgt", "<u4"), ("win", "<u4"), ("hits", "<u4")])               # mcq_hit
 ALIGN_JOB = np.dtype([("sub_off", "<u8"), ("sub_len", "<u4"), ("on", "<u4")])     # mcq_align_job
 ALIGNMENT = np.dtype([("score", "<i4"), ("length", "<u4"), ("reverse", "<u4"), ("status", "<u4")])   # mcq_alignment
 
@@ -217,6 +221,10 @@ def lib():
         if hasattr(L, "mcq_align"):
             L.mcq_align.argtypes = [C.c_void_p, C.POINTER(Batch), C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p,
                                     C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p]
+        if hasattr(L, "mcq_all_hits"):
+            L.mcq_all_hits_count.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(Batch), C.c_void_p, C.c_void_p]
+            L.mcq_all_hits.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(Batch), C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p,
+                                       C.c_void_p, C.c_void_p]
         L.mcq_shard_create.argtypes = [C.c_void_p, C.POINTER(ShardCfg), C.POINTER(C.c_void_p)]
         L.mcq_shard_destroy.argtypes = [C.c_void_p]
         L.mcq_shard_unique_id.argtypes = [C.c_void_p]
@@ -502,6 +510,48 @@ class Workspace:
         if sync:
             self.sync(st)
         return out
+
+    # ---- all hits of a read (mcq_all_hits_count / mcq_all_hits): what -allhits prints
+    def all_hits_count(self, bases_ptr, seq_off_ptr, n_seqs, paired, loc_off_ptr, stream=None, ranges=False, packed_bases=0):
+        """device pointers, enqueue only: loc_off u64 [nq + 1] = exclusive prefix sums of the queries' location counts"""
+        b = Batch(n_seqs, bases_ptr, seq_off_ptr, 1 if paired else 0,
+                  MCQ_DEVICE_PTRS | (MCQ_BATCH_RANGES if ranges else 0) | (MCQ_BATCH_PACKED if packed_bases else 0), packed_bases)
+        _chk(lib().mcq_all_hits_count(self.db.h, self.h, C.byref(b), loc_off_ptr, stream))
+
+    def all_hits(self, bases_ptr, seq_off_ptr, n_seqs, paired, loc_off_ptr, hits_ptr, cap, n_hits_ptr, status_ptr, stream=None,
+                 ranges=False, packed_bases=0):
+        """device pointers, enqueue only: query q's entries (HIT: tgt, win, hits; ascending) to hits[loc_off[q] .. + n_hits[q]); a query
+        with a status bit (MCQ_ALL_HITS_*) gets n_hits = 0 and nothing written"""
+        b = Batch(n_seqs, bases_ptr, seq_off_ptr, 1 if paired else 0,
+                  MCQ_DEVICE_PTRS | (MCQ_BATCH_RANGES if ranges else 0) | (MCQ_BATCH_PACKED if packed_bases else 0), packed_bases)
+        _chk(lib().mcq_all_hits(self.db.h, self.h, C.byref(b), loc_off_ptr, hits_ptr, cap, n_hits_ptr, status_ptr, stream))
+
+    def all_hits_host(self, bases, seq_off, paired, packed=False, ranges=False):
+        """convenience form: numpy in, numpy out (the copies go through torch; waits for the device).  Returns (hits, status): per
+        query its entries as HIT records, and u32 [nq] status words (a query with a status bit has no entries)"""
+        import torch
+        dev = torch.device("cuda", self.db.device)
+        seq_off = np.ascontiguousarray(seq_off, np.uint64)
+        n_seqs = len(seq_off) // 2 if ranges else len(seq_off) - 1
+        nq = n_seqs // 2 if paired else n_seqs
+        raw = np.frombuffer(bases, dtype=np.uint8) if not isinstance(bases, np.ndarray) else bases.view(np.uint8)
+        d_bases = torch.from_numpy(np.concatenate([raw, np.zeros(8, np.uint8)])).to(dev)
+        d_seq = torch.from_numpy(seq_off.view(np.int64)).to(dev) if len(seq_off) else torch.zeros(1, dtype=torch.int64, device=dev)
+        pb = int(seq_off[-1]) if packed else 0
+        st = torch.cuda.current_stream(dev).cuda_stream
+        d_off = torch.zeros(nq + 1, dtype=torch.int64, device=dev)
+        self.all_hits_count(d_bases.data_ptr(), d_seq.data_ptr(), n_seqs, paired, d_off.data_ptr(), stream=st, ranges=ranges, packed_bases=pb)
+        off = d_off.cpu().numpy()
+        total = int(off[nq])
+        d_hits = torch.zeros((max(total, 1), 3), dtype=torch.int32, device=dev)
+        d_n = torch.zeros(max(nq, 1), dtype=torch.int32, device=dev)
+        d_st = torch.zeros(max(nq, 1), dtype=torch.int32, device=dev)
+        self.all_hits(d_bases.data_ptr(), d_seq.data_ptr(), n_seqs, paired, d_off.data_ptr(), d_hits.data_ptr(), total, d_n.data_ptr(),
+                      d_st.data_ptr(), stream=st, ranges=ranges, packed_bases=pb)
+        torch.cuda.synchronize(dev)
+        ent = d_hits.cpu().numpy().view(np.uint32).reshape(-1).view(HIT)
+        n = d_n.cpu().numpy().view(np.uint32)
+        return [ent[int(off[q]):int(off[q]) + int(n[q])].copy() for q in range(nq)], d_st.cpu().numpy().view(np.uint32)[:nq].copy()
 
     # ---- read-to-candidate alignment (mcq_align): what -align prints
     def align_device(self, bases_ptr, seq_off_ptr, n_seqs, paired, subjects_ptr, jobs_ptr, max_query, max_subject, out_ptr,
