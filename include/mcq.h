@@ -794,6 +794,38 @@ int mcq_all_hits_count(const mcq_db* db, mcq_ws* ws, const mcq_batch* in, uint64
 int mcq_all_hits(const mcq_db* db, mcq_ws* ws, const mcq_batch* in, const uint64_t* loc_off, mcq_hit* hits /* device [cap] */,
                  uint64_t cap, uint32_t* n_hits /* device [nq] */, uint32_t* status /* device [nq] */, void* stream);
 
+/* ---- *.accession2taxid text joined against the names of a database's targets (the post-mapping of a build) -----------
+ * What rank_targets_with_mapping_file (src/mode_build.cpp:248-312) does for the targets without a parent, on text of the strict
+ * form.  A line `acc TAB accver TAB taxid TAB gi` names one target at most, a function of the line alone: the target named
+ * exactly accver; if there is none, the first name strictly greater than acc in byte order if it begins with acc
+ * (taxon_with_similar_name, src/sketch_database.h:631-639; a name equal to acc is not found this way); if there is none, the
+ * target named exactly gi.  If that target is unranked it takes the taxid of the FIRST line that names it, in the order (file
+ * ordinal, line number); a taxid of 0 counts.  A line whose target is ranked does nothing (no falling through to acc or gi).
+ * create   names_blob + name_off[n_names + 1]: the sequence-level names of the database back to back, strictly ascending as
+ *          std::string compares (unsigned bytes, then length: MCQ_E_ARG otherwise); name_target[k] < n_targets: the target of
+ *          name k; unranked[t] != 0: target t has no parent.  Host arrays, copied to `device` by the call.
+ * chunk    text: whole lines of ONE file in DEVICE memory (16-B aligned text is read with 16-B loads, any other byte by byte),
+ *          n_bytes < 2^32; file_ordinal < 2^23 orders the files, first_line_no (< 2^40) is the number of the chunk's first line
+ *          in its file; line i of the chunk has the number first_line_no + i.  Any numbering under which a later line has the
+ *          greater number will do, such as the chunk's byte offset in its file (a strict line has at least 8 bytes).
+ *          The chunk is STRICT when every line has four non-empty fields of non-blank bytes (none of space, TAB,
+ *          LF, VT, FF, CR) split by single TABs, ends in LF (one CR before it is allowed and no part of the fourth field), has
+ *          1-19 decimal digits as its third field, and is at most MCQ_ACCMAP_MAX_LINE bytes long with its LF -- then a
+ *          token-stream parser sees the same records.  *strict (host) = 1: the chunk is applied when the call returns;
+ *          0: it is not strict, and NOTHING in the handle has changed (the caller parses it on the host: mcq_accmap_host of
+ *          include/mcq_host.h).  The call waits for `stream`.  Chunks may come in any order: the result depends on their
+ *          ordinals and line numbers only.
+ * finish   found[t] = 1 and parent[t] = the taxid (the uint64 read, as int64) where a line won target t; 0 and 0 elsewhere.
+ *          The handle stays usable.                                                                                        */
+#define MCQ_ACCMAP_MAX_LINE 1024
+typedef struct mcq_accmap mcq_accmap;
+int mcq_accmap_create(const char* names_blob, const uint64_t* name_off, uint64_t n_names, const uint32_t* name_target,
+                      const uint8_t* unranked, uint32_t n_targets, int device, mcq_accmap** out);
+int mcq_accmap_chunk(mcq_accmap* h, const char* text, uint64_t n_bytes, uint32_t file_ordinal, uint64_t first_line_no,
+                     uint32_t* strict, void* stream);
+int mcq_accmap_finish(mcq_accmap* h, int64_t* parent /* host [n_targets] */, uint8_t* found /* host [n_targets] */);
+int mcq_accmap_free(mcq_accmap* h);
+
 /* ---- debug / parity taps ------------------------------------------------------------
  * Row 5 in isolation is mcq_count_windows + mcq_sketch above (the sketches of every window).
  * Rows 7-8 in isolation: the sorted match list of every query (what merge_sort returns,

@@ -300,8 +300,8 @@ int mcq_taxdump_free(mcq_taxdump* t);
 /* name of the sequence-level taxon of a sequence with this header (the '>' line without the '>'): accession.version, else
  * accession, else the gi number, else the whole header (src/sequence_io.cpp:705-719, src/mode_build.cpp:591-596).  Written to
  * buf (NUL-terminated, cut to cap - 1 bytes); returns the length.  mcq_target_parent_taxid: the N of "taxid|N" in the header,
- * 0 if there is none (src/sequence_io.cpp:724-748) -- the parent a target gets when no mapping file names one.  Mapping files
- * (assembly_summary.txt, *.accession2taxid) are not read.                                                               */
+ * 0 if there is none (src/sequence_io.cpp:724-748) -- the parent a target gets when no mapping file names one (mapping files:
+ * mcq_seq2tax_* and mcq_accmap_host below).                                                                             */
 int64_t mcq_target_name(const char* header, uint64_t len, char* buf, size_t cap);
 int64_t mcq_target_parent_taxid(const char* header, uint64_t len);
 /* the files named by the arguments of a build, every directory expanded (recursively, 10 levels), then sorted: the order in
@@ -341,6 +341,47 @@ uint64_t mcq_genome_reader_n_skipped(const mcq_genome_reader* r);
  * non-zero only for the targets rank 0 owns; mcq_refdb_tgt_windows has every target's): out[n_taxa]; name and file point into
  * the handle.  What a `modify` carries forward into the files it writes.                                                  */
 int mcq_refdb_taxa(const mcq_refdb* db, mcq_taxon_rec* out /* [n_taxa] */);
+
+/* ---- mapping files: which taxon a sequence belongs to when its header does not say -----------------------------------
+ * Pre-mapping (make_sequence_to_taxon_id_map and find_taxon_id, src/taxonomy_io.cpp:190-310, src/mode_build.cpp:531-550):
+ * mcq_seq2tax_read reads <dir>/assembly_summary.txt, if it opens, for every distinct directory of the genome FILES (what is in
+ * front of a name's last '/' or '\\'; in std::set order).  mcq_seq2tax_add_file reads one file of that kind into the map
+ * (*opened = 0 and nothing read if it does not open).  A file is read as the reference reads it: up to 10 leading '#' lines, of
+ * which the last is the header row (else the first line is); the header's first word is dropped, the others count from 0;
+ * `taxid` names taxcol, `accession.version` / `assembly_accession` keycol; a line is keycol TABs passed, a word (the key), taxcol
+ * TABs passed, an integer; without a taxid column the whole file is read again as key TAB taxid.  The first entry of a key
+ * stays.  mcq_seq2tax_find: the exact key, else the first key greater than `name` if it begins with it, else 0.  Entries come in
+ * key order.
+ * mcq_genome_reader_open_mapped: mcq_genome_reader_open (existing = NULL) or _open_after with the map (NULL: none; copied).  A
+ * target's parent then is the map's entry for its name, else for the accession string of its FILE's name
+ * (extract_accession_string, no fall-back to the whole name), else the N of taxid|N in its header, else 0
+ * (src/mode_build.cpp:591-604).                                                                                            */
+typedef struct mcq_seq2tax mcq_seq2tax;
+int mcq_seq2tax_create(mcq_seq2tax** out);
+int mcq_seq2tax_add_file(mcq_seq2tax* m, const char* path, int32_t* opened);
+int mcq_seq2tax_read(const char* const* genome_files, uint32_t n_files, mcq_seq2tax** out);
+uint64_t mcq_seq2tax_count(const mcq_seq2tax* m);
+int mcq_seq2tax_entry(mcq_seq2tax* m, uint64_t i, const char** key, int64_t* taxid);
+int64_t mcq_seq2tax_find(const mcq_seq2tax* m, const char* name, uint64_t len);
+int mcq_seq2tax_free(mcq_seq2tax* m);
+int mcq_genome_reader_open_mapped(const char* const* files, uint32_t n_files, uint64_t io_bytes, const mcq_refdb* existing,
+                                  const mcq_seq2tax* seq2tax, mcq_genome_reader** out);
+/* Post-mapping (try_to_rank_unranked_targets, src/mode_build.cpp:493-522, :248-312).  mcq_taxmap_files: the files in the order
+ * they are read: `postmap` (-taxpostmap; NULL or "": none), then nucl_gb, nucl_wgs, nucl_est, nucl_gss .accession2taxid of
+ * `taxdir` (named whether they exist or not; a file that does not open is passed over by the caller), then every other file below
+ * taxdir whose path contains ".accession2taxid" (src/args_handling.cpp:122-145).  DIVERGENCES: those last ones come in name order
+ * (the reference: readdir's order); taxdir NULL or "" names no file but `postmap` (the reference looks in the working directory).
+ * mcq_accmap_host: the reference's parser of one such text: the first line is passed over unread (skip_first_line != 0; 0 for
+ * text that goes on in the middle of a file), then `acc accver taxid gi` are read as blank-separated words that may run across
+ * lines, taxid as an unsigned 64-bit number; the text ends at the first record that does not parse, or when no target is left
+ * unranked.  names_blob / name_off / name_target: the sorted names as mcq_accmap_create (include/mcq.h) takes them.  A record's
+ * target (the one named accver, else the first name greater than acc that begins with it, else the one named gi) gets
+ * parent[t] = taxid and unranked[t] = 0 if unranked[t] was set; other entries of `parent` stay.  *n_records (may be NULL): records
+ * read.  The fall-back of mcq_accmap_chunk for text that is not strict, and the CPU yardstick.                               */
+int mcq_taxmap_files(const char* taxdir, const char* postmap, mcq_file_list** out);
+int mcq_accmap_host(const char* text, uint64_t n_bytes, int32_t skip_first_line, const char* names_blob, const uint64_t* name_off,
+                    uint64_t n_names, const uint32_t* name_target, uint8_t* unranked /* [n_targets] in, out */,
+                    int64_t* parent /* [n_targets] in, out */, uint32_t n_targets, uint64_t* n_records);
 
 /* default of -hitmin when unset: src/mode_query.cpp:247-259 */
 uint32_t mcq_default_hits_min(uint32_t sketch_size);

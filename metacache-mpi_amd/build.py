@@ -16,6 +16,7 @@ _UNITS = {
     os.path.join(_CSRC, "mcq_target_hits.hip"): _INTERNAL, # per-target window hit lists (-hits-per-seq)
     os.path.join(_CSRC, "mcq_align.hip"): _INTERNAL,       # read-to-candidate alignment (-align)
     os.path.join(_CSRC, "mcq_all_hits.hip"): _INTERNAL,    # all hits of a read, run-length compressed (-allhits)
+    os.path.join(_CSRC, "mcq_accmap.hip"): _INTERNAL,      # *.accession2taxid text joined against the targets' names (mcq_accmap_*)
     os.path.join(_CSRC, "mcq_build.hip"): [_HDR],          # table construction (rocPRIM sorts)
     os.path.join(_CSRC, "mcq_classify.hip"): [os.path.join(_CSRC, "mcq_classify.hpp"), _HDR],   # classification + taxon counts
 }

@@ -320,6 +320,8 @@ struct mcq_genome_reader {
     std::set<std::string> names;
     uint32_t first_target = 0;         // mcq_genome_reader_open_after: the targets of the database come before this reader's
     uint64_t n_skipped = 0;
+    std::map<std::string, int64_t> seq2tax;    // mcq_genome_reader_open_mapped: the pre-mapping (empty: the header's taxid|N alone)
+    int64_t parent_of(const std::string& name, const std::string& file) const;
     ~mcq_genome_reader() { if (fd >= 0) ::close(fd); }
     void leave_file() { if (fd >= 0) ::close(fd); fd = -1; }
     bool open_next() {                 // false: no file left
@@ -410,7 +412,7 @@ extern "C" int mcq_genome_reader_next(mcq_genome_reader* r, char* bases, uint64_
                 else {
                     if ((uint64_t)r->first_target + r->targets.size() >= 0xFFFFFFFFull) return fail("more targets than a 32-bit target id holds");
                     r->names.insert(name);
-                    const int64_t parent = header_taxid(r->header);
+                    const int64_t parent = r->parent_of(name, r->files[r->next_file - 1]);
                     r->targets.push_back({std::move(name), parent < 1 ? 0 : parent, (uint32_t)(r->next_file - 1), r->index, 0});
                     r->rec = mcq_genome_reader::ACCEPTED;
                 }
@@ -440,3 +442,237 @@ extern "C" int mcq_genome_reader_target(const mcq_genome_reader* r, uint32_t t, 
     return 0;
 }
 extern "C" int mcq_genome_reader_close(mcq_genome_reader* r) { delete r; return 0; }
+
+// ---- pre-mapping: read_sequence_to_taxon_id_mapping and make_sequence_to_taxon_id_map (src/taxonomy_io.cpp:190-310), find_taxon_id
+// (src/mode_build.cpp:531-550).  The reader with its quirks: up to 10 leading '#' lines, the LAST of them is the header row (without
+// one: the first line); the header's first word is dropped and the others are numbered from 0: `taxid` gives taxcol,
+// `accession.version` / `assembly_accession` keycol; a data line is read as keycol TABs passed, a word, taxcol TABs passed, an
+// integer, the rest of the line passed -- so the taxid is taken from column keycol + taxcol, and both passes run across lines.
+// Without a taxid column (taxcol < 1) the file is read again from its first byte as `key TAB taxid` (keycol stays).  A taxid that
+// does not parse is entered as 0 and ends the file; at the end of the text the taxid of the line before is entered; map.insert
+// keeps the first entry of a key.  Not restated: the entry {"", undefined} the reference makes for a file without any data line
+// (no lookup can find it).
+struct mcq_seq2tax {
+    std::map<std::string, int64_t> map;
+    std::vector<std::map<std::string, int64_t>::const_iterator> order;     // for mcq_seq2tax_entry
+};
+namespace {
+struct LineIn {                        // std::getline on an ifstream: good() until a read has hit the end of the text
+    const char* p; const char* e; bool eof = false, failed = false;
+    bool good() const { return !eof && !failed; }
+    void getline(std::string& line) {
+        if (!good()) { failed = true; return; }                            // (the line keeps its text)
+        const char* q = p < e ? (const char*)std::memchr(p, '\n', (size_t)(e - p)) : nullptr;
+        if (q) { line.assign(p, q); p = q + 1; return; }
+        line.assign(p, e); p = e; eof = true;
+        if (line.empty()) failed = true;
+    }
+};
+void read_seq2tax_text(const std::string& text, std::map<std::string, int64_t>& map) {
+    const char* const b = text.data(); const char* const e = b + text.size();
+    int header_row = 0;
+    {
+        LineIn is{b, e};
+        std::string line;
+        for (int i = 0; i < 10; ++i, ++header_row) { is.getline(line); if (line.empty() || line[0] != '#') break; }
+        if (header_row > 0) --header_row;
+    }
+    LineIn is{b, e};
+    std::string line;
+    for (int i = 0; i < header_row; ++i) is.getline(line);
+    if (!is.good()) return;
+    int keycol = 0, taxcol = 0;
+    {
+        std::string header;
+        is.getline(header);
+        Cursor hs(header);
+        std::string w;
+        int col = 0;
+        hs.word(w);                                                        // "get rid of comment chars"
+        while (hs.ok && hs.word(w)) {
+            if (w == "taxid") taxcol = col;
+            else if (w == "accession.version" || w == "assembly_accession") keycol = col;
+            ++col;
+        }
+    }
+    if (taxcol < 1) { is = LineIn{b, e}; taxcol = 1; }
+    if (!is.good()) return;
+    const std::string rest(is.p, e);
+    Cursor c(rest);
+    std::string key; int64_t taxid = 0; bool have = false;                 // have: taxonId holds a value that was read
+    while (c.good()) {
+        for (int i = 0; i < keycol; ++i) c.past('\t');
+        if (!c.word(key)) break;                                           // (the pair of the line before once more: nothing)
+        for (int i = 0; i < taxcol; ++i) c.past('\t');
+        c.ws();
+        if (c.p >= c.e) { if (have) map.insert({key, taxid}); break; }     // nothing extracted: taxonId keeps the line before's
+        int64_t v = 0;
+        if (!c.integer(v)) { map.insert({key, 0}); break; }                // a failed extraction stores 0; the stream is done
+        taxid = v; have = true;
+        c.past('\n');
+        map.insert({key, taxid});
+    }
+}
+int64_t find_taxon_id(const std::map<std::string, int64_t>& m, const std::string& name) {
+    if (m.empty() || name.empty()) return 0;
+    auto i = m.find(name);
+    if (i != m.end()) return i->second;
+    i = m.upper_bound(name);
+    if (i == m.end()) return 0;
+    if (i->first.compare(0, name.size(), name) != 0) return 0;
+    return i->second;
+}
+}  // namespace
+
+extern "C" int mcq_seq2tax_create(mcq_seq2tax** out) {
+    if (!out) return fail("null argument");
+    *out = new mcq_seq2tax();
+    return 0;
+}
+extern "C" int mcq_seq2tax_add_file(mcq_seq2tax* m, const char* path, int32_t* opened) {
+    if (!m || !path) return fail("null argument");
+    std::string text;
+    const bool ok = slurp(path, text);
+    if (opened) *opened = ok ? 1 : 0;
+    if (ok) { read_seq2tax_text(text, m->map); m->order.clear(); }
+    return 0;
+}
+extern "C" int mcq_seq2tax_read(const char* const* genome_files, uint32_t n_files, mcq_seq2tax** out) {
+    if ((n_files && !genome_files) || !out) return fail("null argument");
+    std::set<std::string> dirs;                                            // unique_directories (src/filesys_utility.cpp:79-89)
+    for (uint32_t i = 0; i < n_files; ++i) {
+        const std::string f = genome_files[i];
+        dirs.insert(f.substr(0, f.find_last_of("/\\")));                   // (a name without a separator stands for itself)
+    }
+    mcq_seq2tax* m = new mcq_seq2tax();
+    for (const std::string& d : dirs) mcq_seq2tax_add_file(m, (d + "/assembly_summary.txt").c_str(), nullptr);
+    *out = m;
+    return 0;
+}
+extern "C" uint64_t mcq_seq2tax_count(const mcq_seq2tax* m) { return m ? m->map.size() : 0; }
+extern "C" int mcq_seq2tax_entry(mcq_seq2tax* m, uint64_t i, const char** key, int64_t* taxid) {
+    if (!m || i >= m->map.size()) return fail("no such entry");
+    if (m->order.size() != m->map.size()) { m->order.clear(); for (auto it = m->map.cbegin(); it != m->map.cend(); ++it) m->order.push_back(it); }
+    if (key) *key = m->order[(size_t)i]->first.c_str();
+    if (taxid) *taxid = m->order[(size_t)i]->second;
+    return 0;
+}
+extern "C" int64_t mcq_seq2tax_find(const mcq_seq2tax* m, const char* name, uint64_t len) {
+    return (m && name) ? find_taxon_id(m->map, std::string(name, (size_t)len)) : 0;
+}
+extern "C" int mcq_seq2tax_free(mcq_seq2tax* m) { delete m; return 0; }
+
+extern "C" int mcq_genome_reader_open_mapped(const char* const* files, uint32_t n_files, uint64_t io_bytes, const mcq_refdb* existing,
+                                             const mcq_seq2tax* seq2tax, mcq_genome_reader** out) {
+    mcq_genome_reader* r = nullptr;
+    if (existing ? mcq_genome_reader_open_after(files, n_files, io_bytes, existing, &r) : mcq_genome_reader_open(files, n_files, io_bytes, &r)) return -1;
+    if (seq2tax) r->seq2tax = seq2tax->map;
+    *out = r;
+    return 0;
+}
+// a target's parent (src/mode_build.cpp:591-604): the map's entry for the sequence id, else for the accession string of the file
+// name, else the header's taxid|N
+int64_t mcq_genome_reader::parent_of(const std::string& name, const std::string& file) const {
+    int64_t parent = find_taxon_id(seq2tax, name);
+    if (parent == 0) {
+        std::string id;
+        if (!file.empty()) { id = accession_version(file); if (id.empty()) id = accession_plain(file); if (id.empty()) id = genbank_id(file); }
+        parent = find_taxon_id(seq2tax, id);
+    }
+    if (parent == 0) parent = header_taxid(header);
+    return parent;
+}
+
+// ---- post-mapping: the files (get_taxonomy_options, src/args_handling.cpp:122-145) and the reference's parser of one of them
+// (rank_targets_with_mapping_file, src/mode_build.cpp:248-312).  The files: -taxpostmap FILE, then nucl_gb / nucl_wgs / nucl_est /
+// nucl_gss .accession2taxid of the taxonomy directory (named whether they exist or not), then every other file below it whose path
+// contains ".accession2taxid".  DIVERGENCE: those come in name order here, in readdir's order in the reference.  Without a
+// taxonomy directory only FILE is named (the reference would look in the working directory).
+extern "C" int mcq_taxmap_files(const char* taxdir, const char* postmap, mcq_file_list** out) {
+    if (!out) return fail("null argument");
+    mcq_file_list* L = new mcq_file_list();
+    if (postmap && *postmap) L->files.push_back(postmap);
+    std::string path = taxdir ? taxdir : "";
+    if (!path.empty()) {
+        if (path.back() != '/') path += '/';
+        for (const char* n : {"nucl_gb", "nucl_wgs", "nucl_est", "nucl_gss"}) L->files.push_back(path + n + ".accession2taxid");
+        std::vector<std::string> more = files_in(path, 10);
+        std::sort(more.begin(), more.end());
+        for (const std::string& f : more)
+            if (f.find(".accession2taxid") != npos && std::find(L->files.begin(), L->files.end(), f) == L->files.end()) L->files.push_back(f);
+    }
+    *out = L;
+    return 0;
+}
+
+namespace {
+struct NameSet {
+    const char* blob; const uint64_t* off; uint64_t n; const uint32_t* target;
+    int cmp(uint64_t k, const std::string& s) const {                      // name k against s, as std::string::compare
+        const uint64_t b = off[k], nl = off[k + 1] - b;
+        const int d = std::memcmp(blob + b, s.data(), (size_t)std::min<uint64_t>(nl, s.size()));
+        return d ? d : (nl < s.size() ? -1 : (nl > s.size() ? 1 : 0));
+    }
+    uint64_t find(const std::string& s) const {                            // taxon_with_name
+        if (s.empty()) return n;
+        uint64_t lo = 0, hi = n;
+        while (lo < hi) { const uint64_t mid = lo + (hi - lo) / 2; if (cmp(mid, s) < 0) lo = mid + 1; else hi = mid; }
+        return (lo < n && cmp(lo, s) == 0) ? lo : n;
+    }
+    uint64_t similar(const std::string& s) const {                         // taxon_with_similar_name (src/sketch_database.h:631-639)
+        if (s.empty()) return n;
+        uint64_t lo = 0, hi = n;
+        while (lo < hi) { const uint64_t mid = lo + (hi - lo) / 2; if (cmp(mid, s) <= 0) lo = mid + 1; else hi = mid; }
+        if (lo >= n) return n;
+        const uint64_t b = off[lo], nl = off[lo + 1] - b;
+        return (nl >= s.size() && std::memcmp(blob + b, s.data(), s.size()) == 0) ? lo : n;
+    }
+};
+}  // namespace
+
+// `is >> acc >> accver >> taxid >> gi` until an extraction fails: words are separated by any white space and run across lines; taxid
+// is a uint64 as num_get reads it (an optional sign -- '-' negates in 64 bits --, then digits up to the first other character, which
+// stays in the stream; no digit, or a value beyond 64 bits, fails).
+extern "C" int mcq_accmap_host(const char* text, uint64_t n_bytes, int32_t skip_first_line, const char* names_blob, const uint64_t* name_off,
+                               uint64_t n_names, const uint32_t* name_target, uint8_t* unranked, int64_t* parent, uint32_t n_targets,
+                               uint64_t* n_records) {
+    if ((n_bytes && !text) || !name_off || (n_names && (!names_blob || !name_target)) || (n_targets && (!unranked || !parent))) return fail("null argument");
+    for (uint64_t k = 0; k < n_names; ++k) if (name_target[k] >= n_targets) return fail("a name's target is outside the targets");
+    const NameSet N{names_blob, name_off, n_names, name_target};
+    uint64_t left = 0, records = 0;
+    for (uint32_t t = 0; t < n_targets; ++t) left += unranked[t] != 0;
+    const char* p = text; const char* const e = text + n_bytes;
+    if (skip_first_line && p < e) { const char* q = (const char*)std::memchr(p, '\n', (size_t)(e - p)); p = q ? q + 1 : e; }
+    auto word = [&](std::string& w) {
+        while (p < e && std::isspace((unsigned char)*p)) ++p;
+        if (p >= e) return false;
+        const char* q = p;
+        while (q < e && !std::isspace((unsigned char)*q)) ++q;
+        w.assign(p, q); p = q;
+        return true;
+    };
+    std::string acc, accver, gi;
+    while (left) {                                                         // (`if(targetTaxa.empty()) break`)
+        if (!word(acc) || !word(accver)) break;
+        while (p < e && std::isspace((unsigned char)*p)) ++p;
+        const char* q = p; bool neg = false;
+        if (q < e && (*q == '-' || *q == '+')) { neg = *q == '-'; ++q; }
+        if (q >= e || *q < '0' || *q > '9') break;
+        uint64_t v = 0; bool over = false;
+        for (; q < e && *q >= '0' && *q <= '9'; ++q) {
+            const uint64_t d = (uint64_t)(*q - '0');
+            if (v > (0xFFFFFFFFFFFFFFFFull - d) / 10) over = true;
+            v = v * 10 + d;
+        }
+        if (over) break;
+        if (neg) v = 0 - v;
+        p = q;
+        if (!word(gi)) break;
+        ++records;
+        uint64_t k = N.find(accver);
+        if (k == N.n) { k = N.similar(acc); if (k == N.n) k = N.find(gi); }
+        if (k != N.n && unranked[name_target[k]]) { unranked[name_target[k]] = 0; parent[name_target[k]] = (int64_t)v; --left; }
+    }
+    if (n_records) *n_records = records;
+    return 0;
+}

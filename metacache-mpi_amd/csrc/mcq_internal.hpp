@@ -3,7 +3,7 @@
 // C ABI, the owners of their GPU resources, error reporting, a few inline helpers, and the declarations of the functions that
 // cross a unit boundary (hidden visibility: none is part of the ABI).  The units: mcq_engine.hip (workspace, fused query, reduce),
 // mcq_table.hip (mcq_db_*), mcq_stages.hip (staged and routing entry points, batch preparation), mcq_shard.hip (mcq_shard_*),
-// mcq_target_hits.hip (mcq_target_*), mcq_align.hip (mcq_align), mcq_all_hits.hip (mcq_all_hits*).  Kernels are not declared here: each is defined in the unit that launches it.
+// mcq_target_hits.hip (mcq_target_*), mcq_align.hip (mcq_align), mcq_all_hits.hip (mcq_all_hits*), mcq_accmap.hip (mcq_accmap_*).  Kernels are not declared here: each is defined in the unit that launches it.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <stdio.h>

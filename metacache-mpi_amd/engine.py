@@ -225,6 +225,11 @@ def lib():
             L.mcq_all_hits_count.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(Batch), C.c_void_p, C.c_void_p]
             L.mcq_all_hits.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(Batch), C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p,
                                        C.c_void_p, C.c_void_p]
+        if hasattr(L, "mcq_accmap_create"):
+            L.mcq_accmap_create.argtypes = [C.c_char_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_uint32, C.c_int, C.POINTER(C.c_void_p)]
+            L.mcq_accmap_chunk.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint32, C.c_uint64, C.POINTER(C.c_uint32), C.c_void_p]
+            L.mcq_accmap_finish.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
+            L.mcq_accmap_free.argtypes = [C.c_void_p]
         L.mcq_shard_create.argtypes = [C.c_void_p, C.POINTER(ShardCfg), C.POINTER(C.c_void_p)]
         L.mcq_shard_destroy.argtypes = [C.c_void_p]
         L.mcq_shard_unique_id.argtypes = [C.c_void_p]
@@ -1094,6 +1099,58 @@ class TableExtend:
     def close(self):
         if getattr(self, "h", None):
             lib().mcq_table_extend_free(self.h); self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+MCQ_ACCMAP_MAX_LINE = 1024
+
+
+def sorted_names(names):
+    """the names of the targets (bytes, target t at index t) as mcq_accmap_create and host.accmap_host take them: (blob, name_off,
+    name_target), ascending as std::string compares (Python's bytes compare the same way), a name that occurs twice kept once"""
+    order = sorted(range(len(names)), key=lambda t: (names[t], t))
+    keep = [t for i, t in enumerate(order) if i == 0 or names[t] != names[order[i - 1]]]
+    off = np.zeros(len(keep) + 1, np.uint64)
+    off[1:] = np.cumsum([len(names[t]) for t in keep])
+    return b"".join(names[t] for t in keep), off, np.asarray(keep, np.uint32)
+
+
+class AccMap:
+    """mcq_accmap_*: *.accession2taxid text joined against the names of a database's targets on the GPU.  names: the target names
+    (bytes; target t at index t); unranked: per target, non-zero where it has no parent.  chunk() takes whole lines of one file in
+    DEVICE memory (a pointer and a byte count, or a torch uint8 tensor on the GPU) and returns whether the chunk was strict (and so
+    applied); finish() returns (parent int64[n_targets], found bool[n_targets])."""
+
+    def __init__(self, names, unranked, device=0):
+        blob, off, tgt = sorted_names([bytes(n) for n in names])
+        u = np.ascontiguousarray(unranked, np.uint8)
+        assert len(u) == len(names)
+        h = C.c_void_p()
+        _chk(lib().mcq_accmap_create(blob, _np_ptr(off), len(tgt), _np_ptr(tgt), _np_ptr(u), len(u), device, C.byref(h)))
+        self.h, self.n_targets = h, len(u)
+
+    def chunk(self, text, n_bytes=None, file_ordinal=0, first_line_no=0, stream=None):
+        if n_bytes is None:
+            ptr, n_bytes = text.data_ptr(), text.numel()
+        else:
+            ptr = int(text)
+        strict = C.c_uint32(0)
+        _chk(lib().mcq_accmap_chunk(self.h, C.c_void_p(ptr), n_bytes, file_ordinal, first_line_no, C.byref(strict), stream))
+        return bool(strict.value)
+
+    def finish(self):
+        parent, found = np.zeros(self.n_targets, np.int64), np.zeros(self.n_targets, np.uint8)
+        _chk(lib().mcq_accmap_finish(self.h, _np_ptr(parent), _np_ptr(found)))
+        return parent, found.astype(bool)
+
+    def close(self):
+        if getattr(self, "h", None):
+            lib().mcq_accmap_free(self.h); self.h = None
 
     def __del__(self):
         try:

@@ -187,6 +187,17 @@ def lib():
         L.mcq_genome_reader_open_after.argtypes = [C.POINTER(C.c_char_p), C.c_uint32, C.c_uint64, C.c_void_p, C.POINTER(C.c_void_p)]
         L.mcq_genome_reader_n_skipped.restype = C.c_uint64; L.mcq_genome_reader_n_skipped.argtypes = [C.c_void_p]
         L.mcq_refdb_taxa.argtypes = [C.c_void_p, C.POINTER(TaxonRec)]
+        L.mcq_seq2tax_create.argtypes = [C.POINTER(C.c_void_p)]
+        L.mcq_seq2tax_add_file.argtypes = [C.c_void_p, C.c_char_p, C.POINTER(C.c_int32)]
+        L.mcq_seq2tax_read.argtypes = [C.POINTER(C.c_char_p), C.c_uint32, C.POINTER(C.c_void_p)]
+        L.mcq_seq2tax_count.restype = C.c_uint64; L.mcq_seq2tax_count.argtypes = [C.c_void_p]
+        L.mcq_seq2tax_entry.argtypes = [C.c_void_p, C.c_uint64, C.POINTER(C.c_char_p), C.POINTER(C.c_int64)]
+        L.mcq_seq2tax_find.restype = C.c_int64; L.mcq_seq2tax_find.argtypes = [C.c_void_p, C.c_char_p, C.c_uint64]
+        L.mcq_seq2tax_free.argtypes = [C.c_void_p]
+        L.mcq_genome_reader_open_mapped.argtypes = [C.POINTER(C.c_char_p), C.c_uint32, C.c_uint64, C.c_void_p, C.c_void_p, C.POINTER(C.c_void_p)]
+        L.mcq_taxmap_files.argtypes = [C.c_char_p, C.c_char_p, C.POINTER(C.c_void_p)]
+        L.mcq_accmap_host.argtypes = [C.c_char_p, C.c_uint64, C.c_int32, C.c_char_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p,
+                                      C.c_uint32, C.POINTER(C.c_uint64)]
         _lib = L
     return _lib
 
@@ -595,14 +606,102 @@ def genome_files(args):
         lib().mcq_file_list_free(h)
 
 
-def read_genomes(files, cap, io_bytes=1 << 20, after=None, skipped=None):
-    """mcq_genome_reader_* over `files` with a buffer of `cap` bases: (bases of all targets back to back as bytes, taxon records of
-    the targets as dicts, lengths, number of fills).  after: a RefDb -- mcq_genome_reader_open_after, the sequences are added to
-    that database (its names are taken, ids go on behind its targets); skipped: a list that gets mcq_genome_reader_n_skipped."""
+class Seq2Tax:
+    """mcq_seq2tax_*: the pre-mapping of sequence ids and file accessions to taxon ids (assembly_summary.txt and its like)"""
+
+    def __init__(self, h=None):
+        if h is None:
+            h = C.c_void_p()
+            if lib().mcq_seq2tax_create(C.byref(h)) != 0:
+                raise _err()
+        self.h = h
+
+    def add_file(self, path):
+        """reads one mapping file into the map; False (and nothing read) if it does not open"""
+        opened = C.c_int32(0)
+        if lib().mcq_seq2tax_add_file(self.h, str(path).encode(), C.byref(opened)) != 0:
+            raise _err()
+        return bool(opened.value)
+
+    def items(self):
+        out = []
+        for i in range(lib().mcq_seq2tax_count(self.h)):
+            k, v = C.c_char_p(), C.c_int64()
+            if lib().mcq_seq2tax_entry(self.h, i, C.byref(k), C.byref(v)) != 0:
+                raise _err()
+            out.append((k.value, int(v.value)))
+        return out
+
+    def find(self, name):
+        return int(lib().mcq_seq2tax_find(self.h, name, len(name)))
+
+    def close(self):
+        if getattr(self, "h", None):
+            lib().mcq_seq2tax_free(self.h); self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def read_seq2tax(dirs):
+    """<dir>/assembly_summary.txt of every directory, in the order given, into one Seq2Tax (the first entry of a key stays)"""
+    m = Seq2Tax()
+    for d in dirs:
+        m.add_file(str(d) + "/assembly_summary.txt")
+    return m
+
+
+def read_seq2tax_for(files):
+    """mcq_seq2tax_read: the same for the distinct directories of the genome files, in the reference's order"""
     arr = (C.c_char_p * len(files))(*[str(f).encode() for f in files])
     h = C.c_void_p()
-    if (lib().mcq_genome_reader_open(arr, len(files), io_bytes, C.byref(h)) if after is None else
-            lib().mcq_genome_reader_open_after(arr, len(files), io_bytes, after.h, C.byref(h))) != 0:
+    if lib().mcq_seq2tax_read(arr, len(files), C.byref(h)) != 0:
+        raise _err()
+    return Seq2Tax(h)
+
+
+def taxmap_files(taxdir, postmap=None):
+    """mcq_taxmap_files: the *.accession2taxid files in reading order (they need not exist)"""
+    h = C.c_void_p()
+    if lib().mcq_taxmap_files(str(taxdir).encode() if taxdir else None, str(postmap).encode() if postmap else None, C.byref(h)) != 0:
+        raise _err()
+    try:
+        return [lib().mcq_file_list_get(h, i).decode() for i in range(lib().mcq_file_list_count(h))]
+    finally:
+        lib().mcq_file_list_free(h)
+
+
+def accmap_host(text, names, unranked, parent, skip_first_line=True):
+    """mcq_accmap_host: the reference's token parser over one mapping text (bytes).  names: the target names (bytes, target t at index
+    t); unranked (uint8) and parent (int64) are numpy arrays that are UPDATED.  Returns the number of records read."""
+    from .engine import sorted_names
+    blob, off, tgt = sorted_names([bytes(n) for n in names])
+    assert unranked.dtype == np.uint8 and parent.dtype == np.int64 and len(unranked) == len(parent) == len(names)
+    n = C.c_uint64(0)
+    if lib().mcq_accmap_host(text, len(text), 1 if skip_first_line else 0, blob, off.ctypes.data_as(C.c_void_p), len(tgt),
+                             tgt.ctypes.data_as(C.c_void_p), unranked.ctypes.data_as(C.c_void_p), parent.ctypes.data_as(C.c_void_p),
+                             len(names), C.byref(n)) != 0:
+        raise _err()
+    return int(n.value)
+
+
+def read_genomes(files, cap, io_bytes=1 << 20, after=None, skipped=None, seq2tax=None):
+    """mcq_genome_reader_* over `files` with a buffer of `cap` bases: (bases of all targets back to back as bytes, taxon records of
+    the targets as dicts, lengths, number of fills).  after: a RefDb -- mcq_genome_reader_open_after, the sequences are added to
+    that database (its names are taken, ids go on behind its targets); skipped: a list that gets mcq_genome_reader_n_skipped;
+    seq2tax: a Seq2Tax -- mcq_genome_reader_open_mapped, the parents come from the map before the header."""
+    arr = (C.c_char_p * len(files))(*[str(f).encode() for f in files])
+    h = C.c_void_p()
+    if seq2tax is not None:
+        rc = lib().mcq_genome_reader_open_mapped(arr, len(files), io_bytes, after.h if after is not None else None, seq2tax.h, C.byref(h))
+    elif after is None:
+        rc = lib().mcq_genome_reader_open(arr, len(files), io_bytes, C.byref(h))
+    else:
+        rc = lib().mcq_genome_reader_open_after(arr, len(files), io_bytes, after.h, C.byref(h))
+    if rc != 0:
         raise _err()
     try:
         buf = C.create_string_buffer(max(1, cap))
