@@ -826,6 +826,51 @@ int mcq_accmap_chunk(mcq_accmap* h, const char* text, uint64_t n_bytes, uint32_t
 int mcq_accmap_finish(mcq_accmap* h, int64_t* parent /* host [n_targets] */, uint8_t* found /* host [n_targets] */);
 int mcq_accmap_free(mcq_accmap* h);
 
+/* ---- merging query result files: the reference's `merge` mode (csrc/mcq_merge.hip) --------------------------------------
+ * What read_results (src/mode_merge.cpp:209-264) does with every mapping line of files written with `-tophits -queryids`, and
+ * classify() of the merged lists.  The handle owns per query a candidate list -- a count and max_cand (taxon index, hits) pairs --
+ * the reference of its header token (file ordinal, byte offset in the file, length; the first line that brings one sets it) and
+ * a count of the items whose taxid the taxonomy does not have (the reference prints `taxid not found` per item).  Every item of a
+ * line goes through best_distinct_matches_in_contiguous_window_ranges::insert (src/candidates.h:236-285) on the list of the line's
+ * query, in item order: the taxon becomes its ancestor at merge_below_rank if it has one (0: never); a taxon in the list takes
+ * more hits and moves ahead of smaller entries, behind equal ones; a new taxon goes in behind equal hits, unless that is the end
+ * of a full list.  The insert depends on order: chunks of a file in file order and files in merge order, all on ONE stream.
+ * create   tx: the ranked lineages (mcq_taxonomy_create), which must outlive the handle; taxid_sorted / taxid_taxon [n_ids]: the
+ *          taxon ids strictly ascending with their taxon indices (host arrays, copied); max_cand 1..16.
+ * chunk    text: whole lines of ONE file in DEVICE memory (16-B aligned text is read with 16-B loads), n_bytes < 2^32;
+ *          chunk_offset: the byte of the file the chunk begins at (header references); tophits_column >= 2: the number of `|` in
+ *          front of the top_hits column.  The chunk is STRICT when every line begins with '#' (skipped), or is: 1-18 digits, the
+ *          query id in 1 .. n_queries; `\t|\t`; the header column, beginning with a non-empty token (up to the first blank); the
+ *          further columns, each ended by `\t|\t`, and no '|' anywhere else in front of the top_hits column; the top_hits column,
+ *          empty or `taxid:hits` items (taxid 1-18 digits, hits 1-9 digits) split by single ',', at most MCQ_MERGE_MAX_ITEMS; a
+ *          TAB.  What follows that TAB is not looked at.  A line is at most MCQ_MERGE_MAX_LINE bytes with its LF (the chunk's last
+ *          line may lack the LF); no id occurs twice in the chunk; there is no empty line.  *strict (host) = 1: the chunk is
+ *          applied when the call returns; 0: it is not strict and NOTHING in the handle has changed (the caller parses it on the
+ *          host and hands the lines to mcq_merge_lines).  The call waits for `stream`.
+ * lines    lines that are parsed already (host arrays): line l names query line_query[l] (0-based: id - 1) and holds the items
+ *          [item_off[l], item_off[l + 1]) of taxid / hits, and its header token at header_off[l] of file file_ordinal, header_len[l]
+ *          bytes (0: none).  One call holds a query at most once (MCQ_E_ARG otherwise, and nothing is applied): a caller with a
+ *          repeated id cuts the call there.  The same apply kernel as chunk.  The call waits for `stream`.
+ * finish   classifies the lists as mcq_classify does candidates: best (device [n_queries], may be NULL), counts (device
+ *          [n_taxa + 1], may be NULL, ADDED to).  Only enqueues work on `stream`.  The handle stays usable.
+ * lists / headers   copy out to host arrays (any may be NULL): n_cand [n_queries], pairs [n_queries * max_cand * 2] (taxon index,
+ *          hits; the slots behind n_cand hold what earlier inserts left), *n_unknown; file / offset / length [n_queries] (length 0:
+ *          no header seen).  They wait for the device.                                                                          */
+#define MCQ_MERGE_MAX_LINE 4096
+#define MCQ_MERGE_MAX_ITEMS 64
+typedef struct mcq_merge mcq_merge;
+int mcq_merge_create(const mcq_taxonomy* tx, const int64_t* taxid_sorted, const uint32_t* taxid_taxon, uint64_t n_ids,
+                     uint64_t n_queries, uint32_t max_cand, uint32_t merge_below_rank, int device, mcq_merge** out);
+int mcq_merge_chunk(mcq_merge* h, const char* text, uint64_t n_bytes, uint32_t file_ordinal, uint64_t chunk_offset,
+                    uint32_t tophits_column, int32_t* strict, void* stream);
+int mcq_merge_lines(mcq_merge* h, const uint32_t* line_query, const uint64_t* item_off /* [n_lines + 1] */, const int64_t* taxid,
+                    const uint32_t* hits, const uint64_t* header_off, const uint32_t* header_len, uint64_t n_lines,
+                    uint32_t file_ordinal, uint32_t flags /* 0 */, void* stream);
+int mcq_merge_finish(mcq_merge* h, const mcq_classify_opts* opts, uint32_t* best, uint64_t* counts, void* stream);
+int mcq_merge_lists(mcq_merge* h, uint32_t* n_cand, uint32_t* pairs, uint64_t* n_unknown);
+int mcq_merge_headers(mcq_merge* h, uint32_t* file, uint64_t* offset, uint32_t* length);
+int mcq_merge_free(mcq_merge* h);
+
 /* ---- debug / parity taps ------------------------------------------------------------
  * Row 5 in isolation is mcq_count_windows + mcq_sketch above (the sketches of every window).
  * Rows 7-8 in isolation: the sorted match list of every query (what merge_sort returns,

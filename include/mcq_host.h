@@ -383,6 +383,37 @@ int mcq_accmap_host(const char* text, uint64_t n_bytes, int32_t skip_first_line,
                     uint64_t n_names, const uint32_t* name_target, uint8_t* unranked /* [n_targets] in, out */,
                     int64_t* parent /* [n_targets] in, out */, uint32_t n_targets, uint64_t* n_records);
 
+/* ---- merging query result files: the host side of the reference's `merge` mode (the device side: mcq_merge_* of include/mcq.h) ----
+ * mcq_refdb_from_taxdump: a database that is a taxonomy alone -- the taxa of a dump in its order, no target, no table; the taxon
+ * functions above (id, name, rank, ancestor, lineages, classify, abundance text, statistics) work on it unchanged.
+ * mcq_refdb_taxid_table: the taxon ids of a database strictly ascending with the taxon index taxon_with_id gives for each (of two
+ * taxa with one id the one the id map holds): what mcq_merge_create takes.  ids / index: [n_taxa]; *n_ids: how many were written.
+ * mcq_results_properties: get_results_file_properties (src/mode_merge.cpp:131-200) -- only '#' lines up to one that begins with
+ * "# Classification" (which must not hold "sequence"), then only '#' lines up to "# TABLE_LAYOUT:", whose first column must be
+ * query_id; *tophits_column = the number of '|' in front of the column named top_hits (it must be 2 or more: behind the query
+ * header); *results_begin = the byte at which the first line that does not begin with '#' begins (the file's size if there is
+ * none); *n_lines = the number of lines from there on that do not begin with '#' (an empty line counts).  Every rejection is an
+ * error whose text names the file.
+ * mcq_merge_host: read_results (src/mode_merge.cpp:209-264) over text that holds whole lines of a results file: lines that begin
+ * with '#' are skipped; of the others the unsigned id is read (white space in front of it skipped, line ends included), the
+ * stream goes behind the next '|', the header is the next blank-delimited token, the stream goes behind tophits_column - 1 more
+ * '|' and behind the next TAB, and until the next character is a TAB it reads taxid (signed 64-bit), goes behind ':', reads hits
+ * (unsigned 64-bit) and one character.  Line l of the output names query line_query[l] (0-based: id - 1), holds the items
+ * [item_off[l], item_off[l + 1]) of taxid / hits and its header token at header_off[l] = text_offset + its place in text, header_len[l]
+ * bytes: the arrays of mcq_merge_lines.  item_off holds line_cap + 1 words; the number of '\n' + 1 and the number of ':' bound the
+ * lines and the items.  Ids may repeat: the caller cuts its mcq_merge_lines calls there.
+ * DIVERGENCES, all errors whose text is `file_name: line N: ...` (N = first_line_no + the line's index in text): where the
+ * reference's stream goes bad inside a line the reference never returns (its loop waits for a TAB); id 0 (the reference takes it
+ * for id 1) and an id beyond n_queries (the reference writes past its vectors); a '|' inside the header token (the reference
+ * parses such a line in two ways, depending on whether it knows the query's header already); hits of 2^32 or more.              */
+int mcq_refdb_from_taxdump(const mcq_taxdump* dump, mcq_refdb** out);
+int mcq_refdb_taxid_table(const mcq_refdb* db, int64_t* ids, uint32_t* index, uint64_t* n_ids);
+int mcq_results_properties(const char* path, uint32_t* tophits_column, uint64_t* results_begin, uint64_t* n_lines);
+int mcq_merge_host(const char* text, uint64_t n_bytes, uint32_t tophits_column, uint64_t n_queries, const char* file_name,
+                   uint64_t first_line_no, uint64_t text_offset, uint32_t* line_query, uint64_t* item_off, int64_t* taxid,
+                   uint32_t* hits, uint64_t* header_off, uint32_t* header_len, uint64_t line_cap, uint64_t item_cap,
+                   uint64_t* n_lines, uint64_t* n_items);
+
 /* default of -hitmin when unset: src/mode_query.cpp:247-259 */
 uint32_t mcq_default_hits_min(uint32_t sketch_size);
 uint32_t mcq_rank_from_name(const char* name);

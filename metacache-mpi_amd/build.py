@@ -17,8 +17,9 @@ _UNITS = {
     os.path.join(_CSRC, "mcq_align.hip"): _INTERNAL,       # read-to-candidate alignment (-align)
     os.path.join(_CSRC, "mcq_all_hits.hip"): _INTERNAL,    # all hits of a read, run-length compressed (-allhits)
     os.path.join(_CSRC, "mcq_accmap.hip"): _INTERNAL,      # *.accession2taxid text joined against the targets' names (mcq_accmap_*)
+    os.path.join(_CSRC, "mcq_merge.hip"): _INTERNAL + [os.path.join(_CSRC, "mcq_classify_one.hpp")],   # merge of query result files (mcq_merge_*)
     os.path.join(_CSRC, "mcq_build.hip"): [_HDR],          # table construction (rocPRIM sorts)
-    os.path.join(_CSRC, "mcq_classify.hip"): [os.path.join(_CSRC, "mcq_classify.hpp"), _HDR],   # classification + taxon counts
+    os.path.join(_CSRC, "mcq_classify.hip"): [os.path.join(_CSRC, h) for h in ("mcq_classify.hpp", "mcq_classify_one.hpp")] + [_HDR],   # classification + taxon counts
 }
 _OBJ = os.path.join(_HERE, "csrc", "_obj")
 
@@ -38,6 +39,10 @@ def cli_path():
 
 def build_cli_path():
     return os.path.join(_HERE, "mcq_build_cli")
+
+
+def merge_cli_path():
+    return os.path.join(_HERE, "mcq_merge_cli")
 
 
 def mpi_cli_path():
@@ -68,8 +73,8 @@ def source_digest():
 
 def build_host(force=False, verbose=False):
     """libmcq_host.so (shard reader and writer, taxonomy, classify, build inputs; g++, no GPU) and the
-    mcq_query_cli and mcq_build_cli binaries (they link both libraries)."""
-    srcs = [os.path.join(_HERE, "csrc", "host", f) for f in ("mcq_host.cpp", "mcq_host_build.cpp")]     # query side, build side
+    mcq_query_cli, mcq_build_cli and mcq_merge_cli binaries (they link both libraries)."""
+    srcs = [os.path.join(_HERE, "csrc", "host", f) for f in ("mcq_host.cpp", "mcq_host_build.cpp", "mcq_host_merge.cpp")]     # query side, build side, merge side
     hdr = os.path.join(os.path.dirname(_HERE), "include", "mcq_host.h")
     out = host_lib_path()
     if force or not os.path.exists(out) or os.path.getmtime(out) < max(os.path.getmtime(f) for f in srcs + [hdr, os.path.join(_HERE, "csrc", "host", "mcq_host_internal.hpp")]):
@@ -95,6 +100,15 @@ def build_host(force=False, verbose=False):
     if force or not os.path.exists(bcli) or os.path.getmtime(bcli) < max(os.path.getmtime(f) for f in shared + [bcli_src]):
         hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
         cmd = [hipcc, "-std=c++14", "-O2", "-pthread", bcli_src, "-o", bcli, "-L" + _HERE, "-lmcq_hip", "-lmcq_host", "-Wl,-rpath,$ORIGIN"]
+        if verbose:
+            print(" ".join(cmd))
+        subprocess.check_call(cmd)
+    # mcq_merge_cli: result files of several databases -> one classification per read
+    mcli_src = os.path.join(_HERE, "csrc", "host", "mcq_merge_cli.cpp")
+    mcli = merge_cli_path()
+    if force or not os.path.exists(mcli) or os.path.getmtime(mcli) < max(os.path.getmtime(f) for f in shared + [mcli_src]):
+        hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
+        cmd = [hipcc, "-std=c++14", "-O2", "-pthread", mcli_src, "-o", mcli, "-L" + _HERE, "-lmcq_hip", "-lmcq_host", "-Wl,-rpath,$ORIGIN"]
         if verbose:
             print(" ".join(cmd))
         subprocess.check_call(cmd)

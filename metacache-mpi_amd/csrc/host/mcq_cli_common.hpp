@@ -349,7 +349,7 @@ static Out make_out(mcq_refdb* rdb, const Options& p) {
 }
 
 // show_query_parameters (src/printing.cpp:40-113) + show_query_mapping_header (src/classification.cpp:486-512)
-static void write_head(std::ostream& os, const Out& o, uint32_t hitmin) {
+static void write_head(std::ostream& os, const Out& o, uint32_t hitmin, bool layout = true) {   // layout false: the head of a merge, which prints no TABLE_LAYOUT line
     const Options& p = o.p; const char* cm = o.comment;
     if (!p.nomap) {
         os << cm << "Reporting per-read mappings (non-mapping lines start with '" << cm << "').\n";
@@ -372,7 +372,7 @@ static void write_head(std::ostream& os, const Out& o, uint32_t hitmin) {
         os << cm << "A list of absolute and relative abundances for each '" << mcq_rank_name(p.abundance_rank)
            << "' will be generated after the read mapping.\n";
     os << cm << "Using " << p.threads << " threads\n";
-    if (!p.nomap) {
+    if (!p.nomap && layout) {
         os << cm << "TABLE_LAYOUT: ";
         if (p.query_ids) os << "query_id" << o.col;                          // showQueryIds, src/query_options.cpp:308, src/classification.cpp:495
         os << "query_header" << o.col;

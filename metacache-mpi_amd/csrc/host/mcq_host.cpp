@@ -1041,3 +1041,38 @@ extern "C" int mcq_reads_parse(const char* text1, uint64_t len1, const char* tex
     info[MCQ_READS_COMPLETE2] = paired ? R[1].n_complete : 0;
     return 0;
 }
+
+// ---- a database that is a taxonomy alone: what `merge` works on (main_mode_merge reads the taxonomy dump, no shard file) ----------
+extern "C" int mcq_refdb_from_taxdump(const mcq_taxdump* dump, mcq_refdb** out) {
+    if (!dump || !out) return fail("bad argument");
+    const uint64_t n = mcq_taxdump_count(dump);
+    if (n == 0 || n >= (1ull << 31)) return fail("a taxonomy of 1 .. 2^31 - 1 taxa");
+    const mcq_taxon_rec* recs = mcq_taxdump_taxa(dump);
+    mcq_refdb* db = new mcq_refdb();
+    db->taxa.reserve(n);
+    for (uint64_t i = 0; i < n; ++i) {
+        Taxon t; t.id = recs[i].id; t.parent = recs[i].parent; t.rank = recs[i].rank; t.name = recs[i].name ? recs[i].name : "";
+        t.file = recs[i].file ? recs[i].file : ""; t.index = recs[i].index; t.windows = recs[i].windows;
+        db->taxa.push_back(std::move(t));
+    }
+    db->info.n_taxa = (uint32_t)n;                // (no targets, no table, no sketching parameters: all 0)
+    build_lineages(db);
+    *out = db;
+    return 0;
+}
+
+extern "C" int mcq_refdb_taxid_table(const mcq_refdb* db, int64_t* ids, uint32_t* index, uint64_t* n_ids) {
+    if (!db || !ids || !index || !n_ids) return fail("bad argument");
+    std::vector<std::pair<int64_t, uint32_t>> v;
+    v.reserve(db->taxa.size());
+    for (uint32_t i = 0; i < db->taxa.size(); ++i) v.emplace_back(db->taxa[i].id, i);
+    std::sort(v.begin(), v.end());
+    uint64_t n = 0;
+    for (size_t i = 0; i < v.size(); ++i)
+        if (i == 0 || v[i].first != v[i - 1].first) {
+            const auto it = db->by_id.find(v[i].first);      // (taxon_with_id: the index the id map holds)
+            ids[n] = v[i].first; index[n] = it != db->by_id.end() ? it->second : v[i].second; ++n;
+        }
+    *n_ids = n;
+    return 0;
+}

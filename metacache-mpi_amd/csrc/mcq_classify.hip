@@ -16,13 +16,14 @@
 #include <string>
 
 #include "mcq_classify.hpp"
+#include "mcq_classify_one.hpp"
 
 namespace {
 
 typedef uint32_t u32;
 typedef uint64_t u64;
 
-constexpr u32 kNumRanks = 21;
+constexpr u32 kNumRanks = mcq::kClsNumRanks;
 constexpr u32 kNone = 0xFFFFFFFFu;
 constexpr int kThreads = 256;
 constexpr int kMaxCand = 16;
@@ -35,41 +36,10 @@ struct ClassifyArgs {
     const u32* n_cand;            // [n]
     u64 n;
     u32 max_cand;
-    const u32* lineage;           // [n_taxa * 21]
-    const uint8_t* rank;          // [n_taxa]
-    u32 n_taxa;
-    u32 hits_min;
-    float frac;
-    u32 highest;
+    mcq::ClassifyRules rules;     // lineage table, ranks and the options: what classify_one (mcq_classify_one.hpp) reads
     u32* best;                    // [n] or null
     unsigned long long* counts;   // [n_taxa + 1] or null
 };
-
-__device__ __forceinline__ bool valid_key(u32 key, u32 n_taxa) { return key != kNone && (key & 0x7FFFFFFFu) < n_taxa; }
-
-// mcq_refdb_classify (csrc/host/mcq_host.cpp) on the (tax, hits) pairs c[0 .. n)
-__device__ u32 classify_one(const uint2* c, u32 n, const ClassifyArgs& a) {
-    if (n == 0 || !valid_key(c[0].x, a.n_taxa)) return kNone;
-    const u32 h0 = c[0].y;
-    if (h0 < a.hits_min) return kNone;
-    u32 lca = c[0].x & 0x7FFFFFFFu;
-    const float thr = h0 > a.hits_min ? __fmul_rn(__uint2float_rn(h0 - a.hits_min), a.frac) : 0.0f;
-    for (u32 i = 1; i < n; ++i) {
-        if (!(__uint2float_rn(c[i].y) > thr)) break;
-        u32 r = kNone;
-        if (valid_key(c[i].x, a.n_taxa)) {
-            const u32* la = a.lineage + (u64)lca * kNumRanks;
-            const u32* lb = a.lineage + (u64)(c[i].x & 0x7FFFFFFFu) * kNumRanks;
-            for (u32 j = 0; j < kNumRanks; ++j) {
-                const u32 x = la[j];
-                if (x != kNone && x == lb[j]) { r = x; break; }
-            }
-        }
-        lca = r;
-        if (lca == kNone || a.rank[lca] > a.highest) return kNone;
-    }
-    return a.rank[lca] <= a.highest ? lca : kNone;
-}
 
 template <bool COUNT>
 __global__ __launch_bounds__(kThreads) void k_classify(ClassifyArgs a) {
@@ -94,9 +64,9 @@ __global__ __launch_bounds__(kThreads) void k_classify(ClassifyArgs a) {
         if (tid < nq) {
             const u64 q = base + tid;
             const u32 n = min(a.n_cand[q], mc);
-            const u32 b = classify_one(&s_cand[tid * mc], n, a);
+            const u32 b = mcq::classify_one(&s_cand[tid * mc], n, a.rules);
             if (a.best) a.best[q] = b;
-            key = b == kNone ? a.n_taxa : b;
+            key = b == kNone ? a.rules.n_taxa : b;
         }
         if (COUNT) {
             bool pending = false;
@@ -184,8 +154,8 @@ extern "C" int mcq_classify(const mcq_taxonomy* tx, const mcq_result* cands, uin
     if (hipSetDevice(tx->device) != hipSuccess) return mcq::set_error(MCQ_E_HIP, "hipSetDevice failed");
     ClassifyArgs a;
     a.cands = reinterpret_cast<const uint4*>(cands->cands); a.n_cand = cands->n_cand; a.n = n_queries; a.max_cand = max_cand;
-    a.lineage = tx->lineage; a.rank = tx->rank; a.n_taxa = tx->n_taxa;
-    a.hits_min = opts->hits_min; a.frac = opts->hits_diff_fraction; a.highest = opts->highest_rank;
+    a.rules.lineage = tx->lineage; a.rules.rank = tx->rank; a.rules.n_taxa = tx->n_taxa;
+    a.rules.hits_min = opts->hits_min; a.rules.frac = opts->hits_diff_fraction; a.rules.highest = opts->highest_rank;
     a.best = best; a.counts = reinterpret_cast<unsigned long long*>(counts);
     const u32 grid = (u32)std::min<u64>(tx->grid[max_cand], (n_queries + kThreads - 1) / kThreads);
     const size_t lds = (size_t)max_cand * kThreads * 8;

@@ -230,6 +230,16 @@ def lib():
             L.mcq_accmap_chunk.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint32, C.c_uint64, C.POINTER(C.c_uint32), C.c_void_p]
             L.mcq_accmap_finish.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
             L.mcq_accmap_free.argtypes = [C.c_void_p]
+        if hasattr(L, "mcq_merge_create"):
+            L.mcq_merge_create.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint64, C.c_uint32, C.c_uint32, C.c_int,
+                                           C.POINTER(C.c_void_p)]
+            L.mcq_merge_chunk.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint32, C.c_uint64, C.c_uint32, C.POINTER(C.c_int32), C.c_void_p]
+            L.mcq_merge_lines.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64,
+                                          C.c_uint32, C.c_uint32, C.c_void_p]
+            L.mcq_merge_finish.argtypes = [C.c_void_p, C.POINTER(ClassifyOpts), C.c_void_p, C.c_void_p, C.c_void_p]
+            L.mcq_merge_lists.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_uint64)]
+            L.mcq_merge_headers.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+            L.mcq_merge_free.argtypes = [C.c_void_p]
         L.mcq_shard_create.argtypes = [C.c_void_p, C.POINTER(ShardCfg), C.POINTER(C.c_void_p)]
         L.mcq_shard_destroy.argtypes = [C.c_void_p]
         L.mcq_shard_unique_id.argtypes = [C.c_void_p]
@@ -1151,6 +1161,88 @@ class AccMap:
     def close(self):
         if getattr(self, "h", None):
             lib().mcq_accmap_free(self.h); self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+MCQ_MERGE_MAX_LINE = 4096
+MCQ_MERGE_MAX_ITEMS = 64
+
+
+class Merge:
+    """mcq_merge_*: the reference's `merge` of query result files on the GPU.  tax: a Taxonomy on `device` (kept alive by this
+    object); table: (taxon ids strictly ascending, taxon index of each) as host.taxid_table(db) gives it.  chunk() takes whole lines
+    of one file in DEVICE memory (a pointer and a byte count, or a torch uint8 tensor on the GPU) and returns whether the chunk was
+    strict (and so applied); lines() takes parsed lines; lists() returns (n_cand u32 [n_queries], pairs u32 [n_queries, max_cand, 2],
+    number of items with an unknown taxid); finish() returns (best u32 [n_queries], counts u64 [n_taxa + 1])."""
+
+    def __init__(self, tax, table, n_queries, max_cand=2, merge_below_rank=4, device=0):
+        self._ids, self._idx = np.ascontiguousarray(table[0], np.int64), np.ascontiguousarray(table[1], np.uint32)
+        assert len(self._ids) == len(self._idx)
+        h = C.c_void_p()
+        _chk(lib().mcq_merge_create(tax.h, _np_ptr(self._ids), _np_ptr(self._idx), len(self._ids), n_queries, max_cand, merge_below_rank,
+                                    device, C.byref(h)))
+        self.h, self.tax, self.n_queries, self.max_cand, self.device = h, tax, n_queries, max_cand, device
+
+    def chunk(self, text, n_bytes=None, file_ordinal=0, chunk_offset=0, tophits_column=2, stream=None):
+        if n_bytes is None:
+            ptr, n_bytes = text.data_ptr(), text.numel()
+        else:
+            ptr = int(text)
+        strict = C.c_int32(0)
+        _chk(lib().mcq_merge_chunk(self.h, C.c_void_p(ptr), n_bytes, file_ordinal, chunk_offset, tophits_column, C.byref(strict), stream))
+        return bool(strict.value)
+
+    def lines(self, line_query, item_off, taxid, hits, header_off=None, header_len=None, file_ordinal=0, stream=None):
+        """parsed lines (host arrays): line l names query line_query[l] (0-based) and holds the items [item_off[l], item_off[l + 1])"""
+        q = np.ascontiguousarray(line_query, np.uint32)
+        off, t, h = np.ascontiguousarray(item_off, np.uint64), np.ascontiguousarray(taxid, np.int64), np.ascontiguousarray(hits, np.uint32)
+        ho = np.zeros(len(q), np.uint64) if header_off is None else np.ascontiguousarray(header_off, np.uint64)
+        hl = np.zeros(len(q), np.uint32) if header_len is None else np.ascontiguousarray(header_len, np.uint32)
+        assert len(off) == len(q) + 1 and len(t) == len(h) == int(off[-1]) and len(ho) == len(hl) == len(q)
+        _chk(lib().mcq_merge_lines(self.h, _np_ptr(q), _np_ptr(off), _np_ptr(t), _np_ptr(h), _np_ptr(ho), _np_ptr(hl), len(q), file_ordinal, 0, stream))
+
+    def lines_cut(self, line_query, item_off, taxid, hits, header_off, header_len, file_ordinal=0, stream=None):
+        """lines() for lines in which a query may repeat (what host.merge_host gives): one call per run of distinct queries"""
+        seen, first = set(), 0
+        for l in range(len(line_query) + 1):
+            if l == len(line_query) or int(line_query[l]) in seen:
+                a, b = int(item_off[first]), int(item_off[l])
+                self.lines(line_query[first:l], np.asarray(item_off[first:l + 1], np.uint64) - np.uint64(a), taxid[a:b], hits[a:b],
+                           header_off[first:l], header_len[first:l], file_ordinal, stream)
+                seen, first = set(), l
+            if l < len(line_query):
+                seen.add(int(line_query[l]))
+
+    def lists(self):
+        n, pairs = np.zeros(self.n_queries, np.uint32), np.zeros((self.n_queries, self.max_cand, 2), np.uint32)
+        unknown = C.c_uint64(0)
+        _chk(lib().mcq_merge_lists(self.h, _np_ptr(n), _np_ptr(pairs), C.byref(unknown)))
+        return n, pairs, int(unknown.value)
+
+    def headers(self):
+        f, o, l = np.zeros(self.n_queries, np.uint32), np.zeros(self.n_queries, np.uint64), np.zeros(self.n_queries, np.uint32)
+        _chk(lib().mcq_merge_headers(self.h, _np_ptr(f), _np_ptr(o), _np_ptr(l)))
+        return f, o, l
+
+    def finish(self, hits_min=5, hits_diff_fraction=1.0, highest_rank=19, stream=None):
+        import torch
+        dev = "cuda:%d" % self.device                          # (the handle's device, whatever torch's current one is)
+        best = torch.zeros(max(1, self.n_queries), dtype=torch.int32, device=dev)
+        counts = torch.zeros(self.tax.n_taxa + 1, dtype=torch.int64, device=dev)
+        torch.cuda.synchronize(dev)
+        o = ClassifyOpts(hits_min, hits_diff_fraction, highest_rank, 0)
+        _chk(lib().mcq_merge_finish(self.h, C.byref(o), C.c_void_p(best.data_ptr()), C.c_void_p(counts.data_ptr()), stream))
+        torch.cuda.synchronize(dev)
+        return best.cpu().numpy().view(np.uint32)[:self.n_queries], counts.cpu().numpy().view(np.uint64)
+
+    def close(self):
+        if getattr(self, "h", None):
+            lib().mcq_merge_free(self.h); self.h = None
 
     def __del__(self):
         try:

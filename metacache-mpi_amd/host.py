@@ -198,6 +198,11 @@ def lib():
         L.mcq_taxmap_files.argtypes = [C.c_char_p, C.c_char_p, C.POINTER(C.c_void_p)]
         L.mcq_accmap_host.argtypes = [C.c_char_p, C.c_uint64, C.c_int32, C.c_char_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p,
                                       C.c_uint32, C.POINTER(C.c_uint64)]
+        L.mcq_refdb_from_taxdump.argtypes = [C.c_void_p, C.POINTER(C.c_void_p)]
+        L.mcq_refdb_taxid_table.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_uint64)]
+        L.mcq_results_properties.argtypes = [C.c_char_p, C.POINTER(C.c_uint32), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
+        L.mcq_merge_host.argtypes = [C.c_char_p, C.c_uint64, C.c_uint32, C.c_uint64, C.c_char_p, C.c_uint64, C.c_uint64] + [C.c_void_p] * 6 + \
+                                    [C.c_uint64, C.c_uint64, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
         _lib = L
     return _lib
 
@@ -563,6 +568,54 @@ def read_taxdump(directory):
         return [_rec(arr[i]) for i in range(lib().mcq_taxdump_count(h))]
     finally:
         lib().mcq_taxdump_free(h)
+
+
+def taxonomy_db(directory):
+    """mcq_refdb_from_taxdump: a RefDb that is the taxonomy of a dump alone (no targets, no table): what a merge works on"""
+    h, d = C.c_void_p(), C.c_void_p()
+    if lib().mcq_taxdump_read(str(directory).encode(), C.byref(d)) != 0:
+        raise _err()
+    try:
+        if lib().mcq_refdb_from_taxdump(d, C.byref(h)) != 0:
+            raise _err()
+    finally:
+        lib().mcq_taxdump_free(d)
+    db = RefDb.__new__(RefDb)
+    db.h, db.info = h, Info()
+    lib().mcq_refdb_get_info(db.h, C.byref(db.info))
+    return db
+
+
+def taxid_table(db):
+    """mcq_refdb_taxid_table: (ids int64 ascending, taxon index u32 of each): what mcq_merge_create takes"""
+    ids, idx, n = np.zeros(db.info.n_taxa, np.int64), np.zeros(db.info.n_taxa, np.uint32), C.c_uint64(0)
+    if lib().mcq_refdb_taxid_table(db.h, ids.ctypes.data_as(C.c_void_p), idx.ctypes.data_as(C.c_void_p), C.byref(n)) != 0:
+        raise _err()
+    return ids[:n.value], idx[:n.value]
+
+
+def results_properties(path):
+    """mcq_results_properties: (top_hits column, byte at which the results begin, number of mapping lines) of a results file"""
+    col, begin, n = C.c_uint32(0), C.c_uint64(0), C.c_uint64(0)
+    if lib().mcq_results_properties(str(path).encode(), C.byref(col), C.byref(begin), C.byref(n)) != 0:
+        raise _err()
+    return int(col.value), int(begin.value), int(n.value)
+
+
+def merge_host(text, n_queries, tophits_column=2, file_name="", first_line_no=1, text_offset=0):
+    """mcq_merge_host: the reference's token parser over whole lines of a results file (bytes) -> (line_query u32, item_off u64,
+    taxid int64, hits u32, header_off u64, header_len u32), the arrays of engine.Merge.lines"""
+    line_cap, item_cap = text.count(b"\n") + 1, text.count(b":") + 1
+    q, off = np.zeros(line_cap, np.uint32), np.zeros(line_cap + 1, np.uint64)
+    tid, hits = np.zeros(item_cap, np.int64), np.zeros(item_cap, np.uint32)
+    ho, hl = np.zeros(line_cap, np.uint64), np.zeros(line_cap, np.uint32)
+    nl, ni = C.c_uint64(0), C.c_uint64(0)
+    p = lambda a: a.ctypes.data_as(C.c_void_p)
+    if lib().mcq_merge_host(text, len(text), tophits_column, n_queries, file_name.encode(), first_line_no, text_offset, p(q), p(off),
+                            p(tid), p(hits), p(ho), p(hl), line_cap, item_cap, C.byref(nl), C.byref(ni)) != 0:
+        raise _err()
+    nl, ni = int(nl.value), int(ni.value)
+    return q[:nl], off[:nl + 1], tid[:ni], hits[:ni], ho[:nl], hl[:nl]
 
 
 def taxa_clade_keys(targets, dump, rank):
