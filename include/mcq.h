@@ -569,6 +569,43 @@ int mcq_parts_builder_add(mcq_parts_builder* b, const uint32_t* feat, const uint
 int mcq_parts_builder_finish(mcq_parts_builder* b, mcq_parts** out);
 int mcq_parts_builder_free(mcq_parts_builder* b);
 
+/* ---- the query-time bucket rules on a chunk of triples (csrc/mcq_bucket_limit.hip) ----------------------
+ * `metacache_mpi query -max-locations-per-feature N [-remove-overpopulated-features]` changes every rank's table right after it is
+ * read (src/mode_query.cpp:354-377): buckets of more than `remove_above` locations are cleared
+ * (remove_features_with_more_locations_than, src/sketch_database.h:381-395), then buckets of more than `keep_first` locations keep
+ * their first `keep_first` (max_locations_per_feature, src/sketch_database.h:356-368).  mcq_bucket_limit does that to a chunk as
+ * mcq_shard_stream_next (include/mcq_host.h) hands it out -- whole key records of one shard file: a maximal run of equal `feat` is
+ * one bucket of one rank; runs of any length are handled.  Removal first, then the shrink.  The triples that stay are compacted to
+ * the front of the three arrays in their order, *n_out says how many (what lies behind them is unspecified); *n_shrunk and
+ * *n_removed count buckets.  n = 0, or both rules 0: nothing is launched, *n_out = n, the arrays are untouched.
+ * Host pointers (flags 0): the call copies in, runs, copies out and returns with the counts set.
+ * Device pointers (MCQ_DEVICE_PTRS): the call only enqueues on `stream` (its scratch is stream-ordered too); the three counts are
+ * copied to the caller's host words in stream order, so THE CALLER synchronises `stream` before reading them or the arrays.
+ * Device memory inside the call: 12 B per triple (+ 12 B with host pointers) and a bit per triple, from the device's stream-ordered
+ * pool (hipMallocAsync on `stream`); a pipeline that allocates with hipMalloc / hipFree between such calls should use
+ * mcq_bucket_limit_ws below ("Whose scratch").
+ * MCQ_E_ARG: a null array with n > 0, a null count, keep_first > 255.  MCQ_E_UNSUPPORTED: 2^40 triples or more.  Text: mcq_last_error. */
+int mcq_bucket_limit(uint32_t* feat, uint32_t* tgt, uint32_t* win, uint64_t n,
+                     uint32_t keep_first,    /* 0 = no shrink; else 1..255 */
+                     uint32_t remove_above,  /* 0 = no removal; else a bucket with more than this many locations goes */
+                     uint32_t flags,         /* MCQ_DEVICE_PTRS */
+                     int32_t device, void* stream,
+                     uint64_t* n_out, uint64_t* n_shrunk, uint64_t* n_removed);
+/* The device form with the caller's scratch (device memory of at least mcq_bucket_limit_scratch_bytes(n) bytes, 256-B aligned, free
+ * for the call's work on `stream`): nothing is allocated, everything is enqueued.  counts_out: three host words -- triples kept,
+ * buckets shrunk, buckets removed -- copied in stream order as above.  What the streaming loader calls per chunk.  */
+uint64_t mcq_bucket_limit_scratch_bytes(uint64_t n);
+int mcq_bucket_limit_ws(uint32_t* feat, uint32_t* tgt, uint32_t* win, uint64_t n, uint32_t keep_first, uint32_t remove_above,
+                        int32_t device, void* stream, void* scratch, uint64_t scratch_bytes, uint64_t* counts_out /* [3] */);
+/* The same rules inside the streaming loader: after this call mcq_parts_builder_add applies them to every chunk on the device
+ * before its own append (a chunk given as device pointers is copied first: the caller's arrays stay as they are).  This puts one
+ * more requirement on the chunks: each holds whole key records of ONE shard file, as mcq_shard_stream_next hands them out (a
+ * bucket cut in two by a chunk boundary, or chunks that mix files, would be judged in pieces).  Both 0 switches the rules off.
+ * Without the call the builder launches and allocates nothing for them.  MCQ_E_ARG: a null builder, keep_first > 255 (text:
+ * mcq_build_last_error).  mcq_parts_builder_bucket_counts: the buckets shrunk and removed over all chunks added so far.     */
+int mcq_parts_builder_set_bucket_limit(mcq_parts_builder* b, uint32_t keep_first, uint32_t remove_above);
+int mcq_parts_builder_bucket_counts(const mcq_parts_builder* b, uint64_t* n_shrunk, uint64_t* n_removed);
+
 /* ---- extending a table: `metacache_mpi modify DB GENOMES...` (main_mode_build_modify, src/mode_build.cpp:1117-1136) ----------
  * The locations an existing database holds and the sketches of new sequences go through the pipeline of mcq_build_table together.
  * mcq_table_extend_add takes the chunks mcq_shard_stream_next (include/mcq_host.h) hands out, as host pointers or as device

@@ -18,6 +18,7 @@ _UNITS = {
     os.path.join(_CSRC, "mcq_all_hits.hip"): _INTERNAL,    # all hits of a read, run-length compressed (-allhits)
     os.path.join(_CSRC, "mcq_accmap.hip"): _INTERNAL,      # *.accession2taxid text joined against the targets' names (mcq_accmap_*)
     os.path.join(_CSRC, "mcq_merge.hip"): _INTERNAL + [os.path.join(_CSRC, "mcq_classify_one.hpp")],   # merge of query result files (mcq_merge_*)
+    os.path.join(_CSRC, "mcq_bucket_limit.hip"): _INTERNAL,   # the query-time bucket rules on a chunk of triples (mcq_bucket_limit)
     os.path.join(_CSRC, "mcq_build.hip"): [_HDR],          # table construction (rocPRIM sorts)
     os.path.join(_CSRC, "mcq_classify.hip"): [os.path.join(_CSRC, h) for h in ("mcq_classify.hpp", "mcq_classify_one.hpp")] + [_HDR],   # classification + taxon counts
 }

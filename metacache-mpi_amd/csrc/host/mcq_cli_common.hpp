@@ -47,7 +47,8 @@
 //            [-maxcand N] [-hitmin N] [-hitdiff X] [-insertsize N] [-threads N] [-tophits] [-taxids] [-taxids-only] [-omit-ranks]
 //            [-lineage] [-mapped-only] [-nomap] [-noquirks] [-abundances [FILE]] [-abundance-per R] [-out FILE] [-batch N]
 //            [-batch-bases N] [-read-chunk BYTES] [-reader gpu|host] [-exclude RANK] [-ground-truth] [-precision] [-hits-per-seq [FILE]]
-//            [-align] [-align-candidate-range] [-queryids] [-locations] [-allhits] [-help]
+//            [-align] [-align-candidate-range] [-queryids] [-locations] [-allhits] [-winlen N] [-winstride N] [-sketchlen N]
+//            [-max-locations-per-feature N] [-remove-overpopulated-features] [-help]
 // (inputs: every argument up to the first option; a directory stands for the files in it (files_in_directory below).  -pairseq
 //  without -pairfiles comes first: every file is interleaved pairs, also the two of `r1 r2` and the one of `r1 -`.  Without it,
 //  `r1 r2` alone is one pair of files in the given order and `r1 -` one single-end file.  Otherwise -pairfiles sorts the names and pairs
@@ -116,6 +117,7 @@ struct Options {
     uint64_t batch = 1u << 19, batch_bases = 256u << 20;   // mcq_query_mpi: queries / bases per rank and batch
     uint64_t read_chunk = 8u << 20;      // mcq_query_cli: bytes per file and chunk (-read-chunk)
     bool host_reader = false;            // mcq_query_cli: -reader host
+    mcq_query_tuning tuning;             // -winlen, -winstride, -sketchlen, -max-locations-per-feature, -remove-overpopulated-features
     bool paired() const { return pairing != NONE; }
 };
 
@@ -221,6 +223,22 @@ static const char* const kQueryUsage =
     "                   -mapped-only, unless -nomap -tophits).  With -exclude RANK the hits on the read's own clade are left out.  A\n"
     "                   batch whose hits need more than 2 GiB, or a read with more locations than the workspace takes, ends the run\n"
     "                   with an ABORT line.  Three batches are in flight: up to 6 GiB on the device and 6 GiB of pinned host memory.\n"
+    "database query options (both programs; get_database_query_options of the reference; written into no output line):\n"
+    "  -winlen N  -winstride N  -sketchlen N   sketch the READS with another window length, window stride or sketch size than the\n"
+    "                   database was built with.  -winlen without -winstride sets the stride to N as well; values below 1 are ignored.\n"
+    "                   The engine's limits: a window of k to 128 bases, a sketch of at most 32 features; a value outside them ends\n"
+    "                   the run with an ABORT line before the database is read.\n"
+    "  -max-locations-per-feature N  (-max_locations_per_feature) shrink every bucket -- the locations of one feature on one rank of\n"
+    "                   the build -- to its first N locations, on the GPU while the shard files are streamed.  As in the reference: N\n"
+    "                   of 1 or less is ignored without the next option; N is taken as an 8-bit bucket size (300 means 44, 256\n"
+    "                   means 1); 254 and 255 mean the largest bucket and change nothing; so does an N at or above the database's\n"
+    "                   own limit.\n"
+    "  -remove-overpopulated-features  (-remove_overpopulated_features) drop every feature of a rank whose bucket there holds more\n"
+    "                   than N - 1 locations (253 without N or with N of 254 and more; at most the database's limit - 1; not applied\n"
+    "                   when that is 0), then shrink to N as above: N = 1 removes nothing and leaves one location per bucket.\n"
+    "                   Either of the two loads the database by the streaming route whatever its size; the numbers of buckets shrunk\n"
+    "                   and removed are printed on stderr.\n"
+    "  -max-load-fac X  is not read: it sizes the reference's hash table and changes no result.\n"
     "rejected:        -taxon-coverage (both programs): the coverage statistics are not reproduced\n";
 
 static bool parse_options(int argc, char** argv, Options& o) {
@@ -283,6 +301,11 @@ static bool parse_options(int argc, char** argv, Options& o) {
         else if (a == "-exclude") { const uint32_t r = mcq_rank_from_name(next()); if (r < MCQ_RANK_ROOT) o.exclude_rank = r; }   // src/query_options.cpp:205-210
         else if (opt_named(a, {"-ground-truth", "-ground_truth", "-groundtruth"})) o.ground_truth = true;                       // :196-198
         else if (a == "-precision") o.precision = true;                                                                         // :203
+        else if (a == "-max-locations-per-feature" || a == "-max_locations_per_feature") o.tuning.max_locs = std::atoi(next());   // src/query_options.cpp:47-49
+        else if (a == "-remove-overpopulated-features" || a == "-remove_overpopulated_features") o.tuning.remove_overpopulated = true;   // :51-53
+        else if (a == "-sketchlen") o.tuning.sketchlen = std::atoi(next());                                                     // :56
+        else if (a == "-winlen") o.tuning.winlen = std::atoi(next());                                                           // :57
+        else if (a == "-winstride") o.tuning.winstride = std::max(0, std::atoi(next()));                                        // :58 (given: -winlen does not set it; below 1: not applied)
         else if (a == "-taxon-coverage") {                                                                                      // :201
             std::fprintf(stderr, "ABORT: -taxon-coverage is not supported: the coverage statistics (a scan over all taxa per read) are not reproduced; "
                                  "-precision alone gives the other statistics\n");
@@ -594,11 +617,14 @@ struct Database {
 };
 static bool open_database(const Options& p, Database& db, uint32_t n_shards, uint32_t shard_id, int device) {
     std::string err; bool streamed = false;
-    if (mcq_open_refdb(p.prefix, p.P, mcq_stream_load_min_bytes(), &db.rdb, &streamed, err)) { std::fprintf(stderr, "ABORT: %s\n", err.c_str()); return false; }
+    if (mcq_open_refdb(p.prefix, p.P, mcq_stream_load_min_bytes(), &db.rdb, &streamed, err, p.tuning)) { std::fprintf(stderr, "ABORT: %s\n", err.c_str()); return false; }
     mcq_refdb_info info; mcq_refdb_get_info(db.rdb, &info);
     db.hitmin = p.hitmin < 1 ? mcq_default_hits_min(info.sketch_size) : p.hitmin;
     db.t2t.resize(info.n_targets);
     if (mcq_refdb_tgt2tax(db.rdb, p.lowest, db.t2t.data())) { std::fprintf(stderr, "ABORT: %s\n", mcq_host_last_error()); return false; }
-    if (mcq_make_db(db.rdb, streamed, db.t2t.data(), n_shards, shard_id, device, &db.edb, err)) { std::fprintf(stderr, "ABORT: %s\n", err.c_str()); return false; }
+    uint64_t n_shrunk = 0, n_removed = 0;
+    if (mcq_make_db(db.rdb, streamed, db.t2t.data(), n_shards, shard_id, device, &db.edb, err, p.tuning, &n_shrunk, &n_removed)) { std::fprintf(stderr, "ABORT: %s\n", err.c_str()); return false; }
+    if (p.tuning.max_locs > 1 || p.tuning.remove_overpopulated)
+        std::fprintf(stderr, "bucket rule: %llu buckets shrunk, %llu removed\n", (unsigned long long)n_shrunk, (unsigned long long)n_removed);
     return true;
 }

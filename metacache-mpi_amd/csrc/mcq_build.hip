@@ -770,6 +770,9 @@ struct mcq_parts_builder {
     Dev<u32> d_hist;                  // device [n_ranges + 1]: chunk histogram, [n_ranges] = bad triples
     Dev<u32> d_feat, d_tgt, d_win; u64 stage_cap = 0;
     u64 n_added = 0, n_kept = 0;
+    u32 keep_first = 0, remove_above = 0;       // the query-time bucket rules (mcq_parts_builder_set_bucket_limit); both 0: off
+    u64 n_shrunk = 0, n_removed = 0;            // ... buckets they shrank / removed so far
+    Dev<char> limit_scratch; u64 limit_scratch_bytes = 0;     // ... and their scratch: there only once a rule is set, grows with the chunks
 };
 namespace {
 __global__ void k_gwoff(const u32* tgt_windows, u32 nt, u32* gw_off) {       // (one thread: nt is at most a few 1e5)
@@ -860,16 +863,35 @@ extern "C" int mcq_parts_builder_add(mcq_parts_builder* b, const uint32_t* feat,
     if (n >= (1ull << 31)) return bfail(MCQ_E_ARG, "a chunk holds fewer than 2^31 triples");
     BCHK(hipSetDevice(b->device));
     const u32 *df = feat, *dt = tgt, *dw = win;
-    if (!(flags & MCQ_DEVICE_PTRS)) {
+    const bool limit = b->keep_first || b->remove_above;       // (the rules compact in place: a device chunk is copied to the stage first)
+    if (!(flags & MCQ_DEVICE_PTRS) || limit) {
+        const hipMemcpyKind kind = (flags & MCQ_DEVICE_PTRS) ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice;
         if (n > b->stage_cap) {
             b->d_feat.reset(); b->d_tgt.reset(); b->d_win.reset(); b->stage_cap = 0;      // (all three go before the larger ones come)
             BCHK(b->d_feat.alloc(n)); BCHK(b->d_tgt.alloc(n)); BCHK(b->d_win.alloc(n));
             b->stage_cap = n;
         }
         df = b->d_feat.get(); dt = b->d_tgt.get(); dw = b->d_win.get();
-        BCHK(hipMemcpyAsync(b->d_feat.get(), feat, n * 4, hipMemcpyHostToDevice, 0));
-        BCHK(hipMemcpyAsync(b->d_tgt.get(), tgt, n * 4, hipMemcpyHostToDevice, 0));
-        BCHK(hipMemcpyAsync(b->d_win.get(), win, n * 4, hipMemcpyHostToDevice, 0));
+        BCHK(hipMemcpyAsync(b->d_feat.get(), feat, n * 4, kind, 0));
+        BCHK(hipMemcpyAsync(b->d_tgt.get(), tgt, n * 4, kind, 0));
+        BCHK(hipMemcpyAsync(b->d_win.get(), win, n * 4, kind, 0));
+    }
+    const u64 n_given = n;
+    if (limit) {                                                // every (feature, rank) bucket of the chunk, before anything else sees it
+        const u64 need = mcq_bucket_limit_scratch_bytes(n);
+        if (need > b->limit_scratch_bytes) {
+            b->limit_scratch.reset(); b->limit_scratch_bytes = 0;
+            BCHK(b->limit_scratch.alloc(need));
+            b->limit_scratch_bytes = need;
+        }
+        uint64_t c[3] = {0, 0, 0};                              // kept, buckets shrunk, buckets removed
+        if (mcq_bucket_limit_ws(b->d_feat.get(), b->d_tgt.get(), b->d_win.get(), n, b->keep_first, b->remove_above, b->device, nullptr,
+                                b->limit_scratch.get(), b->limit_scratch_bytes, c) != MCQ_OK) return bfail(MCQ_E_HIP, std::string("mcq_bucket_limit_ws: ") + mcq_last_error());
+        BCHK(hipStreamSynchronize(0));                          // (the counts arrive in stream order)
+        if (c[0] > n) return bfail(MCQ_E_HIP, "mcq_bucket_limit_ws: more triples kept than given");
+        b->n_shrunk += c[1]; b->n_removed += c[2];
+        n = c[0];
+        if (!n) { b->n_added += n_given; return MCQ_OK; }
     }
     Dev<u32> rng_buf;
     BCHK(rng_buf.alloc(n));
@@ -902,7 +924,20 @@ extern "C" int mcq_parts_builder_add(mcq_parts_builder* b, const uint32_t* feat,
     BCHK(hipDeviceSynchronize());
     BCHK(hipGetLastError());
     for (u32 r = 0; r < b->n_ranges; ++r) { b->cnt[r] += hist[r]; b->n_kept += hist[r]; }
-    b->n_added += n;
+    b->n_added += n_given;
+    return MCQ_OK;
+}
+
+extern "C" int mcq_parts_builder_set_bucket_limit(mcq_parts_builder* b, uint32_t keep_first, uint32_t remove_above) {
+    if (!b) return bfail(MCQ_E_ARG, "null argument");
+    if (keep_first > 255) return bfail(MCQ_E_ARG, "keep_first must be in 0..255");
+    b->keep_first = keep_first; b->remove_above = remove_above;
+    return MCQ_OK;
+}
+
+extern "C" int mcq_parts_builder_bucket_counts(const mcq_parts_builder* b, uint64_t* n_shrunk, uint64_t* n_removed) {
+    if (!b || !n_shrunk || !n_removed) return bfail(MCQ_E_ARG, "null argument");
+    *n_shrunk = b->n_shrunk; *n_removed = b->n_removed;
     return MCQ_OK;
 }
 
@@ -917,6 +952,7 @@ extern "C" int mcq_parts_builder_finish(mcq_parts_builder* b, mcq_parts** out) {
     R->tgt_winstride = b->tgt_winstride;
     R->n_windows = b->n_windows; R->tgt_windows = std::move(b->tgt_windows);
     b->d_feat.reset(); b->d_tgt.reset(); b->d_win.reset(); b->stage_cap = 0;
+    b->limit_scratch.reset(); b->limit_scratch_bytes = 0;
     for (u32 r = 0; r < b->n_ranges; ++r) {
         const u64 n = b->cnt[r];
         u64* fw = nullptr; u32* head = nullptr; u64* kid = nullptr; u64 n_keys = 0;

@@ -187,7 +187,15 @@ def lib():
             L.mcq_parts_builder_add.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint32]
             L.mcq_parts_builder_finish.argtypes = [C.c_void_p, C.POINTER(C.c_void_p)]
             L.mcq_parts_builder_free.argtypes = [C.c_void_p]
-        if hasattr(L, "mcq_table_extend_create"):           # (as above: a parent's library in a same-box A/B has none)
+        if hasattr(L, "mcq_bucket_limit"):                  # (as above)
+            L.mcq_bucket_limit.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint32, C.c_uint32, C.c_uint32, C.c_int32,
+                                           C.c_void_p, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
+            L.mcq_bucket_limit_scratch_bytes.restype = C.c_uint64; L.mcq_bucket_limit_scratch_bytes.argtypes = [C.c_uint64]
+            L.mcq_bucket_limit_ws.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint32, C.c_uint32, C.c_int32, C.c_void_p,
+                                              C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64)]
+            L.mcq_parts_builder_set_bucket_limit.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32]
+            L.mcq_parts_builder_bucket_counts.argtypes = [C.c_void_p, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
+        if hasattr(L, "mcq_table_extend_create"):          # (as above: a parent's library in a same-box A/B has none)
             L.mcq_table_extend_create.argtypes = [C.POINTER(TableExtendDesc), C.POINTER(C.c_void_p)]
             L.mcq_table_extend_add.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint32]
             L.mcq_table_extend_finish.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.POINTER(C.c_void_p)]
@@ -1043,6 +1051,21 @@ class PartsBuilder:
         if rc != 0:
             raise McqError(rc, (lib().mcq_build_last_error() or b"").decode())
 
+    def set_bucket_limit(self, keep_first=0, remove_above=0):
+        """mcq_parts_builder_set_bucket_limit: from now on add() applies the query-time bucket rules (bucket_limit below) to every
+        chunk on the device before its append; every chunk must then hold whole key records of one shard file"""
+        rc = lib().mcq_parts_builder_set_bucket_limit(self.h, keep_first, remove_above)
+        if rc != 0:
+            raise McqError(rc, (lib().mcq_build_last_error() or b"").decode())
+
+    def bucket_counts(self):
+        """(buckets shrunk, buckets removed) over the chunks added so far"""
+        a, b = C.c_uint64(), C.c_uint64()
+        rc = lib().mcq_parts_builder_bucket_counts(self.h, C.byref(a), C.byref(b))
+        if rc != 0:
+            raise McqError(rc, (lib().mcq_build_last_error() or b"").decode())
+        return int(a.value), int(b.value)
+
     def finish(self):
         ph = C.c_void_p()
         rc = lib().mcq_parts_builder_finish(self.h, C.byref(ph))
@@ -1067,6 +1090,40 @@ class PartsBuilder:
             self.close()
         except Exception:
             pass
+
+
+def bucket_limit(feat, tgt, win, keep_first=0, remove_above=0, n=None, device=0, stream=None):
+    """mcq_bucket_limit: the query-time bucket rules on a chunk of (feature, target, window) triples -- a maximal run of equal `feat`
+    is one bucket; one of more than remove_above locations goes, then one of more than keep_first keeps its first keep_first (0: rule
+    off).  Host form (n is None): three numpy u32 arrays in, (feat, tgt, win, n_shrunk, n_removed) out, the arrays cut to what
+    stays.  Device form: three raw device pointers and the count n; the call only enqueues on `stream` and returns the three
+    ctypes counts (n_out, n_shrunk, n_removed), to be read (.value) after the caller has synchronised the stream."""
+    no, ns, nr = C.c_uint64(), C.c_uint64(), C.c_uint64()
+    if n is None:
+        f, t, w = (np.array(x, np.uint32, copy=True) for x in (feat, tgt, win))
+        ptrs = [x.ctypes.data_as(C.c_void_p) if len(x) else None for x in (f, t, w)]
+        rc = lib().mcq_bucket_limit(ptrs[0], ptrs[1], ptrs[2], len(f), keep_first, remove_above, 0, device, stream, C.byref(no), C.byref(ns), C.byref(nr))
+        _chk(rc)
+        k = int(no.value)
+        return f[:k], t[:k], w[:k], int(ns.value), int(nr.value)
+    ptrs = [C.c_void_p(int(x)) if x else None for x in (feat, tgt, win)]
+    _chk(lib().mcq_bucket_limit(ptrs[0], ptrs[1], ptrs[2], n, keep_first, remove_above, MCQ_DEVICE_PTRS, device, stream, C.byref(no), C.byref(ns), C.byref(nr)))
+    return no, ns, nr
+
+
+def bucket_limit_scratch_bytes(n):
+    return int(lib().mcq_bucket_limit_scratch_bytes(n))
+
+
+def bucket_limit_ws(feat_ptr, tgt_ptr, win_ptr, n, keep_first, remove_above, scratch_ptr, scratch_bytes, device=0, stream=None):
+    """mcq_bucket_limit_ws: the device form of bucket_limit with the caller's scratch (bucket_limit_scratch_bytes(n) bytes of device
+    memory): nothing is allocated.  Returns a ctypes array of three counts -- kept, buckets shrunk, buckets removed -- to be read
+    after the caller has synchronised the stream."""
+    counts = (C.c_uint64 * 3)()
+    _chk(lib().mcq_bucket_limit_ws(C.c_void_p(int(feat_ptr)) if feat_ptr else None, C.c_void_p(int(tgt_ptr)) if tgt_ptr else None,
+                                   C.c_void_p(int(win_ptr)) if win_ptr else None, n, keep_first, remove_above, device, stream,
+                                   C.c_void_p(int(scratch_ptr)) if scratch_ptr else None, scratch_bytes, counts))
+    return counts
 
 
 class TableExtend:
