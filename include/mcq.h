@@ -606,6 +606,38 @@ int mcq_bucket_limit_ws(uint32_t* feat, uint32_t* tgt, uint32_t* win, uint64_t n
 int mcq_parts_builder_set_bucket_limit(mcq_parts_builder* b, uint32_t keep_first, uint32_t remove_above);
 int mcq_parts_builder_bucket_counts(const mcq_parts_builder* b, uint64_t* n_shrunk, uint64_t* n_removed);
 
+/* ---- content statistics over chunks of triples (csrc/mcq_content_stats.hip) ------------------------------
+ * What `metacache_mpi info DB statistics` says about a table's buckets (print_content_properties, src/sketch_database.h:1205-1237)
+ * comes from the number of buckets, their largest size and the sums of size, size^2 and size^3 (src/stat_moments.h); the handle
+ * gathers these, a histogram of the sizes and the locations of every target over the chunks it is given.  A chunk is whole key records
+ * of one shard file, as mcq_shard_stream_next (include/mcq_host.h) hands them out: a maximal run of equal `feat` is one bucket (runs of
+ * any length are handled; equal features in two runs that do not touch are two buckets).  `win` is not read and may be null.
+ * Host pointers (flags 0) are copied to a staging buffer of the handle first; device pointers (MCQ_DEVICE_PTRS) are read in place.
+ * Every call works on the handle's stream (the null stream until mcq_content_stats_set_stream gives another; device arrays must be
+ * ready in that stream's order) and returns after the chunk is counted: the totals are integers kept on the host, exact below 2^64
+ * (254^3 times any number of buckets a machine holds).  The handle belongs to the device that was current at create; its memory is
+ * plain hipMalloc memory that grows with the largest host chunk seen, nothing is allocated per chunk.
+ * mcq_content_stats_add: MCQ_E_ARG for a null handle, a null feat or tgt with n > 0, and for a chunk in which a triple names a target
+ *   >= n_targets -- the text (mcq_last_error) names the first such triple and its target; that chunk then counts for nothing: totals
+ *   and target counts are what they were before the call.  MCQ_E_UNSUPPORTED: 2^40 triples or more.
+ * mcq_content_stats_totals: the totals since create or the last reset.  mcq_content_stats_target_locations: locations per target since
+ *   create.  mcq_content_stats_reset (between shards) zeroes the totals and KEEPS the target counts: a target's locations are a
+ *   property of the whole database, its buckets' statistics one of each shard; a caller that wants fresh target counts makes a new
+ *   handle.  mcq_content_stats_free takes a null handle.                                                                          */
+typedef struct {
+    uint64_t n_buckets, n_locations, sum2, sum3, max_size;
+    uint64_t hist[256];         /* hist[s] = buckets of s locations; hist[255] = 255 and more; hist[0] = 0 */
+} mcq_content_totals;
+typedef struct mcq_content_stats mcq_content_stats;
+int mcq_content_stats_create(uint32_t n_targets /* >= 1 */, mcq_content_stats** out);
+int mcq_content_stats_set_stream(mcq_content_stats* h, void* stream);
+int mcq_content_stats_add(mcq_content_stats* h, const uint32_t* feat, const uint32_t* tgt, const uint32_t* win, uint64_t n,
+                          uint32_t flags /* MCQ_DEVICE_PTRS */);
+int mcq_content_stats_totals(mcq_content_stats* h, mcq_content_totals* out);
+int mcq_content_stats_target_locations(mcq_content_stats* h, uint64_t* out /* [n_targets] */);
+int mcq_content_stats_reset(mcq_content_stats* h);
+int mcq_content_stats_free(mcq_content_stats* h);
+
 /* ---- extending a table: `metacache_mpi modify DB GENOMES...` (main_mode_build_modify, src/mode_build.cpp:1117-1136) ----------
  * The locations an existing database holds and the sketches of new sequences go through the pipeline of mcq_build_table together.
  * mcq_table_extend_add takes the chunks mcq_shard_stream_next (include/mcq_host.h) hands out, as host pointers or as device

@@ -19,6 +19,7 @@ _UNITS = {
     os.path.join(_CSRC, "mcq_accmap.hip"): _INTERNAL,      # *.accession2taxid text joined against the targets' names (mcq_accmap_*)
     os.path.join(_CSRC, "mcq_merge.hip"): _INTERNAL + [os.path.join(_CSRC, "mcq_classify_one.hpp")],   # merge of query result files (mcq_merge_*)
     os.path.join(_CSRC, "mcq_bucket_limit.hip"): _INTERNAL,   # the query-time bucket rules on a chunk of triples (mcq_bucket_limit)
+    os.path.join(_CSRC, "mcq_content_stats.hip"): _INTERNAL,  # bucket size statistics and locations per target over chunks of triples (mcq_content_stats_*)
     os.path.join(_CSRC, "mcq_build.hip"): [_HDR],          # table construction (rocPRIM sorts)
     os.path.join(_CSRC, "mcq_classify.hip"): [os.path.join(_CSRC, h) for h in ("mcq_classify.hpp", "mcq_classify_one.hpp")] + [_HDR],   # classification + taxon counts
 }
@@ -44,6 +45,10 @@ def build_cli_path():
 
 def merge_cli_path():
     return os.path.join(_HERE, "mcq_merge_cli")
+
+
+def info_cli_path():
+    return os.path.join(_HERE, "mcq_info_cli")
 
 
 def mpi_cli_path():
@@ -74,7 +79,7 @@ def source_digest():
 
 def build_host(force=False, verbose=False):
     """libmcq_host.so (shard reader and writer, taxonomy, classify, build inputs; g++, no GPU) and the
-    mcq_query_cli, mcq_build_cli and mcq_merge_cli binaries (they link both libraries)."""
+    mcq_query_cli, mcq_build_cli, mcq_merge_cli and mcq_info_cli binaries (they link both libraries)."""
     srcs = [os.path.join(_HERE, "csrc", "host", f) for f in ("mcq_host.cpp", "mcq_host_build.cpp", "mcq_host_merge.cpp")]     # query side, build side, merge side
     hdr = os.path.join(os.path.dirname(_HERE), "include", "mcq_host.h")
     out = host_lib_path()
@@ -110,6 +115,18 @@ def build_host(force=False, verbose=False):
     if force or not os.path.exists(mcli) or os.path.getmtime(mcli) < max(os.path.getmtime(f) for f in shared + [mcli_src]):
         hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
         cmd = [hipcc, "-std=c++14", "-O2", "-pthread", mcli_src, "-o", mcli, "-L" + _HERE, "-lmcq_hip", "-lmcq_host", "-Wl,-rpath,$ORIGIN"]
+        if verbose:
+            print(" ".join(cmd))
+        subprocess.check_call(cmd)
+    # mcq_info_cli: what a database was built with, what it holds, how full its buckets are
+    icli_src = os.path.join(_HERE, "csrc", "host", "mcq_info_cli.cpp")
+    icli = info_cli_path()
+    icli_deps = [out, lib_path(), _HDR, hdr, os.path.join(os.path.dirname(_HERE), "include", "mcq_open.hpp"),
+                 os.path.join(_HERE, "csrc", "host", "mcq_cli_buffers.hpp"), icli_src]
+    if force or not os.path.exists(icli) or os.path.getmtime(icli) < max(os.path.getmtime(f) for f in icli_deps):
+        hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
+        cmd = [hipcc, "-std=c++14", "-O2", "-ffp-contract=off", "-pthread", icli_src, "-o", icli, "-L" + _HERE, "-lmcq_hip", "-lmcq_host",
+               "-Wl,-rpath,$ORIGIN"]     # (no contraction: the moments are the reference's double arithmetic restated op for op)
         if verbose:
             print(" ".join(cmd))
         subprocess.check_call(cmd)

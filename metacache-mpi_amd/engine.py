@@ -115,6 +115,16 @@ class TableExtendDesc(C.Structure):
                 ("n_old_targets", C.c_uint32), ("old_tgt_windows", C.c_void_p), ("expected_old_locations", C.c_uint64)]
 
 
+class ContentTotals(C.Structure):
+    _fields_ = [("n_buckets", C.c_uint64), ("n_locations", C.c_uint64), ("sum2", C.c_uint64), ("sum3", C.c_uint64),
+                ("max_size", C.c_uint64), ("hist", C.c_uint64 * 256)]
+
+    def as_dict(self):
+        d = {k: int(getattr(self, k)) for k, _ in self._fields_[:5]}
+        d["hist"] = np.array(self.hist, dtype=np.uint64)
+        return d
+
+
 class ShardCfg(C.Structure):
     _fields_ = [("n_ranks", C.c_uint32), ("rank", C.c_uint32), ("max_queries", C.c_uint64), ("max_seqs", C.c_uint64),
                 ("max_bases", C.c_uint64), ("max_locs_per_query", C.c_uint64), ("max_features_per_peer", C.c_uint64),
@@ -195,6 +205,14 @@ def lib():
                                               C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64)]
             L.mcq_parts_builder_set_bucket_limit.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32]
             L.mcq_parts_builder_bucket_counts.argtypes = [C.c_void_p, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
+        if hasattr(L, "mcq_content_stats_create"):          # (as above)
+            L.mcq_content_stats_create.argtypes = [C.c_uint32, C.POINTER(C.c_void_p)]
+            L.mcq_content_stats_set_stream.argtypes = [C.c_void_p, C.c_void_p]
+            L.mcq_content_stats_add.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint32]
+            L.mcq_content_stats_totals.argtypes = [C.c_void_p, C.POINTER(ContentTotals)]
+            L.mcq_content_stats_target_locations.argtypes = [C.c_void_p, C.c_void_p]
+            L.mcq_content_stats_reset.argtypes = [C.c_void_p]
+            L.mcq_content_stats_free.argtypes = [C.c_void_p]
         if hasattr(L, "mcq_table_extend_create"):          # (as above: a parent's library in a same-box A/B has none)
             L.mcq_table_extend_create.argtypes = [C.POINTER(TableExtendDesc), C.POINTER(C.c_void_p)]
             L.mcq_table_extend_add.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint32]
@@ -1124,6 +1142,56 @@ def bucket_limit_ws(feat_ptr, tgt_ptr, win_ptr, n, keep_first, remove_above, scr
                                    C.c_void_p(int(win_ptr)) if win_ptr else None, n, keep_first, remove_above, device, stream,
                                    C.c_void_p(int(scratch_ptr)) if scratch_ptr else None, scratch_bytes, counts))
     return counts
+
+
+class ContentStats:
+    """mcq_content_stats_*: bucket size statistics and locations per target over chunks of (feature, target, window) triples -- a
+    maximal run of equal `feat` is one bucket (host.RefDb(meta_only=True).stream() yields such chunks).  add() takes three numpy
+    arrays (win may be None) or three device tensors (anything with data_ptr(): 4-byte integers, contiguous, ready on the null
+    stream); totals() gives a dict (n_buckets, n_locations, sum2, sum3, max_size, hist[256]) since create or the last reset();
+    target_locations() the locations per target since create -- reset() keeps them."""
+
+    def __init__(self, n_targets):
+        h = C.c_void_p()
+        _chk(lib().mcq_content_stats_create(n_targets, C.byref(h)))
+        self.h, self.n_targets = h, n_targets
+
+    def add(self, feat, tgt, win=None):
+        if hasattr(feat, "data_ptr"):
+            n = int(feat.numel())
+            for x in (feat, tgt):
+                if not x.is_cuda or x.element_size() != 4 or not x.is_contiguous() or int(x.numel()) != n:
+                    raise ValueError("ContentStats.add: device tensors of 4-byte integers, contiguous, of one length")
+            ptrs, flags = [C.c_void_p(x.data_ptr()) if n else None for x in (feat, tgt)], MCQ_DEVICE_PTRS
+        else:
+            f, t = (np.ascontiguousarray(x, np.uint32) for x in (feat, tgt))
+            if len(f) != len(t):
+                raise ValueError("ContentStats.add: feat and tgt differ in length")
+            n, ptrs, flags = len(f), [x.ctypes.data_as(C.c_void_p) if len(x) else None for x in (f, t)], 0
+        _chk(lib().mcq_content_stats_add(self.h, ptrs[0], ptrs[1], None, n, flags))
+
+    def totals(self):
+        t = ContentTotals()
+        _chk(lib().mcq_content_stats_totals(self.h, C.byref(t)))
+        return t.as_dict()
+
+    def target_locations(self):
+        out = np.zeros(self.n_targets, np.uint64)
+        _chk(lib().mcq_content_stats_target_locations(self.h, out.ctypes.data_as(C.c_void_p)))
+        return out
+
+    def reset(self):
+        _chk(lib().mcq_content_stats_reset(self.h))
+
+    def close(self):
+        if getattr(self, "h", None):
+            lib().mcq_content_stats_free(self.h); self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
 
 
 class TableExtend:
