@@ -423,6 +423,10 @@ int mcq_fasta_index(const char* text, uint64_t n_bytes, uint64_t* seq_ranges, ui
  * 4-line records (line 1 '@', line 3 '+'), or FASTA of '>' header lines and non-empty sequence lines, one format per
  * text -- and the outputs are not to be used: the host parses that chunk (mcq_reads_parse of include/mcq_host.h, the
  * same contract).  scratch: device memory of mcq_reads_scratch_bytes(len1, len2, max_queries) bytes.  Chunks < 4 GiB.
+ * Still in the strict form, and read as getline reads them: a FASTQ record whose sequence and quality lines are empty and a
+ * FASTA header that the next header or the end of the file follows (a query with no bases), a header with nothing after
+ * '@' / '>' or with a ' ' right after it (an empty hdr range), a sequence line that is only "\r" (one base, the '\r'),
+ * a text of length 0 (no query).  A FASTQ file that ends inside a record -- fewer than 4 lines, a lone '@' -- is not.
  * Flag MCQ_READS_INTERLEAVED (text2 NULL, len2 0): records 2r, 2r+1 of text1 are the mates of one query, as the reference's
  * sequence_pair_reader::next pairs the records of one file under -pairseq (src/sequence_io.cpp:442-462: two next() of the
  * same reader; the second returns an empty sequence once the file has run out).  The outputs have the paired form (mates

@@ -15,6 +15,7 @@ import torch
 from golden_util import Fixture
 from oracle import dbfile
 from read_corpus import corpus, read_records
+from reads_device import _check_chunk, _device_prepare
 
 pytestmark = pytest.mark.gpu
 
@@ -24,51 +25,6 @@ def mods():
     pkg = importlib.import_module("metacache-mpi_amd")
     pkg.build_host()
     return pkg, importlib.import_module("metacache-mpi_amd.engine"), importlib.import_module("metacache-mpi_amd.host")
-
-
-def _dev_bytes(data, dev, shift=0):
-    buf = torch.zeros(len(data) + shift + 1, dtype=torch.uint8, device=dev)
-    if data:
-        buf[shift:shift + len(data)] = torch.from_numpy(np.frombuffer(data, dtype=np.uint8).copy()).to(dev)
-    return buf
-
-
-def _device_prepare(eng, dev, texts, flags, max_q, max_b, shift=0):
-    """mcq_reads_prepare on one chunk per file -> (info, bases, seq_off, hdr) as numpy arrays"""
-    L = [len(t) for t in texts]
-    qcap = max(1, min(max_q, min(L) // 2 + 2))
-    bufs = [_dev_bytes(t, dev, shift) for t in texts]
-    ptr = [b.data_ptr() + shift for b in bufs]
-    L2 = L[1] if len(texts) > 1 else 0
-    sb = eng.reads_scratch_bytes(L[0], L2, qcap)
-    scratch = torch.empty(sb, dtype=torch.uint8, device=dev)
-    bases = torch.zeros(L[0] + L2 + 1, dtype=torch.uint8, device=dev)
-    seq_off = torch.zeros(2 * qcap + 1, dtype=torch.int64, device=dev)
-    hdr = torch.zeros(2 * qcap, dtype=torch.int64, device=dev)
-    info = torch.full((eng.MCQ_READS_INFO_WORDS,), 7, dtype=torch.int64, device=dev)
-    eng.reads_prepare(ptr[0], L[0], ptr[1] if len(texts) > 1 else None, L2, flags, qcap, max_b, scratch.data_ptr(), sb,
-                      bases.data_ptr(), seq_off.data_ptr(), hdr.data_ptr(), info.data_ptr(), torch.cuda.current_stream(dev).cuda_stream)
-    torch.cuda.synchronize()
-    return (info.cpu().numpy().view(np.uint64), bases.cpu().numpy(), seq_off.cpu().numpy().view(np.uint64),
-            hdr.cpu().numpy().view(np.uint64), qcap)
-
-
-def _check_chunk(host, eng, dev, texts, flags, max_q, max_b, seen, shift=0):
-    """the device step on one chunk; equal to the host parser unless it flags the chunk.  Returns what the CLI uses."""
-    info, bases, seq_off, hdr, qcap = _device_prepare(eng, dev, texts, flags, max_q, max_b, shift)
-    h = host.parse_chunk(texts, flags, qcap, max_b)
-    if int(info[host.READS_STATUS]) & host.READS_NOT_STRICT:
-        seen["flagged"] += 1
-        return h
-    seen["clean"] += 1
-    hinfo, hbases, hseq_off, hhdr = h
-    n, mates = int(hinfo[host.READS_N]), len(texts)
-    assert info.tolist() == hinfo.tolist(), (info.tolist(), hinfo.tolist())
-    assert seq_off[: n * mates + 1].tolist() == hseq_off[: n * mates + 1].tolist()
-    nb = int(hinfo[host.READS_BASES])
-    assert bytes(bases[:nb]) == bytes(hbases[:nb])
-    assert hdr[: 2 * n].tolist() == hhdr[: 2 * n].tolist()
-    return info, bases, seq_off, hdr
 
 
 def _write(tmp_path, files):

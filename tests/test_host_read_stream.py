@@ -8,6 +8,7 @@ import numpy as np
 import pytest
 
 from read_corpus import corpus, read_records
+from read_edge_texts import degenerate_corpus, edge_corpus
 
 CHUNKS = list(range(1, 301)) + [4096, 1 << 16]
 
@@ -66,6 +67,45 @@ def test_chunked_reader_gives_the_records_of_the_whole_file_reader(host, name, t
         for cap in caps:                       # memory: the chunk, or twice what one record needs
             for m, c in enumerate(cap):
                 assert c <= max(chunk, 2 * bound[m]), (name, chunk, m, c, bound[m])
+
+
+EDGE_CHUNKS = [1, 2, 3, 16, 37, 97, 300, 4096, 1 << 20]
+
+
+def _edge_groups():
+    """the texts of tests/read_edge_texts.py: the degenerate ones one by one, those with a byte on a load, wave or tile edge
+    by format and kind"""
+    groups = {n: [n] for n in degenerate_corpus()}
+    for n in edge_corpus():
+        groups.setdefault(n[: n.rindex("_")], []).append(n)
+    return groups
+
+
+@pytest.mark.parametrize("group", sorted(_edge_groups()))
+def test_chunked_reader_on_the_edge_texts(host, group, tmp_path):
+    """the texts the device step is tested on (degenerate records; a newline, a record start, a '+' or the end of the text
+    on a 16-byte, 1024-byte or 4096-byte edge): the host parser gives the records of read_records at every chunk size"""
+    both = dict(degenerate_corpus(), **edge_corpus())
+    for name in _edge_groups()[group]:
+        files, _strict = both[name]
+        paths = []
+        for i, data in enumerate(files):
+            p = tmp_path / ("%s_%d.fq" % (name, i + 1))
+            p.write_bytes(data)
+            paths.append(p)
+        exp, _ = _expected(files)
+        exp = [tuple([(e[0][0], e[0][1])] + [(None, m[1]) for m in e[1:]]) for e in exp]
+        for chunk in EDGE_CHUNKS:
+            got, _, _ = _run(host, paths, chunk)
+            assert got == exp, (name, chunk)
+        for flags in (0, host.READS_EOF1 | host.READS_EOF2):          # and as one chunk: what is taken is a prefix of the records
+            info, bases, seq_off, hdr = host.parse_chunk(files, flags, 1 << 40, 1 << 62)
+            n, mates = int(info[host.READS_N]), len(files)
+            assert n == len(exp) if flags else n <= len(exp), (name, flags)
+            for q in range(n):
+                assert files[0][int(hdr[2 * q]):int(hdr[2 * q + 1])] == exp[q][0][0], (name, flags, q)
+                for m in range(mates):
+                    assert bytes(bases[int(seq_off[q * mates + m]):int(seq_off[q * mates + m + 1])]) == exp[q][m][1], (name, flags, q, m)
 
 
 @pytest.mark.parametrize("name", ["fq_lf", "fa_wrap60", "paired_fq", "paired_fa_fq", "long_record_fa"])

@@ -9,6 +9,7 @@ import subprocess
 import pytest
 
 from interleaved_texts import deinterleave, interleaved_records, render
+from read_edge_texts import interleaved_corpus, interleaved_pairs
 
 CHUNKS = list(range(1, 301))
 COARSE = [1, 2, 3, 37, 97, 150, 300]          # the even record count differs from the odd one only at the end of the file
@@ -117,6 +118,19 @@ def test_limits_count_pairs_and_cuts_fall_in_front_of_a_first_mate(host, fmt, ch
         assert at in starts or at == len(whole), (at, whole[at:at + 30])
     if max_b == 20:
         assert all(n == 1 for n, *_ in batches)
+
+
+@pytest.mark.parametrize("name", sorted(interleaved_corpus()))
+def test_interleaved_texts_of_the_device_tests_against_read_records(host, name, tmp_path):
+    """the texts tests/test_gpu_reads_prepare_edges.py runs the device step on (CRLF ones included): the queries are the
+    records of read_records paired two by two, whatever the chunk size"""
+    text, _strict = interleaved_corpus()[name]
+    path = tmp_path / "il.txt"
+    path.write_bytes(text)
+    exp = interleaved_pairs(text)
+    for chunk in COARSE + [4096, 1 << 20]:
+        got, _ = _run(host, path, chunk)
+        assert got == exp, (name, chunk)
 
 
 def _list(pkg, args, cwd):
