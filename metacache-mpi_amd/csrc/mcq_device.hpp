@@ -1030,7 +1030,7 @@ __device__ __forceinline__ u32 wave_sketch_two_windows(const char* __restrict__ 
 }
 
 // ------------------------------------------------------------------ row 6: probe
-// Linear probing over 64-B buckets; one 16-B load returns key and list length -- and, for the short lists most features
+// Linear probing over 64-B buckets; one 16-B word holds key and list length (one load only under probe_t's WHOLE) -- and, for the short lists most features
 // have, the bucket IS the list: its locations are in the same 64-B sector the probe has just brought in, so the gather
 // that follows hits the cache instead of fetching a second random sector (r01: 55 sectors per read, 29 of them list
 // heads).  off = index of the list's first location relative to db.locs, in location units, for both kinds of list.
@@ -1052,11 +1052,16 @@ __device__ __forceinline__ void bucket_list_t(const DbDev& db, u32 idx, const ui
     off = len <= bucket_inline_max(BSH, db.compact) ? ((u64)idx << sh) + (1u << db.compact)      // behind the 8-B head
                                                     : (((u64)db.slot_mask + 1) << sh) + (((u64)sl.w << 32) | sl.z);
 }
-template <u32 BSH>
+// WHOLE: the head is used as the four words one load brought.  Without it the compiler narrows the load to the key and sinks
+// the rest into the branches: a second load for the length behind a match, a third for the offset words of a list that is not
+// inline, each with its own wait.  The empty statement names all four components behind the load, so
+// that they are one global_load_dwordx4 and one wait per bucket; the compiler still counts the load itself.
+template <u32 BSH, bool WHOLE = false>
 __device__ __forceinline__ void probe_t(const DbDev& db, u32 f, u64& off, u32& len) {
     u32 idx = tmh(f) & db.slot_mask;
     while (true) {
-        const uint4 sl = bucket_head_t<BSH>(db, idx);
+        uint4 sl = bucket_head_t<BSH>(db, idx);
+        if constexpr (WHOLE) asm volatile("" : "+v"(sl.x), "+v"(sl.y), "+v"(sl.z), "+v"(sl.w));
         if (sl.x == f) { bucket_list_t<BSH>(db, idx, sl, off, len); return; }
         if (sl.x == MCQ_EMPTY) return;
         idx = (idx + 1) & db.slot_mask;
@@ -1064,12 +1069,12 @@ __device__ __forceinline__ void probe_t(const DbDev& db, u32 f, u64& off, u32& l
 }
 // BSH = 2 / 0: the layout is known at compile time (the wave kernels are instantiated per layout); -1: one wave-uniform
 // branch on db.bsh per probe (workgroup kernel, staged kernels, the match-list taps)
-template <int BSH = -1>
+template <int BSH = -1, bool WHOLE = false>
 __device__ __forceinline__ void probe(const DbDev& db, u32 f, u64& off, u32& len) {
     len = 0; off = 0;
     if (f == MCQ_EMPTY) return;
-    if constexpr (BSH >= 0) probe_t<(u32)BSH>(db, f, off, len);
-    else { if (db.bsh) probe_t<2>(db, f, off, len); else probe_t<0>(db, f, off, len); }
+    if constexpr (BSH >= 0) probe_t<(u32)BSH, WHOLE>(db, f, off, len);
+    else { if (db.bsh) probe_t<2, WHOLE>(db, f, off, len); else probe_t<0, WHOLE>(db, f, off, len); }
 }
 // (the owner-side lookup of the sharded path walks four probes at a time: its own loop, on these)
 __device__ __forceinline__ uint4 bucket_head(const DbDev& db, u32 idx) { return db.slots[(u64)idx << db.bsh]; }

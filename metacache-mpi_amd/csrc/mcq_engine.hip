@@ -624,7 +624,7 @@ __global__ __launch_bounds__(256, sizeof(KeyT) == 4 ? (NL > 1 ? 5 : MCQ_WAVE_OCC
             }
             if (lane < nfeat) myf = feat[lane];
             if (stop == 1) { if (myf == 12345u) out.ncand[q] = nfeat; continue; }
-            probe<BSH>(db, myf, off, len);
+            probe<BSH, LEAN && !PAIRED && !PACKED>(db, myf, off, len);     // (single unpacked lean: a bucket's head in one 16-B load)
             if (stop == 2) { if (len == 0x7FFFFFFFu) out.ncand[q] = (u32)off; continue; }
             }
             u32 incl = wave_incl_scan_dpp(len);
