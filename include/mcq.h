@@ -892,6 +892,15 @@ int mcq_all_hits(const mcq_db* db, mcq_ws* ws, const mcq_batch* in, const uint64
  *          The handle stays usable.                                                                                        */
 #define MCQ_ACCMAP_MAX_LINE 1024
 typedef struct mcq_accmap mcq_accmap;
+/* The rule by which a strict line names a name.  _TARGETS: the three lookups above (mcq_accmap_create).  _ACC, _ACCVER, _GI: the
+ * name that EQUALS the line's first, second or fourth field and nothing else -- no similar-name search, no falling through to
+ * another column: the join of the reference's `annotate` (src/mode_annotate.cpp:181-229: one std::map keyed by the chosen column,
+ * the first entry of a key stays).  Everything else -- the strict form, unranked[], the first line in (file ordinal, line number)
+ * order, a taxid of 0, chunk / finish / free -- is the same under every rule.  An annotate-style caller passes the distinct ids as
+ * names, target k = name k, and unranked all 1.                                                                              */
+enum { MCQ_ACCMAP_RULE_TARGETS = 0, MCQ_ACCMAP_RULE_ACC = 1, MCQ_ACCMAP_RULE_ACCVER = 2, MCQ_ACCMAP_RULE_GI = 3 };
+int mcq_accmap_create_rule(const char* names_blob, const uint64_t* name_off, uint64_t n_names, const uint32_t* name_target,
+                           const uint8_t* unranked, uint32_t n_targets, uint32_t rule, int device, mcq_accmap** out);
 int mcq_accmap_create(const char* names_blob, const uint64_t* name_off, uint64_t n_names, const uint32_t* name_target,
                       const uint8_t* unranked, uint32_t n_targets, int device, mcq_accmap** out);
 int mcq_accmap_chunk(mcq_accmap* h, const char* text, uint64_t n_bytes, uint32_t file_ordinal, uint64_t first_line_no,

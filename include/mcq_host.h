@@ -382,6 +382,36 @@ int mcq_taxmap_files(const char* taxdir, const char* postmap, mcq_file_list** ou
 int mcq_accmap_host(const char* text, uint64_t n_bytes, int32_t skip_first_line, const char* names_blob, const uint64_t* name_off,
                     uint64_t n_names, const uint32_t* name_target, uint8_t* unranked /* [n_targets] in, out */,
                     int64_t* parent /* [n_targets] in, out */, uint32_t n_targets, uint64_t* n_records);
+/* mcq_accmap_host_rule: the same parser -- words across lines, num_get's number, the end at the first record that does not parse or
+ * when nothing is left unranked, the first line passed over on request -- under a rule of mcq_accmap_create_rule (include/mcq.h):
+ * 0 is mcq_accmap_host; under 1 / 2 / 3 a record's target is the one named exactly by its acc / accver / gi word and no other, what
+ * read_mappings_from_file of the reference's `annotate` enters into its map (src/mode_annotate.cpp:181-229; an id keeps its first
+ * taxid).  The fall-back of a handle with that rule for text that is not strict, and the CPU yardstick.
+ * For a caller that streams a file through a buffer: *n_consumed (may be NULL) = the bytes of text up to the end of the last whole
+ * record (the end of the first line passed over if there is none); *stopped (may be NULL) = 0 when the reading ended because the
+ * text ran out, inside a record or between two -- the caller goes on with text + *n_consumed and what follows --, 1 when it ended
+ * for good: a taxid that does not parse, or nothing left unranked.  Text that is not the end of its file should end behind a white
+ * space byte, so that its last word is whole.                                                                                   */
+int mcq_accmap_host_rule(const char* text, uint64_t n_bytes, int32_t skip_first_line, const char* names_blob, const uint64_t* name_off,
+                         uint64_t n_names, const uint32_t* name_target, uint8_t* unranked /* [n_targets] in, out */,
+                         int64_t* parent /* [n_targets] in, out */, uint32_t n_targets, uint32_t rule, uint64_t* n_records,
+                         uint64_t* n_consumed, int32_t* stopped);
+
+/* ---- annotate: taxid|N written into the headers of a genome file (mcq_annotate_cli; src/mode_annotate.cpp:238-311) -----
+ * mcq_annotate_id: the id of a header LINE -- the whole line with its '>' or '@', as annotate_with_taxid hands it to the extractors
+ * (src/sequence_io.cpp:576-700) -- of id_type 1 (acc: extract_ncbi_accession_number), 2 (accver: ..._version_number) or 3 (gi:
+ * extract_genbank_identifier): the values of MCQ_ACCMAP_RULE_ACC / _ACCVER / _GI.  So a header without a known prefix but with a
+ * '.' before byte 25 gives, under accver, an id that begins with '>' and that no mapping line names.  Written to buf
+ * (NUL-terminated, cut to cap - 1 bytes); returns the length (0: no id), -1 on an error.
+ * mcq_annotate_rewrite: the line as annotate writes it.  An old taxid is cut first: from the first "taxid" -- if value_sep occurs
+ * from 4 bytes behind its start on -- through the first field_sep behind that value separator, else through the next value_sep, else
+ * to the end of the line.  Then, if has_id, "taxid" value_sep N field_sep goes in ONE byte behind the start of the first field_sep
+ * (also when field_sep is longer than one byte: the reference's ipos + 1), or field_sep "taxid" value_sep N field_sep is appended
+ * when there is none.  Without an id the line only loses its old taxid.  The separators must not be empty.  Written to buf as
+ * above (the new line is at most len + 25 + 2 x strlen(field_sep) + strlen(value_sep) bytes); returns its length, -1 on an error. */
+int64_t mcq_annotate_id(const char* line, uint64_t len, uint32_t id_type, char* buf, size_t cap);
+int64_t mcq_annotate_rewrite(const char* line, uint64_t len, int32_t has_id, uint64_t taxid, const char* field_sep,
+                             const char* value_sep, char* buf, size_t cap);
 
 /* ---- merging query result files: the host side of the reference's `merge` mode (the device side: mcq_merge_* of include/mcq.h) ----
  * mcq_refdb_from_taxdump: a database that is a taxonomy alone -- the taxa of a dump in its order, no target, no table; the taxon

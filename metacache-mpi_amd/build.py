@@ -51,6 +51,10 @@ def info_cli_path():
     return os.path.join(_HERE, "mcq_info_cli")
 
 
+def annotate_cli_path():
+    return os.path.join(_HERE, "mcq_annotate_cli")
+
+
 def mpi_cli_path():
     """mcq_query_mpi (one process per GPU under mpiexec); built only where an MPI is installed (/opt/conda: MPICH)"""
     return os.path.join(_HERE, "mcq_query_mpi")
@@ -79,7 +83,7 @@ def source_digest():
 
 def build_host(force=False, verbose=False):
     """libmcq_host.so (shard reader and writer, taxonomy, classify, build inputs; g++, no GPU) and the
-    mcq_query_cli, mcq_build_cli, mcq_merge_cli and mcq_info_cli binaries (they link both libraries)."""
+    mcq_query_cli, mcq_build_cli, mcq_merge_cli, mcq_info_cli and mcq_annotate_cli binaries (they link both libraries)."""
     srcs = [os.path.join(_HERE, "csrc", "host", f) for f in ("mcq_host.cpp", "mcq_host_build.cpp", "mcq_host_merge.cpp")]     # query side, build side, merge side
     hdr = os.path.join(os.path.dirname(_HERE), "include", "mcq_host.h")
     out = host_lib_path()
@@ -127,6 +131,16 @@ def build_host(force=False, verbose=False):
         hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
         cmd = [hipcc, "-std=c++14", "-O2", "-ffp-contract=off", "-pthread", icli_src, "-o", icli, "-L" + _HERE, "-lmcq_hip", "-lmcq_host",
                "-Wl,-rpath,$ORIGIN"]     # (no contraction: the moments are the reference's double arithmetic restated op for op)
+        if verbose:
+            print(" ".join(cmd))
+        subprocess.check_call(cmd)
+    # mcq_annotate_cli: taxid|N into the headers of genome files, from *.accession2taxid files
+    acli_src = os.path.join(_HERE, "csrc", "host", "mcq_annotate_cli.cpp")
+    acli = annotate_cli_path()
+    acli_deps = [out, lib_path(), _HDR, hdr, os.path.join(_HERE, "csrc", "host", "mcq_cli_buffers.hpp"), acli_src]
+    if force or not os.path.exists(acli) or os.path.getmtime(acli) < max(os.path.getmtime(f) for f in acli_deps):
+        hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
+        cmd = [hipcc, "-std=c++14", "-O2", "-pthread", acli_src, "-o", acli, "-L" + _HERE, "-lmcq_hip", "-lmcq_host", "-Wl,-rpath,$ORIGIN"]
         if verbose:
             print(" ".join(cmd))
         subprocess.check_call(cmd)

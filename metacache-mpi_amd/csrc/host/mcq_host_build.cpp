@@ -633,9 +633,13 @@ struct NameSet {
 // `is >> acc >> accver >> taxid >> gi` until an extraction fails: words are separated by any white space and run across lines; taxid
 // is a uint64 as num_get reads it (an optional sign -- '-' negates in 64 bits --, then digits up to the first other character, which
 // stays in the stream; no digit, or a value beyond 64 bits, fails).
-extern "C" int mcq_accmap_host(const char* text, uint64_t n_bytes, int32_t skip_first_line, const char* names_blob, const uint64_t* name_off,
-                               uint64_t n_names, const uint32_t* name_target, uint8_t* unranked, int64_t* parent, uint32_t n_targets,
-                               uint64_t* n_records) {
+// rule 0: the record's target is the one named accver, else similar to acc, else named gi; rules 1 to 3 (annotate's map,
+// src/mode_annotate.cpp:210-217): the name equal to the record's acc / accver / gi word and nothing else.
+namespace {
+int accmap_host(const char* text, uint64_t n_bytes, int32_t skip_first_line, const char* names_blob, const uint64_t* name_off,
+                uint64_t n_names, const uint32_t* name_target, uint8_t* unranked, int64_t* parent, uint32_t n_targets, uint32_t rule,
+                uint64_t* n_records, uint64_t* n_consumed, int32_t* stopped) {
+    if (rule > 3) return fail("the rule is 0 (targets), 1 (acc), 2 (accver) or 3 (gi)");
     if ((n_bytes && !text) || !name_off || (n_names && (!names_blob || !name_target)) || (n_targets && (!unranked || !parent))) return fail("null argument");
     for (uint64_t k = 0; k < n_names; ++k) if (name_target[k] >= n_targets) return fail("a name's target is outside the targets");
     const NameSet N{names_blob, name_off, n_names, name_target};
@@ -652,9 +656,12 @@ extern "C" int mcq_accmap_host(const char* text, uint64_t n_bytes, int32_t skip_
         return true;
     };
     std::string acc, accver, gi;
+    const char* whole = p;                                                 // behind the last whole record
+    bool ran_out = false;                                                  // the text ended inside a record or between two
     while (left) {                                                         // (`if(targetTaxa.empty()) break`)
-        if (!word(acc) || !word(accver)) break;
+        if (!word(acc) || !word(accver)) { ran_out = true; break; }
         while (p < e && std::isspace((unsigned char)*p)) ++p;
+        if (p >= e) { ran_out = true; break; }
         const char* q = p; bool neg = false;
         if (q < e && (*q == '-' || *q == '+')) { neg = *q == '-'; ++q; }
         if (q >= e || *q < '0' || *q > '9') break;
@@ -667,12 +674,66 @@ extern "C" int mcq_accmap_host(const char* text, uint64_t n_bytes, int32_t skip_
         if (over) break;
         if (neg) v = 0 - v;
         p = q;
-        if (!word(gi)) break;
-        ++records;
-        uint64_t k = N.find(accver);
-        if (k == N.n) { k = N.similar(acc); if (k == N.n) k = N.find(gi); }
+        if (!word(gi)) { ran_out = true; break; }
+        ++records; whole = p;
+        uint64_t k;
+        if (rule == 0) { k = N.find(accver); if (k == N.n) { k = N.similar(acc); if (k == N.n) k = N.find(gi); } }
+        else k = N.find(rule == 1 ? acc : (rule == 2 ? accver : gi));
         if (k != N.n && unranked[name_target[k]]) { unranked[name_target[k]] = 0; parent[name_target[k]] = (int64_t)v; --left; }
     }
     if (n_records) *n_records = records;
+    if (n_consumed) *n_consumed = (uint64_t)(whole - text);
+    if (stopped) *stopped = ran_out ? 0 : 1;
     return 0;
+}
+}  // namespace
+
+extern "C" int mcq_accmap_host(const char* text, uint64_t n_bytes, int32_t skip_first_line, const char* names_blob, const uint64_t* name_off,
+                               uint64_t n_names, const uint32_t* name_target, uint8_t* unranked, int64_t* parent, uint32_t n_targets,
+                               uint64_t* n_records) {
+    return accmap_host(text, n_bytes, skip_first_line, names_blob, name_off, n_names, name_target, unranked, parent, n_targets, 0, n_records, nullptr, nullptr);
+}
+extern "C" int mcq_accmap_host_rule(const char* text, uint64_t n_bytes, int32_t skip_first_line, const char* names_blob, const uint64_t* name_off,
+                                    uint64_t n_names, const uint32_t* name_target, uint8_t* unranked, int64_t* parent, uint32_t n_targets,
+                                    uint32_t rule, uint64_t* n_records, uint64_t* n_consumed, int32_t* stopped) {
+    return accmap_host(text, n_bytes, skip_first_line, names_blob, name_off, n_names, name_target, unranked, parent, n_targets, rule, n_records,
+                       n_consumed, stopped);
+}
+
+// ---- annotate (src/mode_annotate.cpp:238-311): the id of a header line and the line with its taxid put in ------------------
+// The extractors get the WHOLE line, its '>' or '@' included, as annotate_with_taxid calls them: a header without a known prefix
+// whose first '.' stands before byte 25 gives an id that begins with that character, which no mapping line names.
+extern "C" int64_t mcq_annotate_id(const char* line, uint64_t len, uint32_t id_type, char* buf, size_t cap) {
+    if ((len && !line) || (cap && !buf)) return fail("null argument");
+    if (id_type < 1 || id_type > 3) return fail("the id type is 1 (acc), 2 (accver) or 3 (gi)");
+    const std::string t(line ? line : "", (size_t)len);
+    const std::string s = id_type == 1 ? accession_plain(t) : (id_type == 2 ? accession_version(t) : genbank_id(t));
+    if (cap) { const size_t n = std::min(cap - 1, s.size()); std::memcpy(buf, s.data(), n); buf[n] = 0; }
+    return (int64_t)s.size();
+}
+// :265-298.  The old taxid: from "taxid" through the field separator found behind the value separator (which is looked for 4 bytes
+// into "taxid"), else through the next value separator, else to the end of the line; without a value separator nothing is cut.
+// The new one goes ONE byte behind the first field separator's first byte, however long the separator is.
+extern "C" int64_t mcq_annotate_rewrite(const char* line, uint64_t len, int32_t has_id, uint64_t taxid, const char* field_sep,
+                                        const char* value_sep, char* buf, size_t cap) {
+    if ((len && !line) || (cap && !buf) || !field_sep || !value_sep) return fail("null argument");
+    if (!*field_sep || !*value_sep) return fail("the separators must not be empty");
+    std::string t(line ? line : "", (size_t)len);
+    const std::string fs = field_sep, vs = value_sep;
+    const size_t j = t.find("taxid");
+    if (j != npos) {
+        const size_t k = t.find(vs, j + 4);
+        if (k != npos) {
+            size_t l = t.find(fs, k + 1);
+            if (l == npos) l = t.find(vs, k + 1);
+            t.erase(j, l - j + 1);                                         // (l == npos: npos - j + 1 wraps to "the rest", j >= 1 in a header)
+        }
+    }
+    if (has_id) {
+        const std::string ins = "taxid" + vs + std::to_string((unsigned long long)taxid) + fs;
+        const size_t ipos = t.find(fs);
+        if (ipos == npos) t += fs + ins; else t.insert(ipos + 1, ins);
+    }
+    if (cap) { const size_t n = std::min(cap - 1, t.size()); std::memcpy(buf, t.data(), n); buf[n] = 0; }
+    return (int64_t)t.size();
 }

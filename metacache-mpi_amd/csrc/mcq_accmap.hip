@@ -16,6 +16,9 @@
 // A target that an earlier line of any chunk has won holds a smaller key and is left alone; a chunk fed out of order replaces a
 // larger key and overwrites the taxid.  The result is a function of the set of (ordinal, line, text) alone, never of scheduling.
 // The status word is read back at the end of the call: the call returns when the chunk is applied (or found not strict).
+// A handle made by mcq_accmap_create_rule with MCQ_ACCMAP_RULE_ACC / _ACCVER / _GI joins on ONE column instead: a line names the name
+// equal to its field 0 / 1 / 3 and no other (what `annotate` does with its std::map, src/mode_annotate.cpp:181-229); the strict form,
+// the claim and the write are the same.
 // Stores are plain C++ and vector atomics.
 #include "mcq_internal.hpp"
 
@@ -103,6 +106,9 @@ __device__ __forceinline__ u64 am_similar(const AmNames& N, const unsigned char*
     return lo;
 }
 
+// RULE: MCQ_ACCMAP_RULE_TARGETS (the three lookups of a build's post-mapping) or _ACC / _ACCVER / _GI (the name equal to field 0 / 1 /
+// 3 and nothing else: the exact-column join of `annotate`).  A compile-time axis: the default rule's instantiation is the code it was.
+template <u32 RULE>
 __global__ __launch_bounds__(256) void k_am_parse(AmNames N, AmChunk C) {
     __shared__ uint4 s_text4[AM_LDS / 16];
     __shared__ unsigned short s_start[AM_TILE_LINES + 1];
@@ -163,9 +169,15 @@ __global__ __launch_bounds__(256) void k_am_parse(AmNames N, AmChunk C) {
         ok = ok && ended && f == 3 && flen[3] > 0;                            // (fields 0..2 were closed non-empty)
         const u64 li = line0 + j;
         if (!ok || li >= C.line_cap) { bad = true; continue; }
-        u64 k = am_find(N, s + fbeg[1], flen[1]);
-        if (k == N.n) k = am_similar(N, s + fbeg[0], flen[0]);
-        if (k == N.n) k = am_find(N, s + fbeg[3], flen[3]);
+        u64 k;
+        if constexpr (RULE == MCQ_ACCMAP_RULE_TARGETS) {
+            k = am_find(N, s + fbeg[1], flen[1]);
+            if (k == N.n) k = am_similar(N, s + fbeg[0], flen[0]);
+            if (k == N.n) k = am_find(N, s + fbeg[3], flen[3]);
+        } else {
+            constexpr u32 col = RULE == MCQ_ACCMAP_RULE_ACC ? 0u : (RULE == MCQ_ACCMAP_RULE_ACCVER ? 1u : 3u);
+            k = am_find(N, s + fbeg[col], flen[col]);
+        }
         u32 t = AM_NONE;
         if (k != N.n) { t = N.target[k]; if (!N.unranked[t]) t = AM_NONE; }   // (no falling through when the target is ranked)
         C.line_tgt[li] = t;
@@ -205,6 +217,7 @@ template <class T> struct DevArr {
 
 struct mcq_accmap {
     int device = 0;
+    u32 rule = MCQ_ACCMAP_RULE_TARGETS;
     u64 n_names = 0; u32 n_targets = 0;
     DevArr<unsigned char> blob, unranked;
     DevArr<u64> name_off, taxid, tile_cnt, tile_off, line_tax;
@@ -214,6 +227,12 @@ struct mcq_accmap {
 
 extern "C" int mcq_accmap_create(const char* names_blob, const uint64_t* name_off, uint64_t n_names, const uint32_t* name_target,
                                  const uint8_t* unranked, uint32_t n_targets, int device, mcq_accmap** out) {
+    return mcq_accmap_create_rule(names_blob, name_off, n_names, name_target, unranked, n_targets, MCQ_ACCMAP_RULE_TARGETS, device, out);
+}
+
+extern "C" int mcq_accmap_create_rule(const char* names_blob, const uint64_t* name_off, uint64_t n_names, const uint32_t* name_target,
+                                      const uint8_t* unranked, uint32_t n_targets, uint32_t rule, int device, mcq_accmap** out) {
+    if (rule > MCQ_ACCMAP_RULE_GI) return fail(MCQ_E_ARG, "the rule is one of MCQ_ACCMAP_RULE_*");
     if (!out || !name_off || (n_names && (!name_target || !names_blob)) || (n_targets && !unranked)) return fail(MCQ_E_ARG, "null argument");
     if (name_off[0] != 0) return fail(MCQ_E_ARG, "name_off[0] must be 0");
     for (u64 k = 0; k < n_names; ++k) {
@@ -227,7 +246,7 @@ extern "C" int mcq_accmap_create(const char* names_blob, const uint64_t* name_of
     }
     HIPCHK(hipSetDevice(device));
     std::unique_ptr<mcq_accmap> h(new mcq_accmap());
-    h->device = device; h->n_names = n_names; h->n_targets = n_targets;
+    h->device = device; h->rule = rule; h->n_names = n_names; h->n_targets = n_targets;
     const u64 nb = name_off[n_names];
     int rc;
     if ((rc = h->blob.grow(nb)) || (rc = h->name_off.grow(n_names + 1)) || (rc = h->name_target.grow(n_names)) ||
@@ -263,7 +282,12 @@ extern "C" int mcq_accmap_chunk(mcq_accmap* h, const char* text, uint64_t n_byte
     AmNames N; N.blob = h->blob.p; N.off = h->name_off.p; N.target = h->name_target.p; N.n = h->n_names; N.unranked = h->unranked.p; N.n_targets = h->n_targets;
     AmChunk C; C.text = text; C.n = n_bytes; C.n_tiles = n_tiles; C.tile_off = h->tile_off.p; C.line_tgt = h->line_tgt.p; C.line_tax = h->line_tax.p;
     C.line_cap = line_cap; C.status = h->status.p; C.key0 = ((u64)file_ordinal << 40) | first_line_no;
-    hipLaunchKernelGGL(k_am_parse, dim3((u32)n_tiles), dim3(256), 0, st, N, C);
+    switch (h->rule) {
+        case MCQ_ACCMAP_RULE_ACC:    hipLaunchKernelGGL(k_am_parse<MCQ_ACCMAP_RULE_ACC>, dim3((u32)n_tiles), dim3(256), 0, st, N, C); break;
+        case MCQ_ACCMAP_RULE_ACCVER: hipLaunchKernelGGL(k_am_parse<MCQ_ACCMAP_RULE_ACCVER>, dim3((u32)n_tiles), dim3(256), 0, st, N, C); break;
+        case MCQ_ACCMAP_RULE_GI:     hipLaunchKernelGGL(k_am_parse<MCQ_ACCMAP_RULE_GI>, dim3((u32)n_tiles), dim3(256), 0, st, N, C); break;
+        default:                     hipLaunchKernelGGL(k_am_parse<MCQ_ACCMAP_RULE_TARGETS>, dim3((u32)n_tiles), dim3(256), 0, st, N, C); break;
+    }
     const u32 line_blocks = (u32)((line_cap + 255) / 256);
     hipLaunchKernelGGL(k_am_claim, dim3(line_blocks), dim3(256), 0, st, C, h->key.p);
     hipLaunchKernelGGL(k_am_write, dim3(line_blocks), dim3(256), 0, st, C, (const unsigned long long*)h->key.p, h->taxid.p);

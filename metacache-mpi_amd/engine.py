@@ -253,6 +253,8 @@ def lib():
                                        C.c_void_p, C.c_void_p]
         if hasattr(L, "mcq_accmap_create"):
             L.mcq_accmap_create.argtypes = [C.c_char_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_uint32, C.c_int, C.POINTER(C.c_void_p)]
+            L.mcq_accmap_create_rule.argtypes = [C.c_char_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_int,
+                                                 C.POINTER(C.c_void_p)]
             L.mcq_accmap_chunk.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint32, C.c_uint64, C.POINTER(C.c_uint32), C.c_void_p]
             L.mcq_accmap_finish.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
             L.mcq_accmap_free.argtypes = [C.c_void_p]
@@ -1243,6 +1245,7 @@ class TableExtend:
 
 
 MCQ_ACCMAP_MAX_LINE = 1024
+MCQ_ACCMAP_RULE_TARGETS, MCQ_ACCMAP_RULE_ACC, MCQ_ACCMAP_RULE_ACCVER, MCQ_ACCMAP_RULE_GI = 0, 1, 2, 3
 
 
 def sorted_names(names):
@@ -1259,14 +1262,15 @@ class AccMap:
     """mcq_accmap_*: *.accession2taxid text joined against the names of a database's targets on the GPU.  names: the target names
     (bytes; target t at index t); unranked: per target, non-zero where it has no parent.  chunk() takes whole lines of one file in
     DEVICE memory (a pointer and a byte count, or a torch uint8 tensor on the GPU) and returns whether the chunk was strict (and so
-    applied); finish() returns (parent int64[n_targets], found bool[n_targets])."""
+    applied); finish() returns (parent int64[n_targets], found bool[n_targets]).  rule: MCQ_ACCMAP_RULE_TARGETS (a build's three
+    lookups) or _ACC / _ACCVER / _GI (the name equal to that column and nothing else: mcq_accmap_create_rule)."""
 
-    def __init__(self, names, unranked, device=0):
+    def __init__(self, names, unranked, device=0, rule=MCQ_ACCMAP_RULE_TARGETS):
         blob, off, tgt = sorted_names([bytes(n) for n in names])
         u = np.ascontiguousarray(unranked, np.uint8)
         assert len(u) == len(names)
         h = C.c_void_p()
-        _chk(lib().mcq_accmap_create(blob, _np_ptr(off), len(tgt), _np_ptr(tgt), _np_ptr(u), len(u), device, C.byref(h)))
+        _chk(lib().mcq_accmap_create_rule(blob, _np_ptr(off), len(tgt), _np_ptr(tgt), _np_ptr(u), len(u), rule, device, C.byref(h)))
         self.h, self.n_targets = h, len(u)
 
     def chunk(self, text, n_bytes=None, file_ordinal=0, first_line_no=0, stream=None):

@@ -198,6 +198,11 @@ def lib():
         L.mcq_taxmap_files.argtypes = [C.c_char_p, C.c_char_p, C.POINTER(C.c_void_p)]
         L.mcq_accmap_host.argtypes = [C.c_char_p, C.c_uint64, C.c_int32, C.c_char_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p,
                                       C.c_uint32, C.POINTER(C.c_uint64)]
+        L.mcq_accmap_host_rule.argtypes = [C.c_char_p, C.c_uint64, C.c_int32, C.c_char_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p,
+                                           C.c_uint32, C.c_uint32, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_int32)]
+        L.mcq_annotate_id.restype = C.c_int64; L.mcq_annotate_id.argtypes = [C.c_char_p, C.c_uint64, C.c_uint32, C.c_char_p, C.c_size_t]
+        L.mcq_annotate_rewrite.restype = C.c_int64
+        L.mcq_annotate_rewrite.argtypes = [C.c_char_p, C.c_uint64, C.c_int32, C.c_uint64, C.c_char_p, C.c_char_p, C.c_char_p, C.c_size_t]
         L.mcq_refdb_from_taxdump.argtypes = [C.c_void_p, C.POINTER(C.c_void_p)]
         L.mcq_refdb_taxid_table.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_uint64)]
         L.mcq_results_properties.argtypes = [C.c_char_p, C.POINTER(C.c_uint32), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
@@ -727,18 +732,43 @@ def taxmap_files(taxdir, postmap=None):
         lib().mcq_file_list_free(h)
 
 
-def accmap_host(text, names, unranked, parent, skip_first_line=True):
+def accmap_host(text, names, unranked, parent, skip_first_line=True, rule=None):
     """mcq_accmap_host: the reference's token parser over one mapping text (bytes).  names: the target names (bytes, target t at index
-    t); unranked (uint8) and parent (int64) are numpy arrays that are UPDATED.  Returns the number of records read."""
+    t); unranked (uint8) and parent (int64) are numpy arrays that are UPDATED.  Returns the number of records read.  rule (0 to 3):
+    mcq_accmap_host_rule -- 1 / 2 / 3: a record names the name equal to its acc / accver / gi word and nothing else."""
     from .engine import sorted_names
     blob, off, tgt = sorted_names([bytes(n) for n in names])
     assert unranked.dtype == np.uint8 and parent.dtype == np.int64 and len(unranked) == len(parent) == len(names)
     n = C.c_uint64(0)
-    if lib().mcq_accmap_host(text, len(text), 1 if skip_first_line else 0, blob, off.ctypes.data_as(C.c_void_p), len(tgt),
-                             tgt.ctypes.data_as(C.c_void_p), unranked.ctypes.data_as(C.c_void_p), parent.ctypes.data_as(C.c_void_p),
-                             len(names), C.byref(n)) != 0:
+    head = (text, len(text), 1 if skip_first_line else 0, blob, off.ctypes.data_as(C.c_void_p), len(tgt), tgt.ctypes.data_as(C.c_void_p),
+            unranked.ctypes.data_as(C.c_void_p), parent.ctypes.data_as(C.c_void_p), len(names))
+    rc = lib().mcq_accmap_host(*head, C.byref(n)) if rule is None else lib().mcq_accmap_host_rule(*head, rule, C.byref(n), None, None)
+    if rc != 0:
         raise _err()
     return int(n.value)
+
+
+ID_ACC, ID_ACCVER, ID_GI = 1, 2, 3
+
+
+def annotate_id(line, id_type=ID_ACCVER):
+    """mcq_annotate_id: the id annotate takes from a header line (bytes, WITH its '>' or '@'); b"" if it has none"""
+    n = lib().mcq_annotate_id(line, len(line), id_type, None, 0)
+    if n < 0:
+        raise _err()
+    buf = C.create_string_buffer(n + 1)
+    lib().mcq_annotate_id(line, len(line), id_type, buf, n + 1)
+    return buf.raw[:n]
+
+
+def annotate_rewrite(line, has_id, taxid, field_sep=b" ", value_sep=b"|"):
+    """mcq_annotate_rewrite: the header line (bytes) with its old taxid cut and, if has_id, taxid<vs>N<fs> put in"""
+    n = lib().mcq_annotate_rewrite(line, len(line), 1 if has_id else 0, taxid, field_sep, value_sep, None, 0)
+    if n < 0:
+        raise _err()
+    buf = C.create_string_buffer(n + 1)
+    lib().mcq_annotate_rewrite(line, len(line), 1 if has_id else 0, taxid, field_sep, value_sep, buf, n + 1)
+    return buf.raw[:n]
 
 
 def read_genomes(files, cap, io_bytes=1 << 20, after=None, skipped=None, seq2tax=None):
