@@ -867,6 +867,43 @@ int mcq_all_hits_count(const mcq_db* db, mcq_ws* ws, const mcq_batch* in, uint64
 int mcq_all_hits(const mcq_db* db, mcq_ws* ws, const mcq_batch* in, const uint64_t* loc_off, mcq_hit* hits /* device [cap] */,
                  uint64_t cap, uint32_t* n_hits /* device [nq] */, uint32_t* status /* device [nq] */, void* stream);
 
+/* ---- breadth of coverage per reference sequence: what `-coverage` prints and `-cov-percentile` cuts by (csrc/mcq_coverage.hip) ------
+ * A handle on one device that adds up, over all batches of a run, what mcq_target_hits answers: one bit per (target, window) -- set once
+ * some query had a match there --, and per target a `queries` and a `hits` counter (u64).  A target's segment of the bitmap starts on a
+ * 32-bit word: word_off[t + 1] = word_off[t] + ceil(windows[t] / 32).  Device memory: 4 B per 32 windows and 40 B per target.
+ *   create   windows (host, [n_targets], n_targets >= 1): windows of every target (mcq_refdb_tgt_windows); a target may have none.
+ *   add      ranges, counts: DEVICE, mcq_target_hits' out_ranges / out_counts as they are ([n_queries * n_slots] and
+ *            [n_queries * n_slots * range_cap]; ranges 16-byte aligned).  For every (query, slot) with tgt != MCQ_TARGET_UNUSED and
+ *            n_win > 0: window win_beg + i of tgt gets its bit for every i < n_win with counts[i] > 0 (a window of the range with count
+ *            0 gets none), queries[tgt] += 1, hits[tgt] += the sum of those counts (the `hits` field of the range is not read).  The
+ *            words of counts from n_win on are never read.  A slot with tgt >= n_targets, with win_beg + n_win > windows[tgt], or with
+ *            n_win > range_cap is skipped as a whole and counted in out_of_range: the kernel checks this, nothing outside the target's
+ *            segment is touched.  Only enqueues work on `stream`.
+ *   read     one kernel counts the set bits of every segment, then host_out[t] = {hits, queries, windows_covered} of every target and
+ *            *out_of_range (may be NULL) are copied out; waits for `stream`.  All sums are integers: they do not depend on the order
+ *            of the adds, nor on how an input was cut into batches.
+ *   reset    everything back to zero; only enqueues work on `stream`.
+ *   bitmap   for tests: the bitmap as it is, mcq_coverage_bitmap_words() words -- one guard word, the segments, one guard word; the
+ *            guards are never addressed and stay 0 -- and (may be NULL) word_off[n_targets + 1], counted from the first segment.  Waits. */
+#ifndef MCQ_TARGET_COVERAGE_DEFINED
+#define MCQ_TARGET_COVERAGE_DEFINED
+typedef struct {
+    uint64_t hits;              /* matches of all entries on the target                                     */
+    uint64_t queries;           /* (query, slot) entries on the target: reads that had it as a candidate   */
+    uint32_t windows_covered;   /* windows of the target with at least one match                           */
+    uint32_t reserved;          /* 0                                                                        */
+} mcq_target_coverage;
+#endif
+typedef struct mcq_coverage mcq_coverage;
+int mcq_coverage_create(const uint32_t* windows /* host [n_targets] */, uint32_t n_targets, int32_t device, mcq_coverage** out);
+int mcq_coverage_add(mcq_coverage* cov, const mcq_target_range* ranges, const uint32_t* counts, uint64_t n_queries, uint32_t n_slots,
+                     uint32_t range_cap, void* stream);
+int mcq_coverage_read(mcq_coverage* cov, mcq_target_coverage* host_out /* [n_targets] */, uint64_t* out_of_range, void* stream);
+int mcq_coverage_reset(mcq_coverage* cov, void* stream);
+uint64_t mcq_coverage_bitmap_words(const mcq_coverage* cov);
+int mcq_coverage_bitmap(mcq_coverage* cov, uint32_t* host_words, uint64_t* host_word_off, void* stream);
+int mcq_coverage_free(mcq_coverage* cov);
+
 /* ---- *.accession2taxid text joined against the names of a database's targets (the post-mapping of a build) -----------
  * What rank_targets_with_mapping_file (src/mode_build.cpp:248-312) does for the targets without a parent, on text of the strict
  * form.  A line `acc TAB accver TAB taxid TAB gi` names one target at most, a function of the line alone: the target named

@@ -245,6 +245,33 @@ int mcq_hits_table_free(mcq_hits_table* t);
 uint32_t mcq_refdb_target_key(const mcq_refdb* db, uint32_t target);
 int mcq_refdb_tax2tgt(const mcq_refdb* db, uint32_t* out /* [n_taxa] */);
 
+/* ---- coverage of reference sequences: the cut of `-cov-percentile` and the report of `-coverage` over what mcq_coverage_read of
+ * include/mcq.h returns (cov[n_targets]) and the targets' windows (windows[n_targets]: mcq_refdb_seq_windows, the windows_in_sequence
+ * of the -hits-per-seq table as 32-bit numbers).
+ * mcq_coverage_cut -- the rule is this project's own: the hit targets are those with windows_covered > 0, H of them.  They are ordered
+ * by breadth windows_covered / windows ascending, compared exactly by cross-multiplication in 64 bits (a before b iff a.covered *
+ * b.windows < b.covered * a.windows), never as floats; ties go by ascending target id.  The first K = floor(H * percentile / 100) of
+ * them get removed[t] = 1, every other target 0.  Percentile 0 removes nothing, 100 removes all hit targets; a target without a covered
+ * window is never removed.  percentile outside [0, 100]: an error.
+ * mcq_coverage_text / mcq_coverage_write -- the report block as mcq_hits_table_text / mcq_hits_table_write give theirs: behind `comment`
+ * the line `--- coverage of reference sequences ---`, one line each for reads_skipped and out_of_range if not 0 (queries that were
+ * beyond mcq_target_hits' capacity; ranges mcq_coverage_add refused), and the TABLE_LAYOUT line naming the columns sequence,
+ * windows_in_sequence, windows_covered, coverage, queries, hits, kept; then one row per target with queries > 0 in ascending target
+ * id: show_taxon of the target under `mode` as in the -hits-per-seq table, windows[t], windows_covered, the fraction with six
+ * decimals (0.000000 for a target without windows), queries, hits, and `kept` or `removed` (removed == NULL: all kept).           */
+#ifndef MCQ_TARGET_COVERAGE_DEFINED
+#define MCQ_TARGET_COVERAGE_DEFINED
+typedef struct { uint64_t hits; uint64_t queries; uint32_t windows_covered; uint32_t reserved; } mcq_target_coverage;   /* as in include/mcq.h */
+#endif
+int mcq_refdb_seq_windows(const mcq_refdb* db, uint32_t* out /* [n_targets] */);
+int mcq_coverage_cut(const mcq_target_coverage* cov, const uint32_t* windows, uint32_t n_targets, double percentile, uint8_t* removed /* [n_targets] */);
+int64_t mcq_coverage_text(const mcq_refdb* db, const mcq_target_coverage* cov, const uint32_t* windows, uint32_t n_targets,
+                          const uint8_t* removed, uint64_t reads_skipped, uint64_t out_of_range, const char* comment, const char* column,
+                          const mcq_taxon_print* mode, char* buf, size_t cap);
+int mcq_coverage_write(const mcq_refdb* db, const mcq_target_coverage* cov, const uint32_t* windows, uint32_t n_targets,
+                       const uint8_t* removed, uint64_t reads_skipped, uint64_t out_of_range, const char* comment, const char* column,
+                       const mcq_taxon_print* mode, mcq_text_sink sink, void* user);
+
 /* ---- read files in chunks (mcq_query_cli's input stage) -------------------------------------------------------------
  * mcq_read_stream_fill puts into buf (cap bytes) first the bytes that the last fill left unconsumed, then read()s of the
  * file until buf holds `want` bytes (want <= cap) or the file ends: *len bytes, *eof = 1 when buf[0 .. *len) runs to the end

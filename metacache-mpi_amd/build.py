@@ -16,6 +16,7 @@ _UNITS = {
     os.path.join(_CSRC, "mcq_target_hits.hip"): _INTERNAL, # per-target window hit lists (-hits-per-seq)
     os.path.join(_CSRC, "mcq_align.hip"): _INTERNAL,       # read-to-candidate alignment (-align)
     os.path.join(_CSRC, "mcq_all_hits.hip"): _INTERNAL,    # all hits of a read, run-length compressed (-allhits)
+    os.path.join(_CSRC, "mcq_coverage.hip"): _INTERNAL,    # window coverage per reference sequence over a run (mcq_coverage_*: -coverage, -cov-percentile)
     os.path.join(_CSRC, "mcq_accmap.hip"): _INTERNAL,      # *.accession2taxid text joined against the targets' names (mcq_accmap_*)
     os.path.join(_CSRC, "mcq_merge.hip"): _INTERNAL + [os.path.join(_CSRC, "mcq_classify_one.hpp")],   # merge of query result files (mcq_merge_*)
     os.path.join(_CSRC, "mcq_bucket_limit.hip"): _INTERNAL,   # the query-time bucket rules on a chunk of triples (mcq_bucket_limit)

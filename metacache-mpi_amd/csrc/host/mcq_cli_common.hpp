@@ -110,6 +110,11 @@ struct Options {
     bool allhits = false;                // -allhits: the all_hits column (mcq_query_cli)
     bool hits_per_seq = false;           // -hits-per-seq [FILE]: the per-reference window hit lists, and the query_id column
     std::string hits_file;               // ... its FILE (cleared when it names the -out file: src/query_options.cpp:353)
+    bool coverage = false;               // -coverage [FILE]: the report of window coverage per reference sequence (mcq_query_cli)
+    std::string coverage_file;           // ... its FILE (cleared when it names the -out file)
+    double cov_percentile = -1;          // -cov-percentile P (0..100; below 0: not given): two passes, the least covered sequences removed
+    bool cov_cut() const { return cov_percentile >= 0; }
+    bool cov_on() const { return coverage || cov_cut(); }
     uint32_t exclude_rank = MCQ_RANK_NONE;     // -exclude R (< root): drop the hits on the read's own clade at R
     bool ground_truth = false, precision = false;   // -ground-truth: the truth_ column; -precision: the evaluation statistics
     bool wants_truth() const { return ground_truth || precision || exclude_rank != MCQ_RANK_NONE; }   // prepare_evaluation, src/classification.cpp:172-177
@@ -201,6 +206,17 @@ static const char* const kQueryUsage =
     "                   front of every mapping line.  Rows in ascending target order.  Host memory grows with the input (one\n"
     "                   entry per read and candidate is kept until the end, as in the reference).  A read with more than %u\n"
     "                   distinct (sequence, window) pairs on its candidates ends the run with an ABORT line that names it.\n"
+    "coverage (mcq_query_cli only; mcq_query_mpi rejects both and names mcq_query_cli; not options of the reference):\n"
+    "  -coverage [FILE]  after the mapping lines and the -hits-per-seq table, in front of the abundance tables, or into FILE: for every\n"
+    "                   reference sequence that is a candidate of some read its windows, the windows hit by at least one read, that\n"
+    "                   fraction, the reads that had it as a candidate and their hits -- added up on the GPU, nothing per read is kept.\n"
+    "                   Candidates are taken at sequence level whatever -lowest says (up to 16 per read).  A read beyond the\n"
+    "                   capacity of -hits-per-seq adds nothing and is counted in a # line of the report.  With -splitout the coverage\n"
+    "                   is taken over all units together and written once: into FILE, else to stdout behind the last unit's run.\n"
+    "  -cov-percentile P  (0..100) two passes over the input: the first only gathers the coverage; then the floor(H * P / 100) of the\n"
+    "                   H hit sequences with the least fraction of windows covered (ties: the lower target id first) are removed,\n"
+    "                   and the second pass is the ordinary run in which a removed sequence can be no candidate of any read.  The\n"
+    "                   last column of the -coverage report shows the cut.  Not together with -exclude.\n"
     "alignment:\n"
     "  -align           (mcq_query_cli only; mcq_query_mpi rejects it and names mcq_query_cli; aliases -alignment, -showalignment) with\n"
     "                   -lowest sequence: behind the line of a read classified to a sequence, its semi-global alignment to the top\n"
@@ -293,6 +309,19 @@ static bool parse_options(int argc, char** argv, Options& o) {
             o.hits_per_seq = true; o.query_ids = true;                       // src/query_options.cpp:308
             if (i + 1 < argc && argv[i + 1][0] != '-') o.hits_file = argv[++i];
         }
+        else if (a == "-coverage") {                                         // the FILE is the next token unless it is an option
+            o.coverage = true;
+            if (i + 1 < argc && argv[i + 1][0] != '-') o.coverage_file = argv[++i];
+        }
+        else if (a == "-cov-percentile" || a == "-cov_percentile") {
+            char* end = nullptr; const char* v = next();
+            const double P = std::strtod(v, &end);
+            if (end == v || *end != '\0' || !(P >= 0.0 && P <= 100.0)) {
+                std::fprintf(stderr, "ABORT: -cov-percentile takes a number from 0 to 100, not '%s'\n", v);
+                return false;
+            }
+            o.cov_percentile = P;
+        }
         else if (opt_named(a, {"-align", "-alignment", "-showalignment"})) o.align = true;                                      // src/query_options.cpp:329-331
         else if (a == "-align-candidate-range") o.align_range = true;
         else if (opt_named(a, {"-queryids", "-query-ids", "-query_ids", "-queryid", "-query-id", "-query_id"})) o.query_ids = true;   // src/query_options.cpp:249-250
@@ -314,6 +343,11 @@ static bool parse_options(int argc, char** argv, Options& o) {
     }
     if (o.split && o.outfile.empty()) o.outfile = split_prefix;              // src/query_options.cpp:346-351
     if (o.abundance_file == o.outfile) o.abundance_file.clear();
+    if (o.cov_cut() && o.exclude_rank != MCQ_RANK_NONE) {                   // (both need the workspace's one exclusion table)
+        std::fprintf(stderr, "ABORT: -cov-percentile and -exclude cannot be combined: both use the one exclusion table of the workspace\n");
+        return false;
+    }
+    if (o.coverage_file == o.outfile) o.coverage_file.clear();
     if (o.hits_file == o.outfile) o.hits_file.clear();                       // src/query_options.cpp:353
     if (!make_units(named, pairfiles, pairseq, o)) return false;
     if (o.lowest > o.highest) o.lowest = o.highest;
@@ -391,6 +425,8 @@ static void write_head(std::ostream& os, const Out& o, uint32_t hitmin, bool lay
     if (p.hits_per_seq)                                                     // (both lines hang on -hits-per-seq in the reference: the second one is its quirk, :95-103)
         os << cm << "A list of hits per reference sequence will be generated after the read mapping.\n"
            << cm << "A list of absolute and relative abundances per taxon will be generated after the read mapping.\n";
+    if (p.coverage) os << cm << "A list of window coverage per reference sequence will be generated after the read mapping.\n";
+    if (p.cov_cut()) os << cm << "Reference sequences below coverage percentile " << p.cov_percentile << " were removed before the read mapping.\n";
     if (p.abundance_rank != MCQ_RANK_NONE)
         os << cm << "A list of absolute and relative abundances for each '" << mcq_rank_name(p.abundance_rank)
            << "' will be generated after the read mapping.\n";
@@ -419,6 +455,7 @@ static Options split_options(const Options& p, const ReadUnit& u) {
     if (!p.outfile.empty()) s.outfile = p.outfile + tail;
     if (!p.abundance_file.empty()) s.abundance_file = p.abundance_file + tail;
     if (!p.hits_file.empty()) s.hits_file = p.hits_file + tail;             // src/mode_query.cpp:186-190, :213-218
+    s.coverage = false; s.coverage_file.clear();                            // (the report is written once, over all units together: mcq_query_cli's main)
     return s;
 }
 // -list-inputs
@@ -613,10 +650,11 @@ static bool write_abundances(std::ostream& os, mcq_refdb* rdb, const Options& p,
 // 1024, MB of shard files on)
 struct Database {
     mcq_refdb* rdb = nullptr; mcq_db* edb = nullptr; std::vector<uint32_t> t2t; uint32_t hitmin = 0;     // hitmin: -hitmin or its default
-    ~Database() { mcq_db_destroy(edb); mcq_refdb_close(rdb); }
+    mcq_db* seq_edb = nullptr; bool streamed = false;    // -coverage / -cov-percentile above -lowest sequence: the same table with sequence-level keys
+    ~Database() { mcq_db_destroy(seq_edb); mcq_db_destroy(edb); mcq_refdb_close(rdb); }
 };
 static bool open_database(const Options& p, Database& db, uint32_t n_shards, uint32_t shard_id, int device) {
-    std::string err; bool streamed = false;
+    std::string err; bool& streamed = db.streamed;
     if (mcq_open_refdb(p.prefix, p.P, mcq_stream_load_min_bytes(), &db.rdb, &streamed, err, p.tuning)) { std::fprintf(stderr, "ABORT: %s\n", err.c_str()); return false; }
     mcq_refdb_info info; mcq_refdb_get_info(db.rdb, &info);
     db.hitmin = p.hitmin < 1 ? mcq_default_hits_min(info.sketch_size) : p.hitmin;
@@ -626,5 +664,13 @@ static bool open_database(const Options& p, Database& db, uint32_t n_shards, uin
     if (mcq_make_db(db.rdb, streamed, db.t2t.data(), n_shards, shard_id, device, &db.edb, err, p.tuning, &n_shrunk, &n_removed)) { std::fprintf(stderr, "ABORT: %s\n", err.c_str()); return false; }
     if (p.tuning.max_locs > 1 || p.tuning.remove_overpopulated)
         std::fprintf(stderr, "bucket rule: %llu buckets shrunk, %llu removed\n", (unsigned long long)n_shrunk, (unsigned long long)n_removed);
+    return true;
+}
+// the table of an opened database once more, its candidates at sequence level whatever -lowest says (mcq_query_cli's coverage)
+static bool open_seq_twin(const Options& p, Database& db) {
+    std::string err;
+    std::vector<uint32_t> t2t(db.t2t.size());
+    if (mcq_refdb_tgt2tax(db.rdb, MCQ_RANK_SEQUENCE, t2t.data())) { std::fprintf(stderr, "ABORT: %s\n", mcq_host_last_error()); return false; }
+    if (mcq_make_db(db.rdb, db.streamed, t2t.data(), 1, 0, 0, &db.seq_edb, err, p.tuning)) { std::fprintf(stderr, "ABORT: %s\n", err.c_str()); return false; }
     return true;
 }

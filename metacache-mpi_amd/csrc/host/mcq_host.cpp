@@ -4,6 +4,7 @@
 #include "mcq_host_internal.hpp"
 
 #include <algorithm>
+#include <cmath>
 #include <cstdio>
 #include <cstring>
 #include <map>
@@ -786,6 +787,26 @@ void put_taxon(std::string& s, const mcq_refdb* db, uint32_t idx, uint32_t rank,
     if (m.body != 0) s += id;
     if (m.body == 2) s += ')';
 }
+// the sequence column of a per-target table: show_taxon(os, db, opt, tax) (src/printing.cpp:305-330) of target `tgt`'s sequence-level
+// taxon, as Out::best of mcq_cli_common.hpp writes it (highest_rank beyond root is read as root: the lineage has no entry above it);
+// *windows: its windows_in_sequence.  false: the target has no sequence-level taxon
+bool put_sequence(std::string& s, const mcq_refdb* db, uint32_t tgt, const mcq_taxon_print& mode, uint64_t* windows) {
+    const uint32_t key = mcq_refdb_target_key(db, tgt);
+    if (key == MCQ_NO_TAXON) return false;
+    const uint32_t idx = key & 0x7FFFFFFFu;
+    const uint32_t highest = std::min<uint32_t>(mode.highest_rank, MCQ_RANK_ROOT);
+    if (db->taxa[idx].rank > highest) s += (mode.body == 1 && !mode.show_ranks) ? "0" : "--";
+    else {
+        const uint32_t rmin = std::max<uint32_t>(mode.lowest_rank, db->taxa[idx].rank);
+        const uint32_t rmax = mode.lineage ? highest : rmin;
+        for (uint32_t r = rmin; r <= rmax; ++r) {
+            put_taxon(s, db, db->lineage[(size_t)idx * kNumRanks + r], r, mode);
+            if (r < rmax) s += ',';
+        }
+    }
+    *windows = tgt < db->seq_windows.size() ? db->seq_windows[tgt] : db->taxa[idx].windows;
+    return true;
+}
 }  // namespace
 // the block of show_matches_per_targets, handed to `sink` piece by piece (the head, then one piece per row): nothing of the table's
 // text is held beyond one row
@@ -811,22 +832,8 @@ extern "C" int mcq_hits_table_write(mcq_hits_table* t, const mcq_refdb* db, cons
     // (rows in ascending target id: the reference walks an unordered_map of taxon pointers, an order no two runs need share)
     for (const auto& m : t->per_target) {
         s.clear();
-        const uint32_t key = mcq_refdb_target_key(db, m.first);
-        if (key == MCQ_NO_TAXON) return fail("target " + std::to_string(m.first) + " has no sequence-level taxon");
-        const uint32_t idx = key & 0x7FFFFFFFu;
-        // show_taxon(os, db, opt, tax) (src/printing.cpp:305-330) of a sequence-level taxon, as Out::best of mcq_cli_common.hpp writes it
-        // (highest_rank beyond root is read as root: the lineage has no entry above it)
-        const uint32_t highest = std::min<uint32_t>(mode->highest_rank, MCQ_RANK_ROOT);
-        if (db->taxa[idx].rank > highest) s += (mode->body == 1 && !mode->show_ranks) ? "0" : "--";
-        else {
-            const uint32_t rmin = std::max<uint32_t>(mode->lowest_rank, db->taxa[idx].rank);
-            const uint32_t rmax = mode->lineage ? highest : rmin;
-            for (uint32_t r = rmin; r <= rmax; ++r) {
-                put_taxon(s, db, db->lineage[(size_t)idx * kNumRanks + r], r, *mode);
-                if (r < rmax) s += ',';
-            }
-        }
-        const uint64_t windows = m.first < db->seq_windows.size() ? db->seq_windows[m.first] : db->taxa[idx].windows;
+        uint64_t windows = 0;
+        if (!put_sequence(s, db, m.first, *mode, &windows)) return fail("target " + std::to_string(m.first) + " has no sequence-level taxon");
         s += column; s += std::to_string(windows); s += column;
         bool first = true;
         for (const auto& e : m.second) {
@@ -855,6 +862,77 @@ extern "C" int64_t mcq_hits_table_text(mcq_hits_table* t, const mcq_refdb* db, c
     if (cap && !buf) return fail("bad argument");
     TextBuf b{buf, cap, 0};
     if (mcq_hits_table_write(t, db, comment, column, mode, text_buf_sink, &b)) return -1;
+    if (cap) buf[std::min(b.len, cap - 1)] = 0;
+    return (int64_t)b.len;
+}
+
+// ---- coverage of reference sequences (-coverage, -cov-percentile): the cut and the report over what mcq_coverage_read returns
+extern "C" int mcq_refdb_seq_windows(const mcq_refdb* db, uint32_t* out) {
+    if (!db || !out) return fail("bad argument");
+    for (uint32_t t = 0; t < db->info.n_targets; ++t) {
+        const uint64_t w = t < db->seq_windows.size() ? db->seq_windows[t] : 0;
+        if (w >= (1ull << 32)) return fail("a target with 2^32 windows or more");
+        out[t] = (uint32_t)w;
+    }
+    return 0;
+}
+// THE CUT RULE (the project's own; tests/coverage_ref.py restates it):
+//   * the hit targets are those with windows_covered > 0; H is their number;
+//   * they are ordered by breadth windows_covered / windows ascending -- compared exactly, a before b iff
+//     a.covered * b.windows < b.covered * a.windows in 64 bits (both factors are below 2^32), never as floats; ties go by ascending id;
+//   * the first K = floor(H * percentile / 100) of them (in double arithmetic, at most H) are removed;
+//   * so percentile 0 removes nothing, 100 removes every hit target, and a target without a covered window is never removed.
+extern "C" int mcq_coverage_cut(const mcq_target_coverage* cov, const uint32_t* windows, uint32_t n_targets, double percentile, uint8_t* removed) {
+    if ((n_targets && (!cov || !windows || !removed)) || !(percentile >= 0.0 && percentile <= 100.0)) return fail("mcq_coverage_cut: bad argument (percentile 0..100)");
+    std::vector<uint32_t> hit;
+    for (uint32_t t = 0; t < n_targets; ++t) { removed[t] = 0; if (cov[t].windows_covered > 0) hit.push_back(t); }
+    std::sort(hit.begin(), hit.end(), [&](uint32_t a, uint32_t b) {
+        const uint64_t l = (uint64_t)cov[a].windows_covered * windows[b], r = (uint64_t)cov[b].windows_covered * windows[a];
+        return l != r ? l < r : a < b;
+    });
+    const uint64_t K = std::min<uint64_t>(hit.size(), (uint64_t)std::floor((double)hit.size() * percentile / 100.0));
+    for (uint64_t i = 0; i < K; ++i) removed[hit[i]] = 1;
+    return 0;
+}
+// the report block: two head lines behind `comment`, one more for each of reads_skipped / out_of_range that is not 0, then one row per
+// target with queries > 0 in ascending target id -- sequence (as in the -hits-per-seq table), windows_in_sequence, windows_covered,
+// coverage (the fraction, six decimals; 0 for a target without windows), queries, hits, kept | removed (removed == NULL: all kept)
+extern "C" int mcq_coverage_write(const mcq_refdb* db, const mcq_target_coverage* cov, const uint32_t* windows, uint32_t n_targets,
+                                  const uint8_t* removed, uint64_t reads_skipped, uint64_t out_of_range, const char* comment,
+                                  const char* column, const mcq_taxon_print* mode, mcq_text_sink sink, void* user) {
+    if (!db || (n_targets && (!cov || !windows)) || !comment || !column || !mode || !sink || mode->body > 2) return fail("bad argument");
+    std::string s;
+    s += comment; s += "--- coverage of reference sequences ---\n";
+    if (reads_skipped) { s += comment; s += std::to_string(reads_skipped) + " queries beyond the capacity of mcq_target_hits added nothing\n"; }
+    if (out_of_range) { s += comment; s += std::to_string(out_of_range) + " candidate ranges outside their sequence added nothing\n"; }
+    s += comment; s += "TABLE_LAYOUT:  sequence ";
+    for (const char* c : {"windows_in_sequence", "windows_covered", "coverage", "queries", "hits"}) { s += column; s += ' '; s += c; s += ' '; }
+    s += column; s += " kept\n";
+    if (sink(user, s.data(), s.size())) return fail("the sink refused the report's head");
+    for (uint32_t t = 0; t < n_targets; ++t) {
+        if (!cov[t].queries) continue;
+        s.clear();
+        uint64_t seq_windows = 0;
+        if (!put_sequence(s, db, t, *mode, &seq_windows)) return fail("target " + std::to_string(t) + " has no sequence-level taxon");
+        char frac[64];
+        std::snprintf(frac, sizeof(frac), "%.6f", windows[t] ? (double)cov[t].windows_covered / (double)windows[t] : 0.0);
+        s += column; s += std::to_string(windows[t]);
+        s += column; s += std::to_string(cov[t].windows_covered);
+        s += column; s += frac;
+        s += column; s += std::to_string(cov[t].queries);
+        s += column; s += std::to_string(cov[t].hits);
+        s += column; s += (removed && removed[t]) ? "removed" : "kept";
+        s += '\n';
+        if (sink(user, s.data(), s.size())) return fail("the sink refused a row of the report");
+    }
+    return 0;
+}
+extern "C" int64_t mcq_coverage_text(const mcq_refdb* db, const mcq_target_coverage* cov, const uint32_t* windows, uint32_t n_targets,
+                                     const uint8_t* removed, uint64_t reads_skipped, uint64_t out_of_range, const char* comment,
+                                     const char* column, const mcq_taxon_print* mode, char* buf, size_t cap) {
+    if (cap && !buf) return fail("bad argument");
+    TextBuf b{buf, cap, 0};
+    if (mcq_coverage_write(db, cov, windows, n_targets, removed, reads_skipped, out_of_range, comment, column, mode, text_buf_sink, &b)) return -1;
     if (cap) buf[std::min(b.len, cap - 1)] = 0;
     return (int64_t)b.len;
 }

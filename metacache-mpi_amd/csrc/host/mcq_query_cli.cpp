@@ -32,6 +32,16 @@
 // reference's MPI program; -align-candidate-range first asks mcq_target_slots / mcq_target_hits (one slot) for the real range --,
 // gathers the slices into a pinned buffer, copies them in, calls mcq_align and copies the results back (Run::stage_align).  This
 // host round trip between the query and the alignment is paid by -align alone.  A read beyond the kernel's capacities ends the run.
+//
+// -coverage / -cov-percentile (not options of the reference): behind a batch's query, on the same stream,
+// mcq_target_slots and mcq_target_hits as for -hits-per-seq -- with -hits-per-seq on, its very outputs -- and then mcq_coverage_add, which
+// folds the ranges and count rows into a bitmap of windows and three numbers per sequence ON THE DEVICE (Coverage, Run::stage_cov):
+// only status[] comes back, nothing grows with the input.  The candidates are taken at sequence level: under another -lowest the
+// engine's candidates are taxa above it, so the table is made a second time with sequence-level keys (Database::seq_edb) and every
+// batch is queried there too.  -cov-percentile P runs the input twice: pass 1 is query and coverage alone, without any output; then
+// mcq_coverage_read and mcq_coverage_cut name the removed sequences; pass 2 is the ordinary run with the workspace's exclusion table
+// set to 1 for removed and 0 for kept targets and the key 1 for every query, so a removed sequence is no candidate of any read.  The
+// report shows pass 1's numbers, the ones the cut was made from.
 #include "mcq_cli_common.hpp"
 #include "mcq_read_batches.hpp"
 #include "mcq_align_subjects.hpp"
@@ -54,15 +64,75 @@ struct Slot : ReadSlot {
     DeviceBuf<uint64_t> d_ah_off; DeviceBuf<mcq_hit> d_ah; DeviceBuf<uint32_t> d_ah_n, d_ah_st;
     PinnedBuf<uint64_t> ah_off; PinnedBuf<mcq_hit> ah; PinnedBuf<uint32_t> ah_n, ah_st;
     bool all_hits = false;
+    // -coverage / -cov-percentile: the sequence-level candidates of the batch where the run's own are above it, and whether it was gathered
+    DeviceBuf<mcq_cand> d_cands_seq; DeviceBuf<uint32_t> d_ncand_seq; bool cov = false;
     AlignSlot al;                                                                        // -align
     uint64_t first_id = 0;                                                               // query id of the batch's first query
 };
 constexpr int NS = 3;
 constexpr uint64_t kAllHitsMaxEntries = (2ull << 30) / sizeof(mcq_hit);                  // -allhits: entries of one batch, so of one slot: NS times that in flight
 
+// -coverage / -cov-percentile: the accumulator on the device and what was read from it, over all runs of one command line
+struct Coverage {
+    mcq_coverage* h = nullptr;
+    std::vector<uint32_t> windows;                               // windows of every target
+    std::vector<mcq_target_coverage> rec; uint64_t out_of_range = 0;   // what mcq_coverage_read gave
+    std::vector<uint8_t> removed;                                // -cov-percentile: the cut; empty without
+    std::vector<uint32_t> tgt_clade;                             // ... as the exclusion table of pass 2: 1 removed, 0 kept
+    uint64_t skipped = 0;                                        // queries beyond mcq_target_hits' capacity: they added nothing
+    bool gather = false;                                         // the runs to come add their batches
+    ~Coverage() { mcq_coverage_free(h); }
+    bool create(const Database& db) {
+        mcq_refdb_info info; mcq_refdb_get_info(db.rdb, &info);
+        windows.resize(info.n_targets);
+        if (mcq_refdb_seq_windows(db.rdb, windows.data())) { std::fprintf(stderr, "ABORT: %s\n", mcq_host_last_error()); return false; }
+        if (mcq_coverage_create(windows.data(), info.n_targets, 0, &h)) { std::fprintf(stderr, "ABORT: %s\n", mcq_last_error()); return false; }
+        return true;
+    }
+    bool read() {
+        rec.resize(windows.size());
+        if (mcq_coverage_read(h, rec.data(), &out_of_range, nullptr)) { std::fprintf(stderr, "FAIL: %s\n", mcq_last_error()); return false; }
+        return true;
+    }
+    // mcq_coverage_cut over what pass 1 gathered; one line on stderr
+    bool cut(double percentile) {
+        removed.assign(windows.size(), 0);
+        if (mcq_coverage_cut(rec.data(), windows.data(), (uint32_t)windows.size(), percentile, removed.data())) { std::fprintf(stderr, "ABORT: %s\n", mcq_host_last_error()); return false; }
+        uint64_t hit = 0, gone = 0;
+        tgt_clade.assign(windows.size(), 0);
+        for (size_t t = 0; t < windows.size(); ++t) { hit += rec[t].windows_covered > 0; gone += removed[t]; tgt_clade[t] = removed[t]; }
+        std::fprintf(stderr, "coverage percentile %g: %llu of %llu hit sequences removed\n", percentile, (unsigned long long)gone, (unsigned long long)hit);
+        return true;
+    }
+    // the report into the -coverage FILE if one was named, else into `os`
+    bool write(const Options& p, const Out& o, std::ostream& os) {
+        // (a row names its sequence whatever -lowest says: the lowest rank shown is the sequence's own)
+        const mcq_taxon_print mode = {o.mode.rank_prefix ? 1u : 0u, (uint32_t)o.mode.body, p.lineage ? 1u : 0u, MCQ_RANK_SEQUENCE, p.highest};
+        std::ofstream fc;
+        if (!p.coverage_file.empty()) {
+            fc.open(p.coverage_file);
+            if (!fc.good()) { std::fprintf(stderr, "ABORT: Could not write to file %s\n", p.coverage_file.c_str()); return false; }
+            std::cout << "Per-sequence coverage will be written to file: " << p.coverage_file << std::endl;
+        }
+        std::ostream& co = p.coverage_file.empty() ? os : fc;
+        auto sink = [](void* user, const char* data, size_t n) -> int {
+            std::ostream& out = *static_cast<std::ostream*>(user);
+            out.write(data, (std::streamsize)n);
+            return out.good() ? 0 : 1;
+        };
+        if (mcq_coverage_write(o.db, rec.data(), windows.data(), (uint32_t)windows.size(), removed.empty() ? nullptr : removed.data(), skipped,
+                               out_of_range, o.comment, o.col, &mode, sink, &co)) { std::fprintf(stderr, "ABORT: %s\n", mcq_host_last_error()); return false; }
+        co.flush();
+        return co.good();
+    }
+};
+
 // the batches in flight, the workspace they run in and what their lines add up to
 struct Run {
     const Options& p; const Database& db; const Out o; const mcq_classify_opts co;
+    Coverage* cov = nullptr; bool pass1 = false;                 // -coverage / -cov-percentile; pass1: query and coverage alone, no output
+    mcq_ws* ws_seq = nullptr;                                    // ... the workspace of db.seq_edb
+    DeviceBuf<uint32_t> d_ones; uint64_t n_ones = 0;             // -cov-percentile, pass 2: the key 1 for every query of a batch
     mcq_taxonomy* tx = nullptr;                                  // -abundances / -abundance-per: every batch is also classified on the GPU
     std::vector<uint64_t> tax_counts; mcq_ws* ws = nullptr; uint64_t ws_cap = 0;
     std::ofstream fout; std::ostream* os = nullptr;
@@ -79,10 +149,17 @@ struct Run {
     DeviceBuf<uint32_t> d_tax2tgt; uint32_t n_taxa = 0, n_slots = 0;
     AlignSubjects subjects;                                      // -align: the sequences the database names, in host memory
 
-    Run(const Options& p_, const Database& db_) : p(p_), db(db_), o(make_out(db_.rdb, p_)), co(classify_opts(p_, db_.hitmin)) { std::memset(&eval, 0, sizeof(eval)); }
-    ~Run() { if (pending.valid()) pending.wait(); mcq_ws_destroy(ws); mcq_taxonomy_destroy(tx); for (mcq_hits_table* t : hit_acc) mcq_hits_table_free(t); }
+    Run(const Options& p_, const Database& db_, Coverage* cov_ = nullptr, bool pass1_ = false)
+        : p(p_), db(db_), o(make_out(db_.rdb, p_)), co(classify_opts(p_, db_.hitmin)), cov(cov_), pass1(pass1_) { std::memset(&eval, 0, sizeof(eval)); }
+    ~Run() { if (pending.valid()) pending.wait(); mcq_ws_destroy(ws); mcq_ws_destroy(ws_seq); mcq_taxonomy_destroy(tx); for (mcq_hits_table* t : hit_acc) mcq_hits_table_free(t); }
 
     bool init() {
+        if (pass1) {
+            if (!make_tax2tgt()) return false;
+            if (!s_k.create() || !ev_in.create()) return false;
+            for (Slot& S : slot) if (!S.done.create()) return false;
+            return true;
+        }
         if (p.tax_counts()) {
             if (!(tx = make_taxonomy(db.rdb, 0))) return false;
             mcq_refdb_info rinfo; mcq_refdb_get_info(db.rdb, &rinfo);
@@ -97,14 +174,7 @@ struct Run {
             for (mcq_hits_table*& t : hit_acc) if (mcq_hits_table_create(&t)) return false;
         }
         if (align_on() && !subjects.load(db.rdb)) return false;
-        if (hits_on() || (align_on() && p.align_range && p.P > 1)) {   // candidates above sequence level are skipped: no kernel, no rows
-            mcq_refdb_info rinfo; mcq_refdb_get_info(db.rdb, &rinfo);
-            std::vector<uint32_t> t2g(rinfo.n_taxa);
-            if (mcq_refdb_tax2tgt(db.rdb, t2g.data())) { std::fprintf(stderr, "ABORT: %s\n", mcq_host_last_error()); return false; }
-            n_taxa = rinfo.n_taxa; n_slots = std::min<uint32_t>(std::max(1u, p.maxcand), MCQ_TARGET_HITS_MAX_SLOTS);
-            if (!d_tax2tgt.grow(n_taxa)) return false;
-            MCQ_HIP(hipMemcpy(d_tax2tgt.p, t2g.data(), (size_t)n_taxa * 4, hipMemcpyHostToDevice), return false);
-        }
+        if ((hits_on() || gather_on() || (align_on() && p.align_range && p.P > 1)) && !make_tax2tgt()) return false;   // candidates above sequence level are skipped: no kernel, no rows
         if (!s_k.create() || !ev_in.create()) return false;
         for (Slot& S : slot) if (!S.done.create()) return false;
         os = &open_out(p, fout);
@@ -112,6 +182,18 @@ struct Run {
         return true;
     }
 
+    // what mcq_target_slots needs: the target of every sequence-level taxon, on the device
+    bool make_tax2tgt() {
+        mcq_refdb_info rinfo; mcq_refdb_get_info(db.rdb, &rinfo);
+        std::vector<uint32_t> t2g(rinfo.n_taxa);
+        if (mcq_refdb_tax2tgt(db.rdb, t2g.data())) { std::fprintf(stderr, "ABORT: %s\n", mcq_host_last_error()); return false; }
+        n_taxa = rinfo.n_taxa; n_slots = std::min<uint32_t>(std::max(1u, p.maxcand), MCQ_TARGET_HITS_MAX_SLOTS);
+        if (!d_tax2tgt.grow(n_taxa)) return false;
+        MCQ_HIP(hipMemcpy(d_tax2tgt.p, t2g.data(), (size_t)n_taxa * 4, hipMemcpyHostToDevice), return false);
+        return true;
+    }
+    bool gather_on() const { return cov && cov->gather; }        // this run's batches go into the coverage accumulator
+    bool cut_on() const { return cov && !pass1 && !cov->tgt_clade.empty(); }   // pass 2: the removed sequences are excluded
     bool excluding() const { return p.exclude_rank != MCQ_RANK_NONE; }
     bool hits_on() const { return p.hits_per_seq && p.lowest == MCQ_RANK_SEQUENCE; }
     bool align_on() const { return p.align && !p.nomap && p.lowest == MCQ_RANK_SEQUENCE; }   // (no mapping lines, no blocks: nothing is aligned)
@@ -254,6 +336,52 @@ struct Run {
         MCQ_HIP(hipMemcpyAsync(S.hst.p, S.d_hst.p, n * 4, hipMemcpyDeviceToHost, s_k), return false);
         return true;
     }
+    // -coverage / -cov-percentile: behind the batch's query on s_k (`res`: its sequence-level candidates on `gdb` / `gws`).  With
+    // -hits-per-seq on, stage_hits has made the ranges and count rows already; else they are made here and stay on the device.  Only
+    // status[] comes back.
+    bool stage_cov(Slot& S, const mcq_batch& in, const mcq_result& res, const mcq_db* gdb, mcq_ws* gws, hipStream_t st) {
+        const uint64_t n = S.n, ns = in.n_seqs;
+        if (!S.hits) {
+            const uint64_t* off = S.h_seq_off.data();
+            if (!S.host_parsed) {
+                if (!S.seq_off.grow(ns + 1)) return false;
+                MCQ_HIP(hipMemcpyAsync(S.seq_off.p, S.d_seq_off.p, (ns + 1) * 8, hipMemcpyDeviceToHost, st), return false);
+                MCQ_HIP(hipStreamSynchronize(st), return false);
+                off = S.seq_off.p;
+            }
+            const uint64_t m = in.paired ? 2 : 1;
+            uint64_t longest = 0;
+            for (uint64_t q = 0; q < n; ++q) longest = std::max(longest, off[m * q + m] - off[m * q]);
+            S.range_cap = mcq_target_hits_range_cap(gdb, longest, p.insertsize);
+            const uint64_t words = n * n_slots * S.range_cap;
+            if (words > (1ull << 29)) {                          // 2 GiB of counts: one very long read among many
+                std::fprintf(stderr, "ABORT: -coverage needs %llu MB for the window counts of a batch of %llu reads whose longest has %llu bases: "
+                                     "use a smaller -batch\n", (unsigned long long)(words >> 18), (unsigned long long)n, (unsigned long long)longest);
+                return false;
+            }
+            if (!S.d_tgt.grow(n * n_slots) || !S.d_rng.grow(n * n_slots) || !S.d_cnt.grow(words) || !S.d_hst.grow(n) || !S.hst.grow(n)) return false;
+            if (mcq_target_slots(&res, n, p.maxcand, db.hitmin, d_tax2tgt.p, n_taxa, S.d_tgt.p, n_slots, s_k) ||
+                mcq_target_hits(gdb, gws, &in, S.d_tgt.p, n_slots, p.insertsize, S.range_cap, S.d_rng.p, S.d_cnt.p, S.d_hst.p, s_k)) {
+                std::fprintf(stderr, "FAIL: %s\n", mcq_last_error()); return false;
+            }
+            MCQ_HIP(hipMemcpyAsync(S.hst.p, S.d_hst.p, n * 4, hipMemcpyDeviceToHost, s_k), return false);
+        }
+        if (mcq_coverage_add(cov->h, S.d_rng.p, S.d_cnt.p, n, n_slots, S.range_cap, s_k)) { std::fprintf(stderr, "FAIL: %s\n", mcq_last_error()); return false; }
+        S.cov = true;
+        return true;
+    }
+    // -cov-percentile, pass 2: every query of the batch carries the key 1, the key of the removed sequences
+    bool stage_ones(uint64_t n) {
+        if (n > n_ones) {
+            MCQ_HIP(hipStreamSynchronize(s_k), return false);    // (batches in flight read the array that grow() replaces)
+            if (!d_ones.grow(n)) return false;
+            const std::vector<uint32_t> ones(n, 1u);
+            MCQ_HIP(hipMemcpy(d_ones.p, ones.data(), n * 4, hipMemcpyHostToDevice), return false);
+            n_ones = n;
+        }
+        if (mcq_ws_set_query_clades(ws, d_ones.p, n, MCQ_DEVICE_PTRS)) { std::fprintf(stderr, "FAIL: %s\n", mcq_last_error()); return false; }
+        return true;
+    }
     // the ground truth of query q of the batch in S: from its whole header, which goes on behind the printed token to the end of its line
     uint32_t truth_of(const Slot& S, uint64_t q) const {
         const char* h = S.text[0].p + S.hdr.p[2 * q];
@@ -291,8 +419,10 @@ struct Run {
     bool finish(size_t j) {
         Slot& S = slot[j % NS];
         if (hipEventSynchronize(S.done) != hipSuccess) { std::fprintf(stderr, "FAIL: batch %zu did not complete\n", j); return false; }
-        announce(S.unit + 1);
         const uint64_t n = S.n;
+        if (S.cov && !S.hits) for (uint64_t q = 0; q < n; ++q) if (S.hst.p[q]) ++cov->skipped;   // beyond mcq_target_hits' capacity: it added nothing, and is counted
+        if (pass1) return true;
+        announce(S.unit + 1);
         if (S.hits) for (uint64_t q = 0; q < n; ++q) if (S.hst.p[q]) {        // beyond mcq_target_hits' capacity: reported, never dropped in silence
             std::fprintf(stderr, "ABORT: -hits-per-seq: read %llu (%.*s) %s\n", (unsigned long long)(S.first_id + q),
                          (int)(S.hdr.p[2 * q + 1] - S.hdr.p[2 * q]), S.text[0].p + S.hdr.p[2 * q],
@@ -407,6 +537,12 @@ struct Run {
         if (mcq_ws_create(db.edb, cap, 1, 0, &ws)) { std::fprintf(stderr, "ABORT: %s\n", mcq_last_error()); return false; }
         if (tx && mcq_ws_set_classify(ws, tx, &co)) { std::fprintf(stderr, "ABORT: %s\n", mcq_last_error()); return false; }
         if (excluding() && mcq_ws_set_exclusion(ws, tgt_clade.data(), (uint32_t)tgt_clade.size(), 0)) { std::fprintf(stderr, "ABORT: %s\n", mcq_last_error()); return false; }
+        if (cut_on() && mcq_ws_set_exclusion(ws, cov->tgt_clade.data(), (uint32_t)cov->tgt_clade.size(), 0)) { std::fprintf(stderr, "ABORT: %s\n", mcq_last_error()); return false; }
+        if (gather_on() && db.seq_edb) {                         // the sequence-level twin, under the same exclusion
+            mcq_ws_destroy(ws_seq); ws_seq = nullptr;
+            if (mcq_ws_create(db.seq_edb, cap, 1, 0, &ws_seq)) { std::fprintf(stderr, "ABORT: %s\n", mcq_last_error()); return false; }
+            if (excluding() && mcq_ws_set_exclusion(ws_seq, tgt_clade.data(), (uint32_t)tgt_clade.size(), 0)) { std::fprintf(stderr, "ABORT: %s\n", mcq_last_error()); return false; }
+        }
         ws_cap = cap;
         return true;
     }
@@ -415,11 +551,14 @@ struct Run {
 }  // namespace
 
 // one output: the units of p through the GPU, head, mapping lines, tables and summary into p's -out file
-static int run_queries(const Options& p, const Database& db) {
+// (cov: the coverage accumulator of the command line, or none; pass1: query and coverage alone, nothing is written; report: the
+//  coverage report belongs into this run's output)
+static int run_queries(const Options& p, const Database& db, Coverage* cov = nullptr, bool pass1 = false, bool report = false) {
     const auto t_start = std::chrono::steady_clock::now();                  // the reference times map_queries_to_targets, readers included (src/mode_query.cpp:130-132)
     ReadBatcher reads(p.units, p.read_chunk, p.batch, p.batch_bases, p.host_reader, 0);
-    Run run(p, db);
+    Run run(p, db, cov, pass1);
     if (!reads.ok() || !run.init()) return 1;
+    const bool gather = run.gather_on();
     const mcq_query_opts qo = query_opts(p);
     const int mates = p.paired() ? 2 : 1;
     for (;;) {
@@ -430,7 +569,7 @@ static int run_queries(const Options& p, const Database& db) {
         if (got == ReadBatcher::ERROR) return 1;
         if (got == ReadBatcher::END) break;
         const uint64_t n = S.n;
-        S.first_id = run.next_id; run.next_id += n; S.hits = run.hits_on();
+        S.first_id = run.next_id; run.next_id += n; S.hits = !pass1 && run.hits_on(); S.cov = false;
         if (!run.ensure_ws(n) || !S.d_cands.grow(n * p.maxcand) || !S.d_ncand.grow(n) || !S.cands.grow(n * p.maxcand) || !S.ncand.grow(n)) return 1;
         mcq_batch in; std::memset(&in, 0, sizeof(in));
         in.n_seqs = n * mates; in.bases = S.d_bases.p; in.seq_off = S.d_seq_off.p; in.paired = mates == 2; in.flags = MCQ_DEVICE_PTRS;
@@ -438,21 +577,42 @@ static int run_queries(const Options& p, const Database& db) {
         if (run.excluding() && !run.stage_clades(S, reads.stream())) return 1;
         MCQ_HIP(hipEventRecord(run.ev_in, reads.stream()), return 1);
         MCQ_HIP(hipStreamWaitEvent(run.s_k, run.ev_in, 0), return 1);
-        if (mcq_query(db.edb, run.ws, &in, &qo, &res, run.s_k)) { std::fprintf(stderr, "FAIL: %s\n", mcq_last_error()); return 1; }
-        MCQ_HIP(hipMemcpyAsync(S.cands.p, S.d_cands.p, n * p.maxcand * sizeof(mcq_cand), hipMemcpyDeviceToHost, run.s_k), return 1);
-        MCQ_HIP(hipMemcpyAsync(S.ncand.p, S.d_ncand.p, n * 4, hipMemcpyDeviceToHost, run.s_k), return 1);
-        if (!S.host_parsed && !run.excluding()) MCQ_HIP(hipMemcpyAsync(S.hdr.p, S.d_hdr.p, 2 * n * 8, hipMemcpyDeviceToHost, run.s_k), return 1);
+        const bool seq_twin = gather && db.seq_edb;             // the run's candidates are above sequence level: coverage asks the twin
+        if (!(pass1 && seq_twin)) {
+            if (run.cut_on() && !run.stage_ones(n)) return 1;
+            if (mcq_query(db.edb, run.ws, &in, &qo, &res, run.s_k)) { std::fprintf(stderr, "FAIL: %s\n", mcq_last_error()); return 1; }
+        }
+        if (!pass1) {
+            MCQ_HIP(hipMemcpyAsync(S.cands.p, S.d_cands.p, n * p.maxcand * sizeof(mcq_cand), hipMemcpyDeviceToHost, run.s_k), return 1);
+            MCQ_HIP(hipMemcpyAsync(S.ncand.p, S.d_ncand.p, n * 4, hipMemcpyDeviceToHost, run.s_k), return 1);
+            if (!S.host_parsed && !run.excluding()) MCQ_HIP(hipMemcpyAsync(S.hdr.p, S.d_hdr.p, 2 * n * 8, hipMemcpyDeviceToHost, run.s_k), return 1);
+        }
         if (S.hits && !run.stage_hits(S, in, res, reads.stream())) return 1;
-        S.all_hits = p.allhits && !p.nomap;
+        if (gather) {
+            mcq_result gres = res;
+            if (seq_twin) {
+                if (!S.d_cands_seq.grow(n * p.maxcand) || !S.d_ncand_seq.grow(n)) return 1;
+                gres.cands = S.d_cands_seq.p; gres.n_cand = S.d_ncand_seq.p;
+                if (run.excluding() && mcq_ws_set_query_clades(run.ws_seq, S.d_clade.p, n, MCQ_DEVICE_PTRS)) { std::fprintf(stderr, "FAIL: %s\n", mcq_last_error()); return 1; }
+                if (mcq_query(db.seq_edb, run.ws_seq, &in, &qo, &gres, run.s_k)) { std::fprintf(stderr, "FAIL: %s\n", mcq_last_error()); return 1; }
+            }
+            if (!run.stage_cov(S, in, gres, seq_twin ? db.seq_edb : db.edb, seq_twin ? run.ws_seq : run.ws, reads.stream())) return 1;
+        }
+        S.all_hits = !pass1 && p.allhits && !p.nomap;
         if (S.all_hits && !run.stage_all_hits(S, in)) return 1;
         S.al.on = false;
-        if (run.align_on() && !run.stage_align(S, in, res, reads.stream())) return 1;
+        if (!pass1 && run.align_on() && !run.stage_align(S, in, res, reads.stream())) return 1;
         MCQ_HIP(hipEventRecord(S.done, run.s_k), return 1);
         ++run.issued;
     }
     if (!run.drain()) return 1;
+    if (pass1) return 0;
     run.announce(p.units.size());
     if (p.hits_per_seq && !run.write_hits_table()) return 1;     // before the abundance tables: src/classification.cpp:847-862
+    if (report) {                                                // behind the table, in front of the abundance tables
+        if (gather && !cov->read()) return 1;
+        if (!cov->write(p, run.o, *run.os)) return 1;
+    }
     if (run.tx) {
         if (run.ws && !add_taxon_counts(run.ws, run.tax_counts)) return 1;
         if (!write_abundances(*run.os, db.rdb, p, run.tax_counts, run.assigned)) return 1;
@@ -469,7 +629,25 @@ int main(int argc, char** argv) {
     Database db;
     if (!open_database(p, db, 1, 0, 0)) return 1;
     if (p.split && !inputs_readable(p)) return 1;               // (one run: its ReadBatcher tries them all)
+    Coverage cov;
+    if (p.cov_on()) {
+        if (!cov.create(db)) return 1;
+        if (p.lowest != MCQ_RANK_SEQUENCE && !open_seq_twin(p, db)) return 1;
+    }
+    if (p.cov_cut()) {                                          // pass 1: all units as one input, query and coverage alone
+        Options one = p; one.split = false;
+        cov.gather = true;
+        if (const int rc = run_queries(one, db, &cov, true)) return rc;
+        if (!cov.read() || !cov.cut(p.cov_percentile)) return 1;
+        mcq_db_destroy(db.seq_edb); db.seq_edb = nullptr;      // pass 2 gathers nothing
+    }
+    cov.gather = p.coverage && !p.cov_cut();
+    // (a run of -splitout has no report of its own: split_options; the accumulator goes with every run all the same)
     for (const Options& r : output_runs(p))
-        if (const int rc = run_queries(r, db)) return rc;
+        if (const int rc = run_queries(r, db, p.cov_on() ? &cov : nullptr, false, p.coverage && !p.split)) return rc;
+    if (p.coverage && p.split) {                                // over all units together, written once: into FILE, else to stdout
+        if (cov.gather && !cov.read()) return 1;
+        if (!cov.write(p, make_out(db.rdb, p), std::cout)) return 1;
+    }
     return 0;
 }

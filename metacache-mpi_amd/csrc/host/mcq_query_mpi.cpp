@@ -25,7 +25,8 @@
 //                                   [-batch N] [-batch-bases N]
 // -align (and its aliases) is rejected the same way.
 // -exclude, -ground-truth and -precision are rejected with a line that names mcq_query_cli: the sharded kernels have no exclusion.
-// -hits-per-seq is rejected the same way: mcq_target_hits is a kernel of the one-GPU path.  So is -allhits (mcq_all_hits).
+// -hits-per-seq is rejected the same way: mcq_target_hits is a kernel of the one-GPU path.  So is -allhits (mcq_all_hits), and so
+// are -coverage and -cov-percentile (mcq_coverage_* work on mcq_target_hits' outputs).
 // -queryids and -locations come through the shared parser and writer.
 #include <mpi.h>
 #include <hip/hip_runtime_api.h>
@@ -129,6 +130,10 @@ int main(int argc, char** argv) {
     }
     if (p.allhits) {                                                        // (before any GPU work)
         if (rank == 0) std::fprintf(stderr, "ABORT: -allhits is an option of mcq_query_cli; mcq_query_mpi lists no hits (mcq_all_hits is a kernel of the one-GPU path)\n");
+        MPI_Finalize(); return 2;
+    }
+    if (p.cov_on()) {                                                       // (before any GPU work)
+        if (rank == 0) std::fprintf(stderr, "ABORT: -coverage and -cov-percentile are options of mcq_query_cli; mcq_query_mpi keeps no window coverage (mcq_target_hits is a kernel of the one-GPU path)\n");
         MPI_Finalize(); return 2;
     }
     int n_dev = 0;

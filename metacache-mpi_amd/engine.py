@@ -268,6 +268,14 @@ def lib():
             L.mcq_merge_lists.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_uint64)]
             L.mcq_merge_headers.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
             L.mcq_merge_free.argtypes = [C.c_void_p]
+        if hasattr(L, "mcq_coverage_create"):
+            L.mcq_coverage_create.argtypes = [C.c_void_p, C.c_uint32, C.c_int32, C.POINTER(C.c_void_p)]
+            L.mcq_coverage_add.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint32, C.c_uint32, C.c_void_p]
+            L.mcq_coverage_read.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(C.c_uint64), C.c_void_p]
+            L.mcq_coverage_reset.argtypes = [C.c_void_p, C.c_void_p]
+            L.mcq_coverage_bitmap_words.restype = C.c_uint64; L.mcq_coverage_bitmap_words.argtypes = [C.c_void_p]
+            L.mcq_coverage_bitmap.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+            L.mcq_coverage_free.argtypes = [C.c_void_p]
         L.mcq_shard_create.argtypes = [C.c_void_p, C.POINTER(ShardCfg), C.POINTER(C.c_void_p)]
         L.mcq_shard_destroy.argtypes = [C.c_void_p]
         L.mcq_shard_unique_id.argtypes = [C.c_void_p]
@@ -1188,6 +1196,52 @@ class ContentStats:
     def close(self):
         if getattr(self, "h", None):
             lib().mcq_content_stats_free(self.h); self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+# mcq_target_coverage: one record per target (host.COVERAGE_DTYPE is the same)
+COVERAGE_DTYPE = np.dtype([("hits", "<u8"), ("queries", "<u8"), ("windows_covered", "<u4"), ("reserved", "<u4")])
+
+
+class Coverage:
+    """mcq_coverage_*: window coverage per reference sequence, added up on the device over all batches of a run.  add() takes
+    mcq_target_hits' device outputs as they are (pointers, or anything with data_ptr()) and only enqueues; read() returns a record
+    array of COVERAGE_DTYPE, one per target, and the number of ranges that were refused; reset() zeroes everything."""
+
+    def __init__(self, windows, device=0):
+        w = np.ascontiguousarray(windows, np.uint32)
+        h = C.c_void_p()
+        _chk(lib().mcq_coverage_create(w.ctypes.data_as(C.c_void_p) if len(w) else None, len(w), device, C.byref(h)))
+        self.h, self.n_targets = h, len(w)
+
+    def add(self, ranges, counts, n_queries, n_slots, range_cap, stream=None):
+        ptr = [C.c_void_p(int(x.data_ptr() if hasattr(x, "data_ptr") else x)) if n_queries else None for x in (ranges, counts)]
+        _chk(lib().mcq_coverage_add(self.h, ptr[0], ptr[1], n_queries, n_slots, range_cap, stream))
+
+    def read(self, stream=None):
+        out = np.zeros(self.n_targets, COVERAGE_DTYPE)
+        oor = C.c_uint64(0)
+        _chk(lib().mcq_coverage_read(self.h, out.ctypes.data_as(C.c_void_p), C.byref(oor), stream))
+        return out, int(oor.value)
+
+    def bitmap(self, stream=None):
+        """(words, word_off): the bitmap with its two guard words -- segment t is words[1 + word_off[t] : 1 + word_off[t + 1]]"""
+        words = np.zeros(int(lib().mcq_coverage_bitmap_words(self.h)), np.uint32)
+        off = np.zeros(self.n_targets + 1, np.uint64)
+        _chk(lib().mcq_coverage_bitmap(self.h, words.ctypes.data_as(C.c_void_p), off.ctypes.data_as(C.c_void_p), stream))
+        return words, off
+
+    def reset(self, stream=None):
+        _chk(lib().mcq_coverage_reset(self.h, stream))
+
+    def close(self):
+        if getattr(self, "h", None):
+            lib().mcq_coverage_free(self.h); self.h = None
 
     def __del__(self):
         try:

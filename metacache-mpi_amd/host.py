@@ -142,6 +142,11 @@ def lib():
         L.mcq_hits_table_text.restype = C.c_int64
         L.mcq_hits_table_text.argtypes = [C.c_void_p, C.c_void_p, C.c_char_p, C.c_char_p, C.POINTER(TaxonPrint), C.c_char_p, C.c_size_t]
         L.mcq_hits_table_free.argtypes = [C.c_void_p]
+        L.mcq_refdb_seq_windows.argtypes = [C.c_void_p, C.c_void_p]
+        L.mcq_coverage_cut.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_double, C.c_void_p]
+        L.mcq_coverage_text.restype = C.c_int64
+        L.mcq_coverage_text.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint64, C.c_uint64, C.c_char_p, C.c_char_p,
+                                        C.POINTER(TaxonPrint), C.c_char_p, C.c_size_t]
         L.mcq_refdb_target_key.restype = C.c_uint32; L.mcq_refdb_target_key.argtypes = [C.c_void_p, C.c_uint32]
         L.mcq_refdb_tax2tgt.argtypes = [C.c_void_p, C.c_void_p]
         L.mcq_default_hits_min.restype = C.c_uint32; L.mcq_default_hits_min.argtypes = [C.c_uint32]
@@ -342,6 +347,13 @@ class RefDb:
     def target_key(self, target):
         return int(lib().mcq_refdb_target_key(self.h, int(target)))
 
+    def seq_windows(self):
+        """windows of every target as the -hits-per-seq table and the coverage report print them (mcq_refdb_seq_windows)"""
+        out = np.zeros(self.info.n_targets, np.uint32)
+        if lib().mcq_refdb_seq_windows(self.h, out.ctypes.data_as(C.c_void_p)) != 0:
+            raise RuntimeError(lib().mcq_host_last_error().decode())
+        return out
+
     def tax2tgt(self):
         out = np.zeros(self.info.n_taxa, np.uint32)
         lib().mcq_refdb_tax2tgt(self.h, out.ctypes.data_as(C.c_void_p))
@@ -359,6 +371,46 @@ class RefDb:
         buf = C.create_string_buffer(n + 1)
         lib().mcq_refdb_abundance_text(self.h, c.ctypes.data_as(C.c_void_p), int(total), int(est_rank), buf, n + 1)
         return buf.raw[:n].decode("latin-1")
+
+
+# mcq_target_coverage: what engine.Coverage.read() returns, one record per target
+COVERAGE_DTYPE = np.dtype([("hits", "<u8"), ("queries", "<u8"), ("windows_covered", "<u4"), ("reserved", "<u4")])
+
+
+def _coverage_args(cov, windows):
+    c = np.ascontiguousarray(cov, COVERAGE_DTYPE)
+    w = np.ascontiguousarray(windows, np.uint32)
+    if len(c) != len(w):
+        raise ValueError("coverage records and windows differ in length")
+    return c, w
+
+
+def coverage_cut(cov, windows, percentile):
+    """mcq_coverage_cut: removed[t] (uint8) -- the floor(H * percentile / 100) hit targets of the least breadth (include/mcq_host.h)"""
+    c, w = _coverage_args(cov, windows)
+    removed = np.zeros(len(c), np.uint8)
+    if lib().mcq_coverage_cut(c.ctypes.data_as(C.c_void_p), w.ctypes.data_as(C.c_void_p), len(c), float(percentile),
+                              removed.ctypes.data_as(C.c_void_p)) != 0:
+        raise RuntimeError(lib().mcq_host_last_error().decode())
+    return removed
+
+
+def coverage_text(db, cov, windows, removed=None, reads_skipped=0, out_of_range=0, comment="# ", column="\t|\t", show_ranks=True, body=0,
+                  lineage=False, lowest_rank=0, highest_rank=19):
+    """mcq_coverage_text: the report block of -coverage; body: 0 name, 1 id, 2 name(id)"""
+    c, w = _coverage_args(cov, windows)
+    r = None if removed is None else np.ascontiguousarray(removed, np.uint8)
+    if r is not None and len(r) != len(c):
+        raise ValueError("removed and the coverage records differ in length")
+    m = TaxonPrint(1 if show_ranks else 0, body, 1 if lineage else 0, lowest_rank, highest_rank)
+    args = (db.h, c.ctypes.data_as(C.c_void_p), w.ctypes.data_as(C.c_void_p), len(c), None if r is None else r.ctypes.data_as(C.c_void_p),
+            int(reads_skipped), int(out_of_range), comment.encode(), column.encode(), C.byref(m))
+    n = lib().mcq_coverage_text(*args, None, 0)
+    if n < 0:
+        raise RuntimeError(lib().mcq_host_last_error().decode())
+    buf = C.create_string_buffer(n + 1)
+    lib().mcq_coverage_text(*args, buf, n + 1)
+    return buf.raw[:n].decode("latin-1")
 
 
 class HitsTable:
